@@ -8,17 +8,22 @@ lists over RCCL and merges them on every rank.  `value` counts (query, 10M-row s
 over all ranks, i.e. row.query pairs/s / 1e7.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs out/     # + the last timed step's top-k as out/{scores,rows}.npy
+    python bench.py --gpus 1 --full     # + parity vs the oracle, the sub-records below and the CPU baselines
     python bench.py --gpus 8            # launches its own 8 ranks (torch.distributed.run) before touching the GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...    (the same thing, launched outside)
 
-Prints ONE JSON line (rank 0).  Beside the headline it carries sub-records, each with its own roofline / parity block:
+Prints ONE JSON line (rank 0).  A plain run builds the corpus, warms up, times --steps batches and prints the headline with the
+roofline of those timed batches (the N>1 first-contact checks included); nothing else.  With --full the line also carries the
+parity subsample against the oracle and sub-records, each with its own roofline / parity block:
 `filtered`, `wide` (one 512-query call), `config5` (scan + side-column gather + device hybrid re-rank, checked against the host
 HybridRanker in-run), `f32_store` (ids and scores bit-exact vs the f32 oracle), `embed` (BASELINE configs[1], encoder only),
 `c2` (configs[1] as one pipeline: 100k chunks -> packed encoder -> device-to-device index -> top-100 over the EMBEDDED vectors,
 bit-exact vs the oracle on those vectors, and end-to-end recall against the fp32 pipeline on two weight statistics),
 `embed_e2e` (texts -> provider -> python float lists), `c1` (BASELINE configs[0] shape: ~1k code chunks through the
-reference-shaped surfaces, GPU vs the CPU oracle), `cpu_baseline`.  No reference code or CPU path is inside a timed GPU
-region; the CPU legs (oracle = test infrastructure) run afterwards on rank 0 at N=1 only.
+reference-shaped surfaces, GPU vs the CPU oracle), `cpu_baseline`, and the headline's int8 scan timed once more across all
+three of its launches (`roofline.scan_three_launches_ms`).  No reference code or CPU path is inside a timed GPU region; the
+CPU legs (oracle = test infrastructure) run afterwards on rank 0 at N=1 only.
 
 `--backend gloo` is the launcher rehearsal for machines without a GPU (tests/test_bench_launch.py): the same self-launch,
 rendezvous, exchange-record all-gather, max-over-ranks timing and JSON assembly, with NO device work and `value` null.
@@ -94,8 +99,14 @@ def parse_args():
                     help="weak: --rows per GPU (BASELINE C4a); strong: --rows in total, split over the ranks (C4b)")
     ap.add_argument("--check-rows", type=int, default=1_000_000,
                     help="rows of the parity subsample checked vs the oracle (from 1M rows the sub-index is nominated from its int8 copy, like the timed corpus)")
-    ap.add_argument("--legs", default=None, help="comma list of sub-records to run beside the headline "
-                    f"({','.join(ALL_LEGS)}); default: all at N=1, config5+embed at N>1; 'none' = headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run what checks and extends it: the parity subsample vs the oracle (--check-rows), "
+                         "the sub-records (--legs), the CPU baselines and the three-launch span of the int8 scan; off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k (merged over the ranks when N>1) as DIR/scores.npy (float32) and DIR/rows.npy "
+                         "(float64 global row ids)")
+    ap.add_argument("--legs", default=None, help="comma list of sub-records a --full run carries beside the headline "
+                    f"({','.join(ALL_LEGS)}); default: all at N=1, config5+embed+c2 at N>1; 'none' = headline only")
     ap.add_argument("--sub-steps", type=int, default=20, help="timed steps of the filtered / f32_store / config5 legs")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="time box of each CPU baseline leg")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -103,7 +114,22 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="with --backend gloo on a box with ONE GPU: every rank uses device 0 and the real N>1 path runs with "
                          "host-staged gloo collectives (rehearsal of everything but RCCL; not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.legs not in (None, "none") and not args.full:
+        ap.error("--legs chooses the sub-records of a --full run: add --full")
+    if args.dump_outputs and args.backend == "gloo" and not args.share_gpu:
+        ap.error("--dump-outputs needs device work: the gloo launcher rehearsal computes no top-k")
+    return args
+
+
+def selected_legs(args, world: int) -> set:
+    """The sub-records this run carries beside the headline: none in a plain run."""
+    if not args.full:
+        return set()
+    default = ALL_LEGS if world == 1 else ("config5", "embed", "c2")
+    return set(default) if args.legs is None else set(x for x in args.legs.split(",") if x and x != "none")
 
 
 def main() -> None:
@@ -354,7 +380,7 @@ def rehearse(args, json_fd) -> None:
     # the collectives of the legs an N > 1 run carries beside the headline (config5: the all-gather above + ONE all-reduce that
     # completes the packed side columns -- every candidate is owned by exactly one rank, the others contribute zeros; embed: no
     # data-path collective, barriers + max-over-ranks timing), with their layouts checked
-    legs = set(("config5", "embed", "c2") if args.legs is None else (x for x in args.legs.split(",") if x and x != "none"))
+    legs = selected_legs(args, world)
     legs_ok = {}
     if "config5" in legs:
         n = B * K
@@ -677,8 +703,7 @@ def run(args, json_fd) -> None:
             dist = HostStagedCollectives(dist)
         else:
             dist.init_process_group("nccl", device_id=dev, timeout=limit)
-    legs = set(ALL_LEGS if world == 1 else ("config5", "embed", "c2")) if args.legs is None else \
-        set(x for x in args.legs.split(",") if x and x != "none")
+    legs = selected_legs(args, world)
     unknown = legs - set(ALL_LEGS)
     if unknown:
         raise SystemExit(f"unknown legs: {sorted(unknown)}")
@@ -693,7 +718,8 @@ def run(args, json_fd) -> None:
     dtype = ffi.DTYPE_BF16 if args.dtype == "bf16" else ffi.DTYPE_F32
     stream = torch.cuda.current_stream().cuda_stream
 
-    idx, head, head_codes = build_corpus(torch, ffi, dev, N, dtype, 20251226 + rank, args.check_rows, 1, stream, args.seed_tiles)
+    check_rows = args.check_rows if args.full else 0          # (a plain run keeps no host copy of the parity subsample)
+    idx, head, head_codes = build_corpus(torch, ffi, dev, N, dtype, 20251226 + rank, check_rows, 1, stream, args.seed_tiles)
     log(f"corpus resident: {N} rows x {D} ({args.dtype})")
     qs = np.random.default_rng(7).standard_normal((B, D)).astype(np.float32)
     qd = torch.from_numpy(qs).to(dev)
@@ -754,10 +780,17 @@ def run(args, json_fd) -> None:
     headline_rows = out_r[last].clone()          # this rank's local top-k of the last timed step (global row ids)
     headline_scores = out_s[last].clone()
     nom_mode = idx.nomination()                  # how the timed batches were nominated (2: int8 copy, 1 / 0: bf16 tiles)
-    # outside the timed region: the same batches once more with the library's two events around ALL three launches of the int8
-    # scan (sample tiles, thresholds, pass) -- the span that was one launch, and `kernel_ms`, until late in round 4
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: this rank's top-k, or the merged one when N>1
+        got_s, got_r = (mer_s, mer_r) if dist is not None else (headline_scores, headline_rows)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), got_s.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), got_r.cpu().numpy().astype(np.float64))
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    # --full, outside the timed region: the same batches once more with the library's two events around ALL three launches of
+    # the int8 scan (sample tiles, thresholds, pass) -- the span that was one launch, and `kernel_ms`, until late in round 4
     scan3_ms = None
-    if nom_mode == 2:
+    if nom_mode == 2 and args.full:
         idx.set_profiling(2)
         run_steps(min(20, args.steps), launch, lambda i: None)   # (rank-local: no collective -- the ranks need not agree on the mode)
         idx.search_finish(stream)
@@ -802,7 +835,7 @@ def run(args, json_fd) -> None:
     # ---- parity on a subsample (outside the timed region): first check_rows rows of rank 0 vs the oracle
     parity = None
     orc = None
-    if rank == 0 and head is not None and args.check_rows > 0:
+    if rank == 0 and head is not None and check_rows > 0:
         from oracle import search as orc
         parity = subsample_parity(np, ffi, orc, head, head_codes, qs, K, dtype, local_rank)
         if merge_ok is not None:

@@ -19,7 +19,7 @@ def _run(*argv, env_extra=None):
 
 @pytest.mark.parametrize("n,scaling", [(2, "weak"), (4, "strong")])
 def test_self_launch_prints_one_json_line_with_all_ranks(n, scaling):
-    p = _run("--gpus", str(n), "--backend", "gloo", "--rows", "4096", "--steps", "3", "--warmup", "1", "--scaling", scaling)
+    p = _run("--gpus", str(n), "--backend", "gloo", "--rows", "4096", "--steps", "3", "--warmup", "1", "--scaling", scaling, "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout                      # rank 0 only, nothing else on stdout
@@ -35,7 +35,7 @@ def test_self_launch_prints_one_json_line_with_all_ranks(n, scaling):
 def test_eight_ranks_strong_scaling_with_the_config5_and_embed_collectives():
     """The shape of the first real 8-GPU record (SCALE_rNN): 8 ranks, --scaling strong, the config5 and embed legs beside the
     headline -- every collective those legs issue runs (gloo) and its layout is checked; per-rank device records are there."""
-    p = _run("--gpus", "8", "--backend", "gloo", "--rows", "80000", "--steps", "2", "--warmup", "1", "--scaling", "strong", "--legs", "config5,embed")
+    p = _run("--gpus", "8", "--backend", "gloo", "--rows", "80000", "--steps", "2", "--warmup", "1", "--scaling", "strong", "--full", "--legs", "config5,embed")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -50,6 +50,23 @@ def test_eight_ranks_strong_scaling_with_the_config5_and_embed_collectives():
     assert len(lines[0]) < 4096
     full = json.load(open(os.path.join(ROOT, rec["detail"])))             # the sidecar holds the full per-rank device records
     assert [d["rank"] for d in full["per_rank_device"]] == list(range(8))
+
+
+def test_a_plain_run_rehearses_the_headline_only():
+    """Without --full the N > 1 run carries no sub-records: only the headline's exchange runs (and is checked)."""
+    p = _run("--gpus", "2", "--backend", "gloo", "--rows", "4096", "--steps", "3", "--warmup", "1")
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["exchange_layout_ok"] is True and rec["legs_rehearsed"] == {}
+
+
+@pytest.mark.parametrize("argv,says", [(("--legs", "filtered"), "--full"), (("--steps", "0"), "--steps"),
+                                       (("--backend", "gloo", "--dump-outputs", "out"), "--dump-outputs")])
+def test_arguments_a_run_cannot_honour_are_refused_before_any_work(argv, says):
+    p = _run(*argv)
+    assert p.returncode == 2 and says in p.stderr and p.stdout == ""
 
 
 def test_world_size_mismatch_is_refused():

@@ -17,5 +17,5 @@ step() { # name timeout cmd...
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest 900 python -m pytest tests -q -m gpu -x --timeout 600
 for rows in "$@"; do
-  step bench_$rows 600 python bench.py --rows $rows --steps 20 --warmup 5
+  step bench_$rows 600 python bench.py --rows $rows --steps 20 --warmup 5 --full
 done
