@@ -11,9 +11,11 @@
 //                 kernel, 256x256x64 ping-pong, is g256::k_gemm_pp in crh_gemm256.hpp),
 //                 epilogues: bias | bias+erf-GELU | bias+residual
 //   k_layernorm   in-place row LayerNorm over 768 (one wave per row)
-//   k_attn        per (batch row, head): K and V of the whole row staged once in LDS, S^T = K.Q^T and O^T = V^T.P^T on
-//                 MFMA with the softmax statistics lane-local (query on the lane), V consumed through
+//   k_attn        rows of up to 512 tokens, per (batch row, head): K and V of the whole row staged once in LDS, S^T = K.Q^T and
+//                 O^T = V^T.P^T on MFMA with the softmax statistics lane-local (query on the lane), V consumed through
 //                 ds_read_b64_tr_b16 so it is never transposed in memory; keys masked by the validity bitmask
+//   k_attn_long   rows of 513..1024 tokens: the same 64-key tile update (attn_tile), K/V streamed through LDS in 256-key
+//                 windows, each (row, head) split over workgroups along the query axis
 //   k_pool        masked mean over valid tokens (f32 out, no L2 normalisation)
 #include <algorithm>
 #include <cmath>
@@ -824,8 +826,115 @@ __device__ __forceinline__ void pair32(float x, float &a, float &b)
 }
 #endif
 
+// One 64-key tile of the online softmax for QT query tiles: S^T = K.Q^T, masked by the tile's validity word vm (!= 0), running
+// maximum / sum / output rescaled, O^T += V^T.P^T.  Ks / Vs are the K / V images in LDS, kr the image row of the tile's first key
+// (a multiple of 64).  This is k_attn's key-tile loop body, statement for statement: k_attn_long runs its key tiles through it
+// in key order, so a query tile's result is the same bits whichever kernel computes it (tests/test_long_context_gpu.py pins
+// that).  k_attn keeps its own inline copy: calling this routine from it moved its register allocation (102 -> 108 VGPRs) and
+// cost it ~1 % at L = 128..512; edit both together.
+template <int QT>
+__device__ __forceinline__ void attn_tile(const unsigned char *Ks, const unsigned char *Vs, int kr, unsigned long long vm,
+                                          const bf16x8 (&qf)[QT][2], float (&mrun)[QT], float (&lrun)[QT], f32x4 (&oacc)[QT][4],
+                                          float scale_log2, int g, int c16)
+{
+    f32x4 s[QT][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int qi = 0; qi < QT; ++qi) s[qi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const bf16x8 kf = *reinterpret_cast<const bf16x8 *>(Ks + lds_off(kr + t * 16 + c16, g + 4 * ks));
+#pragma unroll
+            for (int qi = 0; qi < QT; ++qi)
+                s[qi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qi][ks], s[qi][t], 0, 0, 0);
+        }
+    }
+    // s[qi][t][r] = <K[kt*64 + 16t + 4g + r], Q[q0(qi) + c16]>
+    // Softmax of the tile on the VALU, which is what bounds this kernel (16 scores per lane, tile and query tile):
+    // the running maximum is kept on the RAW scores and the 1/sqrt(d)*log2(e) scale is folded into the exponent's fma;
+    // the per-key validity select runs only on a tile that has a masked key (normally just a row's last tile);
+    // fma / sum / rescale go through the packed-f32 pipe two elements at a time, exp2 is the bare v_exp_f32.
+    const bool full = vm == ~0ull;               // wave-uniform
+    const f32x2_t sc2 = {scale_log2, scale_log2};
+    bf16x8 pb[QT][2];
+#pragma unroll
+    for (int qi = 0; qi < QT; ++qi) {
+        float mloc = -INFINITY;
+        if (full) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                mloc = fmaxf(fmaxf(mloc, s[qi][t][0]), s[qi][t][1]);
+                mloc = fmaxf(fmaxf(mloc, s[qi][t][2]), s[qi][t][3]);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool ok = (vm >> (16 * t + 4 * g + r)) & 1ull;
+                    const float v = ok ? s[qi][t][r] : -INFINITY;
+                    s[qi][t][r] = v;
+                    mloc = fmaxf(mloc, v);
+                }
+        }
+        mloc = join32<false>(join16<false>(mloc));
+        const float mnew = fmaxf(mrun[qi], mloc);  // raw-score maximum; finite: vm != 0 guarantees a valid key in this tile
+        const float alpha = __builtin_amdgcn_exp2f((mrun[qi] - mnew) * scale_log2);   // first tile: 2^-inf = 0
+        const float nb = -mnew * scale_log2;
+        const f32x2_t nb2 = {nb, nb};
+        f32x2_t ps2 = {0.f, 0.f};
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            u32x4 pk;
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {         // elements 2*j2, 2*j2+1 of this half: accumulator t = 2*s2 + (j2 >> 1)
+                const f32x4 sv = s[qi][2 * s2 + (j2 >> 1)];
+                const f32x2_t raw = (j2 & 1) ? f32x2_t{sv[2], sv[3]} : f32x2_t{sv[0], sv[1]};
+                const f32x2_t e = __builtin_elementwise_fma(raw, sc2, nb2);   // masked: -inf * scale + nb = -inf -> p = 0
+                const f32x2_t pj = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
+                ps2 += pj;
+                pk[j2] = pack2(pj.x, pj.y);
+            }
+            pb[qi][s2] = __builtin_bit_cast(bf16x8, pk);
+        }
+        float psum = ps2.x + ps2.y;
+        psum = join32<true>(join16<true>(psum));
+        lrun[qi] = lrun[qi] * alpha + psum;
+        mrun[qi] = mnew;
+        const f32x2_t al2 = {alpha, alpha};
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const f32x2_t lo = f32x2_t{oacc[qi][dt][0], oacc[qi][dt][1]} * al2, hi = f32x2_t{oacc[qi][dt][2], oacc[qi][dt][3]} * al2;
+            oacc[qi][dt] = f32x4{lo.x, lo.y, hi.x, hi.y};
+        }
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            // V^T fragment: keys {32*s2 + 4g + 0..3} and {32*s2 + 16 + 4g + 0..3} of d = 16*dt + c16, fetched by the
+            // transposing LDS read: lane 4q+p of each 16-lane group addresses row (key0 + q), 8 bytes at d-offset 4p
+            const int qq = c16 >> 2, pp = c16 & 3;
+            const int k0 = kr + 32 * s2 + 4 * g + qq;
+            const int off0 = lds_off(k0, 2 * dt + (pp >> 1)) + 8 * (pp & 1);
+            const int off1 = lds_off(k0 + 16, 2 * dt + (pp >> 1)) + 8 * (pp & 1);
+            const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (__attribute__((address_space(3))) s16x4 *)(Vs + off0));
+            const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (__attribute__((address_space(3))) s16x4 *)(Vs + off1));
+            typedef __attribute__((ext_vector_type(8))) short s16x8;
+            const s16x8 va = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+#pragma unroll
+            for (int qi = 0; qi < QT; ++qi)
+                oacc[qi][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, va), pb[qi][s2], oacc[qi][dt], 0, 0, 0);
+        }
+    }
+}
+
 // grid = (H, B), block = NW*64.  qkv bf16 [B*L][3*H*64] (q | k | v thirds, head-major inside a third); out bf16 [B*L][H*64].
-// Dynamic LDS: K image [L][64] then V image [L][64], both 128-B rows with the chunk XOR of lds_off().
+// Dynamic LDS: K image [L][64] then V image [L][64], both 128-B rows with the chunk XOR of lds_off().  Rows of up to 512
+// tokens (the images of 1024 keys would need 256 KB of LDS; longer rows go to k_attn_long).
 template <int NW, int QT>
 __global__ __launch_bounds__(NW * 64) void k_attn(const bf16_t *__restrict__ qkv, const unsigned long long *__restrict__ kmask,
                                                   bf16_t *__restrict__ out, int Lpad, int H, float scale_log2,
@@ -999,6 +1108,123 @@ __global__ __launch_bounds__(NW * 64) void k_attn(const bf16_t *__restrict__ qkv
                 *reinterpret_cast<u32x2 *>(orow + dt * 16 + 4 * g) = o;
             }
         }
+    }
+}
+
+// Rows of 513..1024 tokens.  The K and V images of a whole row (256 B per key, 256 KB at 1024 keys) do not fit a CU's 160 KB
+// of LDS, so K/V stream through LDS in windows of kLongWin keys, double-buffered (2 x 64 KB), and each (row, head) is split
+// over S = ceil(tiles / NW) workgroups along the query axis: wave w of split s owns query tile s*NW + w and keeps its softmax
+// state (running max, sum, output) in registers for the whole row.  The next window's K/V come from global memory into
+// registers while the current one is consumed, and go to the other buffer behind it: one barrier per window.
+// The key tiles of a query tile go through attn_tile one by one in key order, as in k_attn: same bits for the same row.
+// grid: one workgroup per (row, head, split), numbered so that the S splits of a (row, head) have the same id mod 8 -- the
+// same XCD, whose L2 serves the K/V images to all of them -- and are dispatched next to each other:
+//   id = ((p >> 3) * S + s) * 8 + (p & 7),  p = b * H + h.
+constexpr int kLongWin = 256;
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void k_attn_long(const bf16_t *__restrict__ qkv, const unsigned long long *__restrict__ kmask,
+                                                       bf16_t *__restrict__ out, int Lpad, int H, int B, int S, float scale_log2,
+                                                       const int32_t *__restrict__ row_off, int T)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char kv[];     // [2][K image kLongWin x 128 B | V image kLongWin x 128 B]
+    const int id = blockIdx.x;
+    const int xcd = id & 7, j = id >> 3;
+    const int s = j % S, p = (j / S) * 8 + xcd;
+    if (p >= B * H) return;
+    const int h = p % H, b = p / H;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, c16 = lane & 15;
+    const int ld = 3 * H * 64;
+    int64_t r0s = (int64_t)b * Lpad;
+    int L = Lpad;
+    if (row_off) packed_row(row_off, b, T, Lpad, r0s, L);   // (clamped to the T tokens of the buffers, whatever row_off holds)
+    const size_t r0 = (size_t)r0s;
+    const int q0 = (s * NW + wave) * 16;             // this wave's query tile
+    if (s * NW * 16 >= L) return;                    // a split past the row's end (packed rows): nothing to store
+    const int nkt = (Lpad + 63) >> 6;
+    const unsigned long long *km = kmask + (size_t)b * nkt;
+    const size_t last_row = (row_off ? (size_t)T : (size_t)B * Lpad) - 1;
+
+    int last = -1;
+    for (int t = 0; t < nkt; ++t)
+        if (km[t] != 0ull) last = t;
+    const int Lk = (last + 1) * 64;
+    const bool live = q0 < L && q0 < Lk;              // wave-uniform
+    bf16_t *orow = out + (r0 + q0 + c16) * (H * 64) + h * 64;
+    const bool store = q0 < L && q0 + c16 < L;        // (a row of the NEXT packed row is computed, never stored)
+    if (s * NW * 16 >= Lk) {                         // no live tile in this split: rows past the last valid key are zeros
+        if (store) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<u32x2 *>(orow + dt * 16 + 4 * g) = u32x2{0u, 0u};
+        }
+        return;
+    }
+
+    bf16x8 qf[1][2];
+    float mrun[1] = {-INFINITY}, lrun[1] = {0.f};
+    f32x4 oacc[1][4];
+    {
+        size_t qr = r0 + (live ? q0 + c16 : 0);
+        qr = qr < last_row ? qr : last_row;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) qf[0][ks] = *reinterpret_cast<const bf16x8 *>(qkv + qr * ld + h * 64 + 32 * ks + 8 * g);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) oacc[0][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    // staging: window key r (0 <= r < kLongWin), chunk c; NW * 64 threads move kLongWin * 8 chunks of K and of V
+    constexpr int kPer = kLongWin * 8 / (NW * 64);
+    static_assert(kLongWin * 8 % (NW * 64) == 0, "whole staging rounds");
+    const bf16_t *hbase = qkv + h * 64;
+    u32x4 pkv[kPer][2];
+    auto fetch = [&](int w0) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int e = tid + i * NW * 64, r = e >> 3, c = e & 7;
+            size_t gr = r0 + w0 + r;                  // keys >= L belong to the next row (or nothing): loaded, never used
+            gr = gr < last_row ? gr : last_row;
+            if (w0 + r < Lk) {
+                pkv[i][0] = *reinterpret_cast<const u32x4 *>(hbase + gr * ld + H * 64 + c * 8);
+                pkv[i][1] = *reinterpret_cast<const u32x4 *>(hbase + gr * ld + 2 * H * 64 + c * 8);
+            }
+        }
+    };
+    auto put = [&](int w0, unsigned char *buf) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int e = tid + i * NW * 64, r = e >> 3, c = e & 7;
+            if (w0 + r < Lk) {
+                *reinterpret_cast<u32x4 *>(buf + lds_off(r, c)) = pkv[i][0];
+                *reinterpret_cast<u32x4 *>(buf + kLongWin * 128 + lds_off(r, c)) = pkv[i][1];
+            }
+        }
+    };
+    fetch(0);
+    put(0, kv);
+    __syncthreads();
+    for (int w0 = 0, cur = 0; w0 < Lk; w0 += kLongWin, cur ^= 1) {
+        const bool more = w0 + kLongWin < Lk;        // block-uniform
+        if (more) fetch(w0 + kLongWin);
+        if (live) {
+            const unsigned char *Ks = kv + cur * (2 * kLongWin * 128), *Vs = Ks + kLongWin * 128;
+            const int kt_end = min(w0 + kLongWin, Lk) >> 6;
+            for (int kt = w0 >> 6; kt < kt_end; ++kt) {
+                const unsigned long long vm = km[kt];
+                if (vm == 0ull) continue;
+                attn_tile<1>(Ks, Vs, kt * 64 - w0, vm, qf, mrun, lrun, oacc, scale_log2, g, c16);
+            }
+        }
+        if (more) put(w0 + kLongWin, kv + (cur ^ 1) * (2 * kLongWin * 128));   // (that buffer was last read before the previous barrier)
+        __syncthreads();
+    }
+    if (!store) return;
+    const float inv = (live && lrun[0] > 0.f) ? 1.f / lrun[0] : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        u32x2 o;
+        o.x = pack2(oacc[0][dt][0] * inv, oacc[0][dt][1] * inv);
+        o.y = pack2(oacc[0][dt][2] * inv, oacc[0][dt][3] * inv);
+        *reinterpret_cast<u32x2 *>(orow + dt * 16 + 4 * g) = o;
     }
 }
 
@@ -1568,10 +1794,23 @@ int crh_attn_fwd_packed(const void *qkv, const int32_t *row_off, const uint64_t 
 static int attn_launch(const void *qkv, const uint64_t *kmask, void *out, const int32_t *row_off, int B, int T, int L, int H, void *stream)
 {
     if (!qkv || !kmask || !out) return fail(CRH_E_INVALID, "attn: NULL pointer");
-    if (B <= 0 || H <= 0 || L <= 0 || L % 16 || L > 512) return fail(CRH_E_INVALID, "attn: B=%d L=%d H=%d (need L%%16==0, L<=512)", B, L, H);
+    if (B <= 0 || H <= 0 || L <= 0 || L % 16 || L > 1024) return fail(CRH_E_INVALID, "attn: B=%d L=%d H=%d (need L%%16==0, L<=1024)", B, L, H);
     const float scale_log2 = 0.125f * 1.4426950408889634f;  // 64^-1/2 * log2(e)
-    const size_t lds = (size_t)((L + 63) & ~63) * 256;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (L > 512) {           // rows of 513..1024 tokens: K/V streamed through LDS in windows, query tiles split over workgroups
+        constexpr int NW = 16;
+        const int S = (L / 16 + NW - 1) / NW;
+        const long long pairs8 = ((long long)B * H + 7) / 8 * 8;
+        if (pairs8 * S > 0x7fffffffLL) return fail(CRH_E_INVALID, "attn: B=%d H=%d: grid too large", B, H);
+        static OncePerDevice once;
+        if (once.need())
+            CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_long<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kLongWin * 256));
+        hipLaunchKernelGGL((k_attn_long<NW>), dim3((unsigned)(pairs8 * S)), dim3(NW * 64), 2 * kLongWin * 256, st, (const bf16_t *)qkv,
+                           (const unsigned long long *)kmask, (bf16_t *)out, L, H, B, S, scale_log2, row_off, T);
+        CRH_HIP(hipGetLastError());
+        return CRH_OK;
+    }
+    const size_t lds = (size_t)((L + 63) & ~63) * 256;
     // One 16-row query tile per wave at a time (101 VGPRs: 4-5 waves per SIMD) and as many waves per CU as the K/V images
     // allow: up to 320 tokens two 8-wave workgroups share a CU's 160 KB, beyond that one 16-wave workgroup.  The kernel is
     // bound by the softmax VALU, so what pays is many resident waves whose VALU, LDS and MFMA phases interleave -- measured

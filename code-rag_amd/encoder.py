@@ -148,10 +148,19 @@ class BpeTokenizer:
         return self._tok.convert_tokens_to_ids(self._tok.tokenize(text))
 
 
+def check_max_length(max_length) -> int:
+    """The token budget of a chunk, as ``UniXcoder.tokenize`` accepts it (``assert max_length < 1024``; the 1026-row position
+    table ends at 1024 tokens) and the four special tokens leave room for at least one body piece: 4 < max_length < 1024.
+    Checked where a call takes it, so a bad value is a ValueError there rather than a native error from the device path."""
+    if isinstance(max_length, bool) or not isinstance(max_length, (int, np.integer)) or not 4 < int(max_length) < 1024:
+        raise ValueError(f"max_length must be an integer with 4 < max_length < 1024, got {max_length!r}")
+    return int(max_length)
+
+
 def wrap_encoder_only(tok, text: str, max_length: int = 512) -> list[int]:
     """``UniXcoder.tokenize(mode="<encoder-only>")`` (unixcoder_provider.py:105-122): body truncated to
     ``max_length - 4`` pieces, wrapped as [<s>, <encoder-only>, </s>] + body + [</s>]."""
-    assert max_length < 1024
+    max_length = check_max_length(max_length)
     body = tok.encode_body(text)[: max_length - 4]
     return [tok.cls_id, tok.enc_only_id, tok.sep_id] + body + [tok.sep_id]
 
@@ -460,7 +469,8 @@ class HipUniXcoder:
         return out
 
     def embed_ids(self, id_lists, max_tokens: int = 65536):
-        """list of token-id lists (each <= 512) -> f32 CUDA tensor [n, 768] in input order."""
+        """list of token-id lists (each <= 1024; rows beyond 512 run the long-row attention kernel) -> f32 CUDA tensor [n, 768]
+        in input order."""
         n = len(id_lists)
         for x in id_lists:
             if len(x) == 0:
@@ -481,6 +491,7 @@ class HipUniXcoder:
         ``body_ids`` int32 [n, >= max_length - 4], ``body_lens`` the untruncated counts.  Rows are wrapped as
         [<s>, <encoder-only>, </s>] + body[: max_length - 4] + [</s>] (unixcoder_provider.py:105-122) while being packed into
         the batch arrays -- no per-token Python work."""
+        max_length = check_max_length(max_length)
         tok = self.tok
         n = int(body_lens.shape[0])
         blen = np.minimum(body_lens.astype(np.int64), max_length - 4)
@@ -510,6 +521,7 @@ class HipUniXcoder:
         tokenizer (its own threads, GIL released) works on chunk i+1 and the float-list conversion on chunk i-1 while the GPU
         runs chunk i; results come back through a side stream into pinned memory.  (Sequentially the host stages were a third
         of the call: 20 k texts took 1.22 s of which the forward 0.8.)"""
+        max_length = check_max_length(max_length)
         if not texts:
             return np.zeros((0, self.cfg.hidden_size), np.float32) if rows == "array" else []
         texts = list(texts)

@@ -112,11 +112,13 @@ class HipUniXcoderProvider(BaseEmbeddingProvider):
     """UniXcoder embeddings from the MI355X HIP encoder.  ``model`` may be a local checkpoint directory
     (``config.json`` + weights + ``vocab.json``/``merges.txt``); the hub name ``microsoft/unixcoder-base`` cannot be
     fetched offline, in which case ``CODERAG_HIP_WEIGHTS`` must point at a local copy, or
-    ``extra={"synthetic_weights": seed}`` selects seeded random weights with the hashing tokenizer (benchmarks/tests)."""
+    ``extra={"synthetic_weights": seed}`` selects seeded random weights with the hashing tokenizer (benchmarks/tests).
+    ``max_length`` (tokens per chunk, specials included; 4 < max_length < 1024, default 512 as in the reference) comes from the
+    argument, else from ``extra["max_length"]`` -- so a provider built by the factory can be configured -- else 512."""
 
     EMBEDDING_DIM = 768
 
-    def __init__(self, config: ProviderConfig | None = None, max_length: int = 512):
+    def __init__(self, config: ProviderConfig | None = None, max_length: int | None = None):
         try:
             import torch  # noqa: F401
         except ImportError as e:  # unixcoder_provider.py:245-249
@@ -124,7 +126,8 @@ class HipUniXcoderProvider(BaseEmbeddingProvider):
         if config is None:
             config = ProviderConfig(provider="unixcoder-hip", model="microsoft/unixcoder-base")
         super().__init__(config)
-        self.max_length = max_length
+        from .encoder import check_max_length
+        self.max_length = check_max_length(max_length if max_length is not None else config.extra.get("max_length", 512))
         self._executor = ThreadPoolExecutor(max_workers=1, thread_name_prefix="hip-unixcoder")
         self._model = None
         # cross-call dynamic batching: concurrent _embed_impl calls -- the orchestrator indexes 3

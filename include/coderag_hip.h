@@ -330,7 +330,9 @@ int crh_layernorm_apply(const void *x, const float *row_stats, const float *gamm
 /* Bidirectional self-attention with key masking.  qkv [B*L, 3*H*64] bf16 exactly as the QKV GEMM writes it
  * (q | k | v thirds, head-major inside each), out [B*L, H*64] bf16.  kmask: uint64 [B, ceil(L/64)], bit j of word t
  * set when token 64t+j of the row is a real token (ids != pad) -- the reference's `mask` (unixcoder_provider.py:148).
- * L % 16 == 0 (padding granularity of a length bucket), L <= 512. */
+ * L % 16 == 0 (padding granularity of a length bucket), L <= 1024.  Rows of up to 512 tokens run k_attn (a row's K/V staged
+ * whole in LDS); 513..1024 run k_attn_long (K/V streamed through LDS in 256-key windows), which gives a row that would fit
+ * k_attn the same bits as k_attn does. */
 int crh_attn_fwd_varlen(const void *qkv, const uint64_t *kmask, void *out, int B, int L, int H, void *stream);
 
 /* out[b, t, :] = LN((word[ids[b,t]] + type[0]) + pos[pos_id]); pos_id = cumsum(ids != pad) * (ids != pad) + pad.
@@ -347,7 +349,8 @@ int crh_masked_mean_pool(const void *tok, const uint64_t *kmask, float *sent, in
 
 /* Packed rows: the same three kernels on a batch WITHOUT padding.  Row b of the batch is the tokens
  * [row_off[b], row_off[b+1]) of one flat token axis of T tokens (ids int32 [T], activations [T, ...]); Lmax (a multiple of
- * 16, >= every row's length, <= 512) sizes the key-mask stride (ceil(Lmax/64) words per row) and the launch.  The GEMM /
+ * 16, >= every row's length, <= 1024) sizes the key-mask stride (ceil(Lmax/64) words per row) and the launch (Lmax > 512:
+ * the long-row attention kernel, the same bits for every row).  The GEMM /
  * LayerNorm entry points above take T tokens as they are.  What it buys: the padded form rounds every row up to its bucket's
  * length (a multiple of 16) -- ~4 % of the tokens of a mean-200 mix -- and every kernel of the forward pays for them.
  * row_off lives on the device, so the library cannot look at it when a call is made: every kernel CLAMPS what it reads from
