@@ -39,10 +39,23 @@ constexpr int kI8Ring = CRH_I8_RING;
 constexpr int kI8SelectParts = 4;   // workgroups per query in k_select behind the int8 scan (64 queries x 4 = the chip)
 constexpr int kStatusSlots = 1024;
 constexpr int64_t kWorkspaceBudget = 48LL << 30;
+constexpr int kSparseDen = 4;   // the sparse route is taken from 1 populated tile in this many down (profiles/sparse_crossover.md)
+
+// A filter in the form the index keeps, compares and uploads: [n conditions, then per condition: column, negate, set size,
+// the set's codes ascending without repeats].  crh_filter lists and crh_condition lists both become one of these.
+using FilterKey = std::vector<int32_t>;
+
+// what build_mask hands a search: the row mask, and -- while the sparse route is enabled -- the ascending list of the tiles
+// whose mask word is not 0 (nlist < 0: no list was made)
+struct MaskRef {
+    const uint32_t *mask = nullptr;
+    const uint32_t *list = nullptr;
+    int64_t nlist = -1;
+};
 
 struct Pending {
-    int nq, k, nfilt;
-    crh_filter filt[CRH_MAX_FILTERS];
+    int nq, k;
+    FilterKey key;
     int64_t row_base;
     const float *q_dev;
     float *out_s;
@@ -90,8 +103,16 @@ struct crh_index {
     // language: query/vector_search.py:83-93), and rebuilding the mask is a pass over the code columns per batch (~20 us at 10M rows).
     uint64_t mutations = 1, mask_built_at = 0;
     hipStream_t mask_stream = nullptr;   // (the stream the kept mask was built on: another stream rebuilds it -- nothing orders the two)
-    int mask_nfilt = -1;
-    crh_filter mask_filt[CRH_MAX_FILTERS];
+    bool mask_valid = false;
+    FilterKey mask_key;                  // (also the host source of the sets' upload)
+    int32_t *mask_sets = nullptr;        // device copy of mask_key: the sets k_filter_mask searches
+    int64_t mask_sets_cap = 0;
+    // The sparse route: a filtered batch of <= batch_q queries whose mask leaves at most 1 tile in
+    // sparse_den populated walks the list of those tiles with k_scan_list instead of streaming every tile.  The list is made
+    // with the mask and kept with it.  crh_index_set_sparse_route / CODERAG_HIP_SPARSE=0, CODERAG_HIP_SPARSE_DEN.
+    bool sparse_on = true;
+    int sparse_den = kSparseDen;
+    int64_t mask_nlist = -1;
     u32x4 *xt = nullptr;
     float *xf32 = nullptr;
     uint32_t *alive = nullptr;
@@ -108,6 +129,7 @@ struct crh_index {
         float *qn = nullptr, *gmax = nullptr, *tau = nullptr, *qpar = nullptr, *qlo = nullptr;
         u32x4 *qfrag = nullptr, *qfrag8 = nullptr, *wave_lists = nullptr, *shi = nullptr;
         uint32_t *effmask = nullptr;
+        uint32_t *tilelist = nullptr;   // [cap_tiles] the populated tiles of effmask, [ceil(cap_tiles / 256)] workgroup counts, [1] the list's length
         u32x2 *qlist = nullptr;
         unsigned long long *skeys = nullptr, *skeys2 = nullptr;
     };
@@ -201,9 +223,11 @@ int ensure_workspace(crh_index *h, crh_index::Workspace &w, int wave_cap, int qc
     }
     if (w.ws_mask_tiles < h->cap_tiles) {
         dev_free(w.effmask);
+        dev_free(w.tilelist);
         w.ws_mask_tiles = 0;
         h->mask_built_at = 0;
         CRH_TRY(dev_alloc(&w.effmask, h->cap_tiles));
+        CRH_TRY(dev_alloc(&w.tilelist, h->cap_tiles + ceil_div(h->cap_tiles, 256) + 1));
         w.ws_mask_tiles = h->cap_tiles;
     }
     if (w.ws_blocks != blocks || w.ws_wave_cap != wave_cap) {
@@ -247,34 +271,113 @@ __global__ void k_fill_pad(float *s, int64_t *r, int64_t n)
     }
 }
 
-int build_mask(crh_index *h, crh_index::Workspace &w, const crh_filter *filters, int nfilt, const uint32_t **mask_out, hipStream_t st)
+// crh_filter list -> key: one-element "in" sets (the code is taken as it is: an equality, -1 included)
+void key_from_filters(const crh_filter *filters, int nfilt, FilterKey &key)
 {
+    key.assign(1, nfilt);
+    for (int f = 0; f < nfilt; ++f) {
+        const int32_t c[4] = {filters[f].col, 0, 1, filters[f].code};
+        key.insert(key.end(), c, c + 4);
+    }
+}
+
+// crh_condition list -> key: arguments checked, every set sorted, repeats and negative codes dropped (no row's code is a
+// negative member: -1 means "key absent", which is in no set)
+int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_conds, bool need_one, FilterKey &key)
+{
+    if (n_conds < (need_one ? 1 : 0) || n_conds > CRH_MAX_FILTERS)
+        return fail(CRH_E_INVALID, "n_conds=%d outside %d..%d%s", n_conds, need_one ? 1 : 0, CRH_MAX_FILTERS, need_one ? " (a delete needs a filter)" : "");
+    if (n_conds > 0 && !conds) return fail(CRH_E_INVALID, "conds is NULL");
+    key.assign(1, n_conds);
+    int64_t total = 0;
+    for (int f = 0; f < n_conds; ++f) {
+        const crh_condition &c = conds[f];
+        if (c.col < 0 || c.col >= h->ncols) return fail(CRH_E_INVALID, "condition %d: column %d out of range (index has %d code columns)", f, c.col, h->ncols);
+        if (c.n < 0) return fail(CRH_E_INVALID, "condition %d: set size %lld is negative", f, (long long)c.n);
+        if (c.n > 0 && !c.codes) return fail(CRH_E_INVALID, "condition %d: codes is NULL with n=%lld", f, (long long)c.n);
+        total += c.n;
+        if (total > (1LL << 28)) return fail(CRH_E_CAPACITY, "the sets of one filter hold more than 2^28 codes");
+        std::vector<int32_t> v;
+        v.reserve((size_t)c.n);
+        for (int64_t i = 0; i < c.n; ++i)
+            if (c.codes[i] >= 0) v.push_back(c.codes[i]);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        const int32_t head[3] = {c.col, c.negate ? 1 : 0, (int32_t)v.size()};
+        key.insert(key.end(), head, head + 3);
+        key.insert(key.end(), v.begin(), v.end());
+    }
+    return CRH_OK;
+}
+
+int build_mask(crh_index *h, crh_index::Workspace &w, const FilterKey &key, MaskRef *out, hipStream_t st)
+{
+    *out = MaskRef{};
+    const int nfilt = key.empty() ? 0 : key[0];
     if (nfilt == 0 || h->count == 0) {   // (an empty index: nothing to mask, and a zero-block launch is an error)
-        *mask_out = h->alive;
+        out->mask = h->alive;
         return CRH_OK;
     }
     FilterSet fs;
     fs.n = nfilt;
-    for (int f = 0; f < nfilt; ++f) {
-        if (filters[f].col < 0 || filters[f].col >= h->ncols)
-            return fail(CRH_E_INVALID, "filter column %d out of range (index has %d code columns)", filters[f].col, h->ncols);
-        fs.col[f] = filters[f].col;
-        fs.code[f] = filters[f].code;
+    bool sets = false;
+    for (size_t at = 1, f = 0; f < (size_t)nfilt; ++f) {
+        if (key[at] < 0 || key[at] >= h->ncols)
+            return fail(CRH_E_INVALID, "filter column %d out of range (index has %d code columns)", key[at], h->ncols);
+        fs.col[f] = key[at];
+        fs.neg[f] = key[at + 1];
+        fs.cnt[f] = key[at + 2];
+        fs.off[f] = (int)at + 3;
+        fs.one[f] = fs.cnt[f] == 1 ? key[at + 3] : 0;
+        sets = sets || fs.cnt[f] > 1;
+        at += 3 + (size_t)fs.cnt[f];
     }
-    const bool same = h->mask_built_at == h->mutations && h->mask_stream == st && h->mask_nfilt == nfilt &&
-                      memcmp(h->mask_filt, filters, sizeof(crh_filter) * (size_t)nfilt) == 0;
+    const bool same = h->mask_valid && h->mask_built_at == h->mutations && h->mask_stream == st && h->mask_key == key &&
+                      (h->mask_nlist >= 0) == h->sparse_on;
     if (!same) {
+        h->mask_valid = false;
+        h->mask_key = key;
+        if (sets) {   // the device copy of the key: fs.off are positions in it
+            if (h->mask_sets_cap < (int64_t)key.size()) {
+                dev_free(h->mask_sets);
+                h->mask_sets_cap = 0;
+                CRH_TRY(dev_alloc(&h->mask_sets, (int64_t)key.size()));
+                h->mask_sets_cap = (int64_t)key.size();
+            }
+            CRH_HIP(hipMemcpyAsync(h->mask_sets, h->mask_key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
+        }
         const int64_t rows = (h->count + 63) & ~63LL;
         hipLaunchKernelGGL(k_filter_mask, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, h->alive, h->codes, h->cap_rows,
-                           h->count, fs, w.effmask);
+                           h->count, fs, h->mask_sets, w.effmask);
         CRH_HIP(hipGetLastError());
+        h->mask_nlist = -1;
+        if (h->sparse_on) {
+            // the populated tiles, in order; their number decides the route, so the host waits for it -- once per mask, not per batch
+            const int64_t ntiles = ceil_div(h->count, kTileRows);
+            const unsigned nb = (unsigned)ceil_div(ntiles, 256);
+            uint32_t *blockcnt = w.tilelist + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
+            hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, w.effmask, ntiles, blockcnt);
+            hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, w.effmask, ntiles, blockcnt, w.tilelist, len);
+            CRH_HIP(hipGetLastError());
+            uint32_t n = 0;
+            CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipStreamSynchronize(st));
+            h->mask_nlist = n;
+        }
         h->mask_built_at = h->mutations;
         h->mask_stream = st;
-        h->mask_nfilt = nfilt;
-        memcpy(h->mask_filt, filters, sizeof(crh_filter) * (size_t)nfilt);
+        h->mask_valid = true;
     }
-    *mask_out = w.effmask;
+    out->mask = w.effmask;
+    out->list = w.tilelist;
+    out->nlist = h->mask_nlist;
     return CRH_OK;
+}
+
+// does a batch of nq queries under this mask take the sparse route?
+bool sparse_use(const crh_index *h, const MaskRef &m, int nq)
+{
+    return h->sparse_on && m.nlist >= 0 && nq <= h->batch_q && m.nlist * h->sparse_den <= ceil_div(h->count, kTileRows);
 }
 
 // scan kernel instantiations: k-steps = dim / 16; 64 queries per pass except for dim 1536 (32: LDS)
@@ -293,6 +396,26 @@ int launch_scan(crh_index *h, crh_index::Workspace &w, int blocks, hipStream_t s
     default: return fail(CRH_E_INTERNAL, "no scan kernel for %d k-steps", h->ksteps);
     }
 #undef CRH_SCAN
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+// the same walk over a list of tiles (the sparse route): every dim the index supports
+template <int MODE>
+int launch_scan_list(crh_index *h, crh_index::Workspace &w, int blocks, hipStream_t st, const MaskRef &m, int nitems, int stride, int wave_cap, int qcap,
+                     SearchStatus *stt)
+{
+#define CRH_SCAN_LIST(KS, QB)                                                                                                       \
+    hipLaunchKernelGGL((k_scan_list<KS, MODE, kWaves, kRing, QB>), dim3(blocks), dim3(kWaves * 64), 0, st, h->xt, w.qfrag, w.tau, \
+                       m.mask, m.list, nitems, stride, w.gmax, w.wave_lists, wave_cap, stt->qcount, w.qlist, qcap, stt)
+    switch (h->ksteps) {
+    case 24: CRH_SCAN_LIST(24, 2); break;
+    case 48: CRH_SCAN_LIST(48, 2); break;
+    case 64: CRH_SCAN_LIST(64, 2); break;
+    case 96: CRH_SCAN_LIST(96, 1); break;
+    default: return fail(CRH_E_INTERNAL, "no list scan kernel for %d k-steps", h->ksteps);
+    }
+#undef CRH_SCAN_LIST
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }
@@ -428,12 +551,21 @@ int launch_scan_wide(crh_index *h, crh_index::Workspace &w, hipStream_t st, cons
 }
 
 // one batch (<= batch_q queries through k_scan, or up to kWideQ through k_scan_wide), everything enqueued on `st`
-int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int nq, int k, const uint32_t *mask, int64_t row_base, float *out_s,
+int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int nq, int k, const MaskRef &mref, int64_t row_base, float *out_s,
                   int64_t *out_r, int slot, hipStream_t st, int *path_out)
 {
     *path_out = CRH_NOMINATE_BF16_3;
+    const uint32_t *mask = mref.mask;
     const int64_t ntiles = ceil_div(h->count, kTileRows);
-    if (ntiles == 0) {
+    const bool sparse = ntiles > 0 && sparse_use(h, mref, nq);
+    if (ntiles == 0 || (sparse && mref.nlist == 0)) {   // (no row can match: the padding the scans would arrive at)
+        if (sparse) {
+            h->stats.batches += 1;
+            if (h->profiling) {   // (finish_pending reads the pair of every batch)
+                CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+                CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+            }
+        }
         CRH_HIP(hipMemsetAsync(h->status + slot, 0, sizeof(SearchStatus), st));
         const int64_t n = (int64_t)nq * k;
         hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out_s, out_r, n);
@@ -448,6 +580,38 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
     const int nblk = (nq + 31) / 32;                       // 32-query blocks in use (wide scan)
     const int width = wide ? nblk * 32 : h->batch_q;       // query slots prepared (slots >= nq are zero queries, tau = +inf)
     const int qstride = wide ? kWideQ : 64;                // row pitch of the seed maxima
+
+    // The sparse route: the mask leaves few tiles populated -- the three-launch bf16 scan over the LIST of those tiles
+    // (k_scan_list), thresholds seeded from listed tiles only; k_select as behind every bf16 scan, so ids and score bits are
+    // what the dense route gives.  It reads nlist tiles instead of ntiles; the int8 copy is not needed at that size.
+    if (sparse) {
+        if (h->dtype == CRH_DTYPE_BF16)
+            hipLaunchKernelGGL((k_prep_queries<true, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
+        else
+            hipLaunchKernelGGL((k_prep_queries<false, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
+        CRH_HIP(hipGetLastError());
+        const int nlist = (int)mref.nlist;
+        const int G = (int)std::min<int64_t>(h->seed_tiles, nlist);
+        const int stride = nlist / G;   // (G * stride <= nlist: every sample position is inside the list)
+        CRH_TRY(launch_scan_list<0>(h, w, scan_blocks(h, G), st, mref, G, stride, wave_cap, qcap, stt));
+        hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, qstride);
+        CRH_HIP(hipGetLastError());
+        if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+        CRH_TRY(launch_scan_list<1>(h, w, scan_blocks(h, nlist), st, mref, nlist, 1, wave_cap, qcap, stt));
+        if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+        if (h->dtype == CRH_DTYPE_F32)
+            hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+        else
+            hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+        CRH_HIP(hipGetLastError());
+        h->stats.rows += std::min<int64_t>(h->count, (int64_t)nlist * kTileRows);
+        h->stats.tiles += nlist;
+        h->stats.seed_tiles += G;
+        h->stats.batches += 1;
+        return CRH_OK;
+    }
 
     // <= batch_q queries, nominated from the int8 copy (crh_i8.hpp): half the bytes of the pass, same results
     if (i8_use(h, nq, k)) {
@@ -651,8 +815,8 @@ int finish_pending(crh_index *h, hipStream_t st)
                 qc = std::max(qc, next_pow2((int64_t)s.max_qcount));
             }
             CRH_TRY(ensure_workspace(h, w, wc, qc));
-            const uint32_t *mask = nullptr;
-            CRH_TRY(build_mask(h, w, p.filt, p.nfilt, &mask, st));
+            MaskRef mask;
+            CRH_TRY(build_mask(h, w, p.key, &mask, st));
             h->i8_suppress = no_i8;
             const int rc = enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, 0, st, &path);
             h->i8_suppress = false;
@@ -735,6 +899,8 @@ int crh_index_create(int dim, int dtype, int64_t capacity_rows, int n_code_cols,
             h->i8_sample_auto = false;
         }
         if (const char *er = getenv("CODERAG_HIP_ROWMAJOR")) h->want_xrow = er[0] != '0';
+        if (const char *ep = getenv("CODERAG_HIP_SPARSE")) h->sparse_on = ep[0] != '0';
+        if (const char *ed = getenv("CODERAG_HIP_SPARSE_DEN")) h->sparse_den = std::max(1, atoi(ed));
     }
     h->dtype = dtype;
     h->ncols = n_code_cols;
@@ -772,6 +938,7 @@ int crh_index_destroy(crh_index *h)
     dev_free(h->alive);
     dev_free(h->codes);
     dev_free(h->scratch_u32);
+    dev_free(h->mask_sets);
     {
         crh_index::Workspace &w = h->ws;
         dev_free(w.qn);
@@ -780,6 +947,7 @@ int crh_index_destroy(crh_index *h)
         dev_free(w.qfrag);
         dev_free(w.wave_lists);
         dev_free(w.effmask);
+        dev_free(w.tilelist);
         dev_free(w.qlist);
         dev_free(w.skeys);
         dev_free(w.qfrag8);
@@ -890,21 +1058,17 @@ int crh_index_tombstone(crh_index *h, int64_t n, const int64_t *rows)
     return CRH_OK;
 }
 
-int crh_index_tombstone_filter(crh_index *h, const crh_filter *filters, int n_filters, int64_t *n_cleared_out)
+static int tombstone_key(crh_index *h, const FilterKey &key, int64_t *n_cleared_out)
 {
-    if (!h) return fail(CRH_E_INVALID, "index is NULL");
-    if (n_cleared_out) *n_cleared_out = 0;
-    if (n_filters <= 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 1..%d (a delete needs a filter)", n_filters, CRH_MAX_FILTERS);
-    if (!filters) return fail(CRH_E_INVALID, "filters is NULL");
     if (h->count == 0) return CRH_OK;
     DeviceGuard g(h->device);
     CRH_HIP(hipDeviceSynchronize());   // searches in flight on other streams read `alive` / the shared mask buffer
     CRH_TRY(ensure_workspace0(h));
-    const uint32_t *mask = nullptr;
-    CRH_TRY(build_mask(h, h->ws, filters, n_filters, &mask, nullptr));
+    MaskRef m;
+    CRH_TRY(build_mask(h, h->ws, key, &m, nullptr));
     const int64_t ntiles = ceil_div(h->count, 32);
     CRH_HIP(hipMemset(h->scratch_u32, 0, 4));
-    hipLaunchKernelGGL(k_tombstone_mask, dim3((unsigned)ceil_div(ntiles, 256)), dim3(256), 0, 0, h->alive, mask, ntiles, h->scratch_u32);
+    hipLaunchKernelGGL(k_tombstone_mask, dim3((unsigned)ceil_div(ntiles, 256)), dim3(256), 0, 0, h->alive, m.mask, ntiles, h->scratch_u32);
     CRH_HIP(hipGetLastError());
     unsigned int cleared = 0;
     CRH_HIP(hipMemcpy(&cleared, h->scratch_u32, 4, hipMemcpyDeviceToHost));
@@ -912,6 +1076,26 @@ int crh_index_tombstone_filter(crh_index *h, const crh_filter *filters, int n_fi
     h->mutations += 1;
     if (n_cleared_out) *n_cleared_out = cleared;
     return CRH_OK;
+}
+
+int crh_index_tombstone_filter(crh_index *h, const crh_filter *filters, int n_filters, int64_t *n_cleared_out)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (n_cleared_out) *n_cleared_out = 0;
+    if (n_filters <= 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 1..%d (a delete needs a filter)", n_filters, CRH_MAX_FILTERS);
+    if (!filters) return fail(CRH_E_INVALID, "filters is NULL");
+    FilterKey key;
+    key_from_filters(filters, n_filters, key);
+    return tombstone_key(h, key, n_cleared_out);
+}
+
+int crh_index_tombstone_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t *n_cleared_out)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (n_cleared_out) *n_cleared_out = 0;
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, true, key));
+    return tombstone_key(h, key, n_cleared_out);
 }
 
 int crh_index_compact(crh_index *h, int64_t *old_to_new_host, int64_t *rows_after)
@@ -1182,9 +1366,7 @@ int crh_debug_read_ceiling(crh_index *h, void *stream)
     if (ntiles == 0) return CRH_OK;
     CRH_TRY(ensure_workspace0(h));
     crh_index::Workspace &w = h->ws;
-    const uint32_t *mask = nullptr;
-    CRH_TRY(build_mask(h, w, nullptr, 0, &mask, static_cast<hipStream_t>(stream)));
-    return launch_scan<2>(h, w, scan_blocks(h, ntiles), static_cast<hipStream_t>(stream), mask, (int)ntiles, 1, w.ws_wave_cap, w.ws_qcap, h->status);
+    return launch_scan<2>(h, w, scan_blocks(h, ntiles), static_cast<hipStream_t>(stream), h->alive, (int)ntiles, 1, w.ws_wave_cap, w.ws_qcap, h->status);
 }
 
 // Moves the int8 copy to a fresh allocation (the new one is taken BEFORE the old one is released, so it lands elsewhere): the
@@ -1250,16 +1432,9 @@ int crh_index_set_tuning(crh_index *h, int seed_tiles, int wave_cand_cap, int qu
     return CRH_OK;
 }
 
-int crh_search(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const crh_filter *filters, int n_filters,
-               int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+static int search_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &key, int64_t row_base,
+                      float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
 {
-    if (!h) return fail(CRH_E_INVALID, "index is NULL");
-    if (nq < 0) return fail(CRH_E_INVALID, "nq < 0");
-    if (nq == 0) return CRH_OK;
-    if (!queries || !out_scores || !out_rows) return fail(CRH_E_INVALID, "NULL query or output pointer");
-    if (k <= 0 || k > CRH_MAX_K) return fail(CRH_E_CAPACITY, "k=%d outside 1..%d", k, CRH_MAX_K);
-    if (n_filters < 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 0..%d", n_filters, CRH_MAX_FILTERS);
-    if (n_filters > 0 && !filters) return fail(CRH_E_INVALID, "filters is NULL");
     DeviceGuard g(h->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
 
@@ -1311,24 +1486,25 @@ int crh_search(crh_index *h, int nq, const float *queries, int queries_on_device
     // more than one k_scan pass worth of queries: up to kWideQ of them share ONE corpus pass through k_scan_wide
     for (int q0 = 0, b = 0; q0 < nq; q0 += b) {
         const int left = nq - q0;
+        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
+        crh_index::Workspace &w = h->ws;
+        MaskRef mask;
+        // (the filter mask lives in the workspace: stream order puts its rebuild behind the previous batch's scan)
+        CRH_TRY(build_mask(h, w, key, &mask, st));
         b = (h->wide_ok && left > h->batch_q) ? std::min(kWideQ, left) : std::min(h->batch_q, left);
         // up to two passes over the int8 copy (2 x ~1.55 ms at 10M rows) beat one wide pass over the bf16 tiles (~4.2 ms)
         if (left > h->batch_q && left <= 2 * h->batch_q && h->count > 0 && i8_use(h, h->batch_q, k)) b = h->batch_q;
-        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
-        crh_index::Workspace &w = h->ws;
+        // a mask sparse enough for the list scan: batch_q queries per pass over the few listed tiles, however many there are
+        if (h->count > 0 && sparse_use(h, mask, h->batch_q)) b = std::min(h->batch_q, left);
         Pending p{};
         p.nq = b;
         p.k = k;
-        p.nfilt = n_filters;
-        for (int f = 0; f < n_filters; ++f) p.filt[f] = filters[f];
+        p.key = key;
         p.row_base = row_base;
         p.q_dev = q_dev + (int64_t)q0 * h->dim;
         p.out_s = os + (int64_t)q0 * k;
         p.out_r = orow + (int64_t)q0 * k;
         p.slot = h->next_slot++;
-        const uint32_t *mask = nullptr;
-        // (the filter mask lives in the workspace: stream order puts its rebuild behind the previous batch's scan)
-        CRH_TRY(build_mask(h, w, filters, n_filters, &mask, st));
         CRH_TRY(enqueue_batch(h, w, p.q_dev, b, k, mask, row_base, p.out_s, p.out_r, p.slot, st, &p.path));
         h->pending.push_back(p);
     }
@@ -1340,6 +1516,46 @@ int crh_search(crh_index *h, int nq, const float *queries, int queries_on_device
             CRH_HIP(hipStreamSynchronize(st));
         }
     }
+    return CRH_OK;
+}
+
+static int search_args(crh_index *h, int nq, const float *queries, int k, float *out_scores, int64_t *out_rows)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (nq < 0) return fail(CRH_E_INVALID, "nq < 0");
+    if (nq == 0) return CRH_OK;
+    if (!queries || !out_scores || !out_rows) return fail(CRH_E_INVALID, "NULL query or output pointer");
+    if (k <= 0 || k > CRH_MAX_K) return fail(CRH_E_CAPACITY, "k=%d outside 1..%d", k, CRH_MAX_K);
+    return CRH_OK;
+}
+
+int crh_search(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const crh_filter *filters, int n_filters,
+               int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+{
+    CRH_TRY(search_args(h, nq, queries, k, out_scores, out_rows));
+    if (nq == 0) return CRH_OK;
+    if (n_filters < 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 0..%d", n_filters, CRH_MAX_FILTERS);
+    if (n_filters > 0 && !filters) return fail(CRH_E_INVALID, "filters is NULL");
+    FilterKey key;
+    key_from_filters(filters, n_filters, key);
+    return search_key(h, nq, queries, queries_on_device, k, key, row_base, out_scores, out_rows, out_on_device, stream);
+}
+
+int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const crh_condition *conds, int n_conds,
+                    int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+{
+    CRH_TRY(search_args(h, nq, queries, k, out_scores, out_rows));
+    if (nq == 0) return CRH_OK;
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    return search_key(h, nq, queries, queries_on_device, k, key, row_base, out_scores, out_rows, out_on_device, stream);
+}
+
+int crh_index_set_sparse_route(crh_index *h, int enable, int max_fraction_den)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (enable >= 0) h->sparse_on = enable != 0;
+    if (max_fraction_den > 0) h->sparse_den = max_fraction_den;
     return CRH_OK;
 }
 
@@ -1408,19 +1624,15 @@ int crh_merge_topk_strided(int nlists, int nq, int k, const float *scores_dev, c
     return CRH_OK;
 }
 
-int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters, int64_t limit, int64_t *rows_out_host, int64_t *n_out)
+static int match_key(crh_index *h, const FilterKey &key, int64_t limit, int64_t *rows_out_host, int64_t *n_out)
 {
-    if (!h || !n_out) return fail(CRH_E_INVALID, "NULL argument");
-    *n_out = 0;
-    if (limit <= 0 || h->count == 0) return CRH_OK;   // (rows_out_host == NULL: count only, up to `limit`)
-    if (n_filters < 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 0..%d", n_filters, CRH_MAX_FILTERS);
     DeviceGuard g(h->device);
     CRH_TRY(ensure_workspace0(h));
-    const uint32_t *mask = nullptr;
-    CRH_TRY(build_mask(h, h->ws, filters, n_filters, &mask, nullptr));
+    MaskRef m;
+    CRH_TRY(build_mask(h, h->ws, key, &m, nullptr));
     const int64_t ntiles = ceil_div(h->count, 32);
     std::vector<uint32_t> hm((size_t)ntiles);
-    CRH_HIP(hipMemcpy(hm.data(), mask, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
+    CRH_HIP(hipMemcpy(hm.data(), m.mask, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
     int64_t found = 0;
     for (int64_t t = 0; t < ntiles && found < limit; ++t) {
         uint32_t m = hm[(size_t)t];
@@ -1433,6 +1645,28 @@ int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters,
     }
     *n_out = found;
     return CRH_OK;
+}
+
+int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters, int64_t limit, int64_t *rows_out_host, int64_t *n_out)
+{
+    if (!h || !n_out) return fail(CRH_E_INVALID, "NULL argument");
+    *n_out = 0;
+    if (limit <= 0 || h->count == 0) return CRH_OK;   // (rows_out_host == NULL: count only, up to `limit`)
+    if (n_filters < 0 || n_filters > CRH_MAX_FILTERS) return fail(CRH_E_INVALID, "n_filters=%d outside 0..%d", n_filters, CRH_MAX_FILTERS);
+    if (n_filters > 0 && !filters) return fail(CRH_E_INVALID, "filters is NULL");
+    FilterKey key;
+    key_from_filters(filters, n_filters, key);
+    return match_key(h, key, limit, rows_out_host, n_out);
+}
+
+int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t limit, int64_t *rows_out_host, int64_t *n_out)
+{
+    if (!h || !n_out) return fail(CRH_E_INVALID, "NULL argument");
+    *n_out = 0;
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    if (limit <= 0 || h->count == 0) return CRH_OK;   // (rows_out_host == NULL: count only, up to `limit`)
+    return match_key(h, key, limit, rows_out_host, n_out);
 }
 
 }  // extern "C"

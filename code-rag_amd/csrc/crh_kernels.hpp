@@ -197,20 +197,44 @@ __global__ void k_tombstone(uint32_t *alive, const int64_t *__restrict__ rows, i
     if (old & bit) atomicAdd(cleared, 1u);
 }
 
-// effective row mask of a filtered search: alive AND every (col == code).  One thread per row.
+// effective row mask of a filtered search: alive AND every condition.  One thread per row, one launch for all conditions.
+// A condition is "the row's code in column col is (neg = 0) / is not (neg = 1) a member of a set".  A one-element set carries
+// its code in `one` (the equality of crh_filter: a plain compare, a code of -1 included); larger sets are ascending runs of
+// `sets`, cnt codes from off, looked up by binary search (a row costs log2(cnt) cached reads: 15 for 20 000 codes).  An empty
+// set has no member: "in" matches nothing, "not in" everything.
 struct FilterSet {
     int n;
     int col[CRH_MAX_FILTERS];
-    int code[CRH_MAX_FILTERS];
+    int neg[CRH_MAX_FILTERS];
+    int cnt[CRH_MAX_FILTERS];
+    int off[CRH_MAX_FILTERS];
+    int one[CRH_MAX_FILTERS];
 };
 __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict__ alive,
                                                      const int32_t *__restrict__ codes, int64_t cap_rows,
-                                                     int64_t count, FilterSet fs, uint32_t *__restrict__ out)
+                                                     int64_t count, FilterSet fs, const int32_t *__restrict__ sets,
+                                                     uint32_t *__restrict__ out)
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool ok = r < count;
     if (ok) {
-        for (int f = 0; f < fs.n; ++f) ok = ok && (codes[(int64_t)fs.col[f] * cap_rows + r] == fs.code[f]);
+        for (int f = 0; f < fs.n; ++f) {
+            const int32_t c = codes[(int64_t)fs.col[f] * cap_rows + r];
+            bool member;
+            if (fs.cnt[f] == 1) {
+                member = c == fs.one[f];
+            } else {
+                const int32_t *s = sets + fs.off[f];
+                int lo = 0, hi = fs.cnt[f];   // first position whose code is >= c
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s[mid] < c) lo = mid + 1;
+                    else hi = mid;
+                }
+                member = lo < fs.cnt[f] && s[lo] == c;
+            }
+            ok = ok && (member != (fs.neg[f] != 0));
+        }
     }
     unsigned long long b = __ballot(ok);
     int lane = lane_id();
@@ -232,6 +256,44 @@ __global__ void k_tombstone_mask(uint32_t *__restrict__ alive, const uint32_t *_
         alive[t] &= ~m;
         atomicAdd(cleared, (unsigned int)__popc(m));
     }
+}
+
+// The tiles a filter mask leaves populated, as an ASCENDING list (what k_scan_list walks): two launches over the mask words,
+// 256 words per workgroup.  k_tilelist_count writes how many non-zero words each workgroup sees; k_tilelist_fill sums the
+// counts of the workgroups before its own (a few thousand words at most: ntiles / 256), ranks its own non-zero words behind
+// them with a ballot prefix and stores their tile numbers; the last workgroup also stores the total in list_len.
+__global__ __launch_bounds__(256) void k_tilelist_count(const uint32_t *__restrict__ mask, int64_t ntiles, uint32_t *__restrict__ blockcnt)
+{
+    __shared__ uint32_t wsum[4];
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool nz = t < ntiles && mask[t] != 0u;
+    const unsigned long long b = __ballot(nz);
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) blockcnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+__global__ __launch_bounds__(256) void k_tilelist_fill(const uint32_t *__restrict__ mask, int64_t ntiles, const uint32_t *__restrict__ blockcnt,
+                                                       uint32_t *__restrict__ list, uint32_t *__restrict__ list_len)
+{
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t wsum[4];
+    uint32_t before = 0;
+    for (unsigned int b = threadIdx.x; b < blockIdx.x; b += 256) before += blockcnt[b];
+    part[threadIdx.x] = before;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool nz = t < ntiles && mask[t] != 0u;
+    const unsigned long long bal = __ballot(nz);
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    uint32_t pos = part[0];
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) pos += wsum[w];
+    pos += __builtin_amdgcn_mbcnt_hi((unsigned int)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)bal, 0u));
+    if (nz) list[pos] = (uint32_t)t;   // (pos < the number of non-zero words <= ntiles: inside the list)
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *list_len = part[0] + wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
 // untile rows [first, first+n) into f32 [n][dim] (the bf16 copy; exact bf16 values)
@@ -428,6 +490,15 @@ __device__ __forceinline__ void nt_wait(u32x4 &dst)
 // per-query threshold is one VGPR per lane and the common case costs 32 v_max + 2 compares a tile.
 // QB = number of 32-query MFMA column blocks per pass: 2 (64 queries) while the query image fits LDS beside the kernel's
 // other needs (dim <= 1024), 1 (32 queries) for dim 1536.
+//
+// k_scan_list (the sparse route of a filtered search): item i is tile tilelist[i * tile_stride] instead of tile
+// i * tile_stride -- the ordered list of the tiles whose mask word is not 0 (k_tilelist_*), so the tiles a selective filter
+// leaves empty are never read.  The list entry is wave-uniform like the mask word: one scalar load per tile, issued a whole
+// tile ahead of the first load that needs it (the entry of the wave's NEXT tile is fetched at the top of the current one,
+// and the run-ahead loads reach into that tile only RING steps before the current one ends).  Everything else -- ring,
+// prefetch distance, MFMA order, candidate logic -- is the same text: both kernels include crh_scan_body.hpp.
+// MODE 0 runs over a sample of the listed tiles (items = sample size, tile_stride = list positions between two sample
+// tiles), MODE 1 over every listed tile (tile_stride 1).  Every list entry is < the number of tiles of the index.
 template <int KSTEPS, int MODE, int WAVES, int RING, int QB = 2>
 __global__ __launch_bounds__(WAVES * 64) void k_scan(
     const u32x4 *__restrict__ xt, const u32x4 *__restrict__ qfrag, const float *__restrict__ tau,
@@ -435,171 +506,21 @@ __global__ __launch_bounds__(WAVES * 64) void k_scan(
     u32x4 *__restrict__ wave_lists, int wave_cap, unsigned int *__restrict__ qcount,
     u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
 {
-    static_assert(KSTEPS % RING == 0, "ring must divide the k-steps of a tile");
-    __shared__ u32x4 qs[QB * KSTEPS * 64];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = lane >> 5;
+#define CRH_SCAN_LIST 0
+#include "crh_scan_body.hpp"
+#undef CRH_SCAN_LIST
+}
 
-    // (Preparing the queries HERE, in the seed scan -- every workgroup building the image in its own LDS, workgroup 0 writing it
-    // out for the later kernels -- was built and measured in round 3: it removes k_prep_queries' launch and adds the same time to
-    // this kernel, 119.7 us against 119.3 us around the main scan.  Not shipped.)
-    for (int i = tid; i < QB * KSTEPS * 64; i += WAVES * 64) qs[i] = qfrag[i];
-    float t0 = 0.f, t1 = 0.f;
-    if (MODE == 1) {
-        t0 = tau[lane & 31];
-        t1 = QB == 2 ? tau[32 + (lane & 31)] : INFINITY;
-    }
-    __syncthreads();
-
-    const int total = gridDim.x * WAVES;
-    const int gw = blockIdx.x * WAVES + wave;
-    u32x4 *mylist = wave_lists + (size_t)gw * wave_cap;
-    unsigned int wcnt = 0;
-
-    int i = gw;
-    const int lslot = lane_slot(lane);   // (the lane's 16 bytes inside a piece)
-    const u32x4 *xp = xt + (size_t)(i < nitems ? (int64_t)i * tile_stride : 0) * (KSTEPS * 64) + lslot;
-    u32x4 ring[RING];
-    if (i < nitems) {
-#pragma unroll
-        for (int d = 0; d < RING; ++d) nt_load(ring[d], xp + piece_off(d));
-    }
-    while (i < nitems) {
-        const int inext = i + total;
-        const int64_t tile = (int64_t)i * tile_stride;
-        const u32x4 *xn = (inext < nitems) ? xt + (size_t)((int64_t)inext * tile_stride) * (KSTEPS * 64) + lslot : xp;
-        const uint32_t vmask = rowmask[tile];  // wave-uniform -> scalar load
-        // the query image is loop-invariant: without this the compiler hoists all 96 LDS pieces (384 VGPRs)
-        // out of the tile loop and spills; the clobber makes it re-read qs per tile, as intended
-        asm volatile("" ::: "memory");
-
-        f32x16 a0 = {0}, a1 = {0};
-        u32x4 b0 = qs[lane], b1 = qs[(QB - 1) * KSTEPS * 64 + lane];
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            // order pinned by the sched_barrier: next step's query pieces (LDS), this step's two MFMAs, then the
-            // load that refills this ring slot RING steps ahead (it may belong to the wave's next tile).
-            const int s1 = (s + 1 < KSTEPS) ? s + 1 : s;
-            const u32x4 nb0 = qs[s1 * 64 + lane];
-            const u32x4 nb1 = qs[((QB - 1) * KSTEPS + s1) * 64 + lane];
-            nt_wait<RING - 1>(ring[s % RING]);   // the oldest of the RING loads in flight has landed (issue order)
-            const bf16x8 xa = __builtin_bit_cast(bf16x8, ring[s % RING]);
-            if (MODE == 2) {   // read-ceiling probe: the loads alone, kept alive by an empty asm
-                asm volatile("" ::"v"(ring[s % RING]));
-            } else {
-                a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, __builtin_bit_cast(bf16x8, b0), a0, 0, 0, 0);
-                if (QB == 2) a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa, __builtin_bit_cast(bf16x8, b1), a1, 0, 0, 0);
-            }
-            const int sp = s + RING;
-            const u32x4 *src = (sp < KSTEPS) ? xp + piece_off(sp) : xn + piece_off(sp - KSTEPS);
-            nt_load(ring[s % RING], src);
-            b0 = nb0;
-            b1 = nb1;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-
-        if (MODE == 2) {
-            // nothing: the probe measures what the same access pattern reads with no arithmetic and no candidate logic
-        } else if (MODE == 0) {
-            float m0 = -INFINITY, m1 = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const bool ok = (vmask >> row) & 1u;
-                m0 = fmaxf(m0, ok ? a0[r] : -INFINITY);
-                m1 = fmaxf(m1, ok ? a1[r] : -INFINITY);
-            }
-            m0 = fmaxf(m0, __shfl_xor(m0, 32));
-            m1 = fmaxf(m1, __shfl_xor(m1, 32));
-            if (h == 0) {
-                gmax[(size_t)i * 64 + lane] = m0;
-                if (QB == 2) gmax[(size_t)i * 64 + 32 + lane] = m1;
-            }
-        } else {
-            float m0 = a0[0], m1 = a1[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) {
-                m0 = fmaxf(m0, a0[r]);
-                m1 = fmaxf(m1, a1[r]);
-            }
-            const bool any = (m0 >= t0) || (m1 >= t1);
-            if (__ballot(any) != 0ull && vmask != 0u) {
-                const uint32_t rowbase = (uint32_t)(tile * 32);
-#pragma unroll
-                for (int qb = 0; qb < QB; ++qb) {
-                    const float tq = qb ? t1 : t0;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                        const float sc = qb ? a1[r] : a0[r];
-                        const bool pass = ((vmask >> row) & 1u) && (sc >= tq);
-                        const unsigned long long pm = __ballot(pass);
-                        if (pm != 0ull) {
-                            const unsigned int pre = __builtin_amdgcn_mbcnt_hi(
-                                (unsigned int)(pm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)pm, 0u));
-                            const unsigned int pos = wcnt + pre;
-                            if (pass && pos < (unsigned int)wave_cap) {
-                                u32x4 e;
-                                e.x = f32_bits(sc);
-                                e.y = rowbase + row;
-                                e.z = (uint32_t)(qb * 32 + (lane & 31));
-                                e.w = 0u;
-                                mylist[pos] = e;
-                            }
-                            wcnt += (unsigned int)__popcll(pm);
-                        }
-                    }
-                }
-            }
-        }
-        xp = xn;
-        i = inext;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the run-ahead loads of the last tile are still in flight
-
-    if (MODE == 1) {
-        // Hand the workgroup's candidates over to the per-query lists: count per query in LDS, reserve
-        // one contiguous range per (workgroup, query) with 64 global atomics, scatter.
-        __syncthreads();  // every wave is done with qs (and its list stores have completed)
-        unsigned int *wc = reinterpret_cast<unsigned int *>(qs);  // [WAVES] counts, [64] hist, [64] base, [64] off
-        unsigned int *hist = wc + WAVES;
-        unsigned int *base = hist + 64;
-        unsigned int *off = base + 64;
-        if (lane == 0) {
-            wc[wave] = wcnt < (unsigned int)wave_cap ? wcnt : (unsigned int)wave_cap;
-            atomicMax(&status->max_wave_cnt, wcnt);
-            if (wcnt > (unsigned int)wave_cap) atomicAdd(&status->wave_overflow, 1u);
-        }
-        if (tid < 64) {
-            hist[tid] = 0u;
-            off[tid] = 0u;
-        }
-        __syncthreads();
-        const u32x4 *wl = wave_lists + (size_t)blockIdx.x * WAVES * wave_cap;
-        for (int w = 0; w < WAVES; ++w) {
-            const unsigned int n = wc[w];
-            for (unsigned int e = tid; e < n; e += WAVES * 64) atomicAdd(&hist[wl[(size_t)w * wave_cap + e].z & 63u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) base[tid] = hist[tid] ? atomicAdd(&qcount[tid], hist[tid]) : 0u;
-        __syncthreads();
-        for (int w = 0; w < WAVES; ++w) {
-            const unsigned int n = wc[w];
-            for (unsigned int e = tid; e < n; e += WAVES * 64) {
-                const u32x4 c = wl[(size_t)w * wave_cap + e];
-                const unsigned int q = c.z & 63u;
-                const unsigned int idx = base[q] + atomicAdd(&off[q], 1u);
-                if (idx < (unsigned int)qcap) {
-                    u32x2 o;
-                    o.x = c.x;
-                    o.y = c.y;
-                    qlist[(size_t)q * qcap + idx] = o;
-                }
-            }
-        }
-    }
+template <int KSTEPS, int MODE, int WAVES, int RING, int QB = 2>
+__global__ __launch_bounds__(WAVES * 64) void k_scan_list(
+    const u32x4 *__restrict__ xt, const u32x4 *__restrict__ qfrag, const float *__restrict__ tau,
+    const uint32_t *__restrict__ rowmask, const uint32_t *__restrict__ tilelist, int nitems, int tile_stride,
+    float *__restrict__ gmax, u32x4 *__restrict__ wave_lists, int wave_cap, unsigned int *__restrict__ qcount,
+    u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
+{
+#define CRH_SCAN_LIST 1
+#include "crh_scan_body.hpp"
+#undef CRH_SCAN_LIST
 }
 
 // ------------------------------------------------------------------ the wide scan (65 .. 256 queries per corpus pass)

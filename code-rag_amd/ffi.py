@@ -30,6 +30,7 @@ EXPORTS = (
     "crh_search", "crh_search_finish", "crh_search_get_stats", "crh_index_set_tuning",
     "crh_index_set_nomination", "crh_index_get_nomination",
     "crh_merge_topk", "crh_merge_topk_strided", "crh_index_match_rows", "crh_index_set_profiling", "crh_index_get_profile",
+    "crh_search_cond", "crh_index_match_rows_cond", "crh_index_tombstone_cond", "crh_index_set_sparse_route",
     "crh_gemm_bf16_bias", "crh_gemm_bf16_bias_res_ln", "crh_gemm_bf16_res_lnstats", "crh_gemm_bf16_lnin", "crh_layernorm_apply", "crh_gemm_bf16_bias_res32_ln", "crh_attn_fwd_varlen", "crh_embed_ln",
     "crh_masked_mean_pool", "crh_gather_rows_i32", "crh_gather_rows_bytes", "crh_gather_rerank_columns", "crh_rerank_vector",
     "crh_embed_ln_packed", "crh_attn_fwd_packed", "crh_masked_mean_pool_packed", "crh_encoder_finish",
@@ -49,6 +50,11 @@ class NativeError(RuntimeError):
 
 class Filter(C.Structure):
     _fields_ = [("col", C.c_int32), ("code", C.c_int32)]
+
+
+class Condition(C.Structure):
+    """``crh_condition``: column ``col`` is (``negate`` = 0) / is not (1) one of the ``n`` int32 codes at ``codes``."""
+    _fields_ = [("col", C.c_int32), ("negate", C.c_int32), ("n", C.c_int64), ("codes", C.c_void_p)]
 
 
 class RerankQuery(C.Structure):
@@ -145,6 +151,10 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_merge_topk.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
     L.crh_merge_topk_strided.argtypes = [i32, i32, i32, vp, vp, i64, i64, vp, vp, vp]
     L.crh_index_match_rows.argtypes = [vp, C.POINTER(Filter), i32, i64, vp, C.POINTER(i64)]
+    L.crh_search_cond.argtypes = [vp, i32, vp, i32, i32, C.POINTER(Condition), i32, i64, vp, vp, i32, vp]
+    L.crh_index_match_rows_cond.argtypes = [vp, C.POINTER(Condition), i32, i64, vp, C.POINTER(i64)]
+    L.crh_index_tombstone_cond.argtypes = [vp, C.POINTER(Condition), i32, C.POINTER(i64)]
+    L.crh_index_set_sparse_route.argtypes = [vp, i32, i32]
     L.crh_gemm_bf16_bias.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.crh_gemm_bf16_bias_res_ln.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, i32, i32, i32, vp]
     L.crh_gemm_bf16_res_lnstats.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp]
@@ -217,6 +227,34 @@ def _filters(filters) -> tuple:
     for i, (col, code) in enumerate(filters):
         arr[i].col, arr[i].code = int(col), int(code)
     return arr, len(filters)
+
+
+def is_set_condition(item) -> bool:
+    """A filter item is ``(column, code)`` -- the equality of ``crh_filter`` -- or a SET condition ``(column, codes, negate)``:
+    the column's code is (``negate`` false) / is not (true) one of ``codes`` (any iterable of ints; ``negate`` may be left out)."""
+    return len(item) == 3 or not isinstance(item[1], (int, np.integer))
+
+
+def _conditions(filters) -> tuple:
+    """Any mix of the two item forms as ``crh_condition``s: (array, n, the numpy sets the array points into -- keep them alive
+    for the call)."""
+    filters = list(filters or [])
+    if len(filters) > MAX_FILTERS:
+        raise NativeError(E_INVALID, f"at most {MAX_FILTERS} filter conditions are supported")
+    arr, keep = (Condition * max(1, len(filters)))(), []
+    for i, item in enumerate(filters):
+        if is_set_condition(item):
+            col, codes, negate = item[0], item[1], (bool(item[2]) if len(item) == 3 else False)
+            codes = np.ascontiguousarray(sorted(int(c) for c in codes) if not isinstance(codes, np.ndarray) else codes, dtype=np.int32).reshape(-1)
+        else:
+            col, codes, negate = item[0], np.asarray([int(item[1])], np.int32), False
+        keep.append(codes)
+        arr[i].col, arr[i].negate, arr[i].n, arr[i].codes = int(col), int(negate), int(codes.size), codes.ctypes.data if codes.size else None
+    return arr, len(filters), keep
+
+
+def _has_sets(filters) -> bool:
+    return any(is_set_condition(item) for item in (filters or []))
 
 
 def _ptr(x) -> int:
@@ -310,12 +348,27 @@ class Index:
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         check(lib().crh_index_tombstone(self._handle(), rows.shape[0], rows.ctypes.data))
 
+    SET_CONDITIONS = True  # filters may hold (column, codes, negate) set conditions (an injected stand-in may know equalities only)
+    device_calls = 0      # filtered deletes / matches issued to the library by all handles (tests count the calls of a job)
+
     def tombstone_filter(self, filters) -> int:
-        """Delete every alive row matching all ``(column, code)`` predicates, on the device; returns how many."""
-        farr, nf = _filters(filters)
+        """Delete every alive row matching all conditions -- ``(column, code)`` equalities and ``(column, codes, negate)`` sets
+        (:func:`is_set_condition`) -- on the device, in ONE call; returns how many."""
         n = C.c_int64(0)
-        check(lib().crh_index_tombstone_filter(self._handle(), farr, nf, C.byref(n)))
+        Index.device_calls += 1
+        if _has_sets(filters):
+            carr, nc, keep = _conditions(filters)
+            check(lib().crh_index_tombstone_cond(self._handle(), carr, nc, C.byref(n)))
+            del keep
+        else:
+            farr, nf = _filters(filters)
+            check(lib().crh_index_tombstone_filter(self._handle(), farr, nf, C.byref(n)))
         return int(n.value)
+
+    def set_sparse_route(self, enable: bool | None = None, max_fraction_den: int = 0) -> None:
+        """The route of filtered searches whose mask leaves at most 1 tile in ``max_fraction_den`` populated (``crh_index_set_sparse_route``;
+        None / 0 = keep).  ``enable=False`` is the A/B switch: every search takes the dense scans."""
+        check(lib().crh_index_set_sparse_route(self._handle(), -1 if enable is None else int(bool(enable)), int(max_fraction_den)))
 
     def compact(self) -> np.ndarray:
         """Reclaim the rows of deleted points (``crh_index_compact``): the alive rows move down in their old order.  Returns
@@ -474,7 +527,6 @@ class Index:
         nq = int(queries.shape[0])
         if nq and int(queries.shape[1]) != self.dim:
             raise NativeError(E_INVALID, f"query dim {queries.shape[1]} != index dim {self.dim}")
-        farr, nf = _filters(filters)
         if not 0 < k <= MAX_K:
             raise NativeError(E_CAPACITY, f"k={k} outside 1..{MAX_K}")
         if out_scores is None:
@@ -485,8 +537,15 @@ class Index:
             _out(out_rows, "int64", "out_rows", (nq, k))
             if _is_dev(out_scores) != _is_dev(out_rows):
                 raise NativeError(E_INVALID, "out_scores and out_rows must live in the same memory space")
-        check(lib().crh_search(self._handle(), nq, _ptr(queries), _is_dev(queries), k, farr, nf, row_base,
-                               _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
+        if _has_sets(filters):
+            carr, nc, keep = _conditions(filters)
+            check(lib().crh_search_cond(self._handle(), nq, _ptr(queries), _is_dev(queries), k, carr, nc, row_base,
+                                        _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
+            del keep
+        else:
+            farr, nf = _filters(filters)
+            check(lib().crh_search(self._handle(), nq, _ptr(queries), _is_dev(queries), k, farr, nf, row_base,
+                                   _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
         return out_scores, out_rows
 
     def search_finish(self, stream: int = 0) -> None:
@@ -509,17 +568,23 @@ class Index:
 
     def count_matching(self, filters=None) -> int:
         """Number of alive rows matching the filters (resolved on the device)."""
-        farr, nf = _filters(filters)
+        return self._match(filters, 1 << 62, None)
+
+    def _match(self, filters, limit: int, out) -> int:
         n = C.c_int64(0)
-        check(lib().crh_index_match_rows(self._handle(), farr, nf, 1 << 62, None, C.byref(n)))
+        Index.device_calls += 1
+        if _has_sets(filters):
+            carr, nc, keep = _conditions(filters)
+            check(lib().crh_index_match_rows_cond(self._handle(), carr, nc, limit, out, C.byref(n)))
+            del keep
+        else:
+            farr, nf = _filters(filters)
+            check(lib().crh_index_match_rows(self._handle(), farr, nf, limit, out, C.byref(n)))
         return int(n.value)
 
     def match_rows(self, filters=None, limit: int = 1) -> np.ndarray:
-        farr, nf = _filters(filters)
         out = np.empty((max(limit, 1),), dtype=np.int64)
-        n = C.c_int64(0)
-        check(lib().crh_index_match_rows(self._handle(), farr, nf, limit, out.ctypes.data, C.byref(n)))
-        return out[: int(n.value)].copy()
+        return out[: self._match(filters, limit, out.ctypes.data)].copy()
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

@@ -347,8 +347,9 @@ class VectorSearcher:
             logger.error(f"{what} search failed: {e}")
             raise IndexingError(f"Failed to search {what.lower()} for query: {query}", stage=stage, cause=e)
 
-    async def search_code(self, query: str, limit: int = 10, language: str | None = None, entity_type: str | None = None,
-                          project_name: str | None = None) -> list[CodeSearchResult]:
+    async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
+                          project_name: str | list[str] | None = None) -> list[CodeSearchResult]:
+        """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant)."""
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
                                _only_set(language=language, entity_type=entity_type, project_name=project_name),
                                "code_search", "Code")

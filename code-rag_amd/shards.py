@@ -242,11 +242,30 @@ class ShardSet:
             if len(sel):
                 ix.tombstone(np.asarray(sel, np.int64))
 
+    # A filter (``dfilt``) is a list of conditions as ``ffi.Index`` takes them: ``(column, code)`` equalities and
+    # ``(column, codes, negate)`` sets.  It travels to every shard as it is -- in this process or, under backend "dist", in the
+    # same call every rank makes -- so set conditions need nothing of the collectives.
+    def _plans(self, dfilt) -> list:
+        """``[dfilt]`` -- or, for injected indexes that know equalities only (no ``SET_CONDITIONS``), the disjoint equality
+        filters whose union it is: one per combination of the sets' codes (a negated set has no such form)."""
+        if all(getattr(ix, "SET_CONDITIONS", False) for ix in self.index.values()) or not any(ffi.is_set_condition(c) for c in dfilt or []):
+            return [dfilt]
+        plans: list[list] = [[]]
+        for cond in dfilt:
+            if not ffi.is_set_condition(cond):
+                opts = [(cond[0], cond[1])]
+            elif len(cond) == 3 and cond[2]:
+                raise ValueError("this index takes equality filters only: no 'not in' condition")
+            else:
+                opts = [(cond[0], int(c)) for c in sorted(set(cond[1]))]
+            plans = [p + [o] for p in plans for o in opts]
+        return plans
+
     def tombstone_filter(self, dfilt) -> int:
-        return self._sum_everyone(sum(ix.tombstone_filter(dfilt) for ix in self.index.values()))
+        return self._sum_everyone(sum(ix.tombstone_filter(p) for ix in self.index.values() for p in self._plans(dfilt)))
 
     def count_matching(self, dfilt) -> int:
-        return self._sum_everyone(sum(ix.count_matching(dfilt) for ix in self.index.values()))
+        return self._sum_everyone(sum(ix.count_matching(p) for ix in self.index.values() for p in self._plans(dfilt)))
 
     def match_rows(self, dfilt, limit: int) -> tuple[np.ndarray, np.ndarray]:
         """(shard, local row) of up to ``limit`` alive matching rows PER SHARD, ascending inside each shard (a caller that wants

@@ -165,22 +165,45 @@ class _Collection:
             side.set_degrees(self._degrees)
 
     # -- filters
-    def device_filters(self, filters: dict[str, Any] | None) -> list[tuple[int, int]] | None:
-        """dict -> [(column, code)]; None when some value was never stored (nothing can match)."""
-        out = []
+    def _column(self, key: str) -> int:
+        if key not in self.keys:
+            raise ValueError(f"collection {self.name!r} cannot filter on payload key {key!r} "
+                             f"(filterable: {', '.join(self.keys)})")
+        return self.keys.index(key)
+
+    def _codes_of(self, key: str, values) -> list[int]:
+        """Codes of the values the column's dictionary knows (a value that was never stored contributes none)."""
+        book = self.payloads.cols[key]
+        return sorted({c for c in (book.code_of(v) for v in values) if c is not None})
+
+    def device_filters(self, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None) -> list[tuple] | None:
+        """dict(s) -> the conditions of ``ffi.Index``: ``(column, code)`` for a plain value, ``(column, codes, False)`` for a
+        list / tuple / set of values (any of them), ``(column, codes, True)`` for a ``must_not`` entry (none of them; one
+        value or a collection).  None when a plain value or a whole any-of collection was never stored (nothing can match);
+        a ``must_not`` entry whose values were never stored excludes nothing and is dropped."""
+        out: list[tuple] = []
         for key, value in (filters or {}).items():
-            if key not in self.keys:
-                raise ValueError(f"collection {self.name!r} cannot filter on payload key {key!r} "
-                                 f"(filterable: {', '.join(self.keys)})")
-            code = self.payloads.cols[key].code_of(value)
-            if code is None:
-                return None
-            out.append((self.keys.index(key), code))
+            col = self._column(key)
+            if isinstance(value, _COLLECTIONS):
+                codes = self._codes_of(key, value)
+                if not codes:
+                    return None
+                out.append((col, codes, False))
+            else:
+                code = self.payloads.cols[key].code_of(value)
+                if code is None:
+                    return None
+                out.append((col, code))
+        for key, value in (must_not or {}).items():
+            col = self._column(key)
+            codes = self._codes_of(key, value if isinstance(value, _COLLECTIONS) else [value])
+            if codes:
+                out.append((col, codes, True))
         return out
 
-    def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None) -> np.ndarray:
-        """Alive slots matching every equality, in insertion order -- resolved on the device from the code columns."""
-        dfilt = self.device_filters(filters)
+    def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None, must_not: dict[str, Any] | None = None) -> np.ndarray:
+        """Alive slots matching every condition, in insertion order -- resolved on the device from the code columns."""
+        dfilt = self.device_filters(filters, must_not)
         if dfilt is None:
             return np.zeros((0,), np.int64)
         sh, lo = self.shards.match_rows(dfilt, sum(self.shards.rows) if limit is None else limit)
@@ -193,10 +216,10 @@ class _Collection:
         if slots.size:
             self.shards.tombstone(*self.rows_of(slots))
 
-    def delete(self, filters: dict[str, Any]) -> int:
-        """client.py:159-169: every point matching the AND of equalities.  An empty filter matches every point, as
+    def delete(self, filters: dict[str, Any], must_not: dict[str, Any] | None = None) -> int:
+        """client.py:159-169: every point matching the AND of the conditions.  An empty filter matches every point, as
         ``Filter(must=[])`` does."""
-        dfilt = self.device_filters(filters)
+        dfilt = self.device_filters(filters, must_not)
         if dfilt is None:
             return 0
         if not dfilt:
@@ -491,11 +514,17 @@ def ffi_index_tensor(vecs, keep):
     return torch.as_tensor(keep, device=vecs.device, dtype=torch.int64)
 
 
+_COLLECTIONS = (list, tuple, set, frozenset)
+
+
+def _value_key(v) -> str:
+    """A filter value as part of a coalescing key: collections compare as sets of their members."""
+    return repr(sorted(repr(x) for x in v)) if isinstance(v, _COLLECTIONS) else "=" + repr(v)
+
+
 class _RawClient:
     """The slice of ``AsyncQdrantClient`` that callers reach through ``QdrantManager.client``
     (health check: client.py:66; admin cleanup: projects/cleanup.py:41-61)."""
-
-    MAX_CODE_COMBINATIONS = 4096
 
     def __init__(self, store: "HipVectorStore"):
         self._store = store
@@ -508,39 +537,43 @@ class _RawClient:
         return await self._store.get_collection_info(collection_name)
 
     @staticmethod
-    def _conditions(flt) -> list[tuple[str, str, Any]]:
-        """Duck-typed qdrant Filter(must=[FieldCondition(key, match=MatchValue|MatchText)]) -> (key, kind, value)."""
+    def _conditions(flt) -> list[tuple[str, str, Any, bool]]:
+        """Duck-typed qdrant ``Filter(must=[...], must_not=[...])`` of ``FieldCondition(key, match=MatchValue | MatchText |
+        MatchAny | MatchExcept)`` -> (key, kind, value, negate); kind: "value", "text", "any" (value: the list)."""
         out = []
-        for cond in (getattr(flt, "must", None) or []):
-            m = getattr(cond, "match", None)
-            if hasattr(m, "text"):
-                out.append((cond.key, "text", m.text))
-            else:
-                out.append((cond.key, "value", getattr(m, "value", None)))
+        for negate, conds in ((False, getattr(flt, "must", None)), (True, getattr(flt, "must_not", None))):
+            if conds is not None and not isinstance(conds, (list, tuple)):
+                conds = [conds]                      # (qdrant accepts a single condition in place of a list)
+            for cond in (conds or []):
+                m = getattr(cond, "match", None)
+                if getattr(m, "text", None) is not None:
+                    out.append((cond.key, "text", m.text, negate))
+                elif getattr(m, "any", None) is not None:
+                    out.append((cond.key, "any", list(m.any), negate))
+                elif getattr(m, "except_", None) is not None:   # MatchExcept(**{"except": [...]}): anything but these
+                    out.append((cond.key, "any", list(m.except_), not negate))
+                else:
+                    out.append((cond.key, "value", getattr(m, "value", None), negate))
         return out
 
-    def _device_plans(self, col: _Collection, conds) -> list[list[tuple[int, int]]] | None:
-        """The conditions as a UNION of device filters ([(column, code)] lists), or None when some condition is on a key the
-        device does not code (then the payloads are walked on the host).  MatchValue on a coded key is one code; MatchText on
-        a coded key is every code whose VALUE contains the text -- the dictionaries are small (distinct files, not rows)."""
-        choices: list[list[tuple[int, int]]] = []
-        for key, kind, value in conds:
+    def _device_filter(self, col: _Collection, conds) -> list[tuple] | None:
+        """The conditions as ONE device filter (``(column, codes, negate)`` per condition), or None when some condition is on a
+        key the device does not code (then the payloads are walked on the host).  MatchValue on a coded key is one code,
+        MatchAny its values' codes, MatchText every code whose VALUE contains the text -- the dictionaries are small (distinct
+        files, not rows), and however many codes that is, the device takes them as one set."""
+        out: list[tuple] = []
+        for key, kind, value, negate in conds:
             if key not in col.keys:
                 return None
-            c = col.keys.index(key)
             book = col.payloads.cols[key]
-            if kind == "value":
-                code = book.code_of(value)
-                opts = [] if code is None else [(c, code)]
+            if kind == "text":
+                codes = [i + 1 for i, v in enumerate(book.values) if isinstance(v, str) and str(value) in v]
             else:
-                opts = [(c, i + 1) for i, v in enumerate(book.values) if isinstance(v, str) and str(value) in v]
-            choices.append(opts)
-        plans: list[list[tuple[int, int]]] = [[]]
-        for opts in choices:
-            plans = [p + [o] for p in plans for o in opts]
-            if len(plans) > self.MAX_CODE_COMBINATIONS:
-                return None
-        return plans
+                codes = col._codes_of(key, value if kind == "any" else [value])
+            out.append((col.keys.index(key), codes, negate))
+        if len(out) > ffi.MAX_FILTERS:
+            return None
+        return out
 
     def _host_select(self, col: _Collection, conds) -> np.ndarray:
         """Slots whose payload meets conditions on keys the device does not code: a walk over the alive slots' columns."""
@@ -550,9 +583,11 @@ class _RawClient:
             if col.partial and int(col.row_shard[t]) not in mine:
                 continue                                  # (one process per shard: a row's text is with its owner, who answers for it)
             ok = True
-            for key, kind, value in conds:
+            for key, kind, value, negate in conds:
                 have = col.payloads.value(int(t), key)
-                ok = ok and ((isinstance(have, str) and str(value) in have) if kind == "text" else have == value)
+                hit = ((isinstance(have, str) and str(value) in have) if kind == "text" else
+                       (have in value) if kind == "any" else have == value)
+                ok = ok and (hit != negate)
             if ok:
                 slots.append(int(t))
         if col.partial:
@@ -564,10 +599,10 @@ class _RawClient:
         def work():
             col = self._store._col(collection_name)
             conds = self._conditions(count_filter)
-            plans = self._device_plans(col, conds)
-            if plans is None:
+            dfilt = self._device_filter(col, conds)
+            if dfilt is None:
                 return int(self._host_select(col, conds).size)
-            return sum(col.shards.count_matching(p) for p in plans)      # (plans differ in at least one code: disjoint)
+            return col.shards.count_matching(dfilt)
         n = await self._store._run(work)
         return type("CountResult", (), {"count": n})()
 
@@ -577,15 +612,13 @@ class _RawClient:
         def work():
             col = self._store._col(collection_name)
             conds = self._conditions(flt)
-            plans = self._device_plans(col, conds)
-            if plans is None:
+            dfilt = self._device_filter(col, conds)
+            if dfilt is None:
                 col.remove_slots(self._host_select(col, conds))
-            else:
-                for p in plans:
-                    if p:
-                        col.shards.tombstone_filter(p)
-                    else:                               # no condition at all: every point
-                        col.remove_slots(col.matching_slots(None))
+            elif dfilt:
+                col.shards.tombstone_filter(dfilt)      # ONE device call per shard, however many codes a MatchText resolves to
+            else:                                       # no condition at all: every point
+                col.remove_slots(col.matching_slots(None))
             col.maybe_compact()
         await self._store._run(work)
 
@@ -795,22 +828,23 @@ class HipVectorStore:
         except Exception as e:
             raise VectorStoreError(f"Failed to upsert vectors to {collection}", cause=e)
 
-    def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None):
+    def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None):
         col = self._col(collection)
-        dfilt = col.device_filters(filters)
+        dfilt = col.device_filters(filters, must_not)
         nq = queries.shape[0]
         if dfilt is None or limit <= 0:
             return col, np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
         scores, slots = col.search(queries, limit, dfilt)
         return col, scores, slots
 
-    def _search_hits_sync(self, collection: str, queries: np.ndarray, limits, filters: dict[str, Any] | None) -> list[list[dict[str, Any]]]:
+    def _search_hits_sync(self, collection: str, queries: np.ndarray, limits, filters: dict[str, Any] | None,
+                          must_not: dict[str, Any] | None = None) -> list[list[dict[str, Any]]]:
         """One pass + the hit dictionaries of every query, built HERE -- inside the worker job, under the store's lock.  Slots
         are positions in the host tables and a compaction renumbers them (the store compacts by itself after deletes and
         replacing upserts): a slot handed back to the event loop could name another point, or none, by the time its payload is
         read.  ``limits``: one int for all queries, or one per query (coalesced callers keep their own prefix)."""
         per = [int(limits)] * queries.shape[0] if isinstance(limits, (int, np.integer)) else [int(v) for v in limits]
-        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters)
+        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not)
         picked = [[(int(r), float(s)) for s, r in zip(srow[:max(lim, 0)], rrow[:max(lim, 0)]) if r >= 0] for lim, srow, rrow in zip(per, scores, slots)]
         flat = col.hits([t for one in picked for t, _ in one], [sc for one in picked for _, sc in one])      # (payloads fetched together)
         out, at = [], 0
@@ -820,14 +854,17 @@ class HipVectorStore:
         return out
 
     async def search(self, collection: str, query_vector: list[float] | None, limit: int = 10,
-                     filters: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+                     filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
         """client.py:132-157: descending cosine, ``[{"id", "score", "payload"}]``.  ``query_vector=None`` is the
-        filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0."""
+        filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0.
+        A ``filters`` value may be a list / tuple / set (any of them: Qdrant's ``MatchAny``); ``must_not`` (not in the
+        reference's signature) names values a hit must NOT have, one or a collection per key (``Filter(must_not=...)``).
+        Values the collection has never stored contribute nothing and never raise."""
         try:
             if query_vector is None:
                 def fetch():
                     col = self._col(collection)
-                    slots = col.matching_slots(filters, limit=limit)
+                    slots = col.matching_slots(filters, limit=limit, must_not=must_not)
                     return col.hits(slots, [0.0] * len(slots))
                 results = await self._run(fetch)
             elif len(query_vector) != self._col(collection).shards.dim:   # (must not fail the pass it would have joined)
@@ -835,32 +872,34 @@ class HipVectorStore:
             elif limit > ffi.MAX_K:                                      # (likewise: only THIS caller is refused)
                 raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
             elif self._search_coalesce:
-                results = await self._search_coalesced(collection, query_vector, limit, filters)
+                results = await self._search_coalesced(collection, query_vector, limit, filters, must_not)
             else:
                 q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
                 self.search_passes += 1
-                results = (await self._run(self._search_hits_sync, collection, q, limit, filters))[0]
+                results = (await self._run(self._search_hits_sync, collection, q, limit, filters, must_not))[0]
             logger.debug(f"Found {len(results)} results in {collection}")
             return results
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
-    async def _search_coalesced(self, collection: str, query_vector, limit: int, filters: dict[str, Any] | None):
+    async def _search_coalesced(self, collection: str, query_vector, limit: int, filters: dict[str, Any] | None,
+                                must_not: dict[str, Any] | None = None):
         """One entry of a coalesced pass: queue the query, let the key's drainer run the batch, return this call's slice.
         Calls are grouped by (collection, filter); the pass asks for the largest limit of the group and each caller keeps
         its own prefix (an exact top-k list is a prefix of every longer one)."""
         loop = asyncio.get_running_loop()
         name = collection.value if isinstance(collection, CollectionName) else collection
-        key = (name, tuple(sorted((k, repr(v)) for k, v in (filters or {}).items())))
+        key = (name, tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
+               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())))
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
         self._search_pending.setdefault(key, []).append((vec, int(limit), fut))
         task = self._search_drainers.get(key)
         if task is None or task.done():
-            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters))
+            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not))
         return await fut
 
-    async def _drain_searches(self, key, name: str, filters) -> None:
+    async def _drain_searches(self, key, name: str, filters, must_not=None) -> None:
         while self._search_pending.get(key):
             await asyncio.sleep(self._search_window_s)       # (0: one turn of the loop, so calls issued together travel together)
             batch = self._search_pending.pop(key, [])
@@ -871,7 +910,7 @@ class HipVectorStore:
                 try:
                     q = np.stack([b[0] for b in part])
                     self.search_passes += (len(part) + 63) // 64
-                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters)
+                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters, must_not)
                     for (_, _, fut), hits in zip(part, per_query):
                         if not fut.done():
                             fut.set_result(hits)
@@ -881,12 +920,12 @@ class HipVectorStore:
                             fut.set_exception(e)
 
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
-                           filters: dict[str, Any] | None = None) -> list[list[dict[str, Any]]]:
+                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
         serves up to 64 queries."""
         try:
             q = np.asarray(query_vectors, dtype=np.float32)
-            return await self._run(self._search_hits_sync, collection, q, limit, filters)
+            return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not)
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
@@ -896,7 +935,7 @@ class HipVectorStore:
         await self._run(lambda: self._col(collection).set_degrees(total_degree))
 
     async def search_rerank_batch(self, collection: str, query_vectors, plans, reranker, limit: int = 20,
-                                  filters: dict[str, Any] | None = None):
+                                  filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None):
         """One corpus scan for all queries, then the hybrid re-rank of every candidate list on the device
         (``ranking.device.DeviceReranker``): returns ``(hits, output, slots, scores)`` -- the :class:`RerankOutput`, the host
         copies of the [nq, limit] candidate slots / scores it indexes, and ``hits``: a :class:`RerankHits` whose
@@ -907,7 +946,7 @@ class HipVectorStore:
         try:
             def work():
                 col = self._col(collection)
-                dfilt = col.device_filters(filters)
+                dfilt = col.device_filters(filters, must_not)
                 q = np.ascontiguousarray(np.asarray(query_vectors, dtype=np.float32))
                 nq = q.shape[0]
                 dev = torch.device("cuda", self._device)
@@ -930,10 +969,10 @@ class HipVectorStore:
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
-    async def delete(self, collection: str, filters: dict[str, Any]) -> None:
-        """client.py:159-169: delete every point matching the AND of equalities."""
+    async def delete(self, collection: str, filters: dict[str, Any], must_not: dict[str, Any] | None = None) -> None:
+        """client.py:159-169: delete every point matching the AND of the conditions (values and ``must_not`` as in :meth:`search`)."""
         try:
-            await self._run(lambda: self._col(collection).delete(filters))
+            await self._run(lambda: self._col(collection).delete(filters, must_not))
             logger.debug(f"Deleted vectors from {collection} with filters: {filters}")
         except Exception as e:
             raise VectorStoreError(f"Failed to delete from {collection}", cause=e)
@@ -969,15 +1008,15 @@ class HipVectorStore:
             return [True] * len(files)
 
     async def delete_files(self, collection: str, file_paths: list[str]) -> None:
-        """``delete(collection, {"file_path": p})`` for many files in ONE job (a path the collection has never stored costs a
-        dictionary look-up and no device call); the collection compacts at most once, at the end."""
+        """``delete(collection, {"file_path": p})`` for many files in ONE job and ONE device call per shard: the paths the
+        collection has stored become one set condition (a path it has never stored costs a dictionary look-up); the collection
+        compacts at most once, at the end."""
         try:
             def work():
                 col = self._col(collection)
-                for p in file_paths:
-                    dfilt = col.device_filters({"file_path": p})
-                    if dfilt:
-                        col.shards.tombstone_filter(dfilt)
+                dfilt = col.device_filters({"file_path": list(file_paths)})
+                if dfilt:
+                    col.shards.tombstone_filter(dfilt)
                 col.maybe_compact()
             await self._run(work)
         except Exception as e:

@@ -66,12 +66,15 @@ class VectorSearcher:
         self.qdrant = qdrant
         self.embedder = embedder
 
-    async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str):
+    async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
+                      must_not: dict | None = None):
         """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
-        the reference's ``find_similar_code`` does (vector_search.py:193-197)."""
+        the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given."""
         try:
             vector = await self.embedder.embed(text)
             kwargs = {} if filters is _NO_FILTER_KWARG else {"filters": filters}
+            if must_not:
+                kwargs["must_not"] = must_not
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, **kwargs)
         except EmbeddingError as e:
             logger.error(f"Embedding error: {e}")
@@ -80,9 +83,9 @@ class VectorSearcher:
             logger.error(f"Vector store error: {e}")
             raise QueryError(store_fail, cause=e)
 
-    async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | None = None,
-                          entity_type: str | None = None, project_name: str | None = None) -> list[dict]:
-        """vector_search.py:60-116."""
+    async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
+                          entity_type: str | None = None, project_name: str | list[str] | None = None) -> list[dict]:
+        """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition)."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
@@ -99,13 +102,18 @@ class VectorSearcher:
                                   "Failed to embed search query", "Failed to search summaries")
         return [_project(h, _SUMMARY_KEYS) for h in hits]
 
-    async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None) -> list[dict]:
-        """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit``."""
+    async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
+                                exact_exclude: bool = False) -> list[dict]:
+        """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
+        back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
+        excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
-        fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file else limit
+        on_device = bool(exact_exclude and exclude_file)
+        fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch, _NO_FILTER_KWARG,
-                                  "Failed to embed code snippet", "Failed to find similar code")
+                                  "Failed to embed code snippet", "Failed to find similar code",
+                                  must_not={"file_path": exclude_file} if on_device else None)
         kept = []
         for h in hits:
             if exclude_file and h["payload"].get("file_path") == exclude_file:
@@ -116,8 +124,8 @@ class VectorSearcher:
         return kept
 
     # ------------------------------------------------------------------ batch entry (not in the reference)
-    async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | None = None,
-                                entity_type: str | None = None, project_name: str | None = None) -> list[list[dict]]:
+    async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
+                                entity_type: str | None = None, project_name: str | list[str] | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         try:

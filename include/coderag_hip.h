@@ -55,6 +55,21 @@ typedef struct crh_filter {
     int32_t code;
 } crh_filter;
 
+/* One payload SET condition: the code of column `col` is (negate = 0) or is not (negate != 0) one of the n codes of `codes`
+ * (host int32[n], any order, repeats allowed; the library copies them and keeps the set in device memory -- n is bounded by
+ * memory, not by CRH_MAX_FILTERS, which bounds the number of CONDITIONS of one filter).  negate = 0 replaces
+ * models.FieldCondition(key, match=MatchAny(any=[...])) -- and MatchValue for n = 1; negate != 0 replaces the same condition
+ * under Filter(must_not=[...]) / MatchExcept(**{"except": [...]}).  The reference itself only ever sends MatchValue
+ * (embeddings/client.py:171-176) and filters the rest on the host (query/vector_search.py:199-215).
+ * An empty set has no member: "in" matches no row, "not in" every row.  A row whose code is -1 (key absent from its payload)
+ * is a member of no set: it fails every "in" and passes every "not in"; negative codes in `codes` are ignored. */
+typedef struct crh_condition {
+    int32_t col;
+    int32_t negate;
+    int64_t n;
+    const int32_t *codes;
+} crh_condition;
+
 /* Counters of the most recent crh_search* call on a handle (diagnostics / bench). */
 typedef struct crh_search_stats {
     int64_t rows;            /* rows scanned */
@@ -109,6 +124,11 @@ int crh_index_tombstone(crh_index *h, int64_t n, const int64_t *rows);
  * n_cleared_out receives how many.  Replaces QdrantManager.delete -> client.delete(FilterSelector(filter))
  * (embeddings/client.py:159-169) without resolving the filter to row numbers on the host. */
 int crh_index_tombstone_filter(crh_index *h, const crh_filter *filters, int n_filters, int64_t *n_cleared_out);
+
+/* The same with set conditions (at least one): ONE call deletes the rows of any number of values -- what
+ * ProjectCleanupService's MatchText delete (projects/cleanup.py:41-61) resolves to, and the per-file deletes of a re-index
+ * (embeddings/indexer.py:61-64), which the reference issues as one client.delete per file. */
+int crh_index_tombstone_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t *n_cleared_out);
 
 /* Reclaim the rows of deleted points -- what Qdrant's optimizer does when it vacuums a segment.  The reference's indexing
  * flow deletes and re-inserts every chunk of a file on every run (embeddings/indexer.py:61-64, called with force=True from
@@ -165,6 +185,23 @@ int crh_index_read_rows(crh_index *h, int64_t first, int64_t n, float *out_host)
 int crh_search(crh_index *h, int nq, const float *queries, int queries_on_device, int k,
                const crh_filter *filters, int n_filters, int64_t row_base, float *out_scores,
                int64_t *out_rows, int out_on_device, void *stream);
+
+/* crh_search with set conditions: the alive rows that satisfy EVERY condition.  Replaces client.query_points with
+ * query_filter=Filter(must=[... MatchAny ...], must_not=[...]) (embeddings/client.py:132-157 builds only the must/MatchValue
+ * form), and with it the host-side exclusion of query/vector_search.py:199-215 (find_similar_code over-fetches by 5 and drops
+ * the excluded file's chunks).  Everything else -- outputs, padding, row_base, device outputs and crh_search_finish -- as
+ * crh_search.  n_conds: 0..CRH_MAX_FILTERS.  Bad columns, n < 0 and NULL codes with n > 0 are CRH_E_INVALID. */
+int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_device, int k,
+                    const crh_condition *conds, int n_conds, int64_t row_base, float *out_scores,
+                    int64_t *out_rows, int out_on_device, void *stream);
+
+/* (No counterpart in the reference: Qdrant's payload indexes make a filtered query cost about what the matching rows cost,
+ * embeddings/client.py:93-113.)  A filtered search of up to 64 queries (32 at dim 1536) whose mask leaves at most one 32-row
+ * tile in `max_fraction_den` populated reads only those tiles: their ascending list is made with the mask and kept with it,
+ * and the three-launch bf16 scan walks the list.  Ids and score bits are those of the dense route; crh_search_stats.rows /
+ * tiles / seed_tiles count what was read.  Larger calls are cut into such batches while the mask is that sparse.
+ * enable: 1 / 0, negative = keep; max_fraction_den: > 0 sets it, otherwise kept (default 4: DESIGN.md section 3). */
+int crh_index_set_sparse_route(crh_index *h, int enable, int max_fraction_den);
 
 /* Completes every crh_search enqueued with device outputs since the last finish. */
 int crh_search_finish(crh_index *h, void *stream);
@@ -283,6 +320,11 @@ int crh_rerank_vector(int nq, int k, const float *scores_dev, const int64_t *row
  * query/context/builder.py:111-119 and the scroll of embeddings/client.py:178-202. */
 int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters, int64_t limit,
                          int64_t *rows_out_host, int64_t *n_out);
+
+/* The same with set conditions (n_conds 0..CRH_MAX_FILTERS): the scroll of embeddings/client.py:178-202 and
+ * client.count(count_filter=Filter(...MatchText...)) of projects/cleanup.py:41-61, any number of values in one call. */
+int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t limit,
+                              int64_t *rows_out_host, int64_t *n_out);
 
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
