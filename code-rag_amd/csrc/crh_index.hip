@@ -1357,6 +1357,23 @@ int crh_index_read_rows(crh_index *h, int64_t first, int64_t n, float *out_host)
     return CRH_OK;
 }
 
+int crh_index_gather_vectors(crh_index *h, int64_t n, const int64_t *rows_dev, int64_t row_base, float *out_dev, void *stream)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (n < 0 || n > (1LL << 40) / h->dim) return fail(CRH_E_INVALID, "gather_vectors: n=%lld out of range", (long long)n);
+    if (n == 0) return CRH_OK;
+    if (!rows_dev || !out_dev) return fail(CRH_E_INVALID, "gather_vectors: NULL pointer");
+    DeviceGuard g(h->device);
+    if (!g.ok) return fail(CRH_E_HIP, "hipSetDevice(%d) failed", h->device);
+    // the row-major bf16 rows hold the tiles the last int8 synchronisation wrote (tiles >= i8_dirty_from are stale or absent)
+    const bool rows_live = h->dtype == CRH_DTYPE_BF16 && h->xrow != nullptr && h->x8_cap_tiles >= h->cap_tiles;
+    hipLaunchKernelGGL(k_gather_vectors, dim3((unsigned)ceil_div(n * (h->dim / 8), 256)), dim3(256), 0, static_cast<hipStream_t>(stream), n, rows_dev,
+                       row_base, h->count, h->dim, h->ksteps, h->dtype == CRH_DTYPE_F32 ? h->xf32 : (const float *)nullptr,
+                       rows_live ? h->xrow : (const u32x4 *)nullptr, rows_live ? h->i8_dirty_from : (int64_t)0, h->xt, out_dev);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
 #ifdef CRH_ENABLE_DEBUG   // libcoderag_hip_debug.so only
 int crh_debug_read_ceiling(crh_index *h, void *stream)
 {

@@ -318,6 +318,39 @@ __global__ void k_untile_rows(const u32x4 *__restrict__ xt, int ksteps, int64_t 
     o[7] = bf16_bits_f32(pk.w >> 16);
 }
 
+// crh_index_gather_vectors: out[i][:] = stored row rows[i] - row_base as f32 when this index owns it (0 <= . < count), zeros
+// otherwise (padding -1 and other shards' rows: a merged list is completed by summing the shards' gathers).  One thread per
+// 8 elements.  The row comes from the f32 master (xf32 != nullptr); else from the row-major bf16 side copy while the row's tile
+// is covered by it (tile < xrow_tiles: the tiles the last int8 synchronisation wrote); else from the tiled image -- the same
+// values whichever it is.
+__global__ void k_gather_vectors(int64_t n, const int64_t *__restrict__ rows, int64_t row_base, int64_t count, int dim, int ksteps,
+                                 const float *__restrict__ xf32, const u32x4 *__restrict__ xrow, int64_t xrow_tiles,
+                                 const u32x4 *__restrict__ xt, float *__restrict__ out)
+{
+    const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int chunks = dim >> 3;
+    if (item >= n * chunks) return;
+    const int64_t i = item / chunks;
+    const int c8 = (int)(item - i * chunks);
+    const int64_t g = rows[i], r = g - row_base;
+    float4 *o = reinterpret_cast<float4 *>(out + i * dim + c8 * 8);
+    if (g < 0 || r < 0 || r >= count) {
+        o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+        o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    if (xf32 != nullptr) {
+        const float4 *x = reinterpret_cast<const float4 *>(xf32 + r * dim + c8 * 8);
+        o[0] = x[0];
+        o[1] = x[1];
+        return;
+    }
+    const u32x4 pk = (xrow != nullptr && (r >> 5) < xrow_tiles) ? xrow[(size_t)r * (size_t)chunks + c8]
+                                                                : xt[tiled_index(r >> 5, ksteps, c8 >> 1, c8 & 1, (int)(r & 31))];
+    o[0] = make_float4(bf16_bits_f32(pk.x & 0xffffu), bf16_bits_f32(pk.x >> 16), bf16_bits_f32(pk.y & 0xffffu), bf16_bits_f32(pk.y >> 16));
+    o[1] = make_float4(bf16_bits_f32(pk.z & 0xffffu), bf16_bits_f32(pk.z >> 16), bf16_bits_f32(pk.w & 0xffffu), bf16_bits_f32(pk.w >> 16));
+}
+
 // ------------------------------------------------------------------ compaction (crh_index_compact)
 
 // Stable compaction of the rows: tile_prefix[t] = alive rows in the tiles before t (host prefix sum of the popcounts).

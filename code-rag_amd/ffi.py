@@ -34,6 +34,7 @@ EXPORTS = (
     "crh_gemm_bf16_bias", "crh_gemm_bf16_bias_res_ln", "crh_gemm_bf16_res_lnstats", "crh_gemm_bf16_lnin", "crh_layernorm_apply", "crh_gemm_bf16_bias_res32_ln", "crh_attn_fwd_varlen", "crh_embed_ln",
     "crh_masked_mean_pool", "crh_gather_rows_i32", "crh_gather_rows_bytes", "crh_gather_rerank_columns", "crh_rerank_vector",
     "crh_embed_ln_packed", "crh_attn_fwd_packed", "crh_masked_mean_pool_packed", "crh_encoder_finish",
+    "crh_index_gather_vectors", "crh_mmr_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move")
@@ -172,6 +173,8 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_gather_rows_bytes.argtypes = [i64, vp, i64, i64, vp, i32, vp, vp]
     L.crh_gather_rerank_columns.argtypes = [i64, vp, i64, i64, vp, vp, vp]
     L.crh_rerank_vector.argtypes = [i32, i32, vp, vp, C.POINTER(RerankColumns), vp, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.crh_index_gather_vectors.argtypes = [vp, i64, vp, i64, vp, vp]
+    L.crh_mmr_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -503,6 +506,24 @@ class Index:
         check(lib().crh_index_read_rows(self._handle(), first, n, out.ctypes.data))
         return out
 
+    def gather_vectors(self, rows, row_base: int = 0, out=None, stream: int = 0):
+        """Stored vectors of a candidate table (``crh_index_gather_vectors``): ``rows`` is a CUDA int64 tensor of GLOBAL rows
+        (any shape); returns / fills ``out``, a CUDA float32 tensor ``rows.shape + (dim,)`` -- the stored row where this index
+        owns it (``row_base <= row < row_base + count``), zeros elsewhere (padding -1 included).  Enqueues only."""
+        import torch
+        if not _is_dev(rows):
+            raise NativeError(E_INVALID, "rows must be a device tensor")
+        rows = _typed(rows, "int64", "rows")
+        shape = tuple(rows.shape) + (self.dim,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+        else:
+            _out(out, "float32", "out", shape)
+            if not _is_dev(out):
+                raise NativeError(E_INVALID, "out must be a device tensor")
+        check(lib().crh_index_gather_vectors(self._handle(), int(rows.numel()), _ptr(rows), int(row_base), _ptr(out), stream))
+        return out
+
     def set_tuning(self, seed_tiles: int = 0, wave_cand_cap: int = 0, query_cand_cap: int = 0,
                    force_fallback: int = -1) -> None:
         check(lib().crh_index_set_tuning(self._handle(), seed_tiles, wave_cand_cap, query_cand_cap, force_fallback))
@@ -605,6 +626,37 @@ def merge_topk(scores, rows, out_scores, out_rows, stream: int = 0) -> None:
     _out(out_scores, "float32", "out_scores", (nq, k))
     _out(out_rows, "int64", "out_rows", (nq, k))
     check(lib().crh_merge_topk_strided(nl, nq, k, _ptr(scores), _ptr(rows), ss, rs, _ptr(out_scores), _ptr(out_rows), stream))
+
+
+def mmr_select(scores, rows, vecs, k: int, diversity: float, out_pos=None, out_rows=None, out_scores=None, out_obj=None, stream: int = 0):
+    """Greedy maximal-marginal-relevance picks (``crh_mmr_select``) over candidate lists left on the device: ``scores`` f32 /
+    ``rows`` i64 [nq, c] as a search or merge returns them, ``vecs`` f32 [nq, c, dim] the candidates' stored vectors.  Returns
+    ``(pos i32, rows i64, scores f32, obj f32)``, each [nq, k], CUDA tensors (given or allocated); enqueues only."""
+    import torch
+    for x, what in ((scores, "scores"), (rows, "rows"), (vecs, "vecs")):
+        if not _is_dev(x):
+            raise NativeError(E_INVALID, f"{what} must be a device tensor")
+    if scores.ndim != 2 or vecs.ndim != 3:
+        raise NativeError(E_INVALID, "scores must be [nq, c] and vecs [nq, c, dim]")
+    nq, c = (int(v) for v in scores.shape)
+    dim = int(vecs.shape[2])
+    _typed(scores, "float32", "scores")
+    _out(rows, "int64", "rows", (nq, c))
+    _out(vecs, "float32", "vecs", (nq, c, dim))
+    k = int(k)
+    outs = []
+    for x, want, what in ((out_pos, "int32", "out_pos"), (out_rows, "int64", "out_rows"), (out_scores, "float32", "out_scores"),
+                          (out_obj, "float32", "out_obj")):
+        if x is None:
+            x = torch.empty((nq, max(k, 0)), dtype=getattr(torch, want), device=scores.device)
+        else:
+            _out(x, want, what, (nq, k))
+            if not _is_dev(x):
+                raise NativeError(E_INVALID, f"{what} must be a device tensor")
+        outs.append(x)
+    use_device(scores.device.index)
+    check(lib().crh_mmr_select(nq, c, k, dim, _ptr(scores), _ptr(rows), _ptr(vecs), float(diversity), *(_ptr(x) for x in outs), stream))
+    return tuple(outs)
 
 
 def topk_exchange_buffers(torch, world: int, nq: int, k: int, device):

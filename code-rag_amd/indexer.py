@@ -332,6 +332,10 @@ def _only_set(**kw: Any) -> dict[str, Any] | None:
     return chosen or None
 
 
+def _only_set_given(**kw: Any) -> dict[str, Any]:
+    return {k: v for k, v in kw.items() if v is not None}
+
+
 class VectorSearcher:
     """Dataclass-returning searcher (indexer.py:162-257); every failure -> ``IndexingError`` (quirk Q5)."""
 
@@ -339,25 +343,30 @@ class VectorSearcher:
         self.qdrant = qdrant
         self.embedder = embedder
 
-    async def _run(self, collection: str, query: str, limit: int, filters: dict | None, stage: str, what: str):
+    async def _run(self, collection: str, query: str, limit: int, filters: dict | None, stage: str, what: str,
+                   diversity: float | None = None, candidates: int | None = None):
         try:
             vector = await self.embedder.embed(query)
-            return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, filters=filters)
+            extra = _only_set_given(diversity=diversity, candidates=candidates)      # (absent unless asked for: the reference's call shape)
+            return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, filters=filters, **extra)
         except Exception as e:
             logger.error(f"{what} search failed: {e}")
             raise IndexingError(f"Failed to search {what.lower()} for query: {query}", stage=stage, cause=e)
 
     async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
-                          project_name: str | list[str] | None = None) -> list[CodeSearchResult]:
-        """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant)."""
+                          project_name: str | list[str] | None = None, *, diversity: float | None = None,
+                          candidates: int | None = None) -> list[CodeSearchResult]:
+        """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant).
+        ``diversity`` / ``candidates`` (not in the reference): the store's diversity-aware top-k, forwarded only when given."""
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
                                _only_set(language=language, entity_type=entity_type, project_name=project_name),
-                               "code_search", "Code")
+                               "code_search", "Code", diversity, candidates)
         return self._format_code_results(hits)
 
-    async def search_summaries(self, query: str, limit: int = 10, entity_type: str | None = None) -> list[SummarySearchResult]:
+    async def search_summaries(self, query: str, limit: int = 10, entity_type: str | None = None, *, diversity: float | None = None,
+                               candidates: int | None = None) -> list[SummarySearchResult]:
         hits = await self._run(CollectionName.SUMMARIES.value, query, limit, _only_set(entity_type=entity_type),
-                               "summary_search", "Summaries")
+                               "summary_search", "Summaries", diversity, candidates)
         return self._format_summary_results(hits)
 
     @staticmethod

@@ -28,11 +28,13 @@ class SearchResult:
 
 
 def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
-    async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None) -> ToolResult:
+    async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
+                              candidates: int | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
-            hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type)
+            extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates)) if v is not None}   # (only when asked for)
+            hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
                 get = h.get if isinstance(h, dict) else (lambda k, _h=h: getattr(_h, k, None))
@@ -52,5 +54,9 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             "query": {"type": "string", "description": "Natural language description of functionality", "required": True},
             "limit": {"type": "integer", "description": "Maximum number of results (default: 5)", "required": False},
             "entity_type": {"type": "string", "description": "Filter by type: function, class, method", "required": False},
+            "diversity": {"type": "number", "description": "0..1: prefer results that differ from each other (maximal marginal relevance); "
+                                                           "omit for the plain top matches", "required": False},
+            "candidates": {"type": "integer", "description": "With diversity: how many top matches to choose among (default: 4 x limit)",
+                           "required": False},
         },
     }

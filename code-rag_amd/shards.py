@@ -336,6 +336,58 @@ class ShardSet:
         if self.dist is not None:
             self.dist.all_reduce(packed, op=self.dist.ReduceOp.SUM, group=self.group)
 
+    # ------------------------------------------------------------------ diversity-aware top-k (MMR)
+    def complete_vectors(self, vecs) -> None:
+        """Candidate vectors of a merged list: every rank gathered the rows it owns (zeros elsewhere); ONE all-reduce(sum)
+        completes them, as :meth:`complete_columns` does for the side columns.  It moves ``nq * candidates * dim * 4`` bytes
+        (3 MB for one 768-wide query at 1024 candidates) and has never run on more than one RCCL rank: the two-rank form is
+        exercised with gloo on host tensors only."""
+        if self.dist is not None:
+            self.dist.all_reduce(vecs, op=self.dist.ReduceOp.SUM, group=self.group)
+
+    def search_mmr_device(self, queries, k: int, candidates: int, diversity: float, dfilt):
+        """Diversity-aware top-k on the device, results left there: :meth:`search_device` for ``candidates`` hits per query,
+        every local shard gathers the stored vectors of the rows it owns into one ``[nq, candidates, dim]`` buffer (a row has
+        one owner and the others contribute zeros: the local shards' gathers are summed, and under backend "dist" one
+        all-reduce(sum) of ``nq * candidates * dim * 4`` bytes completes the buffer -- :meth:`complete_vectors`; never run on
+        more than one RCCL rank), then ``crh_mmr_select``.  Returns CUDA tensors ``(pos i32, GLOBAL rows i64, scores f32,
+        obj f32)``, each [nq, k]; ``scores`` are the hits' cosines, -1 rows are padding."""
+        import torch
+        cs, cr = self.search_device(queries, candidates, dfilt)
+        stream = torch.cuda.current_stream(cs.device).cuda_stream
+        vecs = None
+        for s in self.owned:
+            part = self.index[s].gather_vectors(cr, row_base=s * STRIDE, stream=stream)
+            if vecs is None:
+                vecs = part
+            else:
+                vecs += part
+        self.complete_vectors(vecs)
+        return ffi.mmr_select(cs, cr, vecs, k, diversity, stream=stream)
+
+    def search_mmr(self, queries: np.ndarray, k: int, candidates: int, diversity: float, dfilt) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search` with diversity: (scores [nq, k], shard [nq, k], local row [nq, k]) of the MMR picks among the
+        ``candidates`` best hits of every query; -1 rows are padding.  Indexes that hold a native handle take
+        :meth:`search_mmr_device`; injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
+        if all(hasattr(ix, "_handle") for ix in self.index.values()):
+            _, rd, sd, _ = self.search_mmr_device(queries, k, candidates, diversity, dfilt)
+            scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
+        else:
+            if self.ns == 1:
+                cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
+            else:
+                cs, cr = self._search_host(queries, candidates, dfilt)
+            cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
+            vecs = sum(self.index[s].gather_vectors(cr, row_base=s * STRIDE) for s in self.owned)
+            if self.dist is not None:
+                import torch
+                t = torch.from_numpy(np.ascontiguousarray(vecs, dtype=np.float32))
+                self.complete_vectors(t)
+                vecs = t.numpy()
+            _, rows, scores, _ = ffi.mmr_select(cs, cr, vecs, k, diversity)
+            scores, rows = np.asarray(scores), np.asarray(rows)
+        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
+
     # ------------------------------------------------------------------ maintenance
     def compact(self) -> dict[int, np.ndarray]:
         """``crh_index_compact`` on every shard; returns {shard: old_to_new local rows} for ALL shards on every rank."""

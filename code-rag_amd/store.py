@@ -382,6 +382,12 @@ class _Collection:
         scores, shard, local = self.shards.search(queries, limit, dfilt)
         return scores, self.slots_of(shard, local)
 
+    def search_mmr(self, queries: np.ndarray, limit: int, candidates: int, diversity: float, dfilt) -> tuple[np.ndarray, np.ndarray]:
+        """The same for the diversity-aware top-k: the ``limit`` MMR picks among the ``candidates`` best hits of every query
+        (``ShardSet.search_mmr``); scores are the picks' cosines."""
+        scores, shard, local = self.shards.search_mmr(queries, limit, candidates, diversity, dfilt)
+        return scores, self.slots_of(shard, local)
+
     # -- compaction
     def maybe_compact(self) -> bool:
         rows, alive = self.shards.count()
@@ -828,23 +834,30 @@ class HipVectorStore:
         except Exception as e:
             raise VectorStoreError(f"Failed to upsert vectors to {collection}", cause=e)
 
-    def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None):
+    def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None,
+                     diversity: float | None = None, candidates: int | None = None):
         col = self._col(collection)
         dfilt = col.device_filters(filters, must_not)
         nq = queries.shape[0]
-        if dfilt is None or limit <= 0:
+        if dfilt is None or limit <= 0 or (diversity is not None and nq == 0):
             return col, np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
-        scores, slots = col.search(queries, limit, dfilt)
+        if diversity is None:
+            scores, slots = col.search(queries, limit, dfilt)
+        else:
+            scores, slots = col.search_mmr(queries, limit, candidates, diversity, dfilt)
         return col, scores, slots
 
     def _search_hits_sync(self, collection: str, queries: np.ndarray, limits, filters: dict[str, Any] | None,
-                          must_not: dict[str, Any] | None = None) -> list[list[dict[str, Any]]]:
+                          must_not: dict[str, Any] | None = None, diversity: float | None = None,
+                          candidates: int | None = None) -> list[list[dict[str, Any]]]:
         """One pass + the hit dictionaries of every query, built HERE -- inside the worker job, under the store's lock.  Slots
         are positions in the host tables and a compaction renumbers them (the store compacts by itself after deletes and
         replacing upserts): a slot handed back to the event loop could name another point, or none, by the time its payload is
-        read.  ``limits``: one int for all queries, or one per query (coalesced callers keep their own prefix)."""
+        read.  ``limits``: one int for all queries, or one per query (coalesced callers keep their own prefix).  ``diversity``
+        (with its resolved ``candidates``): the pass is the diversity-aware one; greedy picks over one candidate list are
+        prefix-stable, so the prefixes hold there too."""
         per = [int(limits)] * queries.shape[0] if isinstance(limits, (int, np.integer)) else [int(v) for v in limits]
-        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not)
+        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not, diversity, candidates)
         picked = [[(int(r), float(s)) for s, r in zip(srow[:max(lim, 0)], rrow[:max(lim, 0)]) if r >= 0] for lim, srow, rrow in zip(per, scores, slots)]
         flat = col.hits([t for one in picked for t, _ in one], [sc for one in picked for _, sc in one])      # (payloads fetched together)
         out, at = [], 0
@@ -853,14 +866,39 @@ class HipVectorStore:
             at += len(one)
         return out
 
+    @staticmethod
+    def _mmr_args(limit: int, diversity: float | None, candidates: int | None) -> tuple[float | None, int | None]:
+        """Checked ``(diversity, candidates)`` of one call -- ``(None, None)`` for a plain search.  ``candidates`` defaults to
+        ``min(MAX_K, 4 * limit)``.  Raises ``ValueError`` for the caller alone, before the call joins any pass."""
+        if diversity is None:
+            if candidates is not None:
+                raise ValueError("candidates is only meaningful together with diversity")
+            return None, None
+        diversity = float(diversity)
+        if not 0.0 <= diversity <= 1.0:                                    # (NaN fails both comparisons)
+            raise ValueError(f"diversity {diversity} outside [0, 1]")
+        if candidates is None:
+            candidates = min(ffi.MAX_K, 4 * max(int(limit), 1))
+        candidates = int(candidates)
+        if candidates < limit or candidates < 1 or candidates > ffi.MAX_K:
+            raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and <= {ffi.MAX_K}")
+        return diversity, candidates
+
     async def search(self, collection: str, query_vector: list[float] | None, limit: int = 10,
-                     filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+                     filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                     diversity: float | None = None, candidates: int | None = None) -> list[dict[str, Any]]:
         """client.py:132-157: descending cosine, ``[{"id", "score", "payload"}]``.  ``query_vector=None`` is the
         filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0.
         A ``filters`` value may be a list / tuple / set (any of them: Qdrant's ``MatchAny``); ``must_not`` (not in the
         reference's signature) names values a hit must NOT have, one or a collection per key (``Filter(must_not=...)``).
-        Values the collection has never stored contribute nothing and never raise."""
+        Values the collection has never stored contribute nothing and never raise.
+        ``diversity`` in [0, 1] (not in the reference either; Qdrant's ``Mmr(diversity, candidates_limit)``) asks for the
+        diversity-aware top-k: the ``limit`` greedy maximal-marginal-relevance picks among the ``candidates`` best hits
+        (default ``min(MAX_K, 4 * limit)``; ``limit <= candidates <= MAX_K``), selected on the device.  A hit's
+        ``score`` stays its cosine to the query, so the list is no longer sorted by it.  ``diversity=None`` is the plain search."""
         try:
+            if query_vector is not None:
+                diversity, candidates = self._mmr_args(limit, diversity, candidates)
             if query_vector is None:
                 def fetch():
                     col = self._col(collection)
@@ -872,34 +910,36 @@ class HipVectorStore:
             elif limit > ffi.MAX_K:                                      # (likewise: only THIS caller is refused)
                 raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
             elif self._search_coalesce:
-                results = await self._search_coalesced(collection, query_vector, limit, filters, must_not)
+                results = await self._search_coalesced(collection, query_vector, limit, filters, must_not, diversity, candidates)
             else:
                 q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
                 self.search_passes += 1
-                results = (await self._run(self._search_hits_sync, collection, q, limit, filters, must_not))[0]
+                results = (await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates))[0]
             logger.debug(f"Found {len(results)} results in {collection}")
             return results
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
     async def _search_coalesced(self, collection: str, query_vector, limit: int, filters: dict[str, Any] | None,
-                                must_not: dict[str, Any] | None = None):
+                                must_not: dict[str, Any] | None = None, diversity: float | None = None, candidates: int | None = None):
         """One entry of a coalesced pass: queue the query, let the key's drainer run the batch, return this call's slice.
         Calls are grouped by (collection, filter); the pass asks for the largest limit of the group and each caller keeps
-        its own prefix (an exact top-k list is a prefix of every longer one)."""
+        its own prefix (an exact top-k list is a prefix of every longer one).  Diversified calls are grouped by their
+        (diversity, candidates) as well -- one candidate list, one greedy order, each caller its prefix of it -- and never
+        share a pass with plain ones (whose key carries (None, None))."""
         loop = asyncio.get_running_loop()
         name = collection.value if isinstance(collection, CollectionName) else collection
         key = (name, tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
-               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())))
+               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())), (diversity, candidates))
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
         self._search_pending.setdefault(key, []).append((vec, int(limit), fut))
         task = self._search_drainers.get(key)
         if task is None or task.done():
-            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not))
+            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not, diversity, candidates))
         return await fut
 
-    async def _drain_searches(self, key, name: str, filters, must_not=None) -> None:
+    async def _drain_searches(self, key, name: str, filters, must_not=None, diversity=None, candidates=None) -> None:
         while self._search_pending.get(key):
             await asyncio.sleep(self._search_window_s)       # (0: one turn of the loop, so calls issued together travel together)
             batch = self._search_pending.pop(key, [])
@@ -910,7 +950,7 @@ class HipVectorStore:
                 try:
                     q = np.stack([b[0] for b in part])
                     self.search_passes += (len(part) + 63) // 64
-                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters, must_not)
+                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters, must_not, diversity, candidates)
                     for (_, _, fut), hits in zip(part, per_query):
                         if not fut.done():
                             fut.set_result(hits)
@@ -920,12 +960,14 @@ class HipVectorStore:
                             fut.set_exception(e)
 
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
-                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[list[dict[str, Any]]]:
+                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                           diversity: float | None = None, candidates: int | None = None) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
-        serves up to 64 queries."""
+        serves up to 64 queries.  ``diversity`` / ``candidates`` as in :meth:`search`."""
         try:
+            diversity, candidates = self._mmr_args(limit, diversity, candidates)
             q = np.asarray(query_vectors, dtype=np.float32)
-            return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not)
+            return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates)
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 

@@ -315,6 +315,35 @@ int crh_rerank_vector(int nq, int k, const float *scores_dev, const int64_t *row
                       int centrality_top, int32_t *out_index_dev, double *out_score_dev, double *out_signals_dev,
                       int32_t *out_count_dev, int32_t *out_flags_dev, void *stream);
 
+/* ---- diversity-aware top-k (maximal marginal relevance) on the device.  No counterpart in the reference: it only sends
+ * query_points(query, limit, filter) (embeddings/client.py:142-148).  What it stands in for is Qdrant's Mmr(diversity,
+ * candidates_limit) query and the max_marginal_relevance_search of the RAG frameworks' Qdrant adaptors -- known by description
+ * only, not checkable offline: the arithmetic and the tie rule below are this repository's own definition. */
+
+/* out[i, :] = the stored row rows[i] - row_base as f32 [n, dim] when this index owns it (row_base <= rows[i] < row_base +
+ * count), zeros otherwise (padding -1 included): the vector counterpart of crh_gather_rows_*, so the vectors of a merged
+ * multi-shard candidate list are the sum over the shards' gathers.  The values are those of crh_index_read_rows (the f32 master
+ * of an F32 store; the bf16-rounded values of a BF16 store, read from the row-major side copy while the int8 nomination copy
+ * is live, from the tiled image otherwise).  Tombstoned rows still gather (a candidate list never names one).  Enqueues only;
+ * `stream` is the stream of the searches that made the list (the side copy is brought up to date on it). */
+int crh_index_gather_vectors(crh_index *h, int64_t n, const int64_t *rows_dev, int64_t row_base, float *out_dev, void *stream);
+
+/* Greedy MMR over nq candidate lists of c entries (scores f32 descending / rows int64 as crh_search or crh_merge_topk return
+ * them, rows < 0 = padding, at the end) with the candidates' stored vectors vecs_dev f32 [nq, c, dim] (16-byte aligned).  With
+ * rel[i] the candidate's score and sim(i, s) the CANONICAL dot of two candidate rows (acc = acc + x_i[e] * x_s[e], e ascending,
+ * product and sum rounded separately in f32): pick 1 is position 0; pick t > 1 is, among the real candidates not yet picked,
+ * the largest  obj = (1 - diversity) * rel[i] - diversity * max over picked s of sim(i, s)  -- lam = 1 - diversity, lam * rel,
+ * diversity * max and the difference each rounded to f32, no fused multiply-add; ties go to the lower position.  Padding is
+ * never picked (a list whose position 0 is padding is empty).  Per pick: out_pos (int32 position in the list), out_rows, out_scores
+ * (rel: the hit's score stays its cosine to the query) and out_obj (obj at the moment of the pick; lam * rel for pick 1), each
+ * [nq, k]; with fewer than k real candidates the tail is (-1, -1, -inf, -inf).  diversity = 0 returns the first k candidates
+ * unchanged; the first j picks of a k-pick call are the j-pick call.  1 <= k <= c <= CRH_MAX_K, nq >= 0, dim 384 / 768 / 1024 /
+ * 1536; diversity outside [0, 1] or NaN is CRH_E_INVALID.  Needs no index handle (launches on the current device, like
+ * crh_rerank_vector).  Enqueues only; writes every output slot, so the outputs need no clearing. */
+int crh_mmr_select(int nq, int c, int k, int dim, const float *scores_dev, const int64_t *rows_dev, const float *vecs_dev,
+                   float diversity, int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev, float *out_obj_dev,
+                   void *stream);
+
 /* Filter-only fetch: first `limit` alive rows (ascending) matching the filters, host int64 out;
  * n_out receives how many (rows_out_host may be NULL to count only).  Replaces QdrantManager.search(query_vector=None, ...) as used by
  * query/context/builder.py:111-119 and the scroll of embeddings/client.py:178-202. */
