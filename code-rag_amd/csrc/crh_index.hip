@@ -1374,6 +1374,21 @@ int crh_index_gather_vectors(crh_index *h, int64_t n, const int64_t *rows_dev, i
     return CRH_OK;
 }
 
+int crh_index_gather_codes(crh_index *h, int col, int64_t n, const int64_t *rows_dev, int64_t row_base, int32_t *out_codes_dev, void *stream)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (col < 0 || col >= h->ncols) return fail(CRH_E_INVALID, "gather_codes: column %d outside 0..%d", col, h->ncols - 1);
+    if (n < 0 || n > (1LL << 38)) return fail(CRH_E_INVALID, "gather_codes: n=%lld out of range", (long long)n);
+    if (n == 0) return CRH_OK;
+    if (!rows_dev || !out_codes_dev) return fail(CRH_E_INVALID, "gather_codes: NULL pointer");
+    DeviceGuard g(h->device);
+    if (!g.ok) return fail(CRH_E_HIP, "hipSetDevice(%d) failed", h->device);
+    hipLaunchKernelGGL(k_gather_codes, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), n, rows_dev, row_base,
+                       h->count, h->codes + (int64_t)col * h->cap_rows, out_codes_dev);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
 #ifdef CRH_ENABLE_DEBUG   // libcoderag_hip_debug.so only
 int crh_debug_read_ceiling(crh_index *h, void *stream)
 {

@@ -351,6 +351,19 @@ __global__ void k_gather_vectors(int64_t n, const int64_t *__restrict__ rows, in
     o[1] = make_float4(bf16_bits_f32(pk.z & 0xffffu), bf16_bits_f32(pk.z >> 16), bf16_bits_f32(pk.w & 0xffffu), bf16_bits_f32(pk.w >> 16));
 }
 
+// crh_index_gather_codes: out[i] = the code of one column (col_codes = codes + col * cap_rows) for row rows[i] - row_base when
+// this index owns it (0 <= . < count); every other position is left as the caller filled it (-1), so the shards of a process
+// write into one buffer and an all-reduce(MAX) completes it across processes.  One thread per candidate.
+__global__ void k_gather_codes(int64_t n, const int64_t *__restrict__ rows, int64_t row_base, int64_t count,
+                               const int32_t *__restrict__ col_codes, int32_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = rows[i], r = g - row_base;
+    if (g < 0 || r < 0 || r >= count) return;
+    out[i] = col_codes[r];
+}
+
 // ------------------------------------------------------------------ compaction (crh_index_compact)
 
 // Stable compaction of the rows: tile_prefix[t] = alive rows in the tiles before t (host prefix sum of the popcounts).

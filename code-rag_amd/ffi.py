@@ -35,6 +35,7 @@ EXPORTS = (
     "crh_masked_mean_pool", "crh_gather_rows_i32", "crh_gather_rows_bytes", "crh_gather_rerank_columns", "crh_rerank_vector",
     "crh_embed_ln_packed", "crh_attn_fwd_packed", "crh_masked_mean_pool_packed", "crh_encoder_finish",
     "crh_index_gather_vectors", "crh_mmr_select",
+    "crh_index_gather_codes", "crh_group_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move")
@@ -175,6 +176,8 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_rerank_vector.argtypes = [i32, i32, vp, vp, C.POINTER(RerankColumns), vp, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.crh_index_gather_vectors.argtypes = [vp, i64, vp, i64, vp, vp]
     L.crh_mmr_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
+    L.crh_index_gather_codes.argtypes = [vp, i32, i64, vp, i64, vp, vp]
+    L.crh_group_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -524,6 +527,24 @@ class Index:
         check(lib().crh_index_gather_vectors(self._handle(), int(rows.numel()), _ptr(rows), int(row_base), _ptr(out), stream))
         return out
 
+    def gather_codes(self, rows, col: int, row_base: int = 0, out=None, stream: int = 0):
+        """Codes of payload column ``col`` for a candidate table (``crh_index_gather_codes``): ``rows`` is a CUDA int64 tensor
+        of GLOBAL rows (any shape); fills ``out``, a CUDA int32 tensor of the same shape, where this index owns the row
+        (``row_base <= row < row_base + count``) and leaves every other position as it was -- ``out`` is allocated full of -1
+        when not given, and several shards may be handed the same buffer.  Enqueues only."""
+        import torch
+        if not _is_dev(rows):
+            raise NativeError(E_INVALID, "rows must be a device tensor")
+        rows = _typed(rows, "int64", "rows")
+        if out is None:
+            out = torch.full(tuple(rows.shape), -1, dtype=torch.int32, device=rows.device)
+        else:
+            _out(out, "int32", "out", tuple(rows.shape))
+            if not _is_dev(out):
+                raise NativeError(E_INVALID, "out must be a device tensor")
+        check(lib().crh_index_gather_codes(self._handle(), int(col), int(rows.numel()), _ptr(rows), int(row_base), _ptr(out), stream))
+        return out
+
     def set_tuning(self, seed_tiles: int = 0, wave_cand_cap: int = 0, query_cand_cap: int = 0,
                    force_fallback: int = -1) -> None:
         check(lib().crh_index_set_tuning(self._handle(), seed_tiles, wave_cand_cap, query_cand_cap, force_fallback))
@@ -657,6 +678,31 @@ def mmr_select(scores, rows, vecs, k: int, diversity: float, out_pos=None, out_r
     use_device(scores.device.index)
     check(lib().crh_mmr_select(nq, c, k, dim, _ptr(scores), _ptr(rows), _ptr(vecs), float(diversity), *(_ptr(x) for x in outs), stream))
     return tuple(outs)
+
+
+def group_select(scores, rows, codes, k: int, group_size: int, stream: int = 0):
+    """The capped walk (``crh_group_select``) over candidate lists left on the device: ``scores`` f32 / ``rows`` i64 [nq, c]
+    as a search or merge returns them, ``codes`` i32 [nq, c] the candidates' codes in the group_by column
+    (:meth:`Index.gather_codes`).  Returns CUDA tensors ``(pos i32, rows i64, scores f32, codes i32)``, each [nq, k] -- the
+    first ``k`` candidates whose rank in their group is below ``group_size``, in list order, tail ``(-1, -1, -inf, -1)`` -- and
+    ``info`` i32 [nq, 2] = (kept in the whole list, real candidates).  Enqueues only."""
+    import torch
+    for x, what in ((scores, "scores"), (rows, "rows"), (codes, "codes")):
+        if not _is_dev(x):
+            raise NativeError(E_INVALID, f"{what} must be a device tensor")
+    if scores.ndim != 2:
+        raise NativeError(E_INVALID, "scores must be [nq, c]")
+    nq, c = (int(v) for v in scores.shape)
+    _typed(scores, "float32", "scores")
+    _out(rows, "int64", "rows", (nq, c))
+    _out(codes, "int32", "codes", (nq, c))
+    k = int(k)
+    dev = scores.device
+    outs = tuple(torch.empty((nq, max(k, 0)), dtype=dt, device=dev) for dt in (torch.int32, torch.int64, torch.float32, torch.int32))
+    info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
+    use_device(dev.index)
+    check(lib().crh_group_select(nq, c, k, int(group_size), _ptr(scores), _ptr(rows), _ptr(codes), *(_ptr(x) for x in outs), _ptr(info), stream))
+    return outs + (info,)
 
 
 def topk_exchange_buffers(torch, world: int, nq: int, k: int, device):

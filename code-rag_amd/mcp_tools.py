@@ -29,11 +29,11 @@ class SearchResult:
 
 def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
     async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
-                              candidates: int | None = None) -> ToolResult:
+                              candidates: int | None = None, max_per_file: int | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
-            extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates)) if v is not None}   # (only when asked for)
+            extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -58,5 +58,7 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                                            "omit for the plain top matches", "required": False},
             "candidates": {"type": "integer", "description": "With diversity: how many top matches to choose among (default: 4 x limit)",
                            "required": False},
+            "max_per_file": {"type": "integer", "description": "At most this many results from one file (the list still holds `limit` results)",
+                             "required": False},
         },
     }

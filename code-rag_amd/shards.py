@@ -388,6 +388,60 @@ class ShardSet:
             scores, rows = np.asarray(scores), np.asarray(rows)
         return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
 
+    # ------------------------------------------------------------------ per-group cap (group_by / group_size)
+    def complete_codes(self, codes) -> None:
+        """Group codes of a merged candidate list: the buffer starts full of -1 and every rank wrote the codes of the rows it
+        owns (stored codes are >= -1, a row has one owner); ONE all-reduce(MAX) of ``nq * candidates`` int32 completes it.
+        Like :meth:`complete_vectors` it has never run on more than one RCCL rank: the two-rank form is exercised with gloo
+        on host tensors only."""
+        if self.dist is not None:
+            self.dist.all_reduce(codes, op=self.dist.ReduceOp.MAX, group=self.group)
+
+    def search_grouped_device(self, queries, k: int, candidates: int, col: int, group_size: int, dfilt, ungrouped: int | None = None):
+        """The capped walk on the device, results left there: :meth:`search_device` for ``candidates`` hits per query, every
+        local shard writes the column-``col`` codes of the rows it owns into one ``[nq, candidates]`` int32 buffer pre-filled
+        with -1 (:meth:`complete_codes` finishes it under backend "dist"), then ``crh_group_select``.  ``ungrouped``: a code
+        that names no group (the store's code of "no value"): candidates that carry it are never capped.  Returns CUDA tensors
+        ``(pos i32, GLOBAL rows i64, scores f32, codes i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (kept, real)."""
+        import torch
+        cs, cr = self.search_device(queries, candidates, dfilt)
+        stream = torch.cuda.current_stream(cs.device).cuda_stream
+        codes = torch.full(tuple(cr.shape), -1, dtype=torch.int32, device=cr.device)
+        for s in self.owned:
+            self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes, stream=stream)
+        self.complete_codes(codes)
+        if ungrouped is not None:
+            codes.masked_fill_(codes == int(ungrouped), -1)
+        return ffi.group_select(cs, cr, codes, k, group_size, stream=stream)
+
+    def search_grouped(self, queries: np.ndarray, k: int, candidates: int, col: int, group_size: int, dfilt, ungrouped: int | None = None):
+        """One round of the grouped search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], codes i32 [nq, k],
+        info i32 [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits whose rank in their column-``col`` group is below
+        ``group_size`` (a candidate whose code is negative or ``ungrouped`` is never capped and comes back with code -1); -1 rows
+        are padding; ``info`` = (kept in the whole list, real candidates), what the store's exactness
+        rounds decide on.  Indexes that hold a native handle take :meth:`search_grouped_device`; injected host-side indexes
+        (CPU test tier) run the same steps on numpy arrays."""
+        if all(hasattr(ix, "_handle") for ix in self.index.values()):
+            _, rd, sd, cd, info = self.search_grouped_device(queries, k, candidates, col, group_size, dfilt, ungrouped)
+            return sd.cpu().numpy(), rd.cpu().numpy(), cd.cpu().numpy(), info.cpu().numpy()
+        if self.ns == 1:
+            cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
+        else:
+            cs, cr = self._search_host(queries, candidates, dfilt)
+        cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
+        codes = np.full(cr.shape, -1, np.int32)
+        for s in self.owned:
+            self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes)
+        if self.dist is not None:
+            import torch
+            t = torch.from_numpy(codes)
+            self.complete_codes(t)
+            codes = t.numpy()
+        if ungrouped is not None:
+            codes = np.where(codes == int(ungrouped), -1, codes).astype(np.int32)
+        _, rows, scores, gcodes, info = ffi.group_select(cs, cr, codes, k, group_size)
+        return np.asarray(scores, np.float32), np.asarray(rows, np.int64), np.asarray(gcodes, np.int32), np.asarray(info, np.int32)
+
     # ------------------------------------------------------------------ maintenance
     def compact(self) -> dict[int, np.ndarray]:
         """``crh_index_compact`` on every shard; returns {shard: old_to_new local rows} for ALL shards on every rank."""

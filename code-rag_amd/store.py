@@ -28,7 +28,7 @@ from . import ffi
 from .errors import VectorStoreError
 from .settings import get_settings
 from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet
-from .tables import DICT_KEYS, TEXT_KEYS, IdTable, PayloadTable
+from .tables import DICT_KEYS, NONE as NONE_CODE, TEXT_KEYS, IdTable, PayloadTable
 
 logger = logging.getLogger(__name__)
 
@@ -96,6 +96,7 @@ class _Collection:
         self._device = device
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
+        self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
         # One process per shard (backend "dist"): a rank keeps the payload TEXT (content, summary: 4.2 of the 5.2 GB of host
         # tables per 10M chunks) of its OWN rows only -- everybody else stores an empty string there -- and a hit's payload comes
         # from the rank that owns the row (payloads_of: one byte exchange per search, shards.ShardSet.exchange_bytes).
@@ -387,6 +388,76 @@ class _Collection:
         (``ShardSet.search_mmr``); scores are the picks' cosines."""
         scores, shard, local = self.shards.search_mmr(queries, limit, candidates, diversity, dfilt)
         return scores, self.slots_of(shard, local)
+
+    @staticmethod
+    def _exclude_codes(dfilt: list[tuple], col: int, codes) -> list[tuple]:
+        """``dfilt`` + "column ``col`` is none of ``codes``": merged into the filter's own negated set on that column when it
+        has one, a new condition otherwise (``ValueError`` when that would be one more than the device takes)."""
+        out = list(dfilt)
+        for i, cond in enumerate(out):
+            if ffi.is_set_condition(cond) and len(cond) == 3 and cond[2] and cond[0] == col:
+                out[i] = (col, sorted(set(int(c) for c in cond[1]) | set(codes)), True)
+                return out
+        if len(out) >= ffi.MAX_FILTERS:
+            raise ValueError(f"the grouped search needs one more filter condition than the {ffi.MAX_FILTERS} the device takes "
+                             f"(exclude the saturated groups of {col!r}): use fewer conditions")
+        out.append((col, sorted(set(codes)), True))
+        return out
+
+    def search_grouped(self, queries: np.ndarray, limit: int, candidates: int, group_by: str, group_size: int, dfilt) -> tuple[np.ndarray, np.ndarray]:
+        """(scores [nq, limit], slots [nq, limit]) of the EXACT grouped top-``limit``: the first ``limit`` rows,
+        in the order of the plain search, whose rank in their ``group_by`` group is below ``group_size``; rows without the key
+        (or with the value None: the device column holds code 0 for both) belong to no group and are never capped.  One round of ``ShardSet.search_grouped`` answers a query whose capped walk reached ``limit`` inside
+        the candidate list or whose list came back short (the filter has no more rows).  The others go on, together, at
+        ``MAX_K`` candidates; what is still incomplete then takes exclusion rounds, one query at a time: the groups that
+        reached ``group_size`` keep those rows (a group's best ones) and are excluded from the next search by a negated set
+        condition, until the remembered rows and the new list's walk hold ``limit`` rows or the new list is short.  Every such
+        round with a full list saturates at least one more group, so it ends -- after one round per group at the worst.
+        ``self.group_rounds`` counts the queries asked, those that needed the second round, and the exclusion rounds run."""
+        col = self._column(group_by)
+        nq = int(queries.shape[0])
+        out_s, out_r = np.full((nq, limit), -np.inf, np.float32), np.full((nq, limit), -1, np.int64)
+        stats = self.group_rounds
+        stats["queries"] += nq
+        todo = np.arange(nq)
+        last: dict[int, tuple] = {}                 # query -> (scores, rows, codes) of its incomplete MAX_K-candidate round
+        for rnd, c in enumerate((candidates, ffi.MAX_K)):
+            if rnd == 1:
+                if candidates >= ffi.MAX_K:          # (round 1 already ran at MAX_K)
+                    break
+                stats["round2"] += int(todo.size)
+            s, r, g, info = self.shards.search_grouped(queries[todo], limit, c, col, group_size, dfilt, ungrouped=NONE_CODE)
+            done = (info[:, 0] >= limit) | (info[:, 1] < c)
+            out_s[todo[done]], out_r[todo[done]] = s[done], r[done]
+            if c >= ffi.MAX_K:
+                last = {int(qi): (s[i], r[i], g[i]) for i, qi in enumerate(todo) if not done[i]}
+            todo = todo[~done]
+            if not todo.size:
+                break
+        for qi in todo:
+            s, r, g = last[int(qi)]
+            held: list[tuple[float, int]] = []      # the rows of the excluded groups: (score, global row)
+            excluded: set[int] = set()
+            while True:
+                real = r >= 0                       # (an incomplete list kept fewer than limit rows: all of them are here)
+                codes, counts = np.unique(g[real & (g >= 0)], return_counts=True)
+                full = set(int(v) for v in codes[counts >= group_size]) - excluded
+                if not full:                        # cannot happen (see the docstring); never loop on it
+                    raise RuntimeError("grouped search: a full candidate list saturated no group")
+                sat = real & np.isin(g, sorted(full))
+                held += list(zip(s[sat].tolist(), r[sat].tolist()))
+                excluded |= full
+                stats["exclusion"] += 1
+                s, r, g, info = (a[0] for a in self.shards.search_grouped(queries[qi:qi + 1], limit, ffi.MAX_K, col, group_size,
+                                                                          self._exclude_codes(dfilt, col, excluded), ungrouped=NONE_CODE))
+                if int(info[1]) < ffi.MAX_K or len(held) + int(info[0]) >= limit:
+                    break
+            real = r >= 0
+            both = sorted(held + list(zip(s[real].tolist(), r[real].tolist())), key=lambda t: (-t[0], t[1]))[:limit]
+            out_s[qi, :len(both)] = np.asarray([t[0] for t in both], np.float32)       # (a Python float holds an f32 exactly)
+            out_r[qi, :len(both)] = [t[1] for t in both]
+        shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
+        return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
 
     # -- compaction
     def maybe_compact(self) -> bool:
@@ -835,13 +906,15 @@ class HipVectorStore:
             raise VectorStoreError(f"Failed to upsert vectors to {collection}", cause=e)
 
     def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None,
-                     diversity: float | None = None, candidates: int | None = None):
+                     diversity: float | None = None, candidates: int | None = None, group: tuple | None = None):
         col = self._col(collection)
         dfilt = col.device_filters(filters, must_not)
         nq = queries.shape[0]
-        if dfilt is None or limit <= 0 or (diversity is not None and nq == 0):
+        if dfilt is None or limit <= 0 or ((diversity is not None or group is not None) and nq == 0):
             return col, np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
-        if diversity is None:
+        if group is not None:
+            scores, slots = col.search_grouped(queries, limit, candidates, group[0], group[1], dfilt)
+        elif diversity is None:
             scores, slots = col.search(queries, limit, dfilt)
         else:
             scores, slots = col.search_mmr(queries, limit, candidates, diversity, dfilt)
@@ -849,15 +922,16 @@ class HipVectorStore:
 
     def _search_hits_sync(self, collection: str, queries: np.ndarray, limits, filters: dict[str, Any] | None,
                           must_not: dict[str, Any] | None = None, diversity: float | None = None,
-                          candidates: int | None = None) -> list[list[dict[str, Any]]]:
+                          candidates: int | None = None, group: tuple | None = None) -> list[list[dict[str, Any]]]:
         """One pass + the hit dictionaries of every query, built HERE -- inside the worker job, under the store's lock.  Slots
         are positions in the host tables and a compaction renumbers them (the store compacts by itself after deletes and
         replacing upserts): a slot handed back to the event loop could name another point, or none, by the time its payload is
         read.  ``limits``: one int for all queries, or one per query (coalesced callers keep their own prefix).  ``diversity``
         (with its resolved ``candidates``): the pass is the diversity-aware one; greedy picks over one candidate list are
-        prefix-stable, so the prefixes hold there too."""
+        prefix-stable, so the prefixes hold there too.  ``group`` = ``(group_by, group_size)``: the pass is the grouped one
+        (``_Collection.search_grouped``); the first j rows of its answer are the j-row answer, so the prefixes hold again."""
         per = [int(limits)] * queries.shape[0] if isinstance(limits, (int, np.integer)) else [int(v) for v in limits]
-        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not, diversity, candidates)
+        col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not, diversity, candidates, group)
         picked = [[(int(r), float(s)) for s, r in zip(srow[:max(lim, 0)], rrow[:max(lim, 0)]) if r >= 0] for lim, srow, rrow in zip(per, scores, slots)]
         flat = col.hits([t for one in picked for t, _ in one], [sc for one in picked for _, sc in one])      # (payloads fetched together)
         out, at = [], 0
@@ -884,9 +958,31 @@ class HipVectorStore:
             raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and <= {ffi.MAX_K}")
         return diversity, candidates
 
+    def _group_args(self, collection: str, limit: int, group_by: str | None, group_size: int, diversity: float | None,
+                    candidates: int | None, has_vector: bool = True) -> tuple[tuple | None, int | None]:
+        """Checked ``((group_by, group_size), candidates)`` of one grouped call -- ``(None, candidates)`` untouched for a call
+        without ``group_by``.  ``candidates`` defaults to ``min(MAX_K, 4 * limit)``, bounds as for the diversity-aware search.
+        Raises ``ValueError`` for the caller alone, before the call joins any pass."""
+        if int(group_size) < 1:
+            raise ValueError(f"group_size {group_size} must be >= 1")
+        if group_by is None:
+            return None, candidates
+        if diversity is not None:
+            raise ValueError("group_by and diversity cannot be combined")
+        if not has_vector:
+            raise ValueError("group_by needs a query vector (the filter-only fetch has no order to cap)")
+        self._col(collection)._column(group_by)                             # (ValueError: not a filterable key of the collection)
+        if candidates is None:
+            candidates = min(ffi.MAX_K, 4 * max(int(limit), 1))
+        candidates = int(candidates)
+        if candidates < limit or candidates < 1 or candidates > ffi.MAX_K:
+            raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and <= {ffi.MAX_K}")
+        return (group_by, int(group_size)), candidates
+
     async def search(self, collection: str, query_vector: list[float] | None, limit: int = 10,
                      filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                     diversity: float | None = None, candidates: int | None = None) -> list[dict[str, Any]]:
+                     diversity: float | None = None, candidates: int | None = None,
+                     group_by: str | None = None, group_size: int = 1) -> list[dict[str, Any]]:
         """client.py:132-157: descending cosine, ``[{"id", "score", "payload"}]``.  ``query_vector=None`` is the
         filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0.
         A ``filters`` value may be a list / tuple / set (any of them: Qdrant's ``MatchAny``); ``must_not`` (not in the
@@ -895,9 +991,16 @@ class HipVectorStore:
         ``diversity`` in [0, 1] (not in the reference either; Qdrant's ``Mmr(diversity, candidates_limit)``) asks for the
         diversity-aware top-k: the ``limit`` greedy maximal-marginal-relevance picks among the ``candidates`` best hits
         (default ``min(MAX_K, 4 * limit)``; ``limit <= candidates <= MAX_K``), selected on the device.  A hit's
-        ``score`` stays its cosine to the query, so the list is no longer sorted by it.  ``diversity=None`` is the plain search."""
+        ``score`` stays its cosine to the query, so the list is no longer sorted by it.  ``diversity=None`` is the plain search.
+        ``group_by`` (one of the collection's filterable keys; Qdrant's ``query_points_groups``, the reference's
+        ``max_per_file`` done before the cut instead of after it) caps the hits per value of that key at ``group_size``: the
+        answer is EXACTLY the first ``limit`` rows of the plain order whose rank among the rows of their own value is below
+        ``group_size``, still sorted by score, scores and ids unchanged.  Rows without the key (or with None)
+        are never capped.  ``candidates`` (default ``min(MAX_K, 4 * limit)``) is how many hits the first round looks at; the
+        store goes on by itself when that does not settle the answer.  Not combinable with ``diversity``."""
         try:
-            if query_vector is not None:
+            group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates, query_vector is not None)
+            if query_vector is not None and group is None:
                 diversity, candidates = self._mmr_args(limit, diversity, candidates)
             if query_vector is None:
                 def fetch():
@@ -910,36 +1013,38 @@ class HipVectorStore:
             elif limit > ffi.MAX_K:                                      # (likewise: only THIS caller is refused)
                 raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
             elif self._search_coalesce:
-                results = await self._search_coalesced(collection, query_vector, limit, filters, must_not, diversity, candidates)
+                results = await self._search_coalesced(collection, query_vector, limit, filters, must_not, diversity, candidates, group)
             else:
                 q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
                 self.search_passes += 1
-                results = (await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates))[0]
+                results = (await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates, group))[0]
             logger.debug(f"Found {len(results)} results in {collection}")
             return results
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
     async def _search_coalesced(self, collection: str, query_vector, limit: int, filters: dict[str, Any] | None,
-                                must_not: dict[str, Any] | None = None, diversity: float | None = None, candidates: int | None = None):
+                                must_not: dict[str, Any] | None = None, diversity: float | None = None, candidates: int | None = None,
+                                group: tuple | None = None):
         """One entry of a coalesced pass: queue the query, let the key's drainer run the batch, return this call's slice.
         Calls are grouped by (collection, filter); the pass asks for the largest limit of the group and each caller keeps
         its own prefix (an exact top-k list is a prefix of every longer one).  Diversified calls are grouped by their
         (diversity, candidates) as well -- one candidate list, one greedy order, each caller its prefix of it -- and never
-        share a pass with plain ones (whose key carries (None, None))."""
+        share a pass with plain ones (whose key carries (None, None)).  Grouped calls likewise: their key carries
+        (group_by, group_size, candidates), and the first j rows of a grouped answer are the j-row answer."""
         loop = asyncio.get_running_loop()
         name = collection.value if isinstance(collection, CollectionName) else collection
         key = (name, tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
-               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())), (diversity, candidates))
+               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())), (diversity, candidates), group)
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
         self._search_pending.setdefault(key, []).append((vec, int(limit), fut))
         task = self._search_drainers.get(key)
         if task is None or task.done():
-            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not, diversity, candidates))
+            self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not, diversity, candidates, group))
         return await fut
 
-    async def _drain_searches(self, key, name: str, filters, must_not=None, diversity=None, candidates=None) -> None:
+    async def _drain_searches(self, key, name: str, filters, must_not=None, diversity=None, candidates=None, group=None) -> None:
         while self._search_pending.get(key):
             await asyncio.sleep(self._search_window_s)       # (0: one turn of the loop, so calls issued together travel together)
             batch = self._search_pending.pop(key, [])
@@ -950,7 +1055,7 @@ class HipVectorStore:
                 try:
                     q = np.stack([b[0] for b in part])
                     self.search_passes += (len(part) + 63) // 64
-                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters, must_not, diversity, candidates)
+                    per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], filters, must_not, diversity, candidates, group)
                     for (_, _, fut), hits in zip(part, per_query):
                         if not fut.done():
                             fut.set_result(hits)
@@ -961,13 +1066,53 @@ class HipVectorStore:
 
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
                            filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                           diversity: float | None = None, candidates: int | None = None) -> list[list[dict[str, Any]]]:
+                           diversity: float | None = None, candidates: int | None = None,
+                           group_by: str | None = None, group_size: int = 1) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
-        serves up to 64 queries.  ``diversity`` / ``candidates`` as in :meth:`search`."""
+        serves up to 64 queries.  ``diversity`` / ``candidates`` / ``group_by`` / ``group_size`` as in :meth:`search`."""
         try:
-            diversity, candidates = self._mmr_args(limit, diversity, candidates)
+            group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates)
+            if group is None:
+                diversity, candidates = self._mmr_args(limit, diversity, candidates)
+            elif limit > ffi.MAX_K:
+                raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
             q = np.asarray(query_vectors, dtype=np.float32)
-            return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates)
+            return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates, group)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_groups(self, collection: str, query_vector: list[float], group_by: str, limit: int = 5, group_size: int = 3,
+                            filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+        """Qdrant's ``query_points_groups(group_by, limit, group_size)``, exact: ``[{"id": value, "hits": [...]}]`` -- the
+        ``limit`` values of ``group_by`` whose best hit scores highest, in that order, each with its best ``group_size`` hits
+        (``limit * group_size <= MAX_K``).  Rows without the key (or with None) are left out.  Two grouped searches: one hit
+        per group names the groups; a second one, filtered to those values (a short any-of list: the sparse-mask route),
+        fills them.  The caller's own ``filters`` / ``must_not`` hold in both (the groups found already satisfy them)."""
+        try:
+            limit, group_size = int(limit), int(group_size)
+            if limit < 1 or group_size < 1 or limit * group_size > ffi.MAX_K:
+                raise ValueError(f"search_groups: limit {limit} x group_size {group_size} must be within 1..{ffi.MAX_K}")
+            if query_vector is None:
+                raise ValueError("search_groups needs a query vector")
+            self._col(collection)._column(group_by)
+            banned = dict(must_not or {})
+            mine = banned.get(group_by, [])
+            banned[group_by] = [None] + list(mine if isinstance(mine, _COLLECTIONS) else [mine])       # (no value, no group)
+            first = await self.search(collection, query_vector, limit=limit, filters=filters, must_not=banned, group_by=group_by, group_size=1)
+            values = [h["payload"].get(group_by) for h in first]
+            if not values:
+                return []
+            inside = dict(filters or {})
+            inside[group_by] = values
+            flat = await self.search(collection, query_vector, limit=len(values) * group_size, filters=inside, must_not=must_not,
+                                     group_by=group_by, group_size=group_size)
+            groups: dict[Any, dict[str, Any]] = {}
+            for h in flat:                                                   # (first appearance = the group's best hit: the order asked for)
+                v = h["payload"].get(group_by)
+                groups.setdefault(_value_key(v), {"id": v, "hits": []})["hits"].append(h)
+            return list(groups.values())
+        except VectorStoreError:
+            raise
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 

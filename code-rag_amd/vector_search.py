@@ -64,6 +64,12 @@ def _mmr_kwargs(diversity: float | None, candidates: int | None) -> dict:
     return kw
 
 
+def _group_kwargs(max_per_file: int | None) -> dict:
+    """``max_per_file`` as the store's grouped search (at most that many chunks of one file, decided before the cut: the
+    list stays ``limit`` long) -- only when given."""
+    return {} if max_per_file is None else {"group_by": "file_path", "group_size": max_per_file}
+
+
 def _project(hit: dict, keys: tuple[str, ...]) -> dict:
     payload = hit["payload"]
     row = {"score": hit["score"]}
@@ -78,7 +84,8 @@ class VectorSearcher:
         self.embedder = embedder
 
     async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
-                      must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None):
+                      must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None,
+                      max_per_file: int | None = None):
         """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
         the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given, and
         so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k)."""
@@ -88,6 +95,7 @@ class VectorSearcher:
             if must_not:
                 kwargs["must_not"] = must_not
             kwargs.update(_mmr_kwargs(diversity, candidates))
+            kwargs.update(_group_kwargs(max_per_file))
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, **kwargs)
         except EmbeddingError as e:
             logger.error(f"Embedding error: {e}")
@@ -98,29 +106,34 @@ class VectorSearcher:
 
     async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                           entity_type: str | None = None, project_name: str | list[str] | None = None, *,
-                          diversity: float | None = None, candidates: int | None = None) -> list[dict]:
+                          diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
         ``diversity`` in [0, 1] (not in the reference): ``limit`` maximal-marginal-relevance picks among the ``candidates``
-        best hits instead of the plain top-``limit`` (``HipVectorStore.search``)."""
+        best hits instead of the plain top-``limit`` (``HipVectorStore.search``).  ``max_per_file`` (the reference applies it
+        after the fetch, query/reranker.py:122-145, and comes back short): at most that many chunks of one file among the
+        ``limit`` results, exactly (``group_by="file_path"``); not together with ``diversity``."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
-                                  "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates)
+                                  "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
+                                  max_per_file=max_per_file)
         return [_project(h, _CODE_KEYS) for h in hits]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
-                               diversity: float | None = None, candidates: int | None = None) -> list[dict]:
+                               diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6)."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
-                                  "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates)
+                                  "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
+                                  max_per_file=max_per_file)
         return [_project(h, _SUMMARY_KEYS) for h in hits]
 
     async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
-                                exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None) -> list[dict]:
+                                exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,
+                                max_per_file: int | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``."""
@@ -130,7 +143,8 @@ class VectorSearcher:
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch, _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
-                                  must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates)
+                                  must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
+                                  max_per_file=max_per_file)
         kept = []
         for h in hits:
             if exclude_file and h["payload"].get("file_path") == exclude_file:
@@ -143,7 +157,8 @@ class VectorSearcher:
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
-                                diversity: float | None = None, candidates: int | None = None) -> list[list[dict]]:
+                                diversity: float | None = None, candidates: int | None = None,
+                                max_per_file: int | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         try:
@@ -155,7 +170,8 @@ class VectorSearcher:
                     raise QueryError("Search query cannot be empty")
                 vectors = np.asarray(await self.embedder.embed_batch(texts), dtype=np.float32)
             per_query = await self.qdrant.search_batch(collection=CollectionName.CODE_CHUNKS.value, query_vectors=vectors,
-                                                       limit=limit, filters=filters or None, **_mmr_kwargs(diversity, candidates))
+                                                       limit=limit, filters=filters or None, **_mmr_kwargs(diversity, candidates),
+                                                       **_group_kwargs(max_per_file))
         except EmbeddingError as e:
             raise QueryError("Failed to embed search query", cause=e)
         except VectorStoreError as e:

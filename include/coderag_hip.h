@@ -344,6 +344,32 @@ int crh_mmr_select(int nq, int c, int k, int dim, const float *scores_dev, const
                    float diversity, int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev, float *out_obj_dev,
                    void *stream);
 
+/* ---- exact per-group cap on the device (group_by / group_size).  The reference caps results per file AFTER the fetch
+ * (ResultReranker.deduplicate(max_per_file=3), query/reranker.py:122-145; RankingConfig.max_per_file) and is left short when one
+ * file owns the list; Qdrant's query_points_groups(group_by, limit, group_size) is "best effort".  The definition here is this
+ * repository's own and exact: a candidate's GROUP is its code in one column, its RANK IN ITS GROUP the number
+ * of earlier candidates of the list with the same code; a candidate is kept iff that rank is < group_size.  A negative code
+ * (-1: the key is absent) belongs to no group and is always kept. */
+
+/* out[i] = the code of column `col` of row rows[i] - row_base when this index owns that row (row_base <= rows[i] < row_base +
+ * count); every other position (padding -1, other shards' rows) is left UNTOUCHED: the caller pre-fills the buffer with -1, the
+ * shards of one process write into the same buffer, and across processes one all-reduce(MAX) completes it (stored codes are
+ * >= -1).  Tombstoned rows still gather.  col outside 0..n_code_cols-1 is CRH_E_INVALID.  Enqueues only. */
+int crh_index_gather_codes(crh_index *h, int col, int64_t n, const int64_t *rows_dev, int64_t row_base, int32_t *out_codes_dev,
+                           void *stream);
+
+/* Capped walk over nq candidate lists of c entries (scores f32 / rows int64 as crh_search or crh_merge_topk* return them, rows
+ * < 0 = padding; codes int32 [nq, c] as crh_index_gather_codes completes them).  The kept candidates (real, and code < 0 or rank
+ * in group < group_size; padding neither counts nor is kept) are written in list order, the first k of them: out_pos (int32
+ * position in the list), out_rows, out_scores (the score's bits, unchanged), out_codes, each [nq, k]; the tail is (-1, -1, -inf,
+ * -1).  out_info int32 [nq, 2] = (kept: kept candidates of the WHOLE list, not clipped at k; real: non-padding candidates).
+ * group_size >= c returns the first k candidates unchanged; the first j outputs of a k-output call are the j-output call.
+ * 1 <= k <= c <= CRH_MAX_K, group_size >= 1, nq >= 0, anything else CRH_E_INVALID.  Needs no index handle (launches on the
+ * current device, like crh_mmr_select).  Deterministic; enqueues only; writes every output slot. */
+int crh_group_select(int nq, int c, int k, int group_size, const float *scores_dev, const int64_t *rows_dev,
+                     const int32_t *codes_dev, int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev,
+                     int32_t *out_codes_dev, int32_t *out_info_dev, void *stream);
+
 /* Filter-only fetch: first `limit` alive rows (ascending) matching the filters, host int64 out;
  * n_out receives how many (rows_out_host may be NULL to count only).  Replaces QdrantManager.search(query_vector=None, ...) as used by
  * query/context/builder.py:111-119 and the scroll of embeddings/client.py:178-202. */
