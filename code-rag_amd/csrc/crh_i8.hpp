@@ -16,7 +16,8 @@
 //   * k_select<.., I8>: L = k-th largest lo of the candidates (again a lower bound of the true k-th score), survivors = hi >= L,
 //     canonical re-score and exact top-k as before.
 // Results are bit-identical to the bf16 scan's and the oracle's.  On N(0, I)/sqrt(D) rows at D = 768: s_r ~ 9.6e-4, |d| ~ 8.0
-// (max 8.6), interval half-width ~ 8.3e-3 = 0.23 sigma of the score distribution; ~21 k candidates and ~800 survivors per query
+// (max 8.8 over 60 k rows), interval half-width ~ 8.6e-3 = 0.24 sigma of the score distribution, every allowance included (measured:
+// tests/test_i8_intervals_gpu.py, which holds every interval and threshold against the oracle); ~21 k candidates and ~800 survivors per query
 // and 10M rows, against a pass that reads 7.68 + 0.04 GB instead of 15.36 GB.  Rows with outlier elements get a large s_r and
 // are simply nominated more often; when the candidate buffers overflow the host re-runs the batch on the bf16 scan
 // (finish_pending) and, after three overflows in a row, rests the int8 copy of that index for 4096 batches.
@@ -42,6 +43,16 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int kI8SampleTiles = 8192;   // most sample tiles behind the thresholds of k_scan_i8 (a workgroup keeps one query's maxima in LDS)
 constexpr float kI8QueryLevels = 16256.0f;   // 127 * 128: Q = 128 H + L with H in [-127, 127], L in [-64, 63]
+
+#ifdef CRH_ENABLE_DEBUG
+// libcoderag_hip_debug.so only (crh_debug_i8_intervals, tests/test_i8_intervals_gpu.py): while `lo` is set, the sample launch of
+// k_scan_i8 also leaves both ends of every interval it works out, as f32: [64 query slots][pitch] each, pitch >= 32 * tiles.
+struct I8DebugEnds {
+    float *hi, *lo;
+    long long pitch;
+};
+__device__ I8DebugEnds g_i8_debug_ends;
+#endif
 
 // ------------------------------------------------------------------ stored rows -> int8 tiles + per-row scale
 // One wave per tile.  dn_bits: f32 bits of the running maximum of |d|_2 (+ allowance for the f32 evaluation) over all rows
@@ -409,6 +420,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_scan_i8(
             scan_tile(xp, xn, acc);
             float hi[QB][16];
             intervals(acc, sr, hi);
+#ifdef CRH_ENABLE_DEBUG
+            if (g_i8_debug_ends.lo != nullptr) {         // (the ends as this kernel evaluates them: intervals() and lower_end() themselves)
+#pragma unroll
+                for (int b = 0; b < QB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const size_t at = (size_t)(b * 32 + (lane & 31)) * (size_t)g_i8_debug_ends.pitch + (size_t)tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        g_i8_debug_ends.hi[at] = hi[b][r];
+                        g_i8_debug_ends.lo[at] = lower_end(hi[b][r], sr, b, r);
+                    }
+            }
+#endif
             if (shi != nullptr) {
 #pragma unroll
                 for (int b = 0; b < QB; ++b)

@@ -509,6 +509,23 @@ int i8_sync(crh_index *h, hipStream_t st)
     return CRH_OK;
 }
 
+// what separates a row's canonical score from the exact dot of the QUANTISED-FROM rows and the canonical query: the two f32
+// summation orders only -- the copy of an f32 store is quantised from its f32 master, not from the bf16 tiles
+float i8_c_abs(const crh_index *h) { return 1.5e-4f * (h->dim > 768 ? (float)h->dim / 768.f : 1.f) + 1e-5f; }
+
+// The sample behind the thresholds: G tiles, every S-th one.  It is read twice (its own launch, then the pass) and buys the
+// thresholds: its cost grows with G, the candidates it leaves with 1 / G -- the best G goes with the square root of the corpus.
+// 8192 tiles were tuned at 10M rows (2.6 % of them); the same 8192 are 26 % of a 1M-row corpus (profiles/r04_i8_crossover.txt).
+// An explicit sample size is kept.
+void i8_sample_plan(const crh_index *h, int64_t ntiles, int *G, int *S)
+{
+    int64_t g_auto = h->i8_sample;
+    if (h->seed_tiles == 4096 && h->i8_sample_auto)
+        g_auto = std::max<int64_t>(1024, std::min<int64_t>(h->i8_sample, (int64_t)(h->i8_sample * std::sqrt((double)ntiles / 312500.0))));
+    *G = (int)std::min<int64_t>(h->seed_tiles == 4096 ? g_auto : h->seed_tiles, ntiles);
+    *S = (int)std::max<int64_t>(1, ntiles / *G);
+}
+
 // PART 1: the sample tiles, 2: the thresholds (one workgroup per query), 3: the pass -- three launches, stream order between them
 template <int PART>
 int launch_scan_i8(crh_index *h, crh_index::Workspace &w, int blocks, hipStream_t st, const uint32_t *mask, int ntiles, int G, int S, int k, float c_abs,
@@ -632,17 +649,9 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
 
     if (via_i8) {
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ntiles, kI8Waves), h->cu_count));
-        // The sample is read twice (its own launch, then the pass) and buys the thresholds: its cost grows with G, the candidates
-        // it leaves with 1 / G -- the best G goes with the square root of the corpus.  8192 tiles were tuned at 10M rows (2.6 % of
-        // them); the same 8192 are 26 % of a 1M-row corpus (profiles/r04_i8_crossover.txt).  An explicit sample size is kept.
-        int64_t g_auto = h->i8_sample;
-        if (h->seed_tiles == 4096 && h->i8_sample_auto)
-            g_auto = std::max<int64_t>(1024, std::min<int64_t>(h->i8_sample, (int64_t)(h->i8_sample * std::sqrt((double)ntiles / 312500.0))));
-        const int G8 = (int)std::min<int64_t>(h->seed_tiles == 4096 ? g_auto : h->seed_tiles, ntiles);
-        const int S8 = (int)std::max<int64_t>(1, ntiles / G8);
-        // what separates a row's canonical score from the exact dot of the QUANTISED-FROM rows and the canonical query: the two f32
-        // summation orders only -- the copy of an f32 store is quantised from its f32 master, not from the bf16 tiles
-        const float c_abs = 1.5e-4f * (h->dim > 768 ? (float)h->dim / 768.f : 1.f) + 1e-5f;
+        int G8, S8;
+        i8_sample_plan(h, ntiles, &G8, &S8);
+        const float c_abs = i8_c_abs(h);
         if (h->profiling && h->profile_whole_scan) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));   // (all three launches of the scan)
         // the sample launch records the upper ends of its tiles' rows and the pass takes those tiles' candidates from the record
         // instead of reading and multiplying the tiles again (crh_i8.hpp, `shi`; CODERAG_HIP_I8_SAMPLE_RECORD=0: the pass reads every tile)
@@ -1418,6 +1427,99 @@ int crh_debug_i8_move(crh_index *h)
     h->x8 = nx;
     h->srow = ns;
     h->i8_dirty_from = 0;
+    return CRH_OK;
+}
+
+// What the int8 scan computes before it nominates: the interval of every (query, row), the quantisation parameters and the
+// thresholds, all from the product's own launches (k_requant_i8, k_prep_queries<.., true>, k_scan_i8 PART 1 and PART 2).  Nothing
+// here restates the arithmetic: the upper ends come from the `shi` record of a sample launch over EVERY tile (G = tiles, S = 1),
+// both ends as f32 from the store that launch makes in this build only (crh_i8.hpp, g_i8_debug_ends), the thresholds from a
+// second sample launch with the sample enqueue_batch would take, followed by the threshold launch.  Queries go through in
+// batches of batch_q like a search's.  Host pointers throughout; the index must have no search pending.
+int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, const crh_filter *filters, int n_filters, float *hi_rec_out,
+                           float *hi_out, float *lo_out, float *srow_out, float *qpar_out, float *dn_out, float *c_abs_out, float *tau_out)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (nq < 1 || nq > kMaxQ || !queries) return fail(CRH_E_INVALID, "nq=%d outside 1..%d or no queries", nq, kMaxQ);
+    if (!hi_rec_out || !hi_out || !lo_out || !srow_out || !qpar_out || !dn_out || !c_abs_out || !tau_out) return fail(CRH_E_INVALID, "NULL output pointer");
+    if (n_filters < 0 || n_filters > CRH_MAX_FILTERS || (n_filters > 0 && !filters)) return fail(CRH_E_INVALID, "n_filters=%d outside 0..%d", n_filters, CRH_MAX_FILTERS);
+    if (!h->pending.empty()) return fail(CRH_E_INVALID, "a search is pending: crh_search_finish first");
+    const int64_t ntiles = ceil_div(h->count, kTileRows);
+    if (ntiles < 1 || ntiles > kI8SampleTiles) return fail(CRH_E_INVALID, "%lld tiles outside 1..%d (the record of upper ends holds that many)", (long long)ntiles, kI8SampleTiles);
+    if (!i8_use(h, 1, k)) return fail(CRH_E_INVALID, "this index does not nominate from an int8 copy at k=%d", k);
+    DeviceGuard g(h->device);
+    if (!g.ok) return fail(CRH_E_HIP, "hipSetDevice(%d) failed", h->device);
+    hipStream_t st = nullptr;
+    CRH_TRY(ensure_workspace0(h));
+    crh_index::Workspace &w = h->ws;
+    if ((int64_t)w.ws_seed * kWideQ < (int64_t)kMaxQ * ntiles) return fail(CRH_E_INVALID, "the sample keys of %lld tiles do not fit the workspace", (long long)ntiles);
+    if (!w.shi) CRH_TRY(dev_alloc(&w.shi, (int64_t)kI8SampleTiles * 64 * 4));
+    struct Tmp {
+        float *p = nullptr;
+        ~Tmp() { dev_free(p); }
+    } q_dev, ends;
+    const int64_t pitch = ntiles * 32, count = h->count;
+    CRH_TRY(dev_alloc(&q_dev.p, (int64_t)nq * h->dim));
+    CRH_TRY(dev_alloc(&ends.p, 2 * kMaxQ * pitch));
+    CRH_HIP(hipMemcpy(q_dev.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice));
+    FilterKey key;
+    key_from_filters(filters, n_filters, key);
+    const int QB = h->batch_q / 32;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ntiles, kI8Waves), h->cu_count));
+    const int wave_cap = w.ws_wave_cap * (kWaves / kI8Waves), qcap = w.ws_qcap;
+    const float c_abs = i8_c_abs(h);
+    SearchStatus *stt = h->status;
+    std::vector<uint32_t> rec((size_t)ntiles * QB * 2 * 64 * 4);
+    for (int q0 = 0; q0 < nq; q0 += h->batch_q) {
+        const int b = std::min(h->batch_q, nq - q0);
+        MaskRef mask;
+        CRH_TRY(build_mask(h, w, key, &mask, st));
+        CRH_TRY(i8_sync(h, st));
+        if (!i8_use(h, b, k)) return fail(CRH_E_INVALID, "no memory for the int8 copy");
+        if (h->dtype == CRH_DTYPE_BF16)
+            hipLaunchKernelGGL((k_prep_queries<true, true>), dim3(h->batch_q), dim3(64), 0, st, q_dev.p + (int64_t)q0 * h->dim, b, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
+        else
+            hipLaunchKernelGGL((k_prep_queries<false, true>), dim3(h->batch_q), dim3(64), 0, st, q_dev.p + (int64_t)q0 * h->dim, b, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
+        CRH_HIP(hipGetLastError());
+        // every tile as a sample tile: the record of upper ends, and both ends as f32
+        I8DebugEnds on{ends.p, ends.p + kMaxQ * pitch, pitch}, off{nullptr, nullptr, 0};
+        CRH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_i8_debug_ends), &on, sizeof(on)));
+        const int rc = launch_scan_i8<1>(h, w, blocks, st, mask.mask, (int)ntiles, (int)ntiles, 1, k, c_abs, b, wave_cap, qcap, stt, w.shi);
+        CRH_HIP(hipDeviceSynchronize());
+        CRH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_i8_debug_ends), &off, sizeof(off)));
+        CRH_TRY(rc);
+        CRH_HIP(hipMemcpy(rec.data(), w.shi, rec.size() * 4, hipMemcpyDeviceToHost));
+        for (int q = 0; q < b; ++q) {
+            CRH_HIP(hipMemcpy(hi_out + (int64_t)(q0 + q) * count, on.hi + (int64_t)q * pitch, (size_t)count * 4, hipMemcpyDeviceToHost));
+            CRH_HIP(hipMemcpy(lo_out + (int64_t)(q0 + q) * count, on.lo + (int64_t)q * pitch, (size_t)count * 4, hipMemcpyDeviceToHost));
+        }
+        // the record's layout (crh_i8.hpp, `shi`): [tile][block][v][lane] of four words, two bf16 each; value 8 v + 2 e (+ 1) of a
+        // lane is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the tile for query 32 block + (lane & 31)
+        for (int64_t t = 0; t < ntiles; ++t)
+            for (int blk = 0; blk < QB; ++blk)
+                for (int v = 0; v < 2; ++v)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int e = 0; e < 8; ++e) {
+                            const uint32_t word = rec[((((size_t)t * QB + blk) * 2 + v) * 64 + lane) * 4 + (e >> 1)];
+                            const uint32_t bits = (e & 1) ? (word & 0xffff0000u) : (word << 16);
+                            const int r = 8 * v + e, q = blk * 32 + (lane & 31);
+                            const int64_t row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                            if (q < b && row < count) memcpy(hi_rec_out + (int64_t)(q0 + q) * count + row, &bits, 4);
+                        }
+        // the thresholds: the sample a search takes, then the threshold launch
+        int G8, S8;
+        i8_sample_plan(h, ntiles, &G8, &S8);
+        u32x4 *shi = h->i8_sample_record ? w.shi : nullptr;
+        CRH_TRY(launch_scan_i8<1>(h, w, blocks, st, mask.mask, (int)ntiles, G8, S8, k, c_abs, b, wave_cap, qcap, stt, shi));
+        CRH_TRY(launch_scan_i8<2>(h, w, blocks, st, mask.mask, (int)ntiles, G8, S8, k, c_abs, b, wave_cap, qcap, stt, shi));
+        CRH_HIP(hipDeviceSynchronize());
+        CRH_HIP(hipMemcpy(tau_out + q0, w.tau, (size_t)b * 4, hipMemcpyDeviceToHost));
+        CRH_HIP(hipMemcpy(qpar_out + (int64_t)q0 * 4, w.qpar, (size_t)b * 16, hipMemcpyDeviceToHost));
+    }
+    for (int64_t i = (int64_t)nq * 4; i < (int64_t)kMaxQ * 4; ++i) qpar_out[i] = 0.f;
+    CRH_HIP(hipMemcpy(srow_out, h->srow, (size_t)count * 4, hipMemcpyDeviceToHost));
+    CRH_HIP(hipMemcpy(dn_out, h->i8stat, 4, hipMemcpyDeviceToHost));
+    *c_abs_out = c_abs;
     return CRH_OK;
 }
 #endif  // CRH_ENABLE_DEBUG

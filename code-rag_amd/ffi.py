@@ -38,7 +38,7 @@ EXPORTS = (
     "crh_index_gather_codes", "crh_group_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
-DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move")
+DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
 DEBUG_LIB_PATH = Path(os.environ.get("CODERAG_HIP_DEBUG_LIB", PKG_DIR / "lib" / "libcoderag_hip_debug.so"))
 
 RR_NAME_BYTES, RR_MAX_ENTITIES, RR_ENTITY_BYTES = 64, 8, 48
@@ -183,6 +183,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
         L.crh_debug_read_ceiling.argtypes = [vp, vp]
         L.crh_debug_i8_move.argtypes = [vp]
+        L.crh_debug_i8_intervals.argtypes = [vp, i32, vp, i32, C.POINTER(Filter), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS + (DEBUG_EXPORTS if debug else ()):
         if name != "crh_last_error":
             getattr(L, name).restype = i32
@@ -257,6 +258,23 @@ def _conditions(filters) -> tuple:
         keep.append(codes)
         arr[i].col, arr[i].negate, arr[i].n, arr[i].codes = int(col), int(negate), int(codes.size), codes.ctypes.data if codes.size else None
     return arr, len(filters), keep
+
+
+def debug_i8_intervals(handle, rows: int, dim: int, queries, k: int, filters=None) -> dict:
+    """``crh_debug_i8_intervals`` (debug library only): the int8 scan's intervals, quantisation parameters and thresholds for up to
+    64 raw queries, from the product's own launches.  ``handle`` is a ``crh_index`` created by :func:`debug_lib` -- the two
+    libraries do not share handles."""
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, dim)
+    nq = q.shape[0]
+    out = {"hi_rec": np.empty((nq, rows), np.float32), "hi": np.empty((nq, rows), np.float32), "lo": np.empty((nq, rows), np.float32),
+           "srow": np.empty((rows,), np.float32), "qpar": np.empty((64, 4), np.float32), "dn": np.empty((1,), np.float32),
+           "c_abs": np.empty((1,), np.float32), "tau": np.empty((nq,), np.float32)}
+    farr, nf = _filters(filters)
+    L = debug_lib()
+    check(L.crh_debug_i8_intervals(handle, nq, q.ctypes.data, int(k), farr, nf, *(out[n].ctypes.data for n in
+                                   ("hi_rec", "hi", "lo", "srow", "qpar", "dn", "c_abs", "tau"))), L)
+    out["dn"], out["c_abs"] = np.float32(out["dn"][0]), np.float32(out["c_abs"][0])
+    return out
 
 
 def _has_sets(filters) -> bool:

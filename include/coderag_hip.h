@@ -479,6 +479,19 @@ int crh_debug_read_ceiling(crh_index *h, void *stream);
  * released) and marks it for requantisation -- lets one index try several places in HBM (tools/i8_places.py). */
 int crh_debug_i8_move(crh_index *h);
 
+/* Test support: what the int8 scan computes before it nominates, taken from the product's own launches (requantisation, query
+ * preparation, the sample launch over every tile, the threshold launch) -- never a restatement of their arithmetic.  For up to
+ * 64 raw queries (host, [nq][dim]) and the rows of an index of at most 8192 tiles (CRH_E_INVALID beyond; also when the index
+ * does not nominate from its int8 copy at this k, or a search is pending):
+ *   hi_rec [nq][rows]  upper end of each row's interval as the sample launch records it (bf16, rounded up)
+ *   hi, lo [nq][rows]  both ends as f32, as the kernel evaluates them
+ *   srow   [rows]      per-row scale;  qpar [64][4]: s_q, Qn, gn, 0 per query (zeros beyond nq);  dn, c_abs: one float each
+ *   tau    [nq]        the threshold of each query for this k under the given filters (alive rows only)
+ * All outputs are host pointers.  tests/test_i8_intervals_gpu.py. */
+int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, const crh_filter *filters, int n_filters,
+                           float *hi_rec_out, float *hi_out, float *lo_out, float *srow_out, float *qpar_out, float *dn_out,
+                           float *c_abs_out, float *tau_out);
+
 /* Timing ablations of the GEMM main loop (variant 0 = the real kernel; others skip a pipeline stage and return
  * garbage).  Development aid used by tools/gemm_ablate.py; not part of the product path. */
 int crh_debug_gemm_variant(const void *x, const void *w, const float *bias, void *y, int T, int N, int K,

@@ -47,6 +47,8 @@ def _load():
         lib.orc_preprocess_rows.argtypes = [f32p, f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
         lib.orc_dot.restype = ctypes.c_float
         lib.orc_dot.argtypes = [f32p, f32p, ctypes.c_int]
+        lib.orc_scores.restype = None
+        lib.orc_scores.argtypes = [f32p, ctypes.c_int64, ctypes.c_int, f32p, ctypes.c_int, f32p]
         lib.orc_search.restype = ctypes.c_int
         lib.orc_search.argtypes = [f32p, ctypes.c_int64, ctypes.c_int, u8p, i32p, ctypes.c_int,
                                    i32p, i32p, ctypes.c_int, f32p, ctypes.c_int, ctypes.c_int,
@@ -76,6 +78,17 @@ def dot(a: np.ndarray, b: np.ndarray) -> float:
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
     return float(_load().orc_dot(_p(a, ctypes.c_float), _p(b, ctypes.c_float), a.shape[0]))
+
+
+def scores(corpus_pre: np.ndarray, queries_pre: np.ndarray) -> np.ndarray:
+    """The canonical f32 score of every (query, row) pair of preprocessed inputs -- what :func:`search` ranks by: [nq, n] f32."""
+    x = np.ascontiguousarray(corpus_pre, dtype=np.float32)
+    q = np.ascontiguousarray(queries_pre, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    out = np.empty((q.shape[0], x.shape[0]), dtype=np.float32)
+    _load().orc_scores(_p(x, ctypes.c_float), x.shape[0], x.shape[1], _p(q, ctypes.c_float), q.shape[0], _p(out, ctypes.c_float))
+    return out
 
 
 def search(corpus_pre: np.ndarray, queries_pre: np.ndarray, k: int, alive: np.ndarray | None = None,

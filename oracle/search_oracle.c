@@ -92,6 +92,15 @@ float orc_dot(const float *a, const float *b, int d)
     return acc;
 }
 
+/* The canonical score of EVERY (query, row) pair: out[q * n + r] = orc_dot(query q, row r) -- what orc_search ranks by,
+ * without the ranking (tests/test_i8_intervals_gpu.py checks per-row score intervals against it). */
+void orc_scores(const float *corpus, int64_t n, int d, const float *queries, int nq, float *out)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < n; ++r)
+        for (int q = 0; q < nq; ++q) out[(int64_t)q * n + r] = orc_dot(queries + (int64_t)q * d, corpus + r * d, d);
+}
+
 static int row_passes(int64_t r, const uint8_t *alive, const int32_t *codes, int ncols,
                       const int32_t *fcols, const int32_t *fvals, int nfilt)
 {
