@@ -61,6 +61,8 @@ struct Pending {
     float *out_s;
     int64_t *out_r;
     int slot;
+    bool multi;     // a mixed-filter batch (crh_search_multi): key is the classes' keys behind their number, cls the queries' classes
+    QueryClasses cls;
     int path;       // how enqueue_batch nominated the batch's rows: CRH_NOMINATE_INT8 / _BF16 (one launch) / _BF16_3 (three launches, wide scan)
 };
 
@@ -113,6 +115,17 @@ struct crh_index {
     bool sparse_on = true;
     int sparse_den = kSparseDen;
     int64_t mask_nlist = -1;
+    // The class masks of a mixed-filter call (crh_search_multi) are kept the same way, under their own key -- the classes' keys
+    // one after the other behind their number -- and in their own buffers, so a mixed call and the single-filter calls around
+    // it each find their masks as they left them.
+    uint64_t cmask_built_at = 0;
+    hipStream_t cmask_stream = nullptr;
+    bool cmask_valid = false;
+    FilterKey cmask_key;
+    int32_t *cmask_sets = nullptr;
+    int64_t cmask_sets_cap = 0;
+    int64_t cmask_nlist = -1;
+    FilterClasses *cmask_classes = nullptr;   // device copy of the classes' descriptions (k_filter_mask_classes)
     u32x4 *xt = nullptr;
     float *xf32 = nullptr;
     uint32_t *alive = nullptr;
@@ -129,6 +142,10 @@ struct crh_index {
         float *qn = nullptr, *gmax = nullptr, *tau = nullptr, *qpar = nullptr, *qlo = nullptr;
         u32x4 *qfrag = nullptr, *qfrag8 = nullptr, *wave_lists = nullptr, *shi = nullptr;
         uint32_t *effmask = nullptr;
+        int64_t ws_cmask_tiles = 0;
+        uint32_t *cmask = nullptr;      // [cap_tiles][8] the class words of a mixed-filter batch, interleaved per tile
+        uint32_t *cunion = nullptr;     // [cap_tiles] their OR: the row mask of the union
+        uint32_t *clist = nullptr;      // the union's populated tiles, laid out like tilelist
         uint32_t *tilelist = nullptr;   // [cap_tiles] the populated tiles of effmask, [ceil(cap_tiles / 256)] workgroup counts, [1] the list's length
         u32x2 *qlist = nullptr;
         unsigned long long *skeys = nullptr, *skeys2 = nullptr;
@@ -380,6 +397,98 @@ bool sparse_use(const crh_index *h, const MaskRef &m, int nq)
     return h->sparse_on && m.nlist >= 0 && nq <= h->batch_q && m.nlist * h->sparse_den <= ceil_div(h->count, kTileRows);
 }
 
+// one filter of a key, starting at key[at], as k_filter_mask takes it (set offsets are positions in the key); returns the
+// position behind it, or 0 for a column the index does not have
+size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, FilterSet &fs, bool *sets)
+{
+    const int nfilt = key[at++];
+    fs.n = nfilt;
+    for (int f = 0; f < nfilt; ++f) {
+        if (key[at] < 0 || key[at] >= h->ncols) return 0;
+        fs.col[f] = key[at];
+        fs.neg[f] = key[at + 1];
+        fs.cnt[f] = key[at + 2];
+        fs.off[f] = (int)at + 3;
+        fs.one[f] = fs.cnt[f] == 1 ? key[at + 3] : 0;
+        *sets = *sets || fs.cnt[f] > 1;
+        at += 3 + (size_t)fs.cnt[f];
+    }
+    return at;
+}
+
+// The masks of a mixed-filter batch: ckey = [number of classes, then every class's key].  out->mask is the union's row mask,
+// *cmask_out the interleaved class words; the union's tile list is made while the sparse route is enabled.  Kept like the
+// single mask (key, mutations, stream), in buffers of their own.
+int build_class_masks(crh_index *h, crh_index::Workspace &w, const FilterKey &ckey, MaskRef *out, const uint32_t **cmask_out, hipStream_t st)
+{
+    *out = MaskRef{};
+    *cmask_out = nullptr;
+    if (h->count == 0) return CRH_OK;   // (an empty index: every batch is padding, no mask is read)
+    if (w.ws_cmask_tiles < h->cap_tiles) {
+        dev_free(w.cmask);
+        dev_free(w.cunion);
+        dev_free(w.clist);
+        w.ws_cmask_tiles = 0;
+        h->cmask_valid = false;
+        CRH_TRY(dev_alloc(&w.cmask, h->cap_tiles * CRH_MAX_CLASSES));
+        CRH_TRY(dev_alloc(&w.cunion, h->cap_tiles));
+        CRH_TRY(dev_alloc(&w.clist, h->cap_tiles + ceil_div(h->cap_tiles, 256) + 1));
+        w.ws_cmask_tiles = h->cap_tiles;
+    }
+    const bool same = h->cmask_valid && h->cmask_built_at == h->mutations && h->cmask_stream == st && h->cmask_key == ckey &&
+                      (h->cmask_nlist >= 0) == h->sparse_on;
+    if (!same) {
+        h->cmask_valid = false;
+        h->cmask_key = ckey;
+        FilterClasses fc{};
+        fc.n = ckey[0];
+        bool sets = false;
+        size_t at = 1;
+        for (int c = 0; c < fc.n; ++c) {
+            at = filterset_from_key(h, ckey, at, fc.c[c], &sets);
+            if (at == 0) return fail(CRH_E_INVALID, "class %d: filter column out of range (index has %d code columns)", c, h->ncols);
+        }
+        if (!h->cmask_classes) CRH_TRY(dev_alloc(&h->cmask_classes, 1));
+        // (the source is on this frame: a copy from pageable memory has left it when the call returns)
+        CRH_HIP(hipMemcpyAsync(h->cmask_classes, &fc, sizeof(fc), hipMemcpyHostToDevice, st));
+        if (sets) {
+            if (h->cmask_sets_cap < (int64_t)ckey.size()) {
+                dev_free(h->cmask_sets);
+                h->cmask_sets_cap = 0;
+                CRH_TRY(dev_alloc(&h->cmask_sets, (int64_t)ckey.size()));
+                h->cmask_sets_cap = (int64_t)ckey.size();
+            }
+            CRH_HIP(hipMemcpyAsync(h->cmask_sets, h->cmask_key.data(), ckey.size() * 4, hipMemcpyHostToDevice, st));
+        }
+        CRH_HIP(hipStreamSynchronize(st));
+        const int64_t rows = (h->count + 63) & ~63LL;
+        hipLaunchKernelGGL(k_filter_mask_classes, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, h->alive, h->codes, h->cap_rows,
+                           h->count, h->cmask_classes, h->cmask_sets, w.cmask, w.cunion);
+        CRH_HIP(hipGetLastError());
+        h->cmask_nlist = -1;
+        if (h->sparse_on) {
+            const int64_t ntiles = ceil_div(h->count, kTileRows);
+            const unsigned nb = (unsigned)ceil_div(ntiles, 256);
+            uint32_t *blockcnt = w.clist + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
+            hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, w.cunion, ntiles, blockcnt);
+            hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, w.cunion, ntiles, blockcnt, w.clist, len);
+            CRH_HIP(hipGetLastError());
+            uint32_t n = 0;
+            CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipStreamSynchronize(st));
+            h->cmask_nlist = n;
+        }
+        h->cmask_built_at = h->mutations;
+        h->cmask_stream = st;
+        h->cmask_valid = true;
+    }
+    out->mask = w.cunion;
+    out->list = w.clist;
+    out->nlist = h->cmask_nlist;
+    *cmask_out = w.cmask;
+    return CRH_OK;
+}
+
 // scan kernel instantiations: k-steps = dim / 16; 64 queries per pass except for dim 1536 (32: LDS)
 template <int MODE>
 int launch_scan(crh_index *h, crh_index::Workspace &w, int blocks, hipStream_t st, const uint32_t *mask, int nitems, int stride, int wave_cap, int qcap,
@@ -416,6 +525,34 @@ int launch_scan_list(crh_index *h, crh_index::Workspace &w, int blocks, hipStrea
     default: return fail(CRH_E_INTERNAL, "no list scan kernel for %d k-steps", h->ksteps);
     }
 #undef CRH_SCAN_LIST
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+// the classed scans of a mixed-filter batch: dense (list == false) or over the union's tile list
+// (dim 1024, dense: with the ring of 8 the two picked words cost two spilled VGPRs, and a scratch access inside the tile loop
+// breaks the counted waits -- that one instantiation runs a ring of 4; the others hold 128 VGPRs without a spill)
+constexpr int kClsRing64 = 4;
+template <int MODE>
+int launch_scan_cls(crh_index *h, crh_index::Workspace &w, int blocks, hipStream_t st, const MaskRef &m, const uint32_t *cmask, const QueryClasses &cls,
+                    bool list, int nitems, int stride, int wave_cap, int qcap, SearchStatus *stt)
+{
+    const u32x8 *cm = reinterpret_cast<const u32x8 *>(cmask);
+#define CRH_SCAN_CLS(KS, QB)                                                                                                          \
+    if (list)                                                                                                                         \
+        hipLaunchKernelGGL((k_scan_list_cls<KS, MODE, kWaves, kRing, QB>), dim3(blocks), dim3(kWaves * 64), 0, st, h->xt, w.qfrag, w.tau, \
+                           cm, cls, m.list, nitems, stride, w.gmax, w.wave_lists, wave_cap, stt->qcount, w.qlist, qcap, stt); \
+    else                                                                                                                              \
+        hipLaunchKernelGGL((k_scan_cls<KS, MODE, kWaves, KS == 64 ? kClsRing64 : kRing, QB>), dim3(blocks), dim3(kWaves * 64), 0, st, h->xt, w.qfrag, w.tau,  \
+                           cm, cls, nitems, stride, w.gmax, w.wave_lists, wave_cap, stt->qcount, w.qlist, qcap, stt)
+    switch (h->ksteps) {
+    case 24: CRH_SCAN_CLS(24, 2); break;
+    case 48: CRH_SCAN_CLS(48, 2); break;
+    case 64: CRH_SCAN_CLS(64, 2); break;
+    case 96: CRH_SCAN_CLS(96, 1); break;
+    default: return fail(CRH_E_INTERNAL, "no classed scan kernel for %d k-steps", h->ksteps);
+    }
+#undef CRH_SCAN_CLS
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }
@@ -744,6 +881,60 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
     return CRH_OK;
 }
 
+// One mixed-filter batch (<= batch_q queries, <= CRH_MAX_CLASSES classes): always the three-launch bf16 form, through the
+// classed scans -- over every tile, or over the union's tile list when the union is sparse enough.  k_tau and k_select as
+// behind every bf16 scan.
+int enqueue_batch_multi(crh_index *h, crh_index::Workspace &w, const float *q_dev, int nq, int k, const MaskRef &mref, const uint32_t *cmask,
+                        const QueryClasses &cls, int64_t row_base, float *out_s, int64_t *out_r, int slot, hipStream_t st)
+{
+    const int64_t ntiles = ceil_div(h->count, kTileRows);
+    const bool sparse = ntiles > 0 && sparse_use(h, mref, nq);
+    if (ntiles == 0 || (sparse && mref.nlist == 0)) {   // (no row can match: the padding the scans would arrive at)
+        if (sparse) {
+            h->stats.batches += 1;
+            if (h->profiling) {
+                CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+                CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+            }
+        }
+        CRH_HIP(hipMemsetAsync(h->status + slot, 0, sizeof(SearchStatus), st));
+        const int64_t n = (int64_t)nq * k;
+        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out_s, out_r, n);
+        CRH_HIP(hipGetLastError());
+        return CRH_OK;
+    }
+    const int wave_cap = w.ws_wave_cap, qcap = w.ws_qcap;
+    const float margin = margin_for(h);
+    SearchStatus *stt = h->status + slot;
+    const int width = h->batch_q;
+    if (h->dtype == CRH_DTYPE_BF16)
+        hipLaunchKernelGGL((k_prep_queries<true, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
+    else
+        hipLaunchKernelGGL((k_prep_queries<false, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
+    CRH_HIP(hipGetLastError());
+    const int64_t items = sparse ? mref.nlist : ntiles;   // list positions or tiles
+    const int G = (int)std::min<int64_t>(h->seed_tiles, items);
+    const int stride = (int)(items / G);
+    CRH_TRY(launch_scan_cls<0>(h, w, scan_blocks(h, G), st, mref, cmask, cls, sparse, G, stride, wave_cap, qcap, stt));
+    hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, 64);
+    CRH_HIP(hipGetLastError());
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+    CRH_TRY(launch_scan_cls<1>(h, w, scan_blocks(h, items), st, mref, cmask, cls, sparse, (int)items, 1, wave_cap, qcap, stt));
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+    if (h->dtype == CRH_DTYPE_F32)
+        hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+    else
+        hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+    CRH_HIP(hipGetLastError());
+    h->stats.rows += sparse ? std::min<int64_t>(h->count, items * kTileRows) : h->count;
+    h->stats.tiles += items;
+    h->stats.seed_tiles += G;
+    h->stats.batches += 1;
+    return CRH_OK;
+}
+
 int next_pow2(int64_t v)
 {
     int64_t p = 1;
@@ -825,11 +1016,17 @@ int finish_pending(crh_index *h, hipStream_t st)
             }
             CRH_TRY(ensure_workspace(h, w, wc, qc));
             MaskRef mask;
-            CRH_TRY(build_mask(h, w, p.key, &mask, st));
-            h->i8_suppress = no_i8;
-            const int rc = enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, 0, st, &path);
-            h->i8_suppress = false;
-            CRH_TRY(rc);
+            if (p.multi) {   // a mixed-filter batch runs the classed pipeline again
+                const uint32_t *cmask = nullptr;
+                CRH_TRY(build_class_masks(h, w, p.key, &mask, &cmask, st));
+                CRH_TRY(enqueue_batch_multi(h, w, p.q_dev, p.nq, p.k, mask, cmask, p.cls, p.row_base, p.out_s, p.out_r, 0, st));
+            } else {
+                CRH_TRY(build_mask(h, w, p.key, &mask, st));
+                h->i8_suppress = no_i8;
+                const int rc = enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, 0, st, &path);
+                h->i8_suppress = false;
+                CRH_TRY(rc);
+            }
             CRH_HIP(hipMemcpyAsync(&s, h->status, sizeof(SearchStatus), hipMemcpyDeviceToHost, st));
             CRH_HIP(hipStreamSynchronize(st));
         }
@@ -948,6 +1145,8 @@ int crh_index_destroy(crh_index *h)
     dev_free(h->codes);
     dev_free(h->scratch_u32);
     dev_free(h->mask_sets);
+    dev_free(h->cmask_sets);
+    dev_free(h->cmask_classes);
     {
         crh_index::Workspace &w = h->ws;
         dev_free(w.qn);
@@ -957,6 +1156,9 @@ int crh_index_destroy(crh_index *h)
         dev_free(w.wave_lists);
         dev_free(w.effmask);
         dev_free(w.tilelist);
+        dev_free(w.cmask);
+        dev_free(w.cunion);
+        dev_free(w.clist);
         dev_free(w.qlist);
         dev_free(w.skeys);
         dev_free(w.qfrag8);
@@ -1683,6 +1885,102 @@ int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_d
     FilterKey key;
     CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
     return search_key(h, nq, queries, queries_on_device, k, key, row_base, out_scores, out_rows, out_on_device, stream);
+}
+
+// The mixed-filter search: as search_key, with the classes' masks and the classed batches (<= batch_q queries each, in caller order)
+static int search_multi_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &ckey, const int32_t *query_class,
+                            int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+{
+    DeviceGuard g(h->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool tiny = h->force_fallback == 1 || h->force_fallback == 3;   // (testing: the regrow-and-rerun path, see search_key)
+    const int wc = tiny ? 4 : std::max(h->wave_cap, h->ws.ws_wave_cap);
+    const int qc = tiny ? 8 : std::max(h->qcap, h->ws.ws_qcap);
+    CRH_TRY(ensure_workspace(h, h->ws, wc, qc));
+
+    const float *q_dev = queries;
+    if (!queries_on_device) {
+        const int64_t elems = (int64_t)nq * h->dim;
+        if (h->stage_q_elems < elems) {
+            dev_free(h->stage_q);
+            h->stage_q_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_q, elems));
+            h->stage_q_elems = elems;
+        }
+        CRH_HIP(hipMemcpyAsync(h->stage_q, queries, (size_t)elems * 4, hipMemcpyHostToDevice, st));
+        q_dev = h->stage_q;
+    }
+    float *os = out_scores;
+    int64_t *orow = out_rows;
+    if (!out_on_device) {
+        const int64_t elems = (int64_t)nq * k;
+        if (h->stage_out_elems < elems) {
+            dev_free(h->stage_os);
+            dev_free(h->stage_or);
+            h->stage_out_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_os, elems));
+            CRH_TRY(dev_alloc(&h->stage_or, elems));
+            h->stage_out_elems = elems;
+        }
+        os = h->stage_os;
+        orow = h->stage_or;
+    }
+    if (h->pending.empty()) h->stats = crh_search_stats{};
+
+    for (int q0 = 0; q0 < nq; q0 += h->batch_q) {
+        const int b = std::min(h->batch_q, nq - q0);
+        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
+        crh_index::Workspace &w = h->ws;
+        MaskRef mask;
+        const uint32_t *cmask = nullptr;
+        CRH_TRY(build_class_masks(h, w, ckey, &mask, &cmask, st));
+        Pending p{};
+        p.nq = b;
+        p.k = k;
+        p.key = ckey;
+        p.multi = true;
+        for (int i = 0; i < b; ++i) p.cls.w[i >> 3] |= (uint32_t)query_class[q0 + i] << ((i & 7) * 4);
+        p.row_base = row_base;
+        p.q_dev = q_dev + (int64_t)q0 * h->dim;
+        p.out_s = os + (int64_t)q0 * k;
+        p.out_r = orow + (int64_t)q0 * k;
+        p.slot = h->next_slot++;
+        p.path = CRH_NOMINATE_BF16_3;
+        CRH_TRY(enqueue_batch_multi(h, w, p.q_dev, b, k, mask, cmask, p.cls, row_base, p.out_s, p.out_r, p.slot, st));
+        h->pending.push_back(p);
+    }
+    if (!out_on_device || !queries_on_device) {
+        CRH_TRY(finish_pending(h, st));
+        if (!out_on_device) {
+            CRH_HIP(hipMemcpyAsync(out_scores, h->stage_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipMemcpyAsync(out_rows, h->stage_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipStreamSynchronize(st));
+        }
+    }
+    return CRH_OK;
+}
+
+int crh_search_multi(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const crh_condition *conds,
+                     const int32_t *class_off, int n_classes, const int32_t *query_class, int64_t row_base, float *out_scores,
+                     int64_t *out_rows, int out_on_device, void *stream)
+{
+    CRH_TRY(search_args(h, nq, queries, k, out_scores, out_rows));
+    if (n_classes < 1 || n_classes > CRH_MAX_CLASSES) return fail(CRH_E_INVALID, "n_classes=%d outside 1..%d", n_classes, CRH_MAX_CLASSES);
+    if (!class_off) return fail(CRH_E_INVALID, "class_off is NULL");
+    if (class_off[0] < 0) return fail(CRH_E_INVALID, "class_off[0]=%d is negative", class_off[0]);
+    FilterKey ckey(1, n_classes), key;
+    for (int c = 0; c < n_classes; ++c) {
+        const int n = class_off[c + 1] - class_off[c];
+        if (n < 0) return fail(CRH_E_INVALID, "class_off is not ascending at class %d", c);
+        CRH_TRY(key_from_conditions(h, n > 0 ? conds + class_off[c] : nullptr, n, false, key));
+        ckey.insert(ckey.end(), key.begin(), key.end());
+    }
+    if (nq == 0) return CRH_OK;
+    if (!query_class) return fail(CRH_E_INVALID, "query_class is NULL");
+    for (int i = 0; i < nq; ++i)
+        if (query_class[i] < 0 || query_class[i] >= n_classes)
+            return fail(CRH_E_INVALID, "query_class[%d]=%d outside 0..%d", i, query_class[i], n_classes - 1);
+    return search_multi_key(h, nq, queries, queries_on_device, k, ckey, query_class, row_base, out_scores, out_rows, out_on_device, stream);
 }
 
 int crh_index_set_sparse_route(crh_index *h, int enable, int max_fraction_den)

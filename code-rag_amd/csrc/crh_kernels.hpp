@@ -29,6 +29,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(8))) unsigned int u32x8;
 
 constexpr int kTileRows = 32;
 constexpr int kMaxQ = 64;   // queries per pass of the LDS-query scan k_scan (two 32-column MFMA B blocks)
@@ -243,6 +244,64 @@ __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict_
         uint32_t m = (uint32_t)(lane ? (b >> 32) : b);
         out[tile] = m & alive[tile];
     }
+}
+
+// k_filter_mask's row test once more, for the classed kernel below (that kernel keeps its own text, and with it its code)
+__device__ __forceinline__ bool filter_row_ok(bool ok, const FilterSet &fs, const int32_t *__restrict__ codes, int64_t cap_rows, int64_t r,
+                                              const int32_t *__restrict__ sets)
+{
+    if (ok) {
+        for (int f = 0; f < fs.n; ++f) {
+            const int32_t c = codes[(int64_t)fs.col[f] * cap_rows + r];
+            bool member;
+            if (fs.cnt[f] == 1) {
+                member = c == fs.one[f];
+            } else {
+                const int32_t *s = sets + fs.off[f];
+                int lo = 0, hi = fs.cnt[f];   // first position whose code is >= c
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (s[mid] < c) lo = mid + 1;
+                    else hi = mid;
+                }
+                member = lo < fs.cnt[f] && s[lo] == c;
+            }
+            ok = ok && (member != (fs.neg[f] != 0));
+        }
+    }
+    return ok;
+}
+
+// The masks of a mixed-filter batch (k_scan_cls): the same row test per class, written interleaved -- out8[tile * 8 + c] =
+// alive[tile] AND class c's conditions, 0 for the classes beyond fc.n -- so a tile's 8 words are one 32-byte scalar load, and
+// their OR to out_union[tile], an ordinary [tile] mask the tile-list kernels and the sparse-route decision take as it is.
+// The classes' descriptions live in device memory (8 of them are past what a kernel argument should carry).
+struct FilterClasses {
+    int n;
+    FilterSet c[8];
+};
+__global__ __launch_bounds__(256) void k_filter_mask_classes(const uint32_t *__restrict__ alive, const int32_t *__restrict__ codes,
+                                                             int64_t cap_rows, int64_t count, const FilterClasses *__restrict__ fc,
+                                                             const int32_t *__restrict__ sets, uint32_t *__restrict__ out8,
+                                                             uint32_t *__restrict__ out_union)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = lane_id();
+    const int64_t tile = r >> 5;
+    const bool writer = (lane & 31) == 0 && (tile << 5) < ((count + 31) & ~31LL);
+    const uint32_t al = writer ? alive[tile] : 0u;
+    const int n = fc->n;
+    uint32_t un = 0u;
+    for (int c = 0; c < 8; ++c) {
+        const bool ok = filter_row_ok(c < n && r < count, fc->c[c], codes, cap_rows, r, sets);
+        const unsigned long long b = __ballot(ok);
+        if (writer) {
+            const uint32_t m = (uint32_t)(lane ? (b >> 32) : b) & al;
+            out8[tile * 8 + c] = m;
+            un |= m;
+        }
+    }
+    if (writer) out_union[tile] = un;
 }
 
 // delete-by-filter: clear every alive bit the (already alive-ANDed) filter mask has set; counts the cleared rows
@@ -553,7 +612,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_scan(
     u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
 {
 #define CRH_SCAN_LIST 0
+#define CRH_SCAN_CLASSES 0
 #include "crh_scan_body.hpp"
+#undef CRH_SCAN_CLASSES
 #undef CRH_SCAN_LIST
 }
 
@@ -565,7 +626,57 @@ __global__ __launch_bounds__(WAVES * 64) void k_scan_list(
     u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
 {
 #define CRH_SCAN_LIST 1
+#define CRH_SCAN_CLASSES 0
 #include "crh_scan_body.hpp"
+#undef CRH_SCAN_CLASSES
+#undef CRH_SCAN_LIST
+}
+
+// ---- the classed scans: one corpus pass for a batch whose queries carry DIFFERENT filters (crh_search_multi)
+//
+// A class is one distinct filter; at most CRH_MAX_CLASSES = 8 share a pass.  classmask is [tile][8] u32 -- word c of tile t =
+// alive[t] AND class c's conditions, unused classes 0 (k_filter_mask_classes); the OR of a tile's 8 words is the union's
+// validity word, which the same kernel also writes to an ordinary [tile] mask for the tile list of the sparse route.  The query sits on the lane (column = lane & 31), so a per-query
+// validity word costs one VGPR per column block: see crh_scan_body.hpp, CRH_SCAN_CLASSES.  Each query's thresholds come from
+// the sample maxima over ITS class's rows, so they stay lower bounds of its k-th score; everything behind the nomination
+// (k_tau, the hand-over, k_select) never sees a mask and runs unchanged, which is why ids and score bits are those of a
+// single-filter search.  A mixed batch always takes this three-launch bf16 form, whatever crh_index_set_nomination allows:
+// the int8 pass (219 VGPRs, hand-tuned emit code), the one-launch k_scan_fused and k_scan_wide have no classed variant.
+// MODE 2 is not instantiated.
+struct QueryClasses {
+    uint32_t w[8];   // 4 bits per query: query q's class in bits 4 (q & 7) .. of word q >> 3
+};
+__device__ __forceinline__ uint32_t class_pick(const u32x8 w, uint32_t c)
+{
+    const bool b0 = c & 1u, b1 = c & 2u, b2 = c & 4u;
+    const uint32_t x0 = b0 ? w[1] : w[0], x1 = b0 ? w[3] : w[2], x2 = b0 ? w[5] : w[4], x3 = b0 ? w[7] : w[6];
+    const uint32_t y0 = b1 ? x1 : x0, y1 = b1 ? x3 : x2;
+    return b2 ? y1 : y0;
+}
+template <int KSTEPS, int MODE, int WAVES, int RING, int QB = 2>
+__global__ __launch_bounds__(WAVES * 64) void k_scan_cls(
+    const u32x4 *__restrict__ xt, const u32x4 *__restrict__ qfrag, const float *__restrict__ tau,
+    const u32x8 *__restrict__ classmask, QueryClasses qclass, int nitems, int tile_stride,
+    float *__restrict__ gmax, u32x4 *__restrict__ wave_lists, int wave_cap, unsigned int *__restrict__ qcount,
+    u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
+{
+#define CRH_SCAN_LIST 0
+#define CRH_SCAN_CLASSES 1
+#include "crh_scan_body.hpp"
+#undef CRH_SCAN_CLASSES
+#undef CRH_SCAN_LIST
+}
+template <int KSTEPS, int MODE, int WAVES, int RING, int QB = 2>
+__global__ __launch_bounds__(WAVES * 64) void k_scan_list_cls(
+    const u32x4 *__restrict__ xt, const u32x4 *__restrict__ qfrag, const float *__restrict__ tau,
+    const u32x8 *__restrict__ classmask, QueryClasses qclass, const uint32_t *__restrict__ tilelist, int nitems, int tile_stride,
+    float *__restrict__ gmax, u32x4 *__restrict__ wave_lists, int wave_cap, unsigned int *__restrict__ qcount,
+    u32x2 *__restrict__ qlist, int qcap, SearchStatus *__restrict__ status)
+{
+#define CRH_SCAN_LIST 1
+#define CRH_SCAN_CLASSES 1
+#include "crh_scan_body.hpp"
+#undef CRH_SCAN_CLASSES
 #undef CRH_SCAN_LIST
 }
 

@@ -2,6 +2,14 @@
 // CRH_SCAN_LIST defined 0 / 1.  One text, two kernels: with CRH_SCAN_LIST 0 it is k_scan's body word for word, so that
 // kernel's code does not depend on the list variant existing (tools/isa_diff.py compares the two builds); with 1, item i is
 // tile tilelist[i * tile_stride] instead of tile i * tile_stride.  Not a header: it has no meaning outside those braces.
+//
+// CRH_SCAN_CLASSES 0 / 1 (k_scan_cls, k_scan_list_cls: a batch whose queries carry different filters).  With 0 the text is
+// the one above, token for token after preprocessing.  With 1 every lane tests the rows of a tile against the validity word of
+// ITS query's filter class: the tile's 8 class words (classmask[tile], interleaved so that they are one 32-byte scalar load)
+// are fetched where the plain kernels fetch rowmask[tile] -- their OR is that union word -- and after the MFMAs each lane
+// picks word cls0 (column block 0) / cls1 (block 1) with a v_cndmask tree.  The picked word stands where vmask stands in the
+// MODE 0 maxima and the MODE 1 pass test; the wave-uniform early-out keeps the union word.  No vector load is added to the
+// tile loop: the ring's vmcnt count holds.
     static_assert(KSTEPS % RING == 0, "ring must divide the k-steps of a tile");
     __shared__ u32x4 qs[QB * KSTEPS * 64];
     const int tid = threadIdx.x;
@@ -18,6 +26,15 @@
         t0 = tau[lane & 31];
         t1 = QB == 2 ? tau[32 + (lane & 31)] : INFINITY;
     }
+#if CRH_SCAN_CLASSES
+    // the class of the lane's query in each column block: 4 bits per query, 8 queries per word of the kernel argument
+    // (padding columns of a short batch are class 0; their tau is +inf)
+    const int cq = lane & 31;
+    const uint32_t cw0 = cq < 8 ? qclass.w[0] : cq < 16 ? qclass.w[1] : cq < 24 ? qclass.w[2] : qclass.w[3];
+    const uint32_t cw1 = cq < 8 ? qclass.w[4] : cq < 16 ? qclass.w[5] : cq < 24 ? qclass.w[6] : qclass.w[7];
+    const uint32_t cls0 = (cw0 >> ((cq & 7) * 4)) & 7u;
+    const uint32_t cls1 = QB == 2 ? (cw1 >> ((cq & 7) * 4)) & 7u : 0u;
+#endif
     __syncthreads();
 
     const int total = gridDim.x * WAVES;
@@ -50,7 +67,11 @@
         const int64_t tile = (int64_t)i * tile_stride;
         const u32x4 *xn = (inext < nitems) ? xt + (size_t)((int64_t)inext * tile_stride) * (KSTEPS * 64) + lslot : xp;
 #endif
+#if CRH_SCAN_CLASSES
+        const u32x8 cwords = classmask[tile];  // wave-uniform, 32 bytes aligned -> ONE scalar load of the tile's 8 class words
+#else
         const uint32_t vmask = rowmask[tile];  // wave-uniform -> scalar load
+#endif
         // the query image is loop-invariant: without this the compiler hoists all 96 LDS pieces (384 VGPRs)
         // out of the tile loop and spills; the clobber makes it re-read qs per tile, as intended
         asm volatile("" ::: "memory");
@@ -80,6 +101,14 @@
             __builtin_amdgcn_sched_barrier(0);
         }
 
+#if CRH_SCAN_CLASSES
+        // the union word (what rowmask holds for the tile-list kernels): seven scalar ORs instead of a second load
+        const uint32_t vmask = cwords[0] | cwords[1] | cwords[2] | cwords[3] | cwords[4] | cwords[5] | cwords[6] | cwords[7];
+        const uint32_t vm0 = class_pick(cwords, cls0);
+        const uint32_t vm1 = QB == 2 ? class_pick(cwords, cls1) : 0u;
+#else
+        const uint32_t vm0 = vmask, vm1 = vmask;
+#endif
         if (MODE == 2) {
             // nothing: the probe measures what the same access pattern reads with no arithmetic and no candidate logic
         } else if (MODE == 0) {
@@ -87,9 +116,9 @@
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const bool ok = (vmask >> row) & 1u;
-                m0 = fmaxf(m0, ok ? a0[r] : -INFINITY);
-                m1 = fmaxf(m1, ok ? a1[r] : -INFINITY);
+                const bool ok0 = (vm0 >> row) & 1u, ok1 = (vm1 >> row) & 1u;
+                m0 = fmaxf(m0, ok0 ? a0[r] : -INFINITY);
+                m1 = fmaxf(m1, ok1 ? a1[r] : -INFINITY);
             }
             m0 = fmaxf(m0, __shfl_xor(m0, 32));
             m1 = fmaxf(m1, __shfl_xor(m1, 32));
@@ -110,11 +139,12 @@
 #pragma unroll
                 for (int qb = 0; qb < QB; ++qb) {
                     const float tq = qb ? t1 : t0;
+                    const uint32_t vq = qb ? vm1 : vm0;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
                         const float sc = qb ? a1[r] : a0[r];
-                        const bool pass = ((vmask >> row) & 1u) && (sc >= tq);
+                        const bool pass = ((vq >> row) & 1u) && (sc >= tq);
                         const unsigned long long pm = __ballot(pass);
                         if (pm != 0ull) {
                             const unsigned int pre = __builtin_amdgcn_mbcnt_hi(

@@ -19,6 +19,7 @@ OK, E_INVALID, E_HIP, E_CAPACITY, E_NODEVICE, E_INTERNAL = 0, -1, -2, -3, -4, -5
 DTYPE_F32, DTYPE_BF16 = 0, 1
 NOMINATE_BF16_3, NOMINATE_BF16, NOMINATE_INT8 = 0, 1, 2
 MAX_FILTERS, MAX_K = 8, 1024
+MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
@@ -36,6 +37,7 @@ EXPORTS = (
     "crh_embed_ln_packed", "crh_attn_fwd_packed", "crh_masked_mean_pool_packed", "crh_encoder_finish",
     "crh_index_gather_vectors", "crh_mmr_select",
     "crh_index_gather_codes", "crh_group_select",
+    "crh_search_multi",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -154,6 +156,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_merge_topk_strided.argtypes = [i32, i32, i32, vp, vp, i64, i64, vp, vp, vp]
     L.crh_index_match_rows.argtypes = [vp, C.POINTER(Filter), i32, i64, vp, C.POINTER(i64)]
     L.crh_search_cond.argtypes = [vp, i32, vp, i32, i32, C.POINTER(Condition), i32, i64, vp, vp, i32, vp]
+    L.crh_search_multi.argtypes = [vp, i32, vp, i32, i32, C.POINTER(Condition), vp, i32, vp, i64, vp, vp, i32, vp]
     L.crh_index_match_rows_cond.argtypes = [vp, C.POINTER(Condition), i32, i64, vp, C.POINTER(i64)]
     L.crh_index_tombstone_cond.argtypes = [vp, C.POINTER(Condition), i32, C.POINTER(i64)]
     L.crh_index_set_sparse_route.argtypes = [vp, i32, i32]
@@ -258,6 +261,48 @@ def _conditions(filters) -> tuple:
         keep.append(codes)
         arr[i].col, arr[i].negate, arr[i].n, arr[i].codes = int(col), int(negate), int(codes.size), codes.ctypes.data if codes.size else None
     return arr, len(filters), keep
+
+
+def filter_key(filters) -> tuple:
+    """A filter (list of conditions in either item form) as a hashable key: two filters with the same key select the same rows.
+    Conditions are ordered, a set's codes sorted without repeats; ``(col, code)`` and ``(col, [code])`` are the same condition."""
+    out = []
+    for item in filters or []:
+        if is_set_condition(item):
+            out.append((int(item[0]), bool(item[2]) if len(item) == 3 else False, tuple(sorted({int(c) for c in item[1]}))))
+        else:
+            out.append((int(item[0]), False, (int(item[1]),)))
+    return tuple(sorted(out))
+
+
+def multi_plan(class_filters, query_class) -> tuple[list, np.ndarray, list[np.ndarray]]:
+    """How a mixed-filter batch is issued: ``(classes, qclass, calls)``.  ``classes`` are the DISTINCT filters the queries use
+    (:func:`filter_key`; first use first), ``qclass`` every query's index into them, ``calls`` the query positions of each
+    ``crh_search_multi`` call: all of them, in caller order, while there are at most ``MAX_CLASSES`` classes; otherwise the
+    queries ordered by class and cut so that no call sees more than ``MAX_CLASSES`` of them."""
+    query_class = np.asarray(query_class, dtype=np.int64).reshape(-1)
+    if query_class.size and (query_class.min() < 0 or query_class.max() >= len(class_filters)):
+        raise NativeError(E_INVALID, f"query_class outside 0..{len(class_filters) - 1}")
+    seen: dict[tuple, int] = {}
+    classes, remap = [], {}
+    for c in query_class.tolist():
+        if c not in remap:
+            key = filter_key(class_filters[c])
+            if key not in seen:
+                seen[key] = len(classes)
+                classes.append(list(class_filters[c] or []))
+            remap[c] = seen[key]
+    qclass = np.asarray([remap[c] for c in query_class.tolist()], dtype=np.int32)
+    if len(classes) <= MAX_CLASSES:
+        return classes, qclass, [np.arange(qclass.size)]
+    order = np.argsort(qclass, kind="stable")
+    group = qclass[order] // MAX_CLASSES
+    return classes, qclass, [order[group == g] for g in range((len(classes) + MAX_CLASSES - 1) // MAX_CLASSES)]
+
+
+def multi_passes(class_filters, query_class, batch_q: int = 64) -> int:
+    """Corpus passes a mixed-filter batch costs: every call of :func:`multi_plan` is cut into ``batch_q``-query passes."""
+    return sum((len(c) + batch_q - 1) // batch_q for c in multi_plan(class_filters, query_class)[2])
 
 
 def debug_i8_intervals(handle, rows: int, dim: int, queries, k: int, filters=None) -> dict:
@@ -607,6 +652,82 @@ class Index:
             check(lib().crh_search(self._handle(), nq, _ptr(queries), _is_dev(queries), k, farr, nf, row_base,
                                    _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
         return out_scores, out_rows
+
+    def search_multi(self, queries, k: int, class_filters, query_class, row_base: int = 0, out_scores=None, out_rows=None,
+                     stream: int = 0):
+        """:meth:`search` for a batch whose queries carry DIFFERENT filters: query ``i`` is answered under
+        ``class_filters[query_class[i]]`` (each a filter as :meth:`search` takes it, None / empty = every alive row), and row
+        ``i`` of the result is what :meth:`search` returns for query ``i`` alone under that filter -- ids and score bits.  Up to
+        ``MAX_CLASSES`` distinct filters share each 64-query corpus pass (``crh_search_multi``; always the three-launch bf16 scan).
+        Equal filters are one class however often they are listed.  With more than ``MAX_CLASSES`` distinct filters the queries
+        are ordered by class and issued in several calls, results in caller order (device outputs are then complete on return:
+        the calls are finished here).  A batch that uses ONE distinct filter takes :meth:`search` itself -- the code it runs today."""
+        queries = _typed(queries, "float32", "queries")
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = int(queries.shape[0])
+        if len(query_class) != nq:
+            raise NativeError(E_INVALID, f"query_class has {len(query_class)} entries for {nq} queries")
+        classes, qclass, calls = multi_plan(class_filters, query_class)
+        if len(classes) <= 1:
+            return self.search(queries, k, filters=classes[0] if classes else None, row_base=row_base, out_scores=out_scores, out_rows=out_rows,
+                               stream=stream)
+        if nq and int(queries.shape[1]) != self.dim:
+            raise NativeError(E_INVALID, f"query dim {queries.shape[1]} != index dim {self.dim}")
+        if not 0 < k <= MAX_K:
+            raise NativeError(E_CAPACITY, f"k={k} outside 1..{MAX_K}")
+        if out_scores is None:
+            out_scores = np.empty((nq, k), dtype=np.float32)
+            out_rows = np.empty((nq, k), dtype=np.int64)
+        else:
+            _out(out_scores, "float32", "out_scores", (nq, k))
+            _out(out_rows, "int64", "out_rows", (nq, k))
+            if _is_dev(out_scores) != _is_dev(out_rows):
+                raise NativeError(E_INVALID, "out_scores and out_rows must live in the same memory space")
+        if len(calls) == 1:
+            self._search_multi_native(queries, k, classes, qclass, row_base, out_scores, out_rows, stream)
+            return out_scores, out_rows
+        for sel in calls:
+            used = sorted(set(qclass[sel].tolist()))
+            local = np.asarray([used.index(c) for c in qclass[sel].tolist()], dtype=np.int32)
+            if isinstance(queries, np.ndarray):
+                q = np.ascontiguousarray(queries[sel])
+            else:
+                import torch
+                q = queries[torch.as_tensor(sel, device=queries.device)].contiguous()
+            if _is_dev(out_scores):
+                import torch
+                idx = torch.as_tensor(sel, device=out_scores.device)
+                ps = torch.empty((len(sel), k), dtype=torch.float32, device=out_scores.device)
+                pr = torch.empty((len(sel), k), dtype=torch.int64, device=out_scores.device)
+                self._search_multi_native(q, k, [classes[c] for c in used], local, row_base, ps, pr, stream)
+                self.search_finish(stream)
+                out_scores[idx], out_rows[idx] = ps, pr
+            else:
+                ps, pr = np.empty((len(sel), k), np.float32), np.empty((len(sel), k), np.int64)
+                self._search_multi_native(q, k, [classes[c] for c in used], local, row_base, ps, pr, stream)
+                out_scores[sel], out_rows[sel] = ps, pr
+        return out_scores, out_rows
+
+    def _search_multi_native(self, queries, k: int, classes, qclass, row_base, out_scores, out_rows, stream) -> None:
+        """One ``crh_search_multi`` call: at most ``MAX_CLASSES`` filters, ``qclass`` int32 per query."""
+        flat, off = [], [0]
+        for f in classes:
+            f = list(f or [])
+            if len(f) > MAX_FILTERS:
+                raise NativeError(E_INVALID, f"at most {MAX_FILTERS} filter conditions are supported")
+            flat += f
+            off.append(len(flat))
+        carr, keep = (Condition * max(1, len(flat)))(), []
+        for i, item in enumerate(flat):
+            one, _, kp = _conditions([item])
+            carr[i] = one[0]
+            keep.append(kp)
+        off = np.asarray(off, dtype=np.int32)
+        qclass = np.ascontiguousarray(qclass, dtype=np.int32)
+        check(lib().crh_search_multi(self._handle(), int(queries.shape[0]), _ptr(queries), _is_dev(queries), k, carr, off.ctypes.data, len(classes),
+                                     qclass.ctypes.data, row_base, _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
+        del keep
 
     def search_finish(self, stream: int = 0) -> None:
         check(lib().crh_search_finish(self._handle(), stream))

@@ -288,9 +288,31 @@ class ShardSet:
             scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
         return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
 
-    def _search_host(self, queries, k, dfilt):
+    def search_multi(self, queries: np.ndarray, k: int, class_filters, query_class) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search` for a batch whose queries carry different filters (``ffi.Index.search_multi``): query ``i`` under
+        ``class_filters[query_class[i]]``.  The same per-shard plan as :meth:`search` -- every shard answers the whole batch
+        under the same classes, [one all-gather,] one merge."""
+        multi = (list(class_filters), np.asarray(query_class, np.int32))
+        if self.ns == 1:
+            s, r = self.index[0].search_multi(queries, k, *multi, **({"stream": self.stream} if self.stream else {}))
+            return s, np.zeros(r.shape, np.int32), r
+        if self._merge_host is not None:
+            scores, rows = self._search_host(queries, k, None, multi)
+        else:
+            sd, rd = self.search_device(queries, k, None, multi)
+            scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
+        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
+
+    @staticmethod
+    def _shard_search(ix, queries, k, dfilt, multi, **kw):
+        """One shard's part of a search: under one filter, or -- ``multi`` = (class_filters, query_class) -- under every query's own."""
+        if multi is None:
+            return ix.search(queries, k, filters=dfilt, **kw)
+        return ix.search_multi(queries, k, multi[0], multi[1], **kw)
+
+    def _search_host(self, queries, k, dfilt, multi=None):
         nq = int(queries.shape[0])
-        mine = {s: ix.search(queries, k, filters=dfilt, row_base=s * STRIDE) for s, ix in self.index.items()}
+        mine = {s: self._shard_search(ix, queries, k, dfilt, multi, row_base=s * STRIDE) for s, ix in self.index.items()}
         if self.dist is None:
             parts = mine
         else:                                        # the same single all-gather of [scores | rows] records as on the device
@@ -305,9 +327,10 @@ class ShardSet:
         rr = np.stack([parts[s][1] for s in range(self.ns)])
         return self._merge_host(ss, rr)
 
-    def search_device(self, queries, k: int, dfilt):
+    def search_device(self, queries, k: int, dfilt, multi=None):
         """The same on the device, results left there: (scores f32 [nq, k], GLOBAL rows i64 [nq, k]) CUDA tensors -- per-shard
-        ``crh_search`` with ``row_base`` = shard * STRIDE, [one all-gather of the records,] ``crh_merge_topk_strided``."""
+        ``crh_search`` with ``row_base`` = shard * STRIDE, [one all-gather of the records,] ``crh_merge_topk_strided``.
+        ``multi`` = (class_filters, query_class): every query under its own filter (``crh_search_multi``), ``dfilt`` unused."""
         import torch
         dev = torch.device("cuda", self.device)
         ffi.use_device(self.device)
@@ -317,12 +340,12 @@ class ShardSet:
         local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, dev)
         if self.dist is None:
             for s, ix in self.index.items():         # every shard writes its own record of the "gathered" buffer
-                ix.search(qd, k, filters=dfilt, row_base=s * STRIDE, out_scores=all_s[s], out_rows=all_r[s], stream=stream)
+                self._shard_search(ix, qd, k, dfilt, multi, row_base=s * STRIDE, out_scores=all_s[s], out_rows=all_r[s], stream=stream)
             for ix in self.index.values():
                 ix.search_finish(stream)
         else:
             ix = self.index[self.rank]
-            ix.search(qd, k, filters=dfilt, row_base=self.rank * STRIDE, out_scores=loc_s, out_rows=loc_r, stream=stream)
+            self._shard_search(ix, qd, k, dfilt, multi, row_base=self.rank * STRIDE, out_scores=loc_s, out_rows=loc_r, stream=stream)
             ix.search_finish(stream)
             self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
         out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)

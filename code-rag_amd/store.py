@@ -383,6 +383,11 @@ class _Collection:
         scores, shard, local = self.shards.search(queries, limit, dfilt)
         return scores, self.slots_of(shard, local)
 
+    def search_multi(self, queries: np.ndarray, limit: int, class_dfilts, query_class) -> tuple[np.ndarray, np.ndarray]:
+        """The same for a batch whose queries carry different filters: query ``i`` under ``class_dfilts[query_class[i]]``."""
+        scores, shard, local = self.shards.search_multi(queries, limit, class_dfilts, query_class)
+        return scores, self.slots_of(shard, local)
+
     def search_mmr(self, queries: np.ndarray, limit: int, candidates: int, diversity: float, dfilt) -> tuple[np.ndarray, np.ndarray]:
         """The same for the diversity-aware top-k: the ``limit`` MMR picks among the ``candidates`` best hits of every query
         (``ShardSet.search_mmr``); scores are the picks' cosines."""
@@ -599,6 +604,32 @@ def _value_key(v) -> str:
     return repr(sorted(repr(x) for x in v)) if isinstance(v, _COLLECTIONS) else "=" + repr(v)
 
 
+def _filter_key(filters, must_not) -> tuple:
+    """A (filters, must_not) pair as a key: equal keys select the same points (what the coalescer groups calls by, and what
+    makes two queries of a per-query batch members of one class)."""
+    return (tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
+            tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())))
+
+
+def _per_query(filters, must_not, nq: int):
+    """``filters`` / ``must_not`` of a batch call as per-query lists -- or None when both are the single dict (or None) that
+    holds for the whole batch.  A sequence must have one entry (a dict or None) per query."""
+    seqs = [isinstance(v, (list, tuple)) for v in (filters, must_not)]
+    if not any(seqs):
+        return None
+    out = []
+    for v, is_seq, what in ((filters, seqs[0], "filters"), (must_not, seqs[1], "must_not")):
+        if is_seq:
+            if len(v) != nq:
+                raise ValueError(f"per-query {what} has {len(v)} entries for {nq} queries")
+            if not all(e is None or isinstance(e, dict) for e in v):
+                raise ValueError(f"per-query {what} entries must be dicts or None")
+            out.append(list(v))
+        else:
+            out.append([v] * nq)
+    return out[0], out[1]
+
+
 class _RawClient:
     """The slice of ``AsyncQdrantClient`` that callers reach through ``QdrantManager.client``
     (health check: client.py:66; admin cleanup: projects/cleanup.py:41-61)."""
@@ -708,7 +739,7 @@ class HipVectorStore:
                  device: int | None = None, dim: int | None = None, dtype: str | None = None,
                  initial_capacity: int | None = None, search_window_ms: float | None = None, shards: int | None = None,
                  shard_backend: str | None = None, process_group=None, compact_dead_fraction: float | None = None,
-                 compact_min_dead: int | None = None, stream: str | None = None, _merge_fn=None):
+                 compact_min_dead: int | None = None, stream: str | None = None, coalesce_filters: bool | None = None, _merge_fn=None):
         s = get_settings()
         self._host, self._port, self._grpc_port = host, port, grpc_port
         self._device = s.hip_device if device is None else device
@@ -768,6 +799,12 @@ class HipVectorStore:
         self._search_pending: dict[tuple, list] = {}
         self._search_drainers: dict[tuple, asyncio.Task] = {}
         self.search_passes = 0                      # corpus passes issued by search() (observability / tests)
+        # coalesce_filters (CODERAG_HIP_COALESCE_FILTERS=1; default off): plain concurrent calls for one collection share passes
+        # WHATEVER their filters -- a pass serves up to 8 distinct filters (crh_search_multi), every caller keeps its own filter
+        # and its own limit prefix.  Off: a pass is shared by the calls of one filter only, as before.
+        if coalesce_filters is None:
+            coalesce_filters = os.environ.get("CODERAG_HIP_COALESCE_FILTERS", "0").lower() in ("1", "true", "yes", "on")
+        self._coalesce_filters = bool(coalesce_filters)
 
     # ------------------------------------------------------------------ plumbing
     async def _run(self, fn, *args):
@@ -908,8 +945,24 @@ class HipVectorStore:
     def _search_sync(self, collection: str, queries: np.ndarray, limit: int, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None,
                      diversity: float | None = None, candidates: int | None = None, group: tuple | None = None):
         col = self._col(collection)
-        dfilt = col.device_filters(filters, must_not)
         nq = queries.shape[0]
+        per = _per_query(filters, must_not, nq)
+        if per is not None:
+            if diversity is not None or group is not None:
+                raise ValueError("per-query filters cannot be combined with diversity or group_by (a follow-up: the candidate "
+                                 "lists behind both are per filter)")
+            classes: dict[tuple, int] = {}
+            pairs, qclass = [], []
+            for f, m in zip(*per):                                       # distinct filters -> classes, by the coalescer's normalisation
+                key = _filter_key(f, m)
+                if key not in classes:
+                    classes[key] = len(pairs)
+                    pairs.append((f, m))
+                qclass.append(classes[key])
+            if len(pairs) > 1:
+                return (col,) + self._search_classes(col, queries, limit, pairs, np.asarray(qclass, np.int32))
+            filters, must_not = pairs[0] if pairs else (None, None)      # ONE distinct filter: the batch runs the code it runs today
+        dfilt = col.device_filters(filters, must_not)
         if dfilt is None or limit <= 0 or ((diversity is not None or group is not None) and nq == 0):
             return col, np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
         if group is not None:
@@ -919,6 +972,22 @@ class HipVectorStore:
         else:
             scores, slots = col.search_mmr(queries, limit, candidates, diversity, dfilt)
         return col, scores, slots
+
+    @staticmethod
+    def _search_classes(col, queries: np.ndarray, limit: int, pairs, qclass: np.ndarray):
+        """The mixed-filter pass: ``pairs`` are the distinct (filters, must_not) of the batch, ``qclass`` every query's index
+        into them.  A class naming a value the collection never stored answers its own queries with nothing; the others share
+        corpus passes (``ffi.Index.search_multi``)."""
+        nq = queries.shape[0]
+        scores, slots = np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
+        dfilts = [col.device_filters(f, m) for f, m in pairs]
+        live = np.flatnonzero(np.asarray([dfilts[c] is not None for c in qclass.tolist()], bool))
+        if limit > 0 and live.size:
+            used = sorted(set(qclass[live].tolist()))
+            s, r = col.search_multi(np.ascontiguousarray(queries[live]), limit, [dfilts[c] for c in used],
+                                    np.asarray([used.index(c) for c in qclass[live].tolist()], np.int32))
+            scores[live], slots[live] = s, r
+        return scores, slots
 
     def _search_hits_sync(self, collection: str, queries: np.ndarray, limits, filters: dict[str, Any] | None,
                           must_not: dict[str, Any] | None = None, diversity: float | None = None,
@@ -1034,15 +1103,51 @@ class HipVectorStore:
         (group_by, group_size, candidates), and the first j rows of a grouped answer are the j-row answer."""
         loop = asyncio.get_running_loop()
         name = collection.value if isinstance(collection, CollectionName) else collection
-        key = (name, tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
-               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())), (diversity, candidates), group)
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
+        if self._coalesce_filters and diversity is None and group is None:
+            # plain calls of one collection travel together whatever their filters: each entry carries its own
+            key = (name, "any filter")
+            self._search_pending.setdefault(key, []).append((vec, int(limit), fut, filters, must_not))
+            task = self._search_drainers.get(key)
+            if task is None or task.done():
+                self._search_drainers[key] = loop.create_task(self._drain_searches_mixed(key, name))
+            return await fut
+        key = (name, tuple(sorted((k, _value_key(v)) for k, v in (filters or {}).items())),
+               tuple(sorted((k, _value_key(v)) for k, v in (must_not or {}).items())), (diversity, candidates), group)
         self._search_pending.setdefault(key, []).append((vec, int(limit), fut))
         task = self._search_drainers.get(key)
         if task is None or task.done():
             self._search_drainers[key] = loop.create_task(self._drain_searches(key, name, filters, must_not, diversity, candidates, group))
         return await fut
+
+    async def _drain_searches_mixed(self, key, name: str) -> None:
+        """The drainer of ``coalesce_filters``: like :meth:`_drain_searches`, with every entry's own filter handed on per query.
+        ``search_passes`` counts the corpus passes the batch really costs: 64 queries of up to 8 distinct filters each."""
+        while self._search_pending.get(key):
+            await asyncio.sleep(self._search_window_s)
+            batch = self._search_pending.pop(key, [])
+            if not batch:
+                break
+            for start in range(0, len(batch), 256):
+                part = batch[start:start + 256]
+                try:
+                    q = np.stack([b[0] for b in part])
+                    keys = [_filter_key(b[3], b[4]) for b in part]
+                    distinct = {k: i for i, k in enumerate(dict.fromkeys(keys))}
+                    if len(distinct) == 1:                               # (one filter: the pass of _drain_searches, counted its way)
+                        self.search_passes += (len(part) + 63) // 64
+                        per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], part[0][3], part[0][4])
+                    else:
+                        self.search_passes += ffi.multi_passes([[(0, i)] for i in range(len(distinct))], [distinct[k] for k in keys])
+                        per_query = await self._run(self._search_hits_sync, name, q, [b[1] for b in part], [b[3] for b in part], [b[4] for b in part])
+                    for b, hits in zip(part, per_query):
+                        if not b[2].done():
+                            b[2].set_result(hits)
+                except Exception as e:  # noqa: BLE001 -- every caller of the pass sees the failure (wrapped by search())
+                    for b in part:
+                        if not b[2].done():
+                            b[2].set_exception(e)
 
     async def _drain_searches(self, key, name: str, filters, must_not=None, diversity=None, candidates=None, group=None) -> None:
         while self._search_pending.get(key):
@@ -1065,12 +1170,19 @@ class HipVectorStore:
                             fut.set_exception(e)
 
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
-                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                           filters=None, must_not=None, *,
                            diversity: float | None = None, candidates: int | None = None,
                            group_by: str | None = None, group_size: int = 1) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
-        serves up to 64 queries.  ``diversity`` / ``candidates`` / ``group_by`` / ``group_size`` as in :meth:`search`."""
+        serves up to 64 queries.  ``diversity`` / ``candidates`` / ``group_by`` / ``group_size`` as in :meth:`search`.
+        ``filters`` and ``must_not`` may each be a dict for the whole batch, as in :meth:`search`, or a SEQUENCE with one dict
+        (or None) per query: every query is then answered under its own filter, exactly as a lone :meth:`search` with that
+        filter would answer it, and up to 8 distinct filters share each 64-query pass.  A filter naming a
+        value the collection never stored yields an empty list for its own queries only.  Per-query filters cannot be combined
+        with ``diversity`` or ``group_by`` (``ValueError``; a follow-up)."""
         try:
+            if (isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple))) and (diversity is not None or group_by is not None):
+                raise ValueError("per-query filters cannot be combined with diversity or group_by")
             group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates)
             if group is None:
                 diversity, candidates = self._mmr_args(limit, diversity, candidates)

@@ -158,9 +158,20 @@ class VectorSearcher:
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                                 diversity: float | None = None, candidates: int | None = None,
-                                max_per_file: int | None = None) -> list[list[dict]]:
-        """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors."""
+                                max_per_file: int | None = None,
+                                filters_per_query: list[dict | None] | None = None) -> list[list[dict]]:
+        """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
+        ``filters_per_query``: one filter dict (keys ``language`` / ``entity_type`` / ``project_name``; None = no filter) per
+        query -- every query is answered under its own, and the batch still shares corpus passes (up to 8 distinct filters per
+        64 queries).  Mutually exclusive with the scalar ``language`` / ``entity_type`` / ``project_name``, where a list already
+        means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
+        if filters_per_query is not None:
+            if filters:
+                raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")
+            if len(filters_per_query) != len(queries):
+                raise QueryError(f"filters_per_query has {len(filters_per_query)} entries for {len(queries)} queries")
+            filters = [({k: v for k, v in f.items() if v} or None) if f else None for f in filters_per_query]
         try:
             if isinstance(queries, np.ndarray) or (hasattr(queries, "shape") and not isinstance(queries, (list, tuple))):
                 vectors = queries

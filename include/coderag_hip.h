@@ -195,6 +195,27 @@ int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_d
                     const crh_condition *conds, int n_conds, int64_t row_base, float *out_scores,
                     int64_t *out_rows, int out_on_device, void *stream);
 
+/* A batch whose queries carry DIFFERENT filters, served by shared corpus passes (the reference sends its own payload filter
+ * with every query -- project_name always, language / entity_type often: query/vector_search.py:83-93 -- one query per RPC).
+ * A CLASS is one distinct filter: an AND of 0..CRH_MAX_FILTERS conditions, empty = every alive row.  Class c owns
+ * conds[class_off[c] .. class_off[c+1]) (class_off: host int32[n_classes + 1], ascending); query i belongs to class
+ * query_class[i] (host int32[nq]).  n_classes: 1..CRH_MAX_CLASSES.  nq may be any count: it is cut into batches of 64 queries
+ * (32 at dim 1536) in caller order, and each batch is ONE pass over the corpus in which every query's rows are tested
+ * against its own class's mask.  Row i of the output equals, id for id and f32 score bit for bit, what crh_search_cond
+ * returns for query i alone with its class's conditions.  Outputs, padding, tie order, row_base, device outputs and
+ * crh_search_finish, the overflow regrowth and crh_search_stats are those of crh_search_cond; bad columns, class ids outside
+ * 0..n_classes-1 and n_classes out of range are CRH_E_INVALID.
+ * A mixed batch always runs the three-launch bf16 scan in its classed form, whatever crh_index_set_nomination allows: the
+ * int8 pass, the one-launch scan and the wide scan have no classed variant.  (So a call whose queries all share ONE filter
+ * is better served by crh_search_cond.)  With the sparse route enabled, a batch whose classes TOGETHER leave at most one tile
+ * in max_fraction_den populated walks the list of the union's tiles.  The class masks are kept between calls like the mask of
+ * a single filter, separately from it. */
+#define CRH_MAX_CLASSES 8
+int crh_search_multi(crh_index *h, int nq, const float *queries, int queries_on_device, int k,
+                     const crh_condition *conds, const int32_t *class_off, int n_classes,
+                     const int32_t *query_class, int64_t row_base, float *out_scores, int64_t *out_rows,
+                     int out_on_device, void *stream);
+
 /* (No counterpart in the reference: Qdrant's payload indexes make a filtered query cost about what the matching rows cost,
  * embeddings/client.py:93-113.)  A filtered search of up to 64 queries (32 at dim 1536) whose mask leaves at most one 32-row
  * tile in `max_fraction_den` populated reads only those tiles: their ascending list is made with the mask and kept with it,
