@@ -1098,13 +1098,15 @@ __global__ __launch_bounds__(NW * 64) void k_attn(const bf16_t *__restrict__ qkv
             const int q0 = (qg * QT + qi) * 16;
             if (q0 >= L || q0 + c16 >= L) continue;      // no such tile / a row of the NEXT packed row (never for padded rows: L % 16 == 0)
             bf16_t *orow = out + (r0 + q0 + c16) * (H * 64) + h * 64;
-            // rows past the last valid token (not live): never read as keys nor pooled; written as zeros to stay finite
-            const float inv = (live[qi] && lrun[qi] > 0.f) ? 1.f / lrun[qi] : 0.f;
+            // rows past the last valid token (not live): never read as keys nor pooled; written as zeros to stay finite -- as +0.0,
+            // the bits k_attn_long writes for them (what the key loop summed for query row 0, times inv = 0, is -0.0 where negative)
+            const bool some = live[qi] && lrun[qi] > 0.f;
+            const float inv = some ? 1.f / lrun[qi] : 0.f;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 u32x2 o;
-                o.x = pack2(oacc[qi][dt][0] * inv, oacc[qi][dt][1] * inv);
-                o.y = pack2(oacc[qi][dt][2] * inv, oacc[qi][dt][3] * inv);
+                o.x = some ? pack2(oacc[qi][dt][0] * inv, oacc[qi][dt][1] * inv) : 0u;
+                o.y = some ? pack2(oacc[qi][dt][2] * inv, oacc[qi][dt][3] * inv) : 0u;
                 *reinterpret_cast<u32x2 *>(orow + dt * 16 + 4 * g) = o;
             }
         }
