@@ -53,6 +53,17 @@ struct MaskRef {
     int64_t nlist = -1;
 };
 
+// A kept mask: what it was built from and on, and the device copy of its key.  The mask words themselves are in the workspace.
+struct MaskCache {
+    uint64_t built_at = 0;          // crh_index::mutations when it was built (0: never, or its buffers were reallocated)
+    hipStream_t stream = nullptr;   // (the stream the kept mask was built on: another stream rebuilds it -- nothing orders the two)
+    bool valid = false;
+    FilterKey key;                  // (also the host source of the sets' upload)
+    int32_t *sets = nullptr;        // device copy of key: the sets k_filter_mask / k_filter_mask_classes search
+    int64_t sets_cap = 0;
+    int64_t nlist = -1;             // length of the list of populated tiles made with the mask (< 0: none was made)
+};
+
 struct Pending {
     int nq, k;
     FilterKey key;
@@ -103,28 +114,17 @@ struct crh_index {
     // The validity mask of the last filter is kept while nothing it was built from has changed (rows, alive bits, codes: every
     // mutation bumps `mutations`): the reference's searchers send the same equality filter with query after query (project_name,
     // language: query/vector_search.py:83-93), and rebuilding the mask is a pass over the code columns per batch (~20 us at 10M rows).
-    uint64_t mutations = 1, mask_built_at = 0;
-    hipStream_t mask_stream = nullptr;   // (the stream the kept mask was built on: another stream rebuilds it -- nothing orders the two)
-    bool mask_valid = false;
-    FilterKey mask_key;                  // (also the host source of the sets' upload)
-    int32_t *mask_sets = nullptr;        // device copy of mask_key: the sets k_filter_mask searches
-    int64_t mask_sets_cap = 0;
+    uint64_t mutations = 1;
+    MaskCache mask;
     // The sparse route: a filtered batch of <= batch_q queries whose mask leaves at most 1 tile in
     // sparse_den populated walks the list of those tiles with k_scan_list instead of streaming every tile.  The list is made
     // with the mask and kept with it.  crh_index_set_sparse_route / CODERAG_HIP_SPARSE=0, CODERAG_HIP_SPARSE_DEN.
     bool sparse_on = true;
     int sparse_den = kSparseDen;
-    int64_t mask_nlist = -1;
     // The class masks of a mixed-filter call (crh_search_multi) are kept the same way, under their own key -- the classes' keys
     // one after the other behind their number -- and in their own buffers, so a mixed call and the single-filter calls around
     // it each find their masks as they left them.
-    uint64_t cmask_built_at = 0;
-    hipStream_t cmask_stream = nullptr;
-    bool cmask_valid = false;
-    FilterKey cmask_key;
-    int32_t *cmask_sets = nullptr;
-    int64_t cmask_sets_cap = 0;
-    int64_t cmask_nlist = -1;
+    MaskCache cmask;
     FilterClasses *cmask_classes = nullptr;   // device copy of the classes' descriptions (k_filter_mask_classes)
     u32x4 *xt = nullptr;
     float *xf32 = nullptr;
@@ -228,6 +228,12 @@ int ensure_workspace(crh_index *h, crh_index::Workspace &w, int wave_cap, int qc
     if (!w.tau) CRH_TRY(dev_alloc(&w.tau, kWideQ));
     if (h->i8 && !w.qfrag8) CRH_TRY(dev_alloc(&w.qfrag8, (int64_t)(kMaxQ / 32) * 2 * (h->dim / 32) * 64));
     if (h->i8 && !w.qpar) CRH_TRY(dev_alloc(&w.qpar, kMaxQ * 4));
+    // the sample launch's record of upper ends (crh_i8.hpp, `shi`) is an optimisation: no memory for it -> the pass reads every tile
+    if (h->i8 && !w.shi && hipMalloc(reinterpret_cast<void **>(&w.shi), (size_t)kI8SampleTiles * 64 * 4 * sizeof(u32x4)) != hipSuccess) {
+        (void)hipGetLastError();
+        w.shi = nullptr;
+        h->i8_sample_record = false;
+    }
     if (!h->status) {
         CRH_TRY(dev_alloc(&h->status, kStatusSlots));
         CRH_HIP(hipMemset(h->status, 0, sizeof(SearchStatus) * kStatusSlots));
@@ -242,7 +248,7 @@ int ensure_workspace(crh_index *h, crh_index::Workspace &w, int wave_cap, int qc
         dev_free(w.effmask);
         dev_free(w.tilelist);
         w.ws_mask_tiles = 0;
-        h->mask_built_at = 0;
+        h->mask.built_at = 0;
         CRH_TRY(dev_alloc(&w.effmask, h->cap_tiles));
         CRH_TRY(dev_alloc(&w.tilelist, h->cap_tiles + ceil_div(h->cap_tiles, 256) + 1));
         w.ws_mask_tiles = h->cap_tiles;
@@ -327,84 +333,17 @@ int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_co
     return CRH_OK;
 }
 
-int build_mask(crh_index *h, crh_index::Workspace &w, const FilterKey &key, MaskRef *out, hipStream_t st)
-{
-    *out = MaskRef{};
-    const int nfilt = key.empty() ? 0 : key[0];
-    if (nfilt == 0 || h->count == 0) {   // (an empty index: nothing to mask, and a zero-block launch is an error)
-        out->mask = h->alive;
-        return CRH_OK;
-    }
-    FilterSet fs;
-    fs.n = nfilt;
-    bool sets = false;
-    for (size_t at = 1, f = 0; f < (size_t)nfilt; ++f) {
-        if (key[at] < 0 || key[at] >= h->ncols)
-            return fail(CRH_E_INVALID, "filter column %d out of range (index has %d code columns)", key[at], h->ncols);
-        fs.col[f] = key[at];
-        fs.neg[f] = key[at + 1];
-        fs.cnt[f] = key[at + 2];
-        fs.off[f] = (int)at + 3;
-        fs.one[f] = fs.cnt[f] == 1 ? key[at + 3] : 0;
-        sets = sets || fs.cnt[f] > 1;
-        at += 3 + (size_t)fs.cnt[f];
-    }
-    const bool same = h->mask_valid && h->mask_built_at == h->mutations && h->mask_stream == st && h->mask_key == key &&
-                      (h->mask_nlist >= 0) == h->sparse_on;
-    if (!same) {
-        h->mask_valid = false;
-        h->mask_key = key;
-        if (sets) {   // the device copy of the key: fs.off are positions in it
-            if (h->mask_sets_cap < (int64_t)key.size()) {
-                dev_free(h->mask_sets);
-                h->mask_sets_cap = 0;
-                CRH_TRY(dev_alloc(&h->mask_sets, (int64_t)key.size()));
-                h->mask_sets_cap = (int64_t)key.size();
-            }
-            CRH_HIP(hipMemcpyAsync(h->mask_sets, h->mask_key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
-        }
-        const int64_t rows = (h->count + 63) & ~63LL;
-        hipLaunchKernelGGL(k_filter_mask, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, h->alive, h->codes, h->cap_rows,
-                           h->count, fs, h->mask_sets, w.effmask);
-        CRH_HIP(hipGetLastError());
-        h->mask_nlist = -1;
-        if (h->sparse_on) {
-            // the populated tiles, in order; their number decides the route, so the host waits for it -- once per mask, not per batch
-            const int64_t ntiles = ceil_div(h->count, kTileRows);
-            const unsigned nb = (unsigned)ceil_div(ntiles, 256);
-            uint32_t *blockcnt = w.tilelist + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
-            hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, w.effmask, ntiles, blockcnt);
-            hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, w.effmask, ntiles, blockcnt, w.tilelist, len);
-            CRH_HIP(hipGetLastError());
-            uint32_t n = 0;
-            CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipStreamSynchronize(st));
-            h->mask_nlist = n;
-        }
-        h->mask_built_at = h->mutations;
-        h->mask_stream = st;
-        h->mask_valid = true;
-    }
-    out->mask = w.effmask;
-    out->list = w.tilelist;
-    out->nlist = h->mask_nlist;
-    return CRH_OK;
-}
-
-// does a batch of nq queries under this mask take the sparse route?
-bool sparse_use(const crh_index *h, const MaskRef &m, int nq)
-{
-    return h->sparse_on && m.nlist >= 0 && nq <= h->batch_q && m.nlist * h->sparse_den <= ceil_div(h->count, kTileRows);
-}
-
 // one filter of a key, starting at key[at], as k_filter_mask takes it (set offsets are positions in the key); returns the
-// position behind it, or 0 for a column the index does not have
-size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, FilterSet &fs, bool *sets)
+// position behind it, or 0 -- and the column in *bad_col -- for a column the index does not have
+size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, FilterSet &fs, bool *sets, int *bad_col)
 {
     const int nfilt = key[at++];
     fs.n = nfilt;
     for (int f = 0; f < nfilt; ++f) {
-        if (key[at] < 0 || key[at] >= h->ncols) return 0;
+        if (key[at] < 0 || key[at] >= h->ncols) {
+            *bad_col = key[at];
+            return 0;
+        }
         fs.col[f] = key[at];
         fs.neg[f] = key[at + 1];
         fs.cnt[f] = key[at + 2];
@@ -416,6 +355,83 @@ size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, F
     return at;
 }
 
+// is the kept mask the one of this key, built on this stream from the index as it is now, with a tile list iff the sparse route is on?
+bool mask_is_current(const MaskCache &c, const crh_index *h, const FilterKey &key, hipStream_t st)
+{
+    return c.valid && c.built_at == h->mutations && c.stream == st && c.key == key && (c.nlist >= 0) == h->sparse_on;
+}
+
+// the device copy of the cache's key: FilterSet::off are positions in it
+int upload_sets(MaskCache &c, hipStream_t st)
+{
+    const int64_t n = (int64_t)c.key.size();
+    if (c.sets_cap < n) {
+        dev_free(c.sets);
+        c.sets_cap = 0;
+        CRH_TRY(dev_alloc(&c.sets, n));
+        c.sets_cap = n;
+    }
+    CRH_HIP(hipMemcpyAsync(c.sets, c.key.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return CRH_OK;
+}
+
+// the populated tiles of a row mask, in order, into list_buf (laid out like Workspace::tilelist); their number decides the
+// route, so the host waits for it -- once per mask, not per batch
+int make_tile_list(crh_index *h, const uint32_t *words, uint32_t *list_buf, hipStream_t st, int64_t *nlist)
+{
+    const int64_t ntiles = ceil_div(h->count, kTileRows);
+    const unsigned nb = (unsigned)ceil_div(ntiles, 256);
+    uint32_t *blockcnt = list_buf + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
+    hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt);
+    hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt, list_buf, len);
+    CRH_HIP(hipGetLastError());
+    uint32_t n = 0;
+    CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
+    CRH_HIP(hipStreamSynchronize(st));
+    *nlist = n;
+    return CRH_OK;
+}
+
+int build_mask(crh_index *h, crh_index::Workspace &w, const FilterKey &key, MaskRef *out, hipStream_t st)
+{
+    *out = MaskRef{};
+    const int nfilt = key.empty() ? 0 : key[0];
+    if (nfilt == 0 || h->count == 0) {   // (an empty index: nothing to mask, and a zero-block launch is an error)
+        out->mask = h->alive;
+        return CRH_OK;
+    }
+    FilterSet fs;
+    bool sets = false;
+    int bad_col = 0;
+    if (filterset_from_key(h, key, 0, fs, &sets, &bad_col) == 0)
+        return fail(CRH_E_INVALID, "filter column %d out of range (index has %d code columns)", bad_col, h->ncols);
+    MaskCache &c = h->mask;
+    if (!mask_is_current(c, h, key, st)) {
+        c.valid = false;
+        c.key = key;
+        if (sets) CRH_TRY(upload_sets(c, st));
+        const int64_t rows = (h->count + 63) & ~63LL;
+        hipLaunchKernelGGL(k_filter_mask, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, h->alive, h->codes, h->cap_rows,
+                           h->count, fs, c.sets, w.effmask);
+        CRH_HIP(hipGetLastError());
+        c.nlist = -1;
+        if (h->sparse_on) CRH_TRY(make_tile_list(h, w.effmask, w.tilelist, st, &c.nlist));
+        c.built_at = h->mutations;
+        c.stream = st;
+        c.valid = true;
+    }
+    out->mask = w.effmask;
+    out->list = w.tilelist;
+    out->nlist = c.nlist;
+    return CRH_OK;
+}
+
+// does a batch of nq queries under this mask take the sparse route?
+bool sparse_use(const crh_index *h, const MaskRef &m, int nq)
+{
+    return h->sparse_on && m.nlist >= 0 && nq <= h->batch_q && m.nlist * h->sparse_den <= ceil_div(h->count, kTileRows);
+}
+
 // The masks of a mixed-filter batch: ckey = [number of classes, then every class's key].  out->mask is the union's row mask,
 // *cmask_out the interleaved class words; the union's tile list is made while the sparse route is enabled.  Kept like the
 // single mask (key, mutations, stream), in buffers of their own.
@@ -424,67 +440,48 @@ int build_class_masks(crh_index *h, crh_index::Workspace &w, const FilterKey &ck
     *out = MaskRef{};
     *cmask_out = nullptr;
     if (h->count == 0) return CRH_OK;   // (an empty index: every batch is padding, no mask is read)
+    MaskCache &c = h->cmask;
     if (w.ws_cmask_tiles < h->cap_tiles) {
         dev_free(w.cmask);
         dev_free(w.cunion);
         dev_free(w.clist);
         w.ws_cmask_tiles = 0;
-        h->cmask_valid = false;
+        c.valid = false;
         CRH_TRY(dev_alloc(&w.cmask, h->cap_tiles * CRH_MAX_CLASSES));
         CRH_TRY(dev_alloc(&w.cunion, h->cap_tiles));
         CRH_TRY(dev_alloc(&w.clist, h->cap_tiles + ceil_div(h->cap_tiles, 256) + 1));
         w.ws_cmask_tiles = h->cap_tiles;
     }
-    const bool same = h->cmask_valid && h->cmask_built_at == h->mutations && h->cmask_stream == st && h->cmask_key == ckey &&
-                      (h->cmask_nlist >= 0) == h->sparse_on;
-    if (!same) {
-        h->cmask_valid = false;
-        h->cmask_key = ckey;
+    if (!mask_is_current(c, h, ckey, st)) {
+        c.valid = false;
+        c.key = ckey;
         FilterClasses fc{};
         fc.n = ckey[0];
         bool sets = false;
+        int bad_col = 0;
         size_t at = 1;
-        for (int c = 0; c < fc.n; ++c) {
-            at = filterset_from_key(h, ckey, at, fc.c[c], &sets);
-            if (at == 0) return fail(CRH_E_INVALID, "class %d: filter column out of range (index has %d code columns)", c, h->ncols);
+        for (int cl = 0; cl < fc.n; ++cl) {
+            at = filterset_from_key(h, ckey, at, fc.c[cl], &sets, &bad_col);
+            if (at == 0) return fail(CRH_E_INVALID, "class %d: filter column out of range (index has %d code columns)", cl, h->ncols);
         }
         if (!h->cmask_classes) CRH_TRY(dev_alloc(&h->cmask_classes, 1));
         // (the source is on this frame: a copy from pageable memory has left it when the call returns)
         CRH_HIP(hipMemcpyAsync(h->cmask_classes, &fc, sizeof(fc), hipMemcpyHostToDevice, st));
-        if (sets) {
-            if (h->cmask_sets_cap < (int64_t)ckey.size()) {
-                dev_free(h->cmask_sets);
-                h->cmask_sets_cap = 0;
-                CRH_TRY(dev_alloc(&h->cmask_sets, (int64_t)ckey.size()));
-                h->cmask_sets_cap = (int64_t)ckey.size();
-            }
-            CRH_HIP(hipMemcpyAsync(h->cmask_sets, h->cmask_key.data(), ckey.size() * 4, hipMemcpyHostToDevice, st));
-        }
+        if (sets) CRH_TRY(upload_sets(c, st));
         CRH_HIP(hipStreamSynchronize(st));
         const int64_t rows = (h->count + 63) & ~63LL;
         hipLaunchKernelGGL(k_filter_mask_classes, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, h->alive, h->codes, h->cap_rows,
-                           h->count, h->cmask_classes, h->cmask_sets, w.cmask, w.cunion);
+                           h->count, h->cmask_classes, c.sets, w.cmask, w.cunion);
         CRH_HIP(hipGetLastError());
-        h->cmask_nlist = -1;
-        if (h->sparse_on) {
-            const int64_t ntiles = ceil_div(h->count, kTileRows);
-            const unsigned nb = (unsigned)ceil_div(ntiles, 256);
-            uint32_t *blockcnt = w.clist + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
-            hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, w.cunion, ntiles, blockcnt);
-            hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, w.cunion, ntiles, blockcnt, w.clist, len);
-            CRH_HIP(hipGetLastError());
-            uint32_t n = 0;
-            CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipStreamSynchronize(st));
-            h->cmask_nlist = n;
-        }
-        h->cmask_built_at = h->mutations;
-        h->cmask_stream = st;
-        h->cmask_valid = true;
+        c.nlist = -1;
+        if (h->sparse_on) CRH_TRY(make_tile_list(h, w.cunion, w.clist, st, &c.nlist));
+        c.built_at = h->mutations;
+        c.stream = st;
+        c.valid = true;
     }
     out->mask = w.cunion;
     out->list = w.clist;
-    out->nlist = h->cmask_nlist;
+    out->nlist = c.nlist;
     *cmask_out = w.cmask;
     return CRH_OK;
 }
@@ -704,6 +701,86 @@ int launch_scan_wide(crh_index *h, crh_index::Workspace &w, hipStream_t st, cons
     return CRH_OK;
 }
 
+// the queries of a batch as the scans take them: the bf16 image and the canonical queries, with_i8: the integer images too
+// (width query slots are prepared: slots >= nq are zero queries, tau = +inf)
+int launch_prep(crh_index *h, crh_index::Workspace &w, hipStream_t st, const float *q_dev, int nq, int width, SearchStatus *stt, bool with_i8)
+{
+#define CRH_PREP(BF16, I8)                                                                                                     \
+    hipLaunchKernelGGL((k_prep_queries<BF16, I8>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, \
+                       I8 ? w.qfrag8 : (u32x4 *)nullptr, I8 ? w.qpar : (float *)nullptr)
+    if (h->dtype == CRH_DTYPE_BF16) {
+        if (with_i8) CRH_PREP(true, true); else CRH_PREP(true, false);
+    } else {
+        if (with_i8) CRH_PREP(false, true); else CRH_PREP(false, false);
+    }
+#undef CRH_PREP
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+// the selection behind every bf16 scan: canonical scores of the nominated rows, the k best of each query
+int launch_select_bf16(crh_index *h, crh_index::Workspace &w, hipStream_t st, int nq, int k, float margin, int64_t row_base, float *out_s, int64_t *out_r,
+                       SearchStatus *stt)
+{
+    if (h->dtype == CRH_DTYPE_F32)
+        hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, w.ws_qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+    else
+        hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, w.ws_qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
+                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+// a batch no row can match (an empty index, an empty tile list): the padding the scans would arrive at
+int pad_batch(crh_index *h, int slot, int nq, int k, float *out_s, int64_t *out_r, hipStream_t st, bool sparse)
+{
+    if (sparse) {
+        h->stats.batches += 1;
+        if (h->profiling) {   // (finish_pending reads the pair of every batch)
+            CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+            CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+        }
+    }
+    CRH_HIP(hipMemsetAsync(h->status + slot, 0, sizeof(SearchStatus), st));
+    const int64_t n = (int64_t)nq * k;
+    hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out_s, out_r, n);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+void count_batch(crh_index *h, int64_t rows, int64_t tiles, int64_t seed)
+{
+    h->stats.rows += rows;
+    h->stats.tiles += tiles;
+    h->stats.seed_tiles += seed;
+    h->stats.batches += 1;
+}
+
+// The three-launch bf16 form of a batch: prepare the queries, seed scan over a sample of the items (tiles, or positions of a
+// tile list), thresholds (k_tau), main scan over all of them, selection.  scan(mode, n, stride) launches the scan kernel in
+// mode 0 (seed) / 1 (main), the mode as a std::integral_constant; rows is what the batch counts as read, width the query
+// slots prepared, qstride the row pitch of the seed maxima.
+template <typename Scan>
+int enqueue_three(crh_index *h, crh_index::Workspace &w, const float *q_dev, int nq, int k, int64_t items, int64_t rows, int width, int qstride,
+                  int64_t row_base, float *out_s, int64_t *out_r, int slot, hipStream_t st, Scan scan)
+{
+    const float margin = margin_for(h);
+    SearchStatus *stt = h->status + slot;
+    CRH_TRY(launch_prep(h, w, st, q_dev, nq, width, stt, false));
+    const int G = (int)std::min<int64_t>(h->seed_tiles, items);
+    const int stride = (int)(items / G);   // (G * stride <= items: every sample position is inside them)
+    CRH_TRY(scan(std::integral_constant<int, 0>{}, G, stride));
+    hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, qstride);
+    CRH_HIP(hipGetLastError());
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+    CRH_TRY(scan(std::integral_constant<int, 1>{}, (int)items, 1));
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+    CRH_TRY(launch_select_bf16(h, w, st, nq, k, margin, row_base, out_s, out_r, stt));
+    count_batch(h, rows, items, G);
+    return CRH_OK;
+}
+
 // one batch (<= batch_q queries through k_scan, or up to kWideQ through k_scan_wide), everything enqueued on `st`
 int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int nq, int k, const MaskRef &mref, int64_t row_base, float *out_s,
                   int64_t *out_r, int slot, hipStream_t st, int *path_out)
@@ -712,20 +789,7 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
     const uint32_t *mask = mref.mask;
     const int64_t ntiles = ceil_div(h->count, kTileRows);
     const bool sparse = ntiles > 0 && sparse_use(h, mref, nq);
-    if (ntiles == 0 || (sparse && mref.nlist == 0)) {   // (no row can match: the padding the scans would arrive at)
-        if (sparse) {
-            h->stats.batches += 1;
-            if (h->profiling) {   // (finish_pending reads the pair of every batch)
-                CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
-                CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-            }
-        }
-        CRH_HIP(hipMemsetAsync(h->status + slot, 0, sizeof(SearchStatus), st));
-        const int64_t n = (int64_t)nq * k;
-        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out_s, out_r, n);
-        CRH_HIP(hipGetLastError());
-        return CRH_OK;
-    }
+    if (ntiles == 0 || (sparse && mref.nlist == 0)) return pad_batch(h, slot, nq, k, out_s, out_r, st, sparse);
     const int wave_cap = w.ws_wave_cap, qcap = w.ws_qcap;
     const float margin = margin_for(h);
     SearchStatus *stt = h->status + slot;
@@ -738,53 +802,18 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
     // The sparse route: the mask leaves few tiles populated -- the three-launch bf16 scan over the LIST of those tiles
     // (k_scan_list), thresholds seeded from listed tiles only; k_select as behind every bf16 scan, so ids and score bits are
     // what the dense route gives.  It reads nlist tiles instead of ntiles; the int8 copy is not needed at that size.
-    if (sparse) {
-        if (h->dtype == CRH_DTYPE_BF16)
-            hipLaunchKernelGGL((k_prep_queries<true, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-        else
-            hipLaunchKernelGGL((k_prep_queries<false, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-        CRH_HIP(hipGetLastError());
-        const int nlist = (int)mref.nlist;
-        const int G = (int)std::min<int64_t>(h->seed_tiles, nlist);
-        const int stride = nlist / G;   // (G * stride <= nlist: every sample position is inside the list)
-        CRH_TRY(launch_scan_list<0>(h, w, scan_blocks(h, G), st, mref, G, stride, wave_cap, qcap, stt));
-        hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, qstride);
-        CRH_HIP(hipGetLastError());
-        if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
-        CRH_TRY(launch_scan_list<1>(h, w, scan_blocks(h, nlist), st, mref, nlist, 1, wave_cap, qcap, stt));
-        if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-        if (h->dtype == CRH_DTYPE_F32)
-            hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-        else
-            hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-        CRH_HIP(hipGetLastError());
-        h->stats.rows += std::min<int64_t>(h->count, (int64_t)nlist * kTileRows);
-        h->stats.tiles += nlist;
-        h->stats.seed_tiles += G;
-        h->stats.batches += 1;
-        return CRH_OK;
-    }
+    if (sparse)
+        return enqueue_three(h, w, q_dev, nq, k, mref.nlist, std::min<int64_t>(h->count, mref.nlist * kTileRows), width, qstride, row_base, out_s, out_r, slot, st,
+                             [&](auto mode, int n, int stride) {
+                                 return launch_scan_list<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mref, n, stride, wave_cap, qcap, stt);
+                             });
 
     // <= batch_q queries, nominated from the int8 copy (crh_i8.hpp): half the bytes of the pass, same results
     if (i8_use(h, nq, k)) {
         CRH_TRY(i8_sync(h, st));
     }
-    const bool via_i8 = i8_use(h, nq, k);   // (i8_sync may have given the copy up for lack of memory)
-    if (via_i8) {    // one launch prepares the bf16 image, the canonical queries and the integer images
-        if (h->dtype == CRH_DTYPE_BF16)
-            hipLaunchKernelGGL((k_prep_queries<true, true>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
-        else
-            hipLaunchKernelGGL((k_prep_queries<false, true>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
-    } else if (h->dtype == CRH_DTYPE_BF16) {
-        hipLaunchKernelGGL((k_prep_queries<true, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-    } else {
-        hipLaunchKernelGGL((k_prep_queries<false, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-    }
-    CRH_HIP(hipGetLastError());
-
-    if (via_i8) {
+    if (i8_use(h, nq, k)) {   // (asked again: i8_sync may have given the copy up for lack of memory)
+        CRH_TRY(launch_prep(h, w, st, q_dev, nq, width, stt, true));   // one launch prepares the bf16 image, the canonical queries and the integer images
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ntiles, kI8Waves), h->cu_count));
         int G8, S8;
         i8_sample_plan(h, ntiles, &G8, &S8);
@@ -792,11 +821,7 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
         if (h->profiling && h->profile_whole_scan) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));   // (all three launches of the scan)
         // the sample launch records the upper ends of its tiles' rows and the pass takes those tiles' candidates from the record
         // instead of reading and multiplying the tiles again (crh_i8.hpp, `shi`; CODERAG_HIP_I8_SAMPLE_RECORD=0: the pass reads every tile)
-        u32x4 *shi = nullptr;
-        if (h->i8_sample_record) {
-            if (!w.shi) CRH_TRY(dev_alloc(&w.shi, (int64_t)kI8SampleTiles * 64 * 4));
-            shi = w.shi;
-        }
+        u32x4 *shi = h->i8_sample_record ? w.shi : nullptr;
         CRH_TRY(launch_scan_i8<1>(h, w, blocks, st, mask, (int)ntiles, G8, S8, k, c_abs, nq, wave_cap * (kWaves / kI8Waves), qcap, stt, shi));
         CRH_TRY(launch_scan_i8<2>(h, w, blocks, st, mask, (int)ntiles, G8, S8, k, c_abs, nq, wave_cap * (kWaves / kI8Waves), qcap, stt, shi));
         if (h->profiling && !h->profile_whole_scan) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));   // (the dominant kernel: the pass)
@@ -818,10 +843,7 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
             hipLaunchKernelGGL(k_select_final<false>, dim3(nq, kI8SelectParts), dim3(256), 0, st, w.skeys2, w.skeys, qcap, w.qn, h->xt, h->xf32, h->xrow,
                                h->dim, h->ksteps, k, 2.f * c_abs, row_base, out_s, out_r, stt);
         CRH_HIP(hipGetLastError());
-        h->stats.rows += h->count;
-        h->stats.tiles += ntiles;
-        h->stats.seed_tiles += G8;
-        h->stats.batches += 1;
+        count_batch(h, h->count, ntiles, G8);
         *path_out = CRH_NOMINATE_INT8;
         return CRH_OK;
     }
@@ -831,6 +853,7 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
     // waits: it is never larger than the CU count and a workgroup's LDS footprint leaves room for one per CU.
     if (!wide && h->fused_scan && !h->fused_resting() && h->nominate_max >= CRH_NOMINATE_BF16 && h->seed_tiles == 4096 && h->ksteps != 64) {
         if (h->i8_cooldown > 0 && !h->i8_suppress) h->i8_cooldown -= 1;
+        CRH_TRY(launch_prep(h, w, st, q_dev, nq, width, stt, false));
         const int blocks = scan_blocks(h, ntiles);
         const int waves = blocks * kWaves;
         const int Gf = (int)std::min<int64_t>(std::min(waves, 4096), ntiles);
@@ -838,47 +861,16 @@ int enqueue_batch(crh_index *h, crh_index::Workspace &w, const float *q_dev, int
         if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
         CRH_TRY(launch_scan_fused(h, w, blocks, st, mask, (int)ntiles, Gf, Sf, k, margin, nq, wave_cap, qcap, stt));
         if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-        if (h->dtype == CRH_DTYPE_F32)
-            hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-        else
-            hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                               h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-        CRH_HIP(hipGetLastError());
-        h->stats.rows += h->count;
-        h->stats.tiles += ntiles;
-        h->stats.seed_tiles += Gf;
-        h->stats.batches += 1;
+        CRH_TRY(launch_select_bf16(h, w, st, nq, k, margin, row_base, out_s, out_r, stt));
+        count_batch(h, h->count, ntiles, Gf);
         *path_out = CRH_NOMINATE_BF16;
         return CRH_OK;
     }
     if (!wide && h->i8_cooldown > 0 && !h->i8_suppress) h->i8_cooldown -= 1;
-    const int G = (int)std::min<int64_t>(h->seed_tiles, ntiles);
-    const int stride = (int)(ntiles / G);
-    if (wide)
-        CRH_TRY(launch_scan_wide<0>(h, w, st, mask, G, stride, nblk, wave_cap, qcap, stt));
-    else
-        CRH_TRY(launch_scan<0>(h, w, scan_blocks(h, G), st, mask, G, stride, wave_cap, qcap, stt));
-    hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, qstride);
-    CRH_HIP(hipGetLastError());
-    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
-    if (wide)
-        CRH_TRY(launch_scan_wide<1>(h, w, st, mask, (int)ntiles, 1, nblk, wave_cap, qcap, stt));
-    else
-        CRH_TRY(launch_scan<1>(h, w, scan_blocks(h, ntiles), st, mask, (int)ntiles, 1, wave_cap, qcap, stt));
-    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-    if (h->dtype == CRH_DTYPE_F32)
-        hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-    else
-        hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-    CRH_HIP(hipGetLastError());
-    h->stats.rows += h->count;
-    h->stats.tiles += ntiles;
-    h->stats.seed_tiles += G;
-    h->stats.batches += 1;
-    return CRH_OK;
+    return enqueue_three(h, w, q_dev, nq, k, ntiles, h->count, width, qstride, row_base, out_s, out_r, slot, st, [&](auto mode, int n, int stride) {
+        return wide ? launch_scan_wide<decltype(mode)::value>(h, w, st, mask, n, stride, nblk, wave_cap, qcap, stt)
+                    : launch_scan<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mask, n, stride, wave_cap, qcap, stt);
+    });
 }
 
 // One mixed-filter batch (<= batch_q queries, <= CRH_MAX_CLASSES classes): always the three-launch bf16 form, through the
@@ -889,50 +881,13 @@ int enqueue_batch_multi(crh_index *h, crh_index::Workspace &w, const float *q_de
 {
     const int64_t ntiles = ceil_div(h->count, kTileRows);
     const bool sparse = ntiles > 0 && sparse_use(h, mref, nq);
-    if (ntiles == 0 || (sparse && mref.nlist == 0)) {   // (no row can match: the padding the scans would arrive at)
-        if (sparse) {
-            h->stats.batches += 1;
-            if (h->profiling) {
-                CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
-                CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-            }
-        }
-        CRH_HIP(hipMemsetAsync(h->status + slot, 0, sizeof(SearchStatus), st));
-        const int64_t n = (int64_t)nq * k;
-        hipLaunchKernelGGL(k_fill_pad, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out_s, out_r, n);
-        CRH_HIP(hipGetLastError());
-        return CRH_OK;
-    }
-    const int wave_cap = w.ws_wave_cap, qcap = w.ws_qcap;
-    const float margin = margin_for(h);
-    SearchStatus *stt = h->status + slot;
-    const int width = h->batch_q;
-    if (h->dtype == CRH_DTYPE_BF16)
-        hipLaunchKernelGGL((k_prep_queries<true, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-    else
-        hipLaunchKernelGGL((k_prep_queries<false, false>), dim3(width), dim3(64), 0, st, q_dev, nq, h->dim, h->ksteps, w.qn, w.qfrag, stt, (u32x4 *)nullptr, (float *)nullptr);
-    CRH_HIP(hipGetLastError());
+    if (ntiles == 0 || (sparse && mref.nlist == 0)) return pad_batch(h, slot, nq, k, out_s, out_r, st, sparse);
     const int64_t items = sparse ? mref.nlist : ntiles;   // list positions or tiles
-    const int G = (int)std::min<int64_t>(h->seed_tiles, items);
-    const int stride = (int)(items / G);
-    CRH_TRY(launch_scan_cls<0>(h, w, scan_blocks(h, G), st, mref, cmask, cls, sparse, G, stride, wave_cap, qcap, stt));
-    hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, k, margin, nq, w.tau, 64);
-    CRH_HIP(hipGetLastError());
-    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
-    CRH_TRY(launch_scan_cls<1>(h, w, scan_blocks(h, items), st, mref, cmask, cls, sparse, (int)items, 1, wave_cap, qcap, stt));
-    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
-    if (h->dtype == CRH_DTYPE_F32)
-        hipLaunchKernelGGL(k_select<true>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-    else
-        hipLaunchKernelGGL(k_select<false>, dim3(nq), dim3(1024), 0, st, w.qlist, (const float *)nullptr, stt->qcount, qcap, w.skeys, (unsigned long long *)nullptr, w.qn, h->xt,
-                           h->xf32, h->dim, h->ksteps, k, margin, row_base, out_s, out_r, stt);
-    CRH_HIP(hipGetLastError());
-    h->stats.rows += sparse ? std::min<int64_t>(h->count, items * kTileRows) : h->count;
-    h->stats.tiles += items;
-    h->stats.seed_tiles += G;
-    h->stats.batches += 1;
-    return CRH_OK;
+    return enqueue_three(h, w, q_dev, nq, k, items, sparse ? std::min<int64_t>(h->count, items * kTileRows) : h->count, h->batch_q, 64, row_base, out_s, out_r,
+                         slot, st, [&](auto mode, int n, int stride) {
+                             return launch_scan_cls<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mref, cmask, cls, sparse, n, stride, w.ws_wave_cap, w.ws_qcap,
+                                                                           h->status + slot);
+                         });
 }
 
 int next_pow2(int64_t v)
@@ -940,6 +895,22 @@ int next_pow2(int64_t v)
     int64_t p = 1;
     while (p < v) p <<= 1;
     return (int)std::min<int64_t>(p, 1LL << 30);
+}
+
+// One batch of a search, enqueued on `st` under status slot `slot`: the mask(s) of its filter -- found as the last batch left
+// them, or built -- and the pipeline of its kind.  The driver runs every batch through here, finish_pending the ones it runs again.
+int enqueue_pending(crh_index *h, crh_index::Workspace &w, const Pending &p, int slot, hipStream_t st, int *path_out)
+{
+    MaskRef mask;
+    // (the masks live in the workspace: stream order puts their rebuild behind the previous batch's scan)
+    if (p.multi) {
+        const uint32_t *cmask = nullptr;
+        CRH_TRY(build_class_masks(h, w, p.key, &mask, &cmask, st));
+        *path_out = CRH_NOMINATE_BF16_3;
+        return enqueue_batch_multi(h, w, p.q_dev, p.nq, p.k, mask, cmask, p.cls, p.row_base, p.out_s, p.out_r, slot, st);
+    }
+    CRH_TRY(build_mask(h, w, p.key, &mask, st));
+    return enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, slot, st, path_out);
 }
 
 int finish_pending(crh_index *h, hipStream_t st)
@@ -1015,18 +986,10 @@ int finish_pending(crh_index *h, hipStream_t st)
                 qc = std::max(qc, next_pow2((int64_t)s.max_qcount));
             }
             CRH_TRY(ensure_workspace(h, w, wc, qc));
-            MaskRef mask;
-            if (p.multi) {   // a mixed-filter batch runs the classed pipeline again
-                const uint32_t *cmask = nullptr;
-                CRH_TRY(build_class_masks(h, w, p.key, &mask, &cmask, st));
-                CRH_TRY(enqueue_batch_multi(h, w, p.q_dev, p.nq, p.k, mask, cmask, p.cls, p.row_base, p.out_s, p.out_r, 0, st));
-            } else {
-                CRH_TRY(build_mask(h, w, p.key, &mask, st));
-                h->i8_suppress = no_i8;
-                const int rc = enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, 0, st, &path);
-                h->i8_suppress = false;
-                CRH_TRY(rc);
-            }
+            if (!p.multi) h->i8_suppress = no_i8;
+            const int rc = enqueue_pending(h, w, p, 0, st, &path);
+            h->i8_suppress = false;
+            CRH_TRY(rc);
             CRH_HIP(hipMemcpyAsync(&s, h->status, sizeof(SearchStatus), hipMemcpyDeviceToHost, st));
             CRH_HIP(hipStreamSynchronize(st));
         }
@@ -1034,6 +997,119 @@ int finish_pending(crh_index *h, hipStream_t st)
         h->stats.max_query_cands = std::max<int64_t>(h->stats.max_query_cands, s.max_qcount);
     }
     return CRH_OK;
+}
+
+// The search driver: every batch of a call enqueued on the stream, and -- unless queries and outputs are the caller's device
+// buffers -- finished and copied back.  What differs between the entry points is passed in: i8_presize (the call may nominate
+// from the int8 copy: its candidate buffers are sized beforehand) and plan(p, q0, left, st), which sets the size of the batch
+// that starts at query q0 with `left` queries to go (p.nq) and, for a mixed-filter call, p.multi and p.cls.
+template <typename Plan>
+int search_batches(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &key, bool i8_presize, int64_t row_base,
+                   float *out_scores, int64_t *out_rows, int out_on_device, void *stream, Plan plan)
+{
+    DeviceGuard g(h->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // force_fallback (testing): 1 = start from absurdly small candidate buffers so the regrow-and-rerun path runs (behind the int8
+    // scan: its one regrowth); 3 = the same, and the int8 scan may NOT regrow (its batches go to the bf16 scan: the strike path);
+    // 2 = the one-launch scan's first grid-wide wait expects an arrival too many, so its time-out path runs
+    const bool tiny = h->force_fallback == 1 || h->force_fallback == 3;
+    int wc = tiny ? 4 : std::max(h->wave_cap, h->ws.ws_wave_cap);
+    int qc = tiny ? 8 : std::max(h->qcap, h->ws.ws_qcap);
+    if (i8_presize && !tiny && i8_use(h, 1, k)) {
+        // the int8 intervals nominate a fixed FRACTION of the rows (the thresholds come from a fixed number of sample tiles):
+        // ~21 k per query and ~660 per wave of the int8 scan at 10M rows.  The defaults hold that twice over up to 10M rows; beyond,
+        // the buffers grow with the index (the int8 scan cannot regrow them after the fact: an overflow sends the batch to bf16)
+        const int64_t scale = next_pow2(ceil_div(h->count, 10000000));
+        wc = (int)std::max<int64_t>(wc, std::min<int64_t>(2048 * scale, 1 << 18));
+        qc = (int)std::max<int64_t>(qc, std::min<int64_t>(131072 * scale, 1 << 24));
+    }
+    CRH_TRY(ensure_workspace(h, h->ws, wc, qc));
+
+    const float *q_dev = queries;
+    if (!queries_on_device) {
+        const int64_t elems = (int64_t)nq * h->dim;
+        if (h->stage_q_elems < elems) {
+            dev_free(h->stage_q);
+            h->stage_q_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_q, elems));
+            h->stage_q_elems = elems;
+        }
+        CRH_HIP(hipMemcpyAsync(h->stage_q, queries, (size_t)elems * 4, hipMemcpyHostToDevice, st));
+        q_dev = h->stage_q;
+    }
+    float *os = out_scores;
+    int64_t *orow = out_rows;
+    if (!out_on_device) {
+        const int64_t elems = (int64_t)nq * k;
+        if (h->stage_out_elems < elems) {
+            dev_free(h->stage_os);
+            dev_free(h->stage_or);
+            h->stage_out_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_os, elems));
+            CRH_TRY(dev_alloc(&h->stage_or, elems));
+            h->stage_out_elems = elems;
+        }
+        os = h->stage_os;
+        orow = h->stage_or;
+    }
+    if (h->pending.empty()) h->stats = crh_search_stats{};
+
+    for (int q0 = 0; q0 < nq;) {
+        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
+        Pending p{};
+        CRH_TRY(plan(p, q0, nq - q0, st));
+        p.k = k;
+        p.key = key;
+        p.row_base = row_base;
+        p.q_dev = q_dev + (int64_t)q0 * h->dim;
+        p.out_s = os + (int64_t)q0 * k;
+        p.out_r = orow + (int64_t)q0 * k;
+        p.slot = h->next_slot++;
+        CRH_TRY(enqueue_pending(h, h->ws, p, p.slot, st, &p.path));
+        h->pending.push_back(p);
+        q0 += p.nq;
+    }
+    if (!out_on_device || !queries_on_device) {
+        CRH_TRY(finish_pending(h, st));
+        if (!out_on_device) {
+            CRH_HIP(hipMemcpyAsync(out_scores, h->stage_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipMemcpyAsync(out_rows, h->stage_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+            CRH_HIP(hipStreamSynchronize(st));
+        }
+    }
+    return CRH_OK;
+}
+
+// The single-filter search.  More than one k_scan pass worth of queries: up to kWideQ of them share ONE corpus pass through k_scan_wide
+int search_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &key, int64_t row_base,
+               float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+{
+    return search_batches(h, nq, queries, queries_on_device, k, key, true, row_base, out_scores, out_rows, out_on_device, stream,
+                          [&](Pending &p, int, int left, hipStream_t st) {
+                              MaskRef mask;   // (the sparse rule asks the mask; enqueue_pending then finds it kept)
+                              CRH_TRY(build_mask(h, h->ws, key, &mask, st));
+                              int b = (h->wide_ok && left > h->batch_q) ? std::min(kWideQ, left) : std::min(h->batch_q, left);
+                              // up to two passes over the int8 copy (2 x ~1.55 ms at 10M rows) beat one wide pass over the bf16 tiles (~4.2 ms)
+                              if (left > h->batch_q && left <= 2 * h->batch_q && h->count > 0 && i8_use(h, h->batch_q, k)) b = h->batch_q;
+                              // a mask sparse enough for the list scan: batch_q queries per pass over the few listed tiles, however many there are
+                              if (h->count > 0 && sparse_use(h, mask, h->batch_q)) b = std::min(h->batch_q, left);
+                              p.nq = b;
+                              return (int)CRH_OK;
+                          });
+}
+
+// The mixed-filter search: as search_key, with the classes' masks and the classed batches (<= batch_q queries each, in caller order)
+int search_multi_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &ckey, const int32_t *query_class,
+                     int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
+{
+    return search_batches(h, nq, queries, queries_on_device, k, ckey, false, row_base, out_scores, out_rows, out_on_device, stream,
+                          [&](Pending &p, int q0, int left, hipStream_t) {
+                              p.nq = std::min(h->batch_q, left);
+                              p.multi = true;
+                              for (int i = 0; i < p.nq; ++i) p.cls.w[i >> 3] |= (uint32_t)query_class[q0 + i] << ((i & 7) * 4);
+                              return (int)CRH_OK;
+                          });
 }
 
 }  // namespace
@@ -1144,8 +1220,8 @@ int crh_index_destroy(crh_index *h)
     dev_free(h->alive);
     dev_free(h->codes);
     dev_free(h->scratch_u32);
-    dev_free(h->mask_sets);
-    dev_free(h->cmask_sets);
+    dev_free(h->mask.sets);
+    dev_free(h->cmask.sets);
     dev_free(h->cmask_classes);
     {
         crh_index::Workspace &w = h->ws;
@@ -1633,7 +1709,7 @@ int crh_debug_i8_move(crh_index *h)
 }
 
 // What the int8 scan computes before it nominates: the interval of every (query, row), the quantisation parameters and the
-// thresholds, all from the product's own launches (k_requant_i8, k_prep_queries<.., true>, k_scan_i8 PART 1 and PART 2).  Nothing
+// thresholds, all from the product's own launches (k_requant_i8, launch_prep with the integer images, k_scan_i8 PART 1 and PART 2).  Nothing
 // here restates the arithmetic: the upper ends come from the `shi` record of a sample launch over EVERY tile (G = tiles, S = 1),
 // both ends as f32 from the store that launch makes in this build only (crh_i8.hpp, g_i8_debug_ends), the thresholds from a
 // second sample launch with the sample enqueue_batch would take, followed by the threshold launch.  Queries go through in
@@ -1655,7 +1731,7 @@ int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, co
     CRH_TRY(ensure_workspace0(h));
     crh_index::Workspace &w = h->ws;
     if ((int64_t)w.ws_seed * kWideQ < (int64_t)kMaxQ * ntiles) return fail(CRH_E_INVALID, "the sample keys of %lld tiles do not fit the workspace", (long long)ntiles);
-    if (!w.shi) CRH_TRY(dev_alloc(&w.shi, (int64_t)kI8SampleTiles * 64 * 4));
+    if (!w.shi) return fail(CRH_E_INVALID, "no memory for the record of upper ends");
     struct Tmp {
         float *p = nullptr;
         ~Tmp() { dev_free(p); }
@@ -1678,11 +1754,7 @@ int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, co
         CRH_TRY(build_mask(h, w, key, &mask, st));
         CRH_TRY(i8_sync(h, st));
         if (!i8_use(h, b, k)) return fail(CRH_E_INVALID, "no memory for the int8 copy");
-        if (h->dtype == CRH_DTYPE_BF16)
-            hipLaunchKernelGGL((k_prep_queries<true, true>), dim3(h->batch_q), dim3(64), 0, st, q_dev.p + (int64_t)q0 * h->dim, b, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
-        else
-            hipLaunchKernelGGL((k_prep_queries<false, true>), dim3(h->batch_q), dim3(64), 0, st, q_dev.p + (int64_t)q0 * h->dim, b, h->dim, h->ksteps, w.qn, w.qfrag, stt, w.qfrag8, w.qpar);
-        CRH_HIP(hipGetLastError());
+        CRH_TRY(launch_prep(h, w, st, q_dev.p + (int64_t)q0 * h->dim, b, h->batch_q, stt, true));
         // every tile as a sample tile: the record of upper ends, and both ends as f32
         I8DebugEnds on{ends.p, ends.p + kMaxQ * pitch, pitch}, off{nullptr, nullptr, 0};
         CRH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_i8_debug_ends), &on, sizeof(on)));
@@ -1768,93 +1840,6 @@ int crh_index_set_tuning(crh_index *h, int seed_tiles, int wave_cand_cap, int qu
     return CRH_OK;
 }
 
-static int search_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &key, int64_t row_base,
-                      float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
-{
-    DeviceGuard g(h->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    // force_fallback (testing): 1 = start from absurdly small candidate buffers so the regrow-and-rerun path runs (behind the int8
-    // scan: its one regrowth); 3 = the same, and the int8 scan may NOT regrow (its batches go to the bf16 scan: the strike path);
-    // 2 = the one-launch scan's first grid-wide wait expects an arrival too many, so its time-out path runs
-    const bool tiny = h->force_fallback == 1 || h->force_fallback == 3;
-    int wc = tiny ? 4 : std::max(h->wave_cap, h->ws.ws_wave_cap);
-    int qc = tiny ? 8 : std::max(h->qcap, h->ws.ws_qcap);
-    if (!tiny && i8_use(h, 1, k)) {
-        // the int8 intervals nominate a fixed FRACTION of the rows (the thresholds come from a fixed number of sample tiles):
-        // ~21 k per query and ~660 per wave of the int8 scan at 10M rows.  The defaults hold that twice over up to 10M rows; beyond,
-        // the buffers grow with the index (the int8 scan cannot regrow them after the fact: an overflow sends the batch to bf16)
-        const int64_t scale = next_pow2(ceil_div(h->count, 10000000));
-        wc = (int)std::max<int64_t>(wc, std::min<int64_t>(2048 * scale, 1 << 18));
-        qc = (int)std::max<int64_t>(qc, std::min<int64_t>(131072 * scale, 1 << 24));
-    }
-    CRH_TRY(ensure_workspace(h, h->ws, wc, qc));
-
-    const float *q_dev = queries;
-    if (!queries_on_device) {
-        const int64_t elems = (int64_t)nq * h->dim;
-        if (h->stage_q_elems < elems) {
-            dev_free(h->stage_q);
-            h->stage_q_elems = 0;
-            CRH_TRY(dev_alloc(&h->stage_q, elems));
-            h->stage_q_elems = elems;
-        }
-        CRH_HIP(hipMemcpyAsync(h->stage_q, queries, (size_t)elems * 4, hipMemcpyHostToDevice, st));
-        q_dev = h->stage_q;
-    }
-    float *os = out_scores;
-    int64_t *orow = out_rows;
-    if (!out_on_device) {
-        const int64_t elems = (int64_t)nq * k;
-        if (h->stage_out_elems < elems) {
-            dev_free(h->stage_os);
-            dev_free(h->stage_or);
-            h->stage_out_elems = 0;
-            CRH_TRY(dev_alloc(&h->stage_os, elems));
-            CRH_TRY(dev_alloc(&h->stage_or, elems));
-            h->stage_out_elems = elems;
-        }
-        os = h->stage_os;
-        orow = h->stage_or;
-    }
-    if (h->pending.empty()) h->stats = crh_search_stats{};
-
-    // more than one k_scan pass worth of queries: up to kWideQ of them share ONE corpus pass through k_scan_wide
-    for (int q0 = 0, b = 0; q0 < nq; q0 += b) {
-        const int left = nq - q0;
-        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
-        crh_index::Workspace &w = h->ws;
-        MaskRef mask;
-        // (the filter mask lives in the workspace: stream order puts its rebuild behind the previous batch's scan)
-        CRH_TRY(build_mask(h, w, key, &mask, st));
-        b = (h->wide_ok && left > h->batch_q) ? std::min(kWideQ, left) : std::min(h->batch_q, left);
-        // up to two passes over the int8 copy (2 x ~1.55 ms at 10M rows) beat one wide pass over the bf16 tiles (~4.2 ms)
-        if (left > h->batch_q && left <= 2 * h->batch_q && h->count > 0 && i8_use(h, h->batch_q, k)) b = h->batch_q;
-        // a mask sparse enough for the list scan: batch_q queries per pass over the few listed tiles, however many there are
-        if (h->count > 0 && sparse_use(h, mask, h->batch_q)) b = std::min(h->batch_q, left);
-        Pending p{};
-        p.nq = b;
-        p.k = k;
-        p.key = key;
-        p.row_base = row_base;
-        p.q_dev = q_dev + (int64_t)q0 * h->dim;
-        p.out_s = os + (int64_t)q0 * k;
-        p.out_r = orow + (int64_t)q0 * k;
-        p.slot = h->next_slot++;
-        CRH_TRY(enqueue_batch(h, w, p.q_dev, b, k, mask, row_base, p.out_s, p.out_r, p.slot, st, &p.path));
-        h->pending.push_back(p);
-    }
-    if (!out_on_device || !queries_on_device) {
-        CRH_TRY(finish_pending(h, st));
-        if (!out_on_device) {
-            CRH_HIP(hipMemcpyAsync(out_scores, h->stage_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipMemcpyAsync(out_rows, h->stage_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipStreamSynchronize(st));
-        }
-    }
-    return CRH_OK;
-}
-
 static int search_args(crh_index *h, int nq, const float *queries, int k, float *out_scores, int64_t *out_rows)
 {
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
@@ -1885,79 +1870,6 @@ int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_d
     FilterKey key;
     CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
     return search_key(h, nq, queries, queries_on_device, k, key, row_base, out_scores, out_rows, out_on_device, stream);
-}
-
-// The mixed-filter search: as search_key, with the classes' masks and the classed batches (<= batch_q queries each, in caller order)
-static int search_multi_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const FilterKey &ckey, const int32_t *query_class,
-                            int64_t row_base, float *out_scores, int64_t *out_rows, int out_on_device, void *stream)
-{
-    DeviceGuard g(h->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool tiny = h->force_fallback == 1 || h->force_fallback == 3;   // (testing: the regrow-and-rerun path, see search_key)
-    const int wc = tiny ? 4 : std::max(h->wave_cap, h->ws.ws_wave_cap);
-    const int qc = tiny ? 8 : std::max(h->qcap, h->ws.ws_qcap);
-    CRH_TRY(ensure_workspace(h, h->ws, wc, qc));
-
-    const float *q_dev = queries;
-    if (!queries_on_device) {
-        const int64_t elems = (int64_t)nq * h->dim;
-        if (h->stage_q_elems < elems) {
-            dev_free(h->stage_q);
-            h->stage_q_elems = 0;
-            CRH_TRY(dev_alloc(&h->stage_q, elems));
-            h->stage_q_elems = elems;
-        }
-        CRH_HIP(hipMemcpyAsync(h->stage_q, queries, (size_t)elems * 4, hipMemcpyHostToDevice, st));
-        q_dev = h->stage_q;
-    }
-    float *os = out_scores;
-    int64_t *orow = out_rows;
-    if (!out_on_device) {
-        const int64_t elems = (int64_t)nq * k;
-        if (h->stage_out_elems < elems) {
-            dev_free(h->stage_os);
-            dev_free(h->stage_or);
-            h->stage_out_elems = 0;
-            CRH_TRY(dev_alloc(&h->stage_os, elems));
-            CRH_TRY(dev_alloc(&h->stage_or, elems));
-            h->stage_out_elems = elems;
-        }
-        os = h->stage_os;
-        orow = h->stage_or;
-    }
-    if (h->pending.empty()) h->stats = crh_search_stats{};
-
-    for (int q0 = 0; q0 < nq; q0 += h->batch_q) {
-        const int b = std::min(h->batch_q, nq - q0);
-        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
-        crh_index::Workspace &w = h->ws;
-        MaskRef mask;
-        const uint32_t *cmask = nullptr;
-        CRH_TRY(build_class_masks(h, w, ckey, &mask, &cmask, st));
-        Pending p{};
-        p.nq = b;
-        p.k = k;
-        p.key = ckey;
-        p.multi = true;
-        for (int i = 0; i < b; ++i) p.cls.w[i >> 3] |= (uint32_t)query_class[q0 + i] << ((i & 7) * 4);
-        p.row_base = row_base;
-        p.q_dev = q_dev + (int64_t)q0 * h->dim;
-        p.out_s = os + (int64_t)q0 * k;
-        p.out_r = orow + (int64_t)q0 * k;
-        p.slot = h->next_slot++;
-        p.path = CRH_NOMINATE_BF16_3;
-        CRH_TRY(enqueue_batch_multi(h, w, p.q_dev, b, k, mask, cmask, p.cls, row_base, p.out_s, p.out_r, p.slot, st));
-        h->pending.push_back(p);
-    }
-    if (!out_on_device || !queries_on_device) {
-        CRH_TRY(finish_pending(h, st));
-        if (!out_on_device) {
-            CRH_HIP(hipMemcpyAsync(out_scores, h->stage_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipMemcpyAsync(out_rows, h->stage_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-            CRH_HIP(hipStreamSynchronize(st));
-        }
-    }
-    return CRH_OK;
 }
 
 int crh_search_multi(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const crh_condition *conds,

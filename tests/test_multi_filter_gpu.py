@@ -239,6 +239,101 @@ def test_union_sparse_route_reads_only_the_unions_tiles(gpu, dtype_name, dim):
     idx.close()
 
 
+@pytest.mark.parametrize("dtype_name", ["bf16", "f32"])
+def test_mixed_and_single_filter_calls_each_keep_a_correct_mask(gpu, dtype_name):
+    """A mixed-filter call and the single-filter calls around it keep their masks side by side: each must find its own as it
+    left it, and rebuild it after a mutation, on another stream and when the sparse route is switched.  129 tiles, the last one
+    partial: the tile-list kernels run one block of more than one wave.  The single filter populates 26 tiles (sparse route),
+    the union of the two classes every tile (dense classed scan).  After every call: ids and score bits of the oracle under
+    each query's mask; after a sparse call crh_search_stats.tiles is bounded by the non-zero words of the numpy mask."""
+    import torch
+    ffi = _env()
+    from oracle import search as orc
+    bf16 = dtype_name == "bf16"
+    rows, dim, nq, k = 4113, 384, 40, 10
+    ntiles = (rows + 31) // 32
+    rng = np.random.default_rng(4113 + bf16)
+    x = rng.standard_normal((rows, dim)).astype(np.float32)
+    q = rng.standard_normal((nq, dim)).astype(np.float32)
+    tile = np.arange(rows) // 32
+    col0 = rng.choice(np.asarray([0, 2, 3, 4], np.int32), rows)
+    in_a = (tile % 5 == 3) & (rng.random(rows) < 0.5)             # tiles 3, 8, .. 128 -- the partial one among them
+    in_a[np.arange(3, ntiles, 5) * 32 + 1] = True                 # (each of them for certain)
+    col0[in_a] = 1
+    col0[::32] = 2                                                # every tile has a row of class 0
+    codes = np.stack([col0, rng.integers(-1, 4, rows).astype(np.int32)], axis=1)
+    A = [(0, 1)]
+    classes = [[(0, [1, 2], False)], [(0, [1, 2], True), (1, 3)]]
+    qc = _cycle(2, nq, rng)
+    idx = ffi.Index(dim, ffi.DTYPE_BF16 if bf16 else ffi.DTYPE_F32, capacity_rows=rows, n_code_cols=2)
+    idx.append(x, codes)
+    alive = np.ones(rows, bool)
+    xpre, qpre = orc.preprocess(x, to_bf16=bf16), orc.preprocess(q, to_bf16=bf16)
+
+    def words(mask):
+        return int(np.pad(mask, (0, -rows % 32)).reshape(-1, 32).any(axis=1).sum())
+
+    want = {}
+
+    def refresh():                                                # the oracle's answers and the masks' words, once per state of the index
+        want["A"] = expected(orc, xpre, qpre, k, codes, alive, [A], np.zeros(nq, np.int32))
+        want["M"] = expected(orc, xpre, qpre, k, codes, alive, classes, qc)
+        want["nzA"] = words(np_mask(codes, alive, A))
+        want["nzM"] = words(np_mask(codes, alive, classes[0]) | np_mask(codes, alive, classes[1]))
+        assert 0 < want["nzA"] * 4 <= ntiles and want["nzM"] == ntiles
+
+    def single(step, sparse=True, rerun=False):
+        got = idx.search(q, k, filters=A)
+        st = idx.stats()
+        print(f"step {step}: search(A) tiles {st['tiles']} (mask words {want['nzA']}, all tiles {ntiles}) fallback {st['fallback_used']}")
+        assert _same(got, want["A"]), step
+        assert rerun or (st["batches"] == 1 and (0 < st["tiles"] <= want["nzA"] if sparse else st["tiles"] == ntiles)), step
+        return st
+
+    def multi(step, rerun=False):
+        got = idx.search_multi(q, k, classes, qc)
+        st = idx.stats()
+        print(f"step {step}: search_multi tiles {st['tiles']} (union words {want['nzM']}) fallback {st['fallback_used']}")
+        assert _same(got, want["M"]), step
+        assert rerun or (st["batches"] == 1 and st["tiles"] == ntiles), step   # (the union leaves no tile out: the dense classed scan)
+        return st
+
+    refresh()
+    single(1)
+    multi(2)
+    single(3)
+    dead = np.flatnonzero(np_mask(codes, alive, A))[::3]
+    idx.tombstone(dead)
+    alive[dead] = False
+    refresh()
+    multi(5)
+    single(6)
+    idx.set_sparse_route(False)
+    single(8, sparse=False)
+    multi(9)
+    idx.set_sparse_route(True)
+    # a second stream, device buffers: the kept mask was built on the default stream and nothing orders the two
+    qd = torch.from_numpy(q).cuda()
+    os_ = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+    or_ = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    idx.search(qd, k, filters=A, out_scores=os_, out_rows=or_, stream=side.cuda_stream)
+    idx.search_finish(side.cuda_stream)
+    side.synchronize()
+    st = idx.stats()
+    assert _same((os_.cpu().numpy(), or_.cpu().numpy()), want["A"]), 11
+    assert st["batches"] == 1 and 0 < st["tiles"] <= want["nzA"], 11
+    multi(12)
+    # the regrow-and-rerun path builds the masks and enqueues again, for both kinds (a batch run twice counts its tiles twice)
+    idx.set_tuning(force_fallback=1)
+    st_m = multi(13, rerun=True)
+    st_a = single(14, rerun=True)
+    idx.set_tuning(force_fallback=0)
+    assert st_m["fallback_used"] & 1 and st_a["fallback_used"] & 1
+    idx.close()
+
+
 def _payload(i, file, lang, proj):
     return {"file_path": file, "entity_type": "function", "entity_name": f"ent{i}", "language": lang, "start_line": i, "end_line": i + 3,
             "content": f"def ent{i}(): pass", "graph_node_id": f"mod.ent{i}", "content_hash": "h", "project_name": proj}
