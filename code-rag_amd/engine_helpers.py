@@ -26,6 +26,33 @@ async def execute_vector_search(vector_searcher, query: str, plan, limit: int, l
     return results
 
 
+MAX_QUERY_TEXTS = 16      # CRH_MAX_LISTS: the lists one fusion takes
+
+
+def plan_query_texts(plan, original: str) -> list[str]:
+    """The texts one fused vector search asks (``VectorSearcher.search_code(texts[0], extra_queries=texts[1:])``): the original
+    query, then the distinct non-empty ``query_text`` of the plan's sub-queries whose ``search_type`` is "vector" or "hybrid"
+    (query/query_planner.py:66-91; lower ``priority`` first, the plan's order among equals), at most 16 in all.  The
+    reference's engine plans them and then searches the original text only (query/engine.py:315-346)."""
+    texts = [original]
+    seen = {original.strip()}
+    subs = [sq for sq in (getattr(plan, "sub_queries", None) or []) if str(_field(sq, "search_type", "")).lower() in ("vector", "hybrid")]
+    for sq in sorted(subs, key=lambda sq: _field(sq, "priority", 1)):           # (sorted is stable)
+        text = _field(sq, "query_text", None)
+        if not isinstance(text, str) or not text.strip() or text.strip() in seen:
+            continue
+        if len(texts) == MAX_QUERY_TEXTS:
+            break
+        seen.add(text.strip())
+        texts.append(text)
+    return texts
+
+
+def _field(obj, name: str, default):
+    """A sub-query's field, whether the planner left a dataclass or the parsed JSON object."""
+    return obj.get(name, default) if isinstance(obj, dict) else getattr(obj, name, default)
+
+
 def centrality_candidates(graph_context, vector_results: list[dict[str, Any]]) -> list[str]:
     """engine.py:353-363: names of <= 5 primary graph entities and of the first 5 vector hits (graph node id, else
     entity name), de-duplicated, truncated to ``max_centrality_lookups``.  (The reference iterates a ``set``, so

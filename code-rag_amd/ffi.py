@@ -19,6 +19,9 @@ OK, E_INVALID, E_HIP, E_CAPACITY, E_NODEVICE, E_INTERNAL = 0, -1, -2, -3, -4, -5
 DTYPE_F32, DTYPE_BF16 = 0, 1
 NOMINATE_BF16_3, NOMINATE_BF16, NOMINATE_INT8 = 0, 1, 2
 MAX_FILTERS, MAX_K = 8, 1024
+MAX_LISTS = 16         # CRH_MAX_LISTS: candidate lists one crh_fuse_select call fuses per logical query
+FUSE_RRF, FUSE_MAX = 0, 1
+FUSE_METHODS = {"rrf": FUSE_RRF, "max": FUSE_MAX}
 MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 
@@ -38,6 +41,7 @@ EXPORTS = (
     "crh_index_gather_vectors", "crh_mmr_select",
     "crh_index_gather_codes", "crh_group_select",
     "crh_search_multi",
+    "crh_fuse_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -181,6 +185,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_mmr_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
     L.crh_index_gather_codes.argtypes = [vp, i32, i64, vp, i64, vp, vp]
     L.crh_group_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_fuse_select.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -841,6 +846,60 @@ def group_select(scores, rows, codes, k: int, group_size: int, stream: int = 0):
     info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
     use_device(dev.index)
     check(lib().crh_group_select(nq, c, k, int(group_size), _ptr(scores), _ptr(rows), _ptr(codes), *(_ptr(x) for x in outs), _ptr(info), stream))
+    return outs + (info,)
+
+
+def fuse_method(method) -> int:
+    """``"rrf"`` / ``"max"`` -> CRH_FUSE_*; ``ValueError`` for anything else."""
+    if not isinstance(method, str) or method.lower() not in FUSE_METHODS:
+        raise ValueError(f"unknown fusion {method!r} (one of {sorted(FUSE_METHODS)})")
+    return FUSE_METHODS[method.lower()]
+
+
+def fuse_weights(weights, m: int, method: int):
+    """Checked f32 [m] weights of one fused call (``None`` stays ``None``: every list weighs 1); ``ValueError`` otherwise."""
+    if weights is None:
+        return None
+    if method != FUSE_RRF:
+        raise ValueError("weights are only meaningful with fusion 'rrf'")
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if w.size != m or not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError(f"weights must be {m} finite values >= 0, got {np.asarray(weights).tolist()}")
+    return w
+
+
+def fuse_select(scores, rows, m: int, k: int, method: str = "rrf", rrf_k: int = 60, weights=None, stream: int = 0):
+    """Multi-query fusion (``crh_fuse_select``) over candidate lists left on the device: ``scores`` f32 /
+    ``rows`` i64 ``[nq * m, c]`` or ``[nq, m, c]`` as a search or merge returns them -- the ``m`` lists of one logical query
+    next to each other.  Returns CUDA tensors ``(rows i64, fused f32, cos f32, lists i32, first i32)``, each [nq, k] -- the
+    first ``k`` distinct rows by descending fused score, ties to the lower row, tail ``(-1, -inf, -inf, 0, -1)`` -- and
+    ``info`` i32 [nq, 2] = (distinct rows, real entries).  Enqueues only."""
+    import torch
+    for x, what in ((scores, "scores"), (rows, "rows")):
+        if not _is_dev(x):
+            raise NativeError(E_INVALID, f"{what} must be a device tensor")
+    m = int(m)
+    if scores.ndim == 3:
+        if int(scores.shape[1]) != m:
+            raise NativeError(E_INVALID, f"scores is [nq, {int(scores.shape[1])}, c] but m = {m}")
+        flat = (int(scores.shape[0]) * m, int(scores.shape[2]))
+    elif scores.ndim == 2:
+        flat = tuple(int(v) for v in scores.shape)
+    else:
+        raise NativeError(E_INVALID, "scores must be [nq * m, c] or [nq, m, c]")
+    if m < 1 or flat[0] % m:
+        raise NativeError(E_INVALID, f"{flat[0]} lists are not whole sets of m = {m}")
+    nq, c = flat[0] // m, flat[1]
+    _typed(scores, "float32", "scores")
+    _out(rows, "int64", "rows", tuple(scores.shape))
+    k = int(k)
+    code = fuse_method(method)
+    w = fuse_weights(weights, m, code)
+    dev = scores.device
+    outs = tuple(torch.empty((nq, max(k, 0)), dtype=dt, device=dev) for dt in (torch.int64, torch.float32, torch.float32, torch.int32, torch.int32))
+    info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
+    use_device(dev.index)
+    check(lib().crh_fuse_select(nq, m, c, k, code, int(rrf_k), _ptr(w), _ptr(scores), _ptr(rows), *(_ptr(x) for x in outs), _ptr(info), stream))
     return outs + (info,)
 
 

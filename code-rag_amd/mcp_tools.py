@@ -29,11 +29,13 @@ class SearchResult:
 
 def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
     async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
-                              candidates: int | None = None, max_per_file: int | None = None) -> ToolResult:
+                              candidates: int | None = None, max_per_file: int | None = None, extra_queries: list[str] | None = None,
+                              fusion: str | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
-            extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file)) if v is not None}   # (only when asked for)
+            extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
+                                       ("extra_queries", extra_queries or None), ("fusion", fusion)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -60,5 +62,9 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                            "required": False},
             "max_per_file": {"type": "integer", "description": "At most this many results from one file (the list still holds `limit` results)",
                              "required": False},
+            "extra_queries": {"type": "array", "description": "Other wordings of the same question (up to 15); the results of all "
+                                                              "wordings are fused into one list", "required": False},
+            "fusion": {"type": "string", "description": "With extra_queries: 'rrf' (reciprocal-rank fusion, the default) or 'max' "
+                                                        "(best match over the wordings)", "required": False},
         },
     }

@@ -465,6 +465,44 @@ class ShardSet:
         _, rows, scores, gcodes, info = ffi.group_select(cs, cr, codes, k, group_size)
         return np.asarray(scores, np.float32), np.asarray(rows, np.int64), np.asarray(gcodes, np.int32), np.asarray(info, np.int32)
 
+    # ------------------------------------------------------------------ multi-query fusion (RRF / best match)
+    def search_fused_device(self, queries, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
+        """Fusion on the device, results left there: ``queries`` [nq, m, dim] -- the ``m`` sub-queries of ``nq`` logical ones --
+        are searched as ``nq * m`` plain queries (:meth:`search_device`, ``candidates`` hits each: the merged lists carry
+        GLOBAL rows), then ``crh_fuse_select`` turns every ``m`` lists into one.  ``live`` (bool [nq, m], host): the real
+        members of ragged sets; the lists of the others are overwritten with padding before the fusion.  Under backend "dist"
+        every rank holds the same merged lists and fuses them itself: no collective is added.  Returns CUDA tensors ``(GLOBAL
+        rows i64, fused f32, cos f32, lists i32, first i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (distinct, real)."""
+        import torch
+        nq, m = int(queries.shape[0]), int(queries.shape[1])
+        flat = queries.reshape(nq * m, int(queries.shape[2]))
+        cs, cr = self.search_device(flat, candidates, dfilt)
+        stream = torch.cuda.current_stream(cs.device).cuda_stream
+        if live is not None:
+            dead = torch.from_numpy(~np.asarray(live, bool).reshape(nq * m)).to(cs.device)
+            cs.masked_fill_(dead[:, None], float("-inf"))
+            cr.masked_fill_(dead[:, None], -1)
+        return ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights, stream=stream)
+
+    def search_fused(self, queries: np.ndarray, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
+        """:meth:`search_fused_device` as host arrays: ``(GLOBAL rows i64, fused f32, cos f32, lists i32, first i32)``, each
+        [nq, k], and ``info`` i32 [nq, 2]; -1 rows are padding.  Indexes that hold a native handle take the device form;
+        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
+        if all(hasattr(ix, "_handle") for ix in self.index.values()):
+            return tuple(t.cpu().numpy() for t in self.search_fused_device(queries, k, candidates, dfilt, method, rrf_k, weights, live))
+        queries = np.asarray(queries, np.float32)
+        nq, m = int(queries.shape[0]), int(queries.shape[1])
+        flat = np.ascontiguousarray(queries.reshape(nq * m, queries.shape[2]))
+        if self.ns == 1:
+            cs, cr = self.index[0].search(flat, candidates, filters=dfilt)
+        else:
+            cs, cr = self._search_host(flat, candidates, dfilt)
+        cs, cr = np.array(cs, np.float32), np.array(cr, np.int64)
+        if live is not None:
+            dead = ~np.asarray(live, bool).reshape(nq * m)
+            cs[dead], cr[dead] = -np.inf, -1
+        return tuple(np.asarray(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights))
+
     # ------------------------------------------------------------------ maintenance
     def compact(self) -> dict[int, np.ndarray]:
         """``crh_index_compact`` on every shard; returns {shard: old_to_new local rows} for ALL shards on every rank."""

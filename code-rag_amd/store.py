@@ -464,6 +464,13 @@ class _Collection:
         shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
         return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
 
+    def search_fused(self, queries: np.ndarray, limit: int, candidates: int, dfilt, method: str, rrf_k: int, weights, live=None):
+        """The fused top-``limit`` of every logical query of ``queries`` [nq, m, dim] (``ShardSet.search_fused``):
+        (slots i64, fused f32, cos f32, lists i32), each [nq, limit]; -1 slots are padding."""
+        rows, fused, cos, lists, _, _ = self.shards.search_fused(queries, limit, candidates, dfilt, method, rrf_k, weights, live)
+        shard = np.where(rows >= 0, rows // SHARD_STRIDE, 0).astype(np.int32)
+        return self.slots_of(shard, np.where(rows >= 0, rows % SHARD_STRIDE, -1)), fused, cos, lists
+
     # -- compaction
     def maybe_compact(self) -> bool:
         rows, alive = self.shards.count()
@@ -1192,6 +1199,94 @@ class HipVectorStore:
             return await self._run(self._search_hits_sync, collection, q, limit, filters, must_not, diversity, candidates, group)
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    def _fused_args(self, collection: str, sets, limit: int, fusion, rrf_k: int, weights, candidates: int | None):
+        """Checked ``(queries [nq, m, dim], live [nq, m] or None, method, rrf_k, weights, candidates)`` of one fused call; raises
+        ``ValueError`` for the caller alone.  ``candidates`` -- the depth of every sub-query's list -- defaults to
+        ``min(MAX_K // m, 4 * limit)``."""
+        method = ffi.fuse_method(fusion)
+        dim = self._col(collection).shards.dim
+        sets = [np.asarray(one, dtype=np.float32) for one in sets]
+        sets = [one.reshape(0, dim) if one.size == 0 else one for one in sets]
+        for one in sets:
+            if one.ndim != 2 or one.shape[1] != dim:
+                raise ValueError(f"a fused query is a set of vectors [m, {dim}], got shape {tuple(one.shape)}")
+        m = max((len(one) for one in sets), default=1)
+        if m < 1 or any(len(one) < 1 for one in sets):
+            raise ValueError("a fused query needs at least one query vector")
+        if m > ffi.MAX_LISTS:
+            raise ValueError(f"{m} query vectors exceed the {ffi.MAX_LISTS} lists one fusion takes")
+        limit, rrf_k = int(limit), int(rrf_k)
+        if limit > ffi.MAX_K:
+            raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
+        if rrf_k < 0 or rrf_k > 2**31 - 1:
+            raise ValueError(f"rrf_k {rrf_k} must be >= 0")
+        weights = ffi.fuse_weights(weights, m, method)
+        if candidates is None:
+            candidates = min(ffi.MAX_K // m, 4 * max(limit, 1))
+        candidates = int(candidates)
+        if candidates < limit or candidates < 1 or m * candidates > ffi.MAX_K:
+            raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and {m} lists x candidates <= {ffi.MAX_K}")
+        queries = np.zeros((len(sets), m, dim), np.float32)
+        live = np.zeros((len(sets), m), bool)
+        for i, one in enumerate(sets):
+            queries[i, :len(one)] = one
+            live[i, :len(one)] = True
+        return queries, (None if live.all() else live), fusion.lower(), rrf_k, weights, candidates
+
+    def _search_fused_sync(self, collection: str, queries: np.ndarray, live, limit: int, filters, must_not, method: str, rrf_k: int,
+                           weights, candidates: int) -> list[list[dict[str, Any]]]:
+        """One fused pass + the hit dictionaries of every logical query, built inside the worker job, under the store's lock
+        (slots are only good until the next compaction: :meth:`_search_hits_sync`)."""
+        col = self._col(collection)
+        nq = queries.shape[0]
+        dfilt = col.device_filters(filters, must_not)
+        if dfilt is None or limit <= 0 or nq == 0:
+            return [[] for _ in range(nq)]
+        slots, fused, cos, lists = col.search_fused(queries, limit, candidates, dfilt, method, rrf_k, weights, live)
+        keep = slots >= 0
+        flat = col.hits(slots[keep].tolist(), fused[keep].tolist())              # (payloads fetched together)
+        for h, cv, bits in zip(flat, cos[keep].tolist(), lists[keep].tolist()):
+            h["cosine"] = cv
+            h["matched"] = [j for j in range(ffi.MAX_LISTS) if bits >> j & 1]
+        out, at = [], 0
+        for n in keep.sum(1).tolist():
+            out.append(flat[at:at + n])
+            at += n
+        return out
+
+    async def search_fused_batch(self, collection: str, query_vector_sets, limit: int = 10,
+                                 filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                                 fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None) -> list[list[dict[str, Any]]]:
+        """Batched :meth:`search_fused`: ``query_vector_sets`` is a list of sets of query vectors, one set per logical query;
+        the sets may differ in size (a shorter one fuses its own lists only, and ``weights`` / the default ``candidates`` go by
+        the largest).  All sub-queries of the batch share corpus passes of 64, under ONE filter.  The batch is searched as
+        ``len(sets) * m`` queries with ``m`` the largest set: the absent members of shorter sets are searched as zero vectors
+        and their lists discarded -- wasted slots of the pass, so sets of very different sizes are better sent apart.
+        ``search_passes`` counts ``ceil(len(sets) * m / 64)`` for every call that passes its argument checks, also when the
+        filter names a value the collection never stored and nothing is searched."""
+        try:
+            q, live, method, rrf_k, weights, candidates = self._fused_args(collection, list(query_vector_sets), limit, fusion, rrf_k, weights, candidates)
+            self.search_passes += (q.shape[0] * q.shape[1] + 63) // 64
+            return await self._run(self._search_fused_sync, collection, q, live, int(limit), filters, must_not, method, rrf_k, weights, candidates)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_fused(self, collection: str, query_vectors, limit: int = 10,
+                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                           fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None) -> list[dict[str, Any]]:
+        """ONE logical query asked in ``m`` ways (``query_vectors`` [m, dim], m <= 16: the original text and its reformulations,
+        a HyDE answer, ...): every vector's ``candidates`` best hits, fused on the device into one list of ``limit`` (DESIGN.md
+        3.16; Qdrant's ``prefetch=[...]`` + ``FusionQuery``; not in the reference, whose engine searches the original text only).
+        ``fusion="rrf"``: reciprocal-rank fusion, a hit's ``score`` is the sum over the lists that hold it of ``weights[j] /
+        (rrf_k + rank + 1)`` (rank 0 = best; ``weights`` default to 1).  ``fusion="max"``: ``score`` is the hit's best cosine over
+        the ``m`` vectors -- exactly the top-``limit`` of the corpus under that maximum.  Hits are ``{"id", "score", "payload",
+        "cosine", "matched"}``: ``cosine`` the best cosine among the lists that hold the hit, ``matched`` the ascending indexes
+        of those lists.  ``candidates`` (default ``min(MAX_K // m, 4 * limit)``; ``limit <= candidates``, ``m * candidates <=
+        MAX_K``) is the depth of every list.  ``filters`` / ``must_not`` as in :meth:`search`, one filter for all ``m`` vectors.
+        A fused call takes a pass of its own (it never joins the coalescer)."""
+        return (await self.search_fused_batch(collection, [query_vectors], limit, filters, must_not, fusion=fusion, rrf_k=rrf_k,
+                                              weights=weights, candidates=candidates))[0]
 
     async def search_groups(self, collection: str, query_vector: list[float], group_by: str, limit: int = 5, group_size: int = 3,
                             filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:

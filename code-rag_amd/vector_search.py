@@ -78,6 +78,11 @@ def _project(hit: dict, keys: tuple[str, ...]) -> dict:
     return row
 
 
+def _fused_keys(hit: dict) -> tuple[str, ...]:
+    """The two extra result keys of a fused hit (``HipVectorStore.search_fused``); none for a plain one."""
+    return ("cosine", "matched") if "matched" in hit else ()
+
+
 class VectorSearcher:
     def __init__(self, qdrant, embedder):
         self.qdrant = qdrant
@@ -85,15 +90,28 @@ class VectorSearcher:
 
     async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
                       must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None,
-                      max_per_file: int | None = None):
+                      max_per_file: int | None = None, extra_queries: list[str] | None = None, fusion: str = "rrf"):
         """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
         the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given, and
-        so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k)."""
+        so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k).  ``extra_queries`` (reformulations of
+        ``text``): all texts are embedded in ONE provider batch and the store fuses their hit lists
+        (``HipVectorStore.search_fused``); without them the call is the plain one, keyword for keyword."""
+        extra = [t for t in (extra_queries or []) if t and t.strip()]
+        if extra and (diversity is not None or max_per_file is not None):
+            raise ValueError("extra_queries cannot be combined with diversity or max_per_file")
         try:
-            vector = await self.embedder.embed(text)
             kwargs = {} if filters is _NO_FILTER_KWARG else {"filters": filters}
             if must_not:
                 kwargs["must_not"] = must_not
+            if extra:
+                vectors = np.asarray(await self.embedder.embed_batch([text] + extra), dtype=np.float32)
+                if candidates is not None:
+                    kwargs["candidates"] = candidates
+                hits = await self.qdrant.search_fused(collection=collection, query_vectors=vectors, limit=limit, fusion=fusion, **kwargs)
+                for h in hits:                      # (what _project copies: the fused score stays "score")
+                    h["payload"] = dict(h["payload"], cosine=h["cosine"], matched=h["matched"])
+                return hits
+            vector = await self.embedder.embed(text)
             kwargs.update(_mmr_kwargs(diversity, candidates))
             kwargs.update(_group_kwargs(max_per_file))
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, **kwargs)
@@ -106,30 +124,37 @@ class VectorSearcher:
 
     async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                           entity_type: str | None = None, project_name: str | list[str] | None = None, *,
-                          diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None) -> list[dict]:
+                          diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
+                          extra_queries: list[str] | None = None, fusion: str = "rrf") -> list[dict]:
         """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
         ``diversity`` in [0, 1] (not in the reference): ``limit`` maximal-marginal-relevance picks among the ``candidates``
         best hits instead of the plain top-``limit`` (``HipVectorStore.search``).  ``max_per_file`` (the reference applies it
         after the fetch, query/reranker.py:122-145, and comes back short): at most that many chunks of one file among the
-        ``limit`` results, exactly (``group_by="file_path"``); not together with ``diversity``."""
+        ``limit`` results, exactly (``group_by="file_path"``); not together with ``diversity``.
+        ``extra_queries`` (not in the reference, whose engine searches the original text only, query/engine.py:315-346):
+        reformulations of ``query`` -- the planner's sub-queries, a HyDE answer -- embedded with it in one batch; the store
+        fuses the hit lists of all of them (``fusion`` = "rrf" or "max", ``HipVectorStore.search_fused``), ``score`` is the fused
+        score and every result also carries ``cosine`` and ``matched``.  Not together with ``diversity`` / ``max_per_file``."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file)
-        return [_project(h, _CODE_KEYS) for h in hits]
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion)
+        return [_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
-                               diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None) -> list[dict]:
-        """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6)."""
+                               diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
+                               extra_queries: list[str] | None = None, fusion: str = "rrf") -> list[dict]:
+        """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
+        ``extra_queries`` / ``fusion`` as in :meth:`search_code`."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file)
-        return [_project(h, _SUMMARY_KEYS) for h in hits]
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion)
+        return [_project(h, _SUMMARY_KEYS + _fused_keys(h)) for h in hits]
 
     async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
                                 exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,

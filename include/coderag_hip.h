@@ -391,6 +391,34 @@ int crh_group_select(int nq, int c, int k, int group_size, const float *scores_d
                      const int32_t *codes_dev, int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev,
                      int32_t *out_codes_dev, int32_t *out_info_dev, void *stream);
 
+/* ---- multi-query fusion on the device (reciprocal-rank fusion / best match).  The reference's planner writes reformulations of
+ * a question (QueryPlan.sub_queries[].query_text, query/query_planner.py:66-91) and its engine searches the original text only
+ * (query/engine.py:315-346); Qdrant's counterpart is query_points(prefetch=[...], query=FusionQuery(RRF)).  The definition here
+ * is this repository's own.
+ *
+ * Per logical query: m lists of c entries (scores f32 descending / rows int64 as crh_search or crh_merge_topk* return them, rows
+ * < 0 = padding, at the end of each list), [nq, m, c]; entry (j, p) has flat index u = j * c + p; padding takes no part.
+ *   contribution of (j, p):  RRF  w_j / (float)(rrf_k + p + 1) -- one f32 division, correctly rounded; weights_host[j] or 1
+ *                            MAX  the entry's score
+ *   fused score of a row:    RRF  +0.0f plus the contributions of its entries in ascending u, every addition rounded to f32
+ *                            MAX  its largest contribution
+ *   cos = its largest score, lists = bit j set when list j holds it, first = its smallest u.
+ * "Largest" and the output order compare the order-preserving integer image of f32 (-0.0 < +0.0).  Outputs, each [nq, k]: the
+ * first k distinct rows by descending fused score, ties to the lower row -- out_rows, out_fused, out_cos, out_lists, out_first;
+ * the tail is (-1, -inf, -inf, 0, -1).  out_info int32 [nq, 2] = (distinct rows of the m lists, real entries).  The first j
+ * outputs of a k-output call are the j-output call; m = 1 returns the list itself; MAX with c >= k is the exact top-k of the
+ * corpus under max_j cos(q_j, x) when every list is an exact top-c.
+ * 1 <= m <= CRH_MAX_LISTS, c >= 1, m * c <= CRH_MAX_K, 1 <= k <= m * c, nq >= 0, rrf_k >= 0, weights finite and >= 0 (NULL: all
+ * 1; non-NULL with MAX is refused), anything else CRH_E_INVALID with nothing launched.  Needs no index handle (launches on the
+ * current device, like crh_group_select).  Deterministic; enqueues only; writes every output slot. */
+#define CRH_FUSE_RRF 0
+#define CRH_FUSE_MAX 1
+#define CRH_MAX_LISTS 16
+int crh_fuse_select(int nq, int m, int c, int k, int method, int rrf_k, const float *weights_host /* [m] or NULL */,
+                    const float *scores_dev, const int64_t *rows_dev,            /* [nq, m, c] */
+                    int64_t *out_rows_dev, float *out_fused_dev, float *out_cos_dev, int32_t *out_lists_dev,
+                    int32_t *out_first_dev, /* each [nq, k] */ int32_t *out_info_dev /* [nq, 2] */, void *stream);
+
 /* Filter-only fetch: first `limit` alive rows (ascending) matching the filters, host int64 out;
  * n_out receives how many (rows_out_host may be NULL to count only).  Replaces QdrantManager.search(query_vector=None, ...) as used by
  * query/context/builder.py:111-119 and the scroll of embeddings/client.py:178-202. */
