@@ -22,6 +22,9 @@ MAX_FILTERS, MAX_K = 8, 1024
 MAX_LISTS = 16         # CRH_MAX_LISTS: candidate lists one crh_fuse_select call fuses per logical query
 FUSE_RRF, FUSE_MAX = 0, 1
 FUSE_METHODS = {"rrf": FUSE_RRF, "max": FUSE_MAX}
+MAX_POS, MAX_NEG = 8, 8   # CRH_MAX_POS / CRH_MAX_NEG: live examples of one recommend query (crh_recommend_*)
+RECOMMEND_AVERAGE, RECOMMEND_BEST = 0, 1
+RECOMMEND_STRATEGIES = {"average": RECOMMEND_AVERAGE, "best": RECOMMEND_BEST}
 MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 
@@ -42,6 +45,7 @@ EXPORTS = (
     "crh_index_gather_codes", "crh_group_select",
     "crh_search_multi",
     "crh_fuse_select",
+    "crh_recommend_query", "crh_recommend_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -186,6 +190,8 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_index_gather_codes.argtypes = [vp, i32, i64, vp, i64, vp, vp]
     L.crh_group_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.crh_fuse_select.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_recommend_query.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.crh_recommend_select.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -900,6 +906,84 @@ def fuse_select(scores, rows, m: int, k: int, method: str = "rrf", rrf_k: int = 
     info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
     use_device(dev.index)
     check(lib().crh_fuse_select(nq, m, c, k, code, int(rrf_k), _ptr(w), _ptr(scores), _ptr(rows), *(_ptr(x) for x in outs), _ptr(info), stream))
+    return outs + (info,)
+
+
+def recommend_strategy(strategy) -> int:
+    """``"average"`` / ``"best"`` -> CRH_RECOMMEND_*; ``ValueError`` for anything else."""
+    if not isinstance(strategy, str) or strategy.lower() not in RECOMMEND_STRATEGIES:
+        raise ValueError(f"unknown strategy {strategy!r} (one of {sorted(RECOMMEND_STRATEGIES)})")
+    return RECOMMEND_STRATEGIES[strategy.lower()]
+
+
+def _recommend_counts(n_pos, n_neg, nq: int):
+    """The ragged sets' live counts as host int32 [nq] arrays (``None`` stays ``None``: every slot is live)."""
+    out = []
+    for x, what in ((n_pos, "n_pos"), (n_neg, "n_neg")):
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
+            if x.size != nq:
+                raise NativeError(E_INVALID, f"{what} has {x.size} entries for {nq} queries")
+        out.append(x)
+    return out
+
+
+def recommend_query(examples, P: int, N: int, n_pos=None, n_neg=None, stream: int = 0):
+    """The "average" query of every example set (``crh_recommend_query``): ``examples`` f32 CUDA tensor
+    ``[nq, P + N, dim]`` -- stored rows as :meth:`Index.gather_vectors` returns them, positives first; ``n_pos`` / ``n_neg``
+    (host int [nq] or ``None``) the live counts of ragged sets.  Returns a CUDA tensor f32 ``[nq, dim]``; enqueues only."""
+    import torch
+    if not _is_dev(examples):
+        raise NativeError(E_INVALID, "examples must be a device tensor")
+    P, N = int(P), int(N)
+    if examples.ndim != 3 or int(examples.shape[1]) != P + N:
+        raise NativeError(E_INVALID, f"examples must be [nq, P + N = {P + N}, dim], got shape {tuple(examples.shape)}")
+    _typed(examples, "float32", "examples")
+    nq, dim = int(examples.shape[0]), int(examples.shape[2])
+    n_pos, n_neg = _recommend_counts(n_pos, n_neg, nq)
+    out = torch.empty((nq, dim), dtype=torch.float32, device=examples.device)
+    use_device(examples.device.index)
+    check(lib().crh_recommend_query(nq, P, N, dim, _ptr(examples), _ptr(n_pos), _ptr(n_neg), _ptr(out), stream))
+    return out
+
+
+def recommend_select(scores, rows, cand_vecs, examples, example_rows, P: int, N: int, k: int, strategy: str = "best", bf16: bool = False,
+                     n_pos=None, n_neg=None, stream: int = 0):
+    """The recommend selection (``crh_recommend_select``) over candidate lists left on the device.  ``"best"``:
+    ``scores`` f32 / ``rows`` i64 ``[nq, P, c]`` the exact top-``c`` lists of the positives, ``cand_vecs`` f32 ``[nq, P * c, dim]``
+    the candidates' stored vectors, ``examples`` f32 ``[nq, P + N, dim]`` the raw examples, ``example_rows`` i64 ``[nq, P + N]``
+    their rows (-1: unused slot), ``bf16`` whether the store rounds its queries to bf16.  ``"average"``: ``[nq, 1, c]`` lists of
+    the average query; ``cand_vecs`` / ``examples`` may be ``None``.  Returns CUDA tensors ``(rows i64, score f32, neg f32, best
+    i32)``, each [nq, k] -- the first ``k`` kept rows by descending score, ties to the lower row, tail ``(-1, -inf, -inf, -1)``
+    -- and ``info`` i32 [nq, 4] = (kept, settled, distinct, vetoed).  Enqueues only."""
+    import torch
+    code = recommend_strategy(strategy)
+    for x, what in ((scores, "scores"), (rows, "rows"), (example_rows, "example_rows")) + (((cand_vecs, "cand_vecs"), (examples, "examples")) if code else ()):
+        if not _is_dev(x):
+            raise NativeError(E_INVALID, f"{what} must be a device tensor")
+    P, N, k = int(P), int(N), int(k)
+    m = P if code == RECOMMEND_BEST else 1
+    if scores.ndim != 3 or int(scores.shape[1]) != m:
+        raise NativeError(E_INVALID, f"scores must be [nq, {m}, c], got shape {tuple(scores.shape)}")
+    nq, c = int(scores.shape[0]), int(scores.shape[2])
+    _typed(scores, "float32", "scores")
+    _out(rows, "int64", "rows", (nq, m, c))
+    _out(example_rows, "int64", "example_rows", (nq, P + N))
+    if code == RECOMMEND_BEST:
+        if examples.ndim != 3:
+            raise NativeError(E_INVALID, "examples must be [nq, P + N, dim]")
+        dim = int(examples.shape[2])
+        _out(examples, "float32", "examples", (nq, P + N, dim))
+        _out(cand_vecs, "float32", "cand_vecs", (nq, m * c, dim))
+    else:
+        dim, cand_vecs, examples = 384, None, None        # (not read)
+    n_pos, n_neg = _recommend_counts(n_pos, n_neg, nq)
+    dev = scores.device
+    outs = tuple(torch.empty((nq, max(k, 0)), dtype=dt, device=dev) for dt in (torch.int64, torch.float32, torch.float32, torch.int32))
+    info = torch.empty((nq, 4), dtype=torch.int32, device=dev)
+    use_device(dev.index)
+    check(lib().crh_recommend_select(nq, P, N, c, k, dim, code, int(bool(bf16)), _ptr(scores), _ptr(rows), _ptr(cand_vecs), _ptr(examples),
+                                     _ptr(example_rows), _ptr(n_pos), _ptr(n_neg), *(_ptr(x) for x in outs), _ptr(info), stream))
     return outs + (info,)
 
 

@@ -30,10 +30,17 @@ class SearchResult:
 def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
     async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
                               candidates: int | None = None, max_per_file: int | None = None, extra_queries: list[str] | None = None,
-                              fusion: str | None = None) -> ToolResult:
+                              fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
+            if like_ids or unlike_ids:           # recommend by example: the query text is not embedded
+                if not like_ids:
+                    raise ValueError("unlike_ids needs like_ids")
+                hits = await searcher.find_similar_to(positive_ids=list(like_ids), negative_ids=list(unlike_ids or []), limit=limit)
+                data = [vars(SearchResult(qualified_name=h.get("entity_name"), entity_type=h.get("entity_type"), file_path=h.get("file_path"),
+                                          score=h.get("score"), summary=h.get("summary"))) for h in hits]
+                return ToolResult(success=True, data=data, message=f"Found {len(data)} matches like {len(like_ids)} example(s).")
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
                                        ("extra_queries", extra_queries or None), ("fusion", fusion)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
@@ -66,5 +73,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                                               "wordings are fused into one list", "required": False},
             "fusion": {"type": "string", "description": "With extra_queries: 'rrf' (reciprocal-rank fusion, the default) or 'max' "
                                                         "(best match over the wordings)", "required": False},
+            "like_ids": {"type": "array", "description": "Ids of results to find more of (up to 8): the answer is built from these "
+                                                         "stored examples instead of the query text", "required": False},
+            "unlike_ids": {"type": "array", "description": "With like_ids: ids of results to steer away from (up to 8)", "required": False},
         },
     }

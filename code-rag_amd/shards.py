@@ -503,6 +503,117 @@ class ShardSet:
             cs[dead], cr[dead] = -np.inf, -1
         return tuple(np.asarray(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights))
 
+    # ------------------------------------------------------------------ recommend by example
+    def rows_alive(self, shard: np.ndarray, local: np.ndarray) -> np.ndarray:
+        """Whether every row (shard, local) is alive, from the owners' validity words (one all-reduce under backend "dist")."""
+        shard, local = np.asarray(shard, np.int64), np.asarray(local, np.int64)
+        out = np.zeros(local.shape, np.int64)
+        for s in self.owned:
+            m = shard == s
+            if m.any():
+                words = np.asarray(self.index[s].alive_words(), np.uint32)
+                out[m] = (words[local[m] >> 5] >> (local[m] & 31).astype(np.uint32)) & 1
+        if self.dist is not None:
+            import torch
+            t = torch.from_numpy(out).to(self._tensor_device())
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+            out = t.cpu().numpy()
+        return out.astype(bool)
+
+    def _gather_everywhere(self, rows_dev, stream):
+        """Stored vectors of a table of GLOBAL rows, completed across the shards as :meth:`search_mmr_device` does."""
+        vecs = None
+        for s in self.owned:
+            part = self.index[s].gather_vectors(rows_dev, row_base=s * STRIDE, stream=stream)
+            if vecs is None:
+                vecs = part
+            else:
+                vecs += part
+        self.complete_vectors(vecs)
+        return vecs
+
+    def recommend_device(self, example_rows, P: int, N: int, k: int, candidates: int, dfilt, strategy: str = "average", n_pos=None, n_neg=None):
+        """Recommend by example on the device, results left there.  ``example_rows`` (host int64 [nq, P + N]): the GLOBAL rows
+        of every query's examples, positives first, -1 for an unused slot; ``n_pos`` / ``n_neg`` (host int [nq] or None) the
+        live counts of ragged sets.  The examples' stored vectors are gathered across the shards (:meth:`complete_vectors`
+        under backend "dist").  ``"average"``: ``crh_recommend_query`` makes one query per set, :meth:`search_device` answers it
+        with ``candidates`` hits and ``crh_recommend_select`` drops the example rows.  ``"best"``: the ``nq * P`` positives are
+        searched as plain device queries (``candidates`` hits each; the lists of absent positives are overwritten with
+        padding), the candidates' vectors gathered, and ``crh_recommend_select`` applies the veto, ranks and counts the settled
+        prefix.  Returns CUDA tensors ``(GLOBAL rows i64, score f32, neg f32, best i32)``, each [nq, k], ``info`` i32 [nq, 4] =
+        (kept, settled, distinct, vetoed) and ``full`` bool [nq]: whether any of the query's lists came back full."""
+        import torch
+        code = ffi.recommend_strategy(strategy)
+        dev = torch.device("cuda", self.device)
+        ffi.use_device(self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        er = torch.from_numpy(np.ascontiguousarray(example_rows, dtype=np.int64)).to(dev)
+        nq, E = int(er.shape[0]), P + N
+        examples = self._gather_everywhere(er, stream)                    # [nq, P + N, dim]
+        bf16 = self.dtype == ffi.DTYPE_BF16
+        if code == ffi.RECOMMEND_AVERAGE:
+            q = ffi.recommend_query(examples, P, N, n_pos, n_neg, stream=stream)
+            cs, cr = self.search_device(q, candidates, dfilt)
+            cs, cr = cs.view(nq, 1, candidates), cr.view(nq, 1, candidates)
+            vecs = None
+        else:
+            cs, cr = self.search_device(examples[:, :P].reshape(nq * P, self.dim), candidates, dfilt)
+            if n_pos is not None:
+                dead = torch.from_numpy((np.arange(P)[None, :] >= np.asarray(n_pos).reshape(nq, 1)).reshape(nq * P)).to(dev)
+                cs.masked_fill_(dead[:, None], float("-inf"))
+                cr.masked_fill_(dead[:, None], -1)
+            vecs = self._gather_everywhere(cr, stream).view(nq, P * candidates, self.dim)
+            cs, cr = cs.view(nq, P, candidates), cr.view(nq, P, candidates)
+        full = (cr[:, :, -1] >= 0).any(1)
+        return ffi.recommend_select(cs, cr, vecs, examples, er, P, N, k, strategy, bf16, n_pos, n_neg, stream=stream) + (full,)
+
+    def _read_global(self, rows: np.ndarray) -> np.ndarray:
+        """``read_rows`` of a table of GLOBAL rows on host arrays (zeros for padding and for rows of shards owned elsewhere,
+        which :meth:`complete_vectors` adds)."""
+        rows = np.asarray(rows, np.int64)
+        out = np.zeros(rows.shape + (self.dim,), np.float32)
+        flat_r, flat_o = rows.reshape(-1), out.reshape(-1, self.dim)
+        for i in np.flatnonzero(flat_r >= 0):
+            s, lo = int(flat_r[i] // STRIDE), int(flat_r[i] % STRIDE)
+            if s in self.index:
+                flat_o[i] = self.index[s].read_rows(lo, 1)[0]
+        if self.dist is not None:
+            import torch
+            t = torch.from_numpy(out)
+            self.complete_vectors(t)
+        return out
+
+    def recommend(self, example_rows, P: int, N: int, k: int, candidates: int, dfilt, strategy: str = "average", n_pos=None, n_neg=None):
+        """:meth:`recommend_device` as host arrays: ``(GLOBAL rows i64, score f32, neg f32, best i32)``, each [nq, k], ``info``
+        i32 [nq, 4] and ``full`` bool [nq]; -1 rows are padding.  Indexes that hold a native handle take the device form;
+        injected host-side indexes (CPU test tier) run the same steps on numpy arrays out of ``search`` and ``read_rows``."""
+        if all(hasattr(ix, "_handle") for ix in self.index.values()):
+            return tuple(t.cpu().numpy() for t in self.recommend_device(example_rows, P, N, k, candidates, dfilt, strategy, n_pos, n_neg))
+        code = ffi.recommend_strategy(strategy)
+        er = np.ascontiguousarray(example_rows, dtype=np.int64)
+        nq = int(er.shape[0])
+        examples = self._read_global(er)
+
+        def search(queries):
+            if self.ns == 1:
+                s, r = self.index[0].search(queries, candidates, filters=dfilt)
+            else:
+                s, r = self._search_host(queries, candidates, dfilt)
+            return np.array(s, np.float32), np.array(r, np.int64)
+        bf16 = self.dtype == ffi.DTYPE_BF16
+        if code == ffi.RECOMMEND_AVERAGE:
+            cs, cr = search(np.asarray(ffi.recommend_query(examples, P, N, n_pos, n_neg), np.float32))
+            cs, cr, vecs = cs.reshape(nq, 1, candidates), cr.reshape(nq, 1, candidates), None
+        else:
+            cs, cr = search(np.ascontiguousarray(examples[:, :P].reshape(nq * P, self.dim)))
+            if n_pos is not None:
+                dead = (np.arange(P)[None, :] >= np.asarray(n_pos).reshape(nq, 1)).reshape(nq * P)
+                cs[dead], cr[dead] = -np.inf, -1
+            vecs = self._read_global(cr).reshape(nq, P * candidates, self.dim)
+            cs, cr = cs.reshape(nq, P, candidates), cr.reshape(nq, P, candidates)
+        full = (cr[:, :, -1] >= 0).any(1)
+        return tuple(np.asarray(a) for a in ffi.recommend_select(cs, cr, vecs, examples, er, P, N, k, strategy, bf16, n_pos, n_neg)) + (full,)
+
     # ------------------------------------------------------------------ maintenance
     def compact(self) -> dict[int, np.ndarray]:
         """``crh_index_compact`` on every shard; returns {shard: old_to_new local rows} for ALL shards on every rank."""

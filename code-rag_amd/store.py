@@ -97,6 +97,7 @@ class _Collection:
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
+        self.recommend_rounds = {"queries": 0, "round2": 0, "short": 0}    # recommend: queries asked / sent to round 2 / answered short
         # One process per shard (backend "dist"): a rank keeps the payload TEXT (content, summary: 4.2 of the 5.2 GB of host
         # tables per 10M chunks) of its OWN rows only -- everybody else stores an empty string there -- and a hit's payload comes
         # from the rank that owns the row (payloads_of: one byte exchange per search, shards.ShardSet.exchange_bytes).
@@ -470,6 +471,58 @@ class _Collection:
         rows, fused, cos, lists, _, _ = self.shards.search_fused(queries, limit, candidates, dfilt, method, rrf_k, weights, live)
         shard = np.where(rows >= 0, rows // SHARD_STRIDE, 0).astype(np.int32)
         return self.slots_of(shard, np.where(rows >= 0, rows % SHARD_STRIDE, -1)), fused, cos, lists
+
+    def example_rows(self, slots: np.ndarray) -> np.ndarray:
+        """GLOBAL rows of a table of example slots (-1 stays -1)."""
+        slots = np.asarray(slots, np.int64)
+        shard, local = self.rows_of(np.maximum(slots, 0))
+        return np.where(slots >= 0, np.asarray(shard, np.int64) * SHARD_STRIDE + np.asarray(local, np.int64), -1)
+
+    def recommend(self, slots: np.ndarray, P: int, N: int, limit: int, candidates: int, dfilt, strategy: str, n_pos=None, n_neg=None):
+        """Recommend by example for ``nq`` logical queries whose examples are the slots ``slots`` [nq, P + N]
+        (positives first, -1 for an unused slot): (slots i64, score f32, neg f32, best i32), each [nq, limit]; -1 slots are
+        padding.  ``"average"`` is one round at ``limit + P + N`` candidates.  ``"best"`` holds the rounds: round 1 runs at
+        ``candidates`` per positive; a query whose settled prefix reaches ``limit``, or none of whose lists came back full (the
+        filter has no more rows), is done; the others go on together at ``MAX_K // P``; what is still unsettled then comes back
+        SHORT -- its settled prefix only, every returned hit the exact hit of its position.  ``self.recommend_rounds`` counts
+        the queries asked, those sent to round 2 and those answered short."""
+        ex = self.example_rows(slots)
+        nq = int(ex.shape[0])
+        stats = self.recommend_rounds
+        stats["queries"] += nq
+        out = (np.full((nq, limit), -1, np.int64), np.full((nq, limit), -np.inf, np.float32), np.full((nq, limit), -np.inf, np.float32),
+               np.full((nq, limit), -1, np.int32))
+        if strategy == "average":
+            c = limit + P + N
+            rows, score, neg, best, _, _ = self.shards.recommend(ex, P, N, min(limit, c), c, dfilt, strategy, n_pos, n_neg)
+            for o, v in zip(out, (rows, score, neg, best)):
+                o[:, :v.shape[1]] = v
+        else:
+            todo = np.arange(nq)
+            deep = ffi.MAX_K // P
+            for rnd, c in enumerate((candidates, deep)):
+                if rnd == 1:
+                    if candidates >= deep:            # (round 1 already ran as deep as a round can)
+                        stats["short"] += int(todo.size)
+                        break
+                    stats["round2"] += int(todo.size)
+                k = min(limit, P * c)
+                sub = lambda a: None if a is None else np.asarray(a)[todo]   # noqa: E731
+                rows, score, neg, best, info, full = self.shards.recommend(ex[todo], P, N, k, c, dfilt, strategy, sub(n_pos), sub(n_neg))
+                settled = np.minimum(info[:, 1], k)
+                done = (info[:, 1] >= limit) | ~full
+                take = done if rnd == 0 and candidates < deep else np.ones_like(done)
+                for i in np.flatnonzero(take):
+                    w = int(settled[i])
+                    for o, v in zip(out, (rows, score, neg, best)):
+                        o[todo[i], :w] = v[i, :w]
+                if rnd == 1:
+                    stats["short"] += int((~done).sum())
+                todo = todo[~done]
+                if not todo.size:
+                    break
+        shard = np.where(out[0] >= 0, out[0] // SHARD_STRIDE, 0).astype(np.int32)
+        return (self.slots_of(shard, np.where(out[0] >= 0, out[0] % SHARD_STRIDE, -1)),) + out[1:]
 
     # -- compaction
     def maybe_compact(self) -> bool:
@@ -1287,6 +1340,103 @@ class HipVectorStore:
         A fused call takes a pass of its own (it never joins the coalescer)."""
         return (await self.search_fused_batch(collection, [query_vectors], limit, filters, must_not, fusion=fusion, rrf_k=rrf_k,
                                               weights=weights, candidates=candidates))[0]
+
+    def _recommend_args(self, collection: str, sets, limit: int, strategy, candidates: int | None):
+        """Checked ``(positive ids, negative ids, P, N, strategy, candidates)`` of one recommend call; raises ``ValueError`` for
+        the caller alone.  ``candidates`` -- the depth of every positive's list in round 1 of ``"best"`` -- defaults to
+        ``4 * limit``, clipped so that ``P * candidates <= MAX_K``."""
+        ffi.recommend_strategy(strategy)
+        strategy = strategy.lower()
+        self._col(collection)
+        pos, neg = [], []
+        for one in sets:
+            if isinstance(one, (str, bytes)) or len(one) != 2:
+                raise ValueError("a recommend query is a pair (positive ids, negative ids)")
+            p_ids, n_ids = ([one[0]] if isinstance(one[0], str) else list(one[0])), ([one[1]] if isinstance(one[1], str) else list(one[1] or ()))
+            if not 1 <= len(p_ids) <= ffi.MAX_POS or len(n_ids) > ffi.MAX_NEG:
+                raise ValueError(f"a recommend query takes 1..{ffi.MAX_POS} positive and 0..{ffi.MAX_NEG} negative ids, got {len(p_ids)} and {len(n_ids)}")
+            pos.append([str(i) for i in p_ids])
+            neg.append([str(i) for i in n_ids])
+        P, N = max((len(p) for p in pos), default=1), max((len(n) for n in neg), default=0)
+        limit = int(limit)
+        if limit > ffi.MAX_K or (strategy == "average" and limit + P + N > ffi.MAX_K):
+            raise ValueError(f"limit {limit} (plus the examples under 'average') exceeds the index's maximum k of {ffi.MAX_K}")
+        if candidates is None:
+            candidates = max(1, min(ffi.MAX_K // P, 4 * max(limit, 1)))
+        candidates = int(candidates)
+        if candidates < 1 or P * candidates > ffi.MAX_K:
+            raise ValueError(f"candidates {candidates} must be >= 1 and {P} lists x candidates <= {ffi.MAX_K}")
+        return pos, neg, P, N, strategy, candidates
+
+    def _recommend_sync(self, collection: str, pos, neg, P: int, N: int, limit: int, filters, must_not, strategy: str,
+                        candidates: int) -> list[list[dict[str, Any]]]:
+        """The ids resolved, one recommend call and the hit dictionaries of every logical query, built inside the worker job,
+        under the store's lock (slots are only good until the next compaction: :meth:`_search_hits_sync`)."""
+        col = self._col(collection)
+        nq = len(pos)
+        slots = np.full((nq, P + N), -1, np.int64)
+        flat = [i for p, n in zip(pos, neg) for i in p + n]
+        found = col.ids.lookup(flat) if flat else np.zeros((0,), np.int64)
+        alive = np.zeros(found.shape, bool)
+        if (found >= 0).any():
+            alive[found >= 0] = col.shards.rows_alive(*col.rows_of(found[found >= 0]))
+        missing = [i for i, ok in zip(flat, alive) if not ok]
+        if missing:
+            raise ValueError(f"unknown or deleted point id {missing[0]!r}")
+        at = 0
+        for q, (p, n) in enumerate(zip(pos, neg)):
+            slots[q, :len(p)] = found[at:at + len(p)]
+            slots[q, P:P + len(n)] = found[at + len(p):at + len(p) + len(n)]
+            at += len(p) + len(n)
+        dfilt = col.device_filters(filters, must_not)
+        if dfilt is None or limit <= 0 or nq == 0:
+            return [[] for _ in range(nq)]
+        n_pos, n_neg = np.asarray([len(p) for p in pos], np.int32), np.asarray([len(n) for n in neg], np.int32)
+        ragged = bool((n_pos != P).any() or (n_neg != N).any())
+        got, score, nscore, best = col.recommend(slots, P, N, limit, candidates, dfilt, strategy, n_pos if ragged else None, n_neg if ragged else None)
+        keep = got >= 0
+        hits = col.hits(got[keep].tolist(), score[keep].tolist())            # (payloads fetched together)
+        if strategy == "best":
+            qi = np.nonzero(keep)[0]
+            for h, q, nv, b in zip(hits, qi.tolist(), nscore[keep].tolist(), best[keep].tolist()):
+                h["negative_score"] = nv
+                h["matched_positive"] = pos[q][b]
+        out, at = [], 0
+        for n in keep.sum(1).tolist():
+            out.append(hits[at:at + n])
+            at += n
+        return out
+
+    async def recommend_batch(self, collection: str, example_sets, limit: int = 10, strategy: str = "average",
+                              filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None,
+                              candidates: int | None = None) -> list[list[dict[str, Any]]]:
+        """Batched :meth:`recommend`: ``example_sets`` is a list of ``(positive ids, negative ids)`` pairs, one per logical
+        query; the sets may differ in size (the batch runs at the largest ``P`` and ``N``; under ``"best"`` the absent positives
+        are searched as zero vectors and their lists discarded).  All queries of the batch share corpus passes of 64, under ONE
+        filter.  ``search_passes`` counts the passes of round 1."""
+        try:
+            pos, neg, P, N, strategy, candidates = self._recommend_args(collection, list(example_sets), limit, strategy, candidates)
+            self.search_passes += (len(pos) * (P if strategy == "best" else 1) + 63) // 64
+            return await self._run(self._recommend_sync, collection, pos, neg, P, N, int(limit), filters, must_not, strategy, candidates)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to recommend in {collection}", cause=e)
+
+    async def recommend(self, collection: str, positive, negative=(), limit: int = 10, strategy: str = "average",
+                        filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None,
+                        candidates: int | None = None) -> list[dict[str, Any]]:
+        """"More like these, not like those" (Qdrant's ``RecommendQuery(positive, negative, strategy)``; the
+        reference's ``find_similar`` intent can only embed a snippet): ``positive`` (1..8) and ``negative`` (0..8) are ids of
+        stored points -- no text is embedded again; an unknown or deleted id raises ``VectorStoreError`` naming it.  The example
+        points themselves never appear in the answer; ``filters`` / ``must_not`` as in :meth:`search`.
+        ``strategy="average"``: the exact top-``limit`` for the vector ``2 * mean(positive) - mean(negative)`` (the mean of the
+        positives without negatives), computed on the device from the stored rows.  Hits are ``{"id", "score", "payload"}``.
+        ``strategy="best"``: a point's ``score`` is its best cosine to a positive; it is dropped (not ranked last, as Qdrant
+        does) when a negative is at least as close.  Hits also carry ``negative_score`` (the best cosine to a negative, -inf
+        without negatives) and ``matched_positive`` (the id of the positive that gave ``score``).  The answer is exact: every
+        returned hit is the hit of its position over the whole filtered collection; when two rounds of candidates (``candidates``
+        per positive, default ``4 * limit``, then ``MAX_K // P``) cannot settle ``limit`` hits -- negatives that veto most of the
+        positives' neighbourhood -- the list comes back shorter than ``limit``.  A recommend call takes passes of its own."""
+        return (await self.recommend_batch(collection, [(positive, negative)], limit, strategy, filters, must_not, candidates))[0]
 
     async def search_groups(self, collection: str, query_vector: list[float], group_by: str, limit: int = 5, group_size: int = 3,
                             filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:

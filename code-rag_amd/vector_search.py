@@ -83,6 +83,16 @@ def _fused_keys(hit: dict) -> tuple[str, ...]:
     return ("cosine", "matched") if "matched" in hit else ()
 
 
+def _transform_similar_code_result(hit: dict) -> dict:
+    """A store hit in the result shape of ``find_similar_code`` (vector_search.py:199-216); a recommend hit under strategy
+    "best" keeps its two extra keys."""
+    row = _project(hit, _SIMILAR_KEYS)
+    for k in ("negative_score", "matched_positive"):
+        if k in hit:
+            row[k] = hit[k]
+    return row
+
+
 class VectorSearcher:
     def __init__(self, qdrant, embedder):
         self.qdrant = qdrant
@@ -178,6 +188,30 @@ class VectorSearcher:
             if len(kept) >= limit:
                 break
         return kept
+
+    async def find_similar_to(self, positive_ids, negative_ids=None, limit: int = DEFAULT_SEARCH_LIMIT, strategy: str = "average",
+                              language: str | list[str] | None = None, exclude_files: list[str] | None = None) -> list[dict]:
+        """"Other functions like X" from hits the caller already holds (not in the reference, whose ``find_similar`` intent can
+        only embed a snippet): ``positive_ids`` / ``negative_ids`` are point ids of code chunks -- nothing is embedded --
+        answered by ``HipVectorStore.recommend`` (``strategy`` "average" or "best"), in the result shape of
+        :meth:`find_similar_code`.  ``language`` filters, ``exclude_files`` drops whole files, both on the device; the example
+        chunks themselves never come back."""
+        positive = [positive_ids] if isinstance(positive_ids, str) else list(positive_ids or [])
+        negative = [negative_ids] if isinstance(negative_ids, str) else list(negative_ids or [])
+        if not positive:
+            raise QueryError("find_similar_to needs at least one positive id")
+        kwargs = {}
+        if language:
+            kwargs["filters"] = {"language": language}
+        if exclude_files:
+            kwargs["must_not"] = {"file_path": list(exclude_files)}
+        try:
+            hits = await self.qdrant.recommend(collection=CollectionName.CODE_CHUNKS.value, positive=positive, negative=negative, limit=limit,
+                                               strategy=strategy, **kwargs)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to find similar code", cause=e)
+        return [_transform_similar_code_result(h) for h in hits]
 
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,

@@ -419,6 +419,51 @@ int crh_fuse_select(int nq, int m, int c, int k, int method, int rrf_k, const fl
                     int64_t *out_rows_dev, float *out_fused_dev, float *out_cos_dev, int32_t *out_lists_dev,
                     int32_t *out_first_dev, /* each [nq, k] */ int32_t *out_info_dev /* [nq, 2] */, void *stream);
 
+/* ---- recommend by example on the device ("more like these, not like those").  The reference's planner has a find_similar
+ * intent and can only embed a snippet for it; Qdrant's counterpart is RecommendQuery(positive, negative, strategy), known by
+ * description only.  The definitions here are this repository's own.
+ *
+ * A logical query is P positive and N negative EXAMPLES, each a stored row as crh_index_gather_vectors returns it.  Its slots
+ * are [P positives | N negatives]; n_pos_host / n_neg_host (int32 [nq], host, copied by the call; NULL: every slot is live) give
+ * ragged sets: the first n_pos positives and the first n_neg negatives of a query are live, 1 <= n_pos <= P, 0 <= n_neg <= N. */
+#define CRH_MAX_POS 8
+#define CRH_MAX_NEG 8
+#define CRH_RECOMMEND_AVERAGE 0
+#define CRH_RECOMMEND_BEST 1
+
+/* The "average" query: out[q, i] = (ap + ap) - an with ap = sp / (float)n_pos, an = sn / (float)n_neg, sp / sn = +0.0f plus the
+ * live positives' / negatives' elements in ascending slot order; with n_neg = 0, out[q, i] = ap.  Every operation is rounded to
+ * f32 separately (no fused multiply-add).  examples_dev f32 [nq, P + N, dim], out_queries_dev f32 [nq, dim].  nq >= 0, 1 <= P <=
+ * CRH_MAX_POS, 0 <= N <= CRH_MAX_NEG, dim 384 / 768 / 1024 / 1536, counts in range; anything else CRH_E_INVALID with nothing
+ * launched.  Needs no index handle; deterministic; enqueues only. */
+int crh_recommend_query(int nq, int P, int N, int dim, const float *examples_dev, const int32_t *n_pos_host,
+                        const int32_t *n_neg_host, float *out_queries_dev, void *stream);
+
+/* The selection.  Method BEST: scores_dev f32 / rows_dev int64 [nq, P, c] are the exact top-c lists of the P positives (rows < 0
+ * = padding, at the end of a list; the lists of slots that are not live must be all padding), cand_vecs_dev f32 [nq, P * c, dim]
+ * the candidates' stored vectors, examples_dev f32 [nq, P + N, dim] the RAW examples (both 16-byte aligned), example_rows_dev
+ * int64 [nq, P + N] their rows (-1: unused slot).  s(e, x) is the score crh_search gives row x for the raw query e: Qdrant's
+ * cosine_preprocess of e in sequential f32 arithmetic (then rounded to bf16 when round_bf16 = 1: the store's dtype is BF16),
+ * then the canonical dot (acc = acc + e[i] * x[i], i ascending, product and sum rounded separately).  Per distinct row (its
+ * first flat entry stands for it): p = max over the live positives of s, best = the lowest slot that attains it, n = max over
+ * the live negatives (-inf without one).  A row is KEPT iff it is no example row and ord(p) > ord(n) on the order-preserving
+ * integer image of f32 (-0.0 < +0.0).  Outputs, each [nq, k]: the first k kept rows by descending p, ties to the lower row --
+ * out_rows, out_score (p), out_neg (n), out_best (int32); the tail is (-1, -inf, -inf, -1).  out_info int32 [nq, 4] = (kept,
+ * settled, distinct real candidates, vetoed = distinct - kept), none clipped at k.  SETTLED: with T the largest last score over
+ * the lists whose c entries are all real, the kept rows with ord(p) > ord(T) -- every row of the corpus with p > T is in some
+ * list, so they are a prefix of the exact answer; without a full list every kept row is settled.
+ * Method AVERAGE: ONE list per query, [nq, 1, c] (the search for crh_recommend_query's vector); it only removes the example rows:
+ * out_score is the list's score, out_neg -inf, out_best -1, every kept row settled; cand_vecs_dev / examples_dev are not read.
+ * The first j outputs of a k-output call are the j-output call.  With `lists` = P (BEST) or 1 (AVERAGE): c >= 1, lists * c <=
+ * CRH_MAX_K, 1 <= k <= lists * c, P / N / dim / counts as above, round_bf16 0 or 1; anything else CRH_E_INVALID with nothing
+ * launched.  Needs no index handle (launches on the current device, like crh_fuse_select).  Deterministic; enqueues only;
+ * writes every output slot. */
+int crh_recommend_select(int nq, int P, int N, int c, int k, int dim, int method, int round_bf16, const float *scores_dev,
+                         const int64_t *rows_dev, const float *cand_vecs_dev, const float *examples_dev,
+                         const int64_t *example_rows_dev, const int32_t *n_pos_host, const int32_t *n_neg_host,
+                         int64_t *out_rows_dev, float *out_score_dev, float *out_neg_dev, int32_t *out_best_dev, /* each [nq, k] */
+                         int32_t *out_info_dev /* [nq, 4] */, void *stream);
+
 /* Filter-only fetch: first `limit` alive rows (ascending) matching the filters, host int64 out;
  * n_out receives how many (rows_out_host may be NULL to count only).  Replaces QdrantManager.search(query_vector=None, ...) as used by
  * query/context/builder.py:111-119 and the scroll of embeddings/client.py:178-202. */
