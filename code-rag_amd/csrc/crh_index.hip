@@ -14,6 +14,7 @@
 #include "crh_common.h"
 #include "crh_kernels.hpp"
 #include "crh_i8.hpp"
+#include "crh_range.hpp"
 
 namespace crh {
 std::string &last_error_ref()
@@ -39,6 +40,7 @@ constexpr int kI8Ring = CRH_I8_RING;
 constexpr int kI8SelectParts = 4;   // workgroups per query in k_select behind the int8 scan (64 queries x 4 = the chip)
 constexpr int kStatusSlots = 1024;
 constexpr int64_t kWorkspaceBudget = 48LL << 30;
+constexpr int kRangeParts = 8;  // workgroups per query in k_range_count (crh_range.hpp)
 constexpr int kSparseDen = 4;   // the sparse route is taken from 1 populated tile in this many down (profiles/sparse_crossover.md)
 
 // A filter in the form the index keeps, compares and uploads: [n conditions, then per condition: column, negate, set size,
@@ -74,6 +76,9 @@ struct Pending {
     int slot;
     bool multi;     // a mixed-filter batch (crh_search_multi): key is the classes' keys behind their number, cls the queries' classes
     QueryClasses cls;
+    bool range;     // a range batch (crh_search_range): thr the queries' thresholds, counts their in-range totals (device; nullptr: list only)
+    RangeThr thr;
+    unsigned long long *counts;
     int path;       // how enqueue_batch nominated the batch's rows: CRH_NOMINATE_INT8 / _BF16 (one launch) / _BF16_3 (three launches, wide scan)
 };
 
@@ -157,6 +162,8 @@ struct crh_index {
     float *stage_os = nullptr;
     int64_t *stage_or = nullptr;
     int64_t stage_out_elems = 0;
+    unsigned long long *stage_cnt = nullptr;   // the in-range counts of a crh_search_range call with host outputs
+    int64_t stage_cnt_elems = 0;
     void *stage_in = nullptr;
     int64_t stage_in_bytes = 0;
 
@@ -890,6 +897,55 @@ int enqueue_batch_multi(crh_index *h, crh_index::Workspace &w, const float *q_de
                          });
 }
 
+// One range batch (<= batch_q queries; crh_range.hpp): always the three-launch bf16 form -- over every tile, or over the
+// mask's tile list when it is sparse enough -- with k_range_tau between the thresholds and the main scan, and the count and
+// the cut behind k_select.  List only: the seed scan and k_tau run as in enqueue_three and the threshold can only raise tau.
+// With counts: tau is the threshold's lower band edge alone, so there is nothing to seed.
+int enqueue_batch_range(crh_index *h, crh_index::Workspace &w, const Pending &p, const MaskRef &mref, int slot, hipStream_t st)
+{
+    const int64_t ntiles = ceil_div(h->count, kTileRows);
+    const bool sparse = ntiles > 0 && sparse_use(h, mref, p.nq);
+    if (ntiles == 0 || (sparse && mref.nlist == 0)) {
+        if (p.counts) CRH_HIP(hipMemsetAsync(p.counts, 0, sizeof(unsigned long long) * (size_t)p.nq, st));
+        return pad_batch(h, slot, p.nq, p.k, p.out_s, p.out_r, st, sparse);
+    }
+    const int64_t items = sparse ? mref.nlist : ntiles;   // list positions or tiles
+    const int wave_cap = w.ws_wave_cap, qcap = w.ws_qcap, width = h->batch_q;
+    const float margin = margin_for(h);
+    SearchStatus *stt = h->status + slot;
+    auto scan = [&](auto mode, int n, int stride) {
+        return sparse ? launch_scan_list<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mref, n, stride, wave_cap, qcap, stt)
+                      : launch_scan<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mref.mask, n, stride, wave_cap, qcap, stt);
+    };
+    CRH_TRY(launch_prep(h, w, st, p.q_dev, p.nq, width, stt, false));   // (zeroes the slot's SearchStatus)
+    int G = 0;
+    if (!p.counts) {
+        G = (int)std::min<int64_t>(h->seed_tiles, items);
+        CRH_TRY(scan(std::integral_constant<int, 0>{}, G, (int)(items / G)));
+        hipLaunchKernelGGL(k_tau, dim3(width), dim3(256), (size_t)G * 4, st, w.gmax, G, p.k, margin, p.nq, w.tau, 64);
+        CRH_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_range_tau, dim3(1), dim3(width), 0, st, p.thr, margin, p.nq, w.tau, p.counts);
+    CRH_HIP(hipGetLastError());
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot], st));
+    CRH_TRY(scan(std::integral_constant<int, 1>{}, (int)items, 1));
+    if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
+    CRH_TRY(launch_select_bf16(h, w, st, p.nq, p.k, margin, p.row_base, p.out_s, p.out_r, stt));
+    if (p.counts) {
+        if (h->dtype == CRH_DTYPE_F32)
+            hipLaunchKernelGGL(k_range_count<true>, dim3(p.nq, kRangeParts), dim3(256), 0, st, w.qlist, stt->qcount, qcap, p.thr, margin, w.qn, h->xt, h->xf32,
+                               h->dim, h->ksteps, p.counts);
+        else
+            hipLaunchKernelGGL(k_range_count<false>, dim3(p.nq, kRangeParts), dim3(256), 0, st, w.qlist, stt->qcount, qcap, p.thr, margin, w.qn, h->xt, h->xf32,
+                               h->dim, h->ksteps, p.counts);
+        CRH_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_range_cut, dim3(p.nq), dim3(256), 0, st, p.thr, p.k, p.out_s, p.out_r);
+    CRH_HIP(hipGetLastError());
+    count_batch(h, sparse ? std::min<int64_t>(h->count, items * kTileRows) : h->count, items, G);
+    return CRH_OK;
+}
+
 int next_pow2(int64_t v)
 {
     int64_t p = 1;
@@ -910,6 +966,10 @@ int enqueue_pending(crh_index *h, crh_index::Workspace &w, const Pending &p, int
         return enqueue_batch_multi(h, w, p.q_dev, p.nq, p.k, mask, cmask, p.cls, p.row_base, p.out_s, p.out_r, slot, st);
     }
     CRH_TRY(build_mask(h, w, p.key, &mask, st));
+    if (p.range) {
+        *path_out = CRH_NOMINATE_BF16_3;
+        return enqueue_batch_range(h, w, p, mask, slot, st);
+    }
     return enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, slot, st, path_out);
 }
 
@@ -985,6 +1045,11 @@ int finish_pending(crh_index *h, hipStream_t st)
                 wc = std::max(wc, next_pow2((int64_t)s.max_wave_cnt));
                 qc = std::max(qc, next_pow2((int64_t)s.max_qcount));
             }
+            // A range batch lists every row at or above its threshold's band: a threshold so low that the lists would not fit
+            // the budget is refused here, by the true count -- never answered with a clipped one.
+            if (p.range && ((int64_t)kWideQ * qc * 16 > kWorkspaceBudget || (int64_t)h->cu_count * kWaves * wc * 16 > kWorkspaceBudget))
+                return fail(CRH_E_CAPACITY, "range search: a query has %u candidate rows at or above its threshold's band (a wave of the scan: %u), "
+                            "more than the candidate workspace may hold -- raise the threshold or narrow the filter", s.max_qcount, s.max_wave_cnt);
             CRH_TRY(ensure_workspace(h, w, wc, qc));
             if (!p.multi) h->i8_suppress = no_i8;
             const int rc = enqueue_pending(h, w, p, 0, st, &path);
@@ -1108,6 +1173,21 @@ int search_multi_key(crh_index *h, int nq, const float *queries, int queries_on_
                               p.nq = std::min(h->batch_q, left);
                               p.multi = true;
                               for (int i = 0; i < p.nq; ++i) p.cls.w[i >> 3] |= (uint32_t)query_class[q0 + i] << ((i & 7) * 4);
+                              return (int)CRH_OK;
+                          });
+}
+
+// The range search (crh_range.hpp): the same filter for every query, <= batch_q queries per batch in caller order, each batch
+// with its own thresholds; counts_dev: the totals' device buffer, or nullptr for the list alone
+int search_range_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const float *thresholds, const FilterKey &key,
+                     int64_t row_base, float *out_scores, int64_t *out_rows, unsigned long long *counts_dev, int out_on_device, void *stream)
+{
+    return search_batches(h, nq, queries, queries_on_device, k, key, false, row_base, out_scores, out_rows, out_on_device, stream,
+                          [&](Pending &p, int q0, int left, hipStream_t) {
+                              p.nq = std::min(h->batch_q, left);
+                              p.range = true;
+                              for (int i = 0; i < p.nq; ++i) p.thr.v[i] = thresholds[q0 + i];
+                              p.counts = counts_dev ? counts_dev + q0 : nullptr;
                               return (int)CRH_OK;
                           });
 }
@@ -1251,6 +1331,7 @@ int crh_index_destroy(crh_index *h)
     dev_free(h->stage_q);
     dev_free(h->stage_os);
     dev_free(h->stage_or);
+    dev_free(h->stage_cnt);
     if (h->stage_in) (void)hipFree(h->stage_in);
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     delete h;
@@ -1893,6 +1974,41 @@ int crh_search_multi(crh_index *h, int nq, const float *queries, int queries_on_
         if (query_class[i] < 0 || query_class[i] >= n_classes)
             return fail(CRH_E_INVALID, "query_class[%d]=%d outside 0..%d", i, query_class[i], n_classes - 1);
     return search_multi_key(h, nq, queries, queries_on_device, k, ckey, query_class, row_base, out_scores, out_rows, out_on_device, stream);
+}
+
+int crh_search_range(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const float *thresholds_host,
+                     const crh_condition *conds, int n_conds, int64_t row_base, float *out_scores, int64_t *out_rows, int64_t *out_counts,
+                     int out_on_device, void *stream)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (nq < 0) return fail(CRH_E_INVALID, "nq < 0");
+    if (k <= 0 || k > CRH_MAX_K) return fail(CRH_E_INVALID, "k=%d outside 1..%d", k, CRH_MAX_K);
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    if (nq == 0) return CRH_OK;
+    if (!queries || !out_scores || !out_rows) return fail(CRH_E_INVALID, "NULL query or output pointer");
+    if (!thresholds_host) return fail(CRH_E_INVALID, "thresholds_host is NULL");
+    for (int i = 0; i < nq; ++i)
+        if (!std::isfinite(thresholds_host[i])) return fail(CRH_E_INVALID, "thresholds_host[%d]=%g is not a finite number", i, (double)thresholds_host[i]);
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(out_counts);
+    if (out_counts && !out_on_device) {
+        DeviceGuard g(h->device);
+        if (h->stage_cnt_elems < nq) {
+            dev_free(h->stage_cnt);
+            h->stage_cnt_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_cnt, nq));
+            h->stage_cnt_elems = nq;
+        }
+        cnt = h->stage_cnt;
+    }
+    CRH_TRY(search_range_key(h, nq, queries, queries_on_device, k, thresholds_host, key, row_base, out_scores, out_rows, cnt, out_on_device, stream));
+    if (out_counts && !out_on_device) {   // (host outputs: the batches are finished, the totals final)
+        DeviceGuard g(h->device);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        CRH_HIP(hipMemcpyAsync(out_counts, h->stage_cnt, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+        CRH_HIP(hipStreamSynchronize(st));
+    }
+    return CRH_OK;
 }
 
 int crh_index_set_sparse_route(crh_index *h, int enable, int max_fraction_den)

@@ -46,6 +46,7 @@ EXPORTS = (
     "crh_search_multi",
     "crh_fuse_select",
     "crh_recommend_query", "crh_recommend_select",
+    "crh_search_range",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -165,6 +166,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_index_match_rows.argtypes = [vp, C.POINTER(Filter), i32, i64, vp, C.POINTER(i64)]
     L.crh_search_cond.argtypes = [vp, i32, vp, i32, i32, C.POINTER(Condition), i32, i64, vp, vp, i32, vp]
     L.crh_search_multi.argtypes = [vp, i32, vp, i32, i32, C.POINTER(Condition), vp, i32, vp, i64, vp, vp, i32, vp]
+    L.crh_search_range.argtypes = [vp, i32, vp, i32, i32, vp, C.POINTER(Condition), i32, i64, vp, vp, vp, i32, vp]
     L.crh_index_match_rows_cond.argtypes = [vp, C.POINTER(Condition), i32, i64, vp, C.POINTER(i64)]
     L.crh_index_tombstone_cond.argtypes = [vp, C.POINTER(Condition), i32, C.POINTER(i64)]
     L.crh_index_set_sparse_route.argtypes = [vp, i32, i32]
@@ -331,6 +333,17 @@ def debug_i8_intervals(handle, rows: int, dim: int, queries, k: int, filters=Non
                                    ("hi_rec", "hi", "lo", "srow", "qpar", "dn", "c_abs", "tau"))), L)
     out["dn"], out["c_abs"] = np.float32(out["dn"][0]), np.float32(out["c_abs"][0])
     return out
+
+
+def range_thresholds(thresholds, nq: int) -> np.ndarray:
+    """The thresholds of a range search as float32 ``[nq]``: a scalar stands for every query; NaN and infinities are refused."""
+    thr = np.asarray(thresholds, dtype=np.float32)
+    thr = np.full((nq,), thr, np.float32) if thr.ndim == 0 else np.ascontiguousarray(thr.reshape(-1))
+    if thr.shape[0] != nq:
+        raise NativeError(E_INVALID, f"{thr.shape[0]} thresholds for {nq} queries")
+    if not np.isfinite(thr).all():
+        raise NativeError(E_INVALID, "a score threshold must be a finite number")
+    return thr
 
 
 def _has_sets(filters) -> bool:
@@ -739,6 +752,46 @@ class Index:
         check(lib().crh_search_multi(self._handle(), int(queries.shape[0]), _ptr(queries), _is_dev(queries), k, carr, off.ctypes.data, len(classes),
                                      qclass.ctypes.data, row_base, _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
         del keep
+
+    def search_range(self, queries, k: int, thresholds, filters=None, row_base: int = 0, counts: bool = True, out_scores=None, out_rows=None,
+                     out_counts=None, stream: int = 0):
+        """:meth:`search` with a score threshold per query (``crh_search_range``): ``thresholds`` is a scalar or ``[nq]``, finite.
+        A row is IN RANGE iff it is alive, passes ``filters`` and its score is ``>=`` the query's threshold as f32 values
+        (inclusive).  Returns ``(scores, rows, counts)``: the exact top-``k`` cut after its last in-range entry, padded with
+        ``(-inf, -1)``, and -- with ``counts`` -- int64 ``[nq]``, the number of in-range rows however many there are (not clipped
+        at ``k``); ``counts=False`` is the list-only mode and returns ``None`` there.  With ``out_*`` CUDA tensors (``out_counts``
+        as well when counts are wanted) the call is asynchronous: finish with :meth:`search_finish`."""
+        queries = _typed(queries, "float32", "queries")
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = int(queries.shape[0])
+        if nq and int(queries.shape[1]) != self.dim:
+            raise NativeError(E_INVALID, f"query dim {queries.shape[1]} != index dim {self.dim}")
+        if not 0 < k <= MAX_K:
+            raise NativeError(E_INVALID, f"k={k} outside 1..{MAX_K}")
+        thr = range_thresholds(thresholds, nq)
+        if out_scores is None:
+            if out_rows is not None or out_counts is not None:
+                raise NativeError(E_INVALID, "out_rows / out_counts without out_scores")
+            out_scores = np.empty((nq, k), dtype=np.float32)
+            out_rows = np.empty((nq, k), dtype=np.int64)
+            out_counts = np.empty((nq,), dtype=np.int64) if counts else None
+        else:
+            _out(out_scores, "float32", "out_scores", (nq, k))
+            _out(out_rows, "int64", "out_rows", (nq, k))
+            if counts:
+                if out_counts is None:
+                    raise NativeError(E_INVALID, "counts are wanted: out_counts must be given with out_scores / out_rows")
+                _out(out_counts, "int64", "out_counts", (nq,))
+            elif out_counts is not None:
+                raise NativeError(E_INVALID, "out_counts given with counts=False")
+            if _is_dev(out_scores) != _is_dev(out_rows) or (counts and _is_dev(out_counts) != _is_dev(out_scores)):
+                raise NativeError(E_INVALID, "out_scores, out_rows and out_counts must live in the same memory space")
+        carr, nc, keep = _conditions(filters)
+        check(lib().crh_search_range(self._handle(), nq, _ptr(queries), _is_dev(queries), k, thr.ctypes.data, carr, nc, row_base,
+                                     _ptr(out_scores), _ptr(out_rows), _ptr(out_counts) if counts else None, _is_dev(out_scores), stream))
+        del keep
+        return out_scores, out_rows, (out_counts if counts else None)
 
     def search_finish(self, stream: int = 0) -> None:
         check(lib().crh_search_finish(self._handle(), stream))

@@ -344,12 +344,15 @@ class VectorSearcher:
         self.embedder = embedder
 
     async def _run(self, collection: str, query: str, limit: int, filters: dict | None, stage: str, what: str,
-                   diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None):
+                   diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
+                   min_score: float | None = None):
         try:
             vector = await self.embedder.embed(query)
             extra = _only_set_given(diversity=diversity, candidates=candidates)      # (absent unless asked for: the reference's call shape)
             if max_per_file is not None:                                             # (the store's exact per-file cap)
                 extra.update(group_by="file_path", group_size=max_per_file)
+            if min_score is not None:                                                # (the store's score threshold)
+                extra.update(score_threshold=min_score)
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, filters=filters, **extra)
         except Exception as e:
             logger.error(f"{what} search failed: {e}")
@@ -357,19 +360,23 @@ class VectorSearcher:
 
     async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
                           project_name: str | list[str] | None = None, *, diversity: float | None = None,
-                          candidates: int | None = None, max_per_file: int | None = None) -> list[CodeSearchResult]:
+                          candidates: int | None = None, max_per_file: int | None = None,
+                          min_score: float | None = None) -> list[CodeSearchResult]:
         """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant).
         ``diversity`` / ``candidates`` (not in the reference): the store's diversity-aware top-k, forwarded only when given;
-        ``max_per_file`` likewise: at most that many chunks of one file among the ``limit`` results (the store's grouped search)."""
+        ``max_per_file`` likewise: at most that many chunks of one file among the ``limit`` results (the store's grouped search);
+        ``min_score`` likewise: only results whose score is at least that (the store's ``score_threshold``), possibly fewer
+        than ``limit``."""
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
                                _only_set(language=language, entity_type=entity_type, project_name=project_name),
-                               "code_search", "Code", diversity, candidates, max_per_file)
+                               "code_search", "Code", diversity, candidates, max_per_file, min_score)
         return self._format_code_results(hits)
 
     async def search_summaries(self, query: str, limit: int = 10, entity_type: str | None = None, *, diversity: float | None = None,
-                               candidates: int | None = None, max_per_file: int | None = None) -> list[SummarySearchResult]:
+                               candidates: int | None = None, max_per_file: int | None = None,
+                               min_score: float | None = None) -> list[SummarySearchResult]:
         hits = await self._run(CollectionName.SUMMARIES.value, query, limit, _only_set(entity_type=entity_type),
-                               "summary_search", "Summaries", diversity, candidates, max_per_file)
+                               "summary_search", "Summaries", diversity, candidates, max_per_file, min_score)
         return self._format_summary_results(hits)
 
     @staticmethod

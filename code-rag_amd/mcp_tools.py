@@ -30,7 +30,8 @@ class SearchResult:
 def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
     async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
                               candidates: int | None = None, max_per_file: int | None = None, extra_queries: list[str] | None = None,
-                              fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None) -> ToolResult:
+                              fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None,
+                              min_score: float | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -42,14 +43,17 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                           score=h.get("score"), summary=h.get("summary"))) for h in hits]
                 return ToolResult(success=True, data=data, message=f"Found {len(data)} matches like {len(like_ids)} example(s).")
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
-                                       ("extra_queries", extra_queries or None), ("fusion", fusion)) if v is not None}   # (only when asked for)
+                                       ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
                 get = h.get if isinstance(h, dict) else (lambda k, _h=h: getattr(_h, k, None))
                 rows.append(SearchResult(qualified_name=get("entity_name"), entity_type=get("entity_type"),
                                          file_path=get("file_path"), score=get("score"), summary=get("summary")))
-            return ToolResult(success=True, data=[vars(r) for r in rows], message=f"Found {len(rows)} matches for '{query}'.")
+            message = f"Found {len(rows)} matches for '{query}'."
+            if min_score is not None and len(rows) < limit:   # (a thresholded list shorter than `limit` holds EVERY row in range)
+                message = f"Found {len(rows)} matches for '{query}': only {len(rows)} rows score at least {min_score}."
+            return ToolResult(success=True, data=[vars(r) for r in rows], message=message)
         except Exception as e:  # the reference's catch-all (tools.py:431-436)
             logger.error(f"[Tool:SemanticSearch] Error: {e}", exc_info=True)
             return ToolResult(success=False, error=str(e))
@@ -73,6 +77,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                                               "wordings are fused into one list", "required": False},
             "fusion": {"type": "string", "description": "With extra_queries: 'rrf' (reciprocal-rank fusion, the default) or 'max' "
                                                         "(best match over the wordings)", "required": False},
+            "min_score": {"type": "number", "description": "Only results whose similarity score is at least this; fewer than `limit` "
+                                                           "(or none) come back when nothing else is that relevant", "required": False},
             "like_ids": {"type": "array", "description": "Ids of results to find more of (up to 8): the answer is built from these "
                                                          "stored examples instead of the query text", "required": False},
             "unlike_ids": {"type": "array", "description": "With like_ids: ids of results to steer away from (up to 8)", "required": False},

@@ -353,6 +353,78 @@ class ShardSet:
         ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
         return out_s, out_r
 
+    # ------------------------------------------------------------------ score threshold and in-range counts
+    def complete_counts(self, counts) -> None:
+        """In-range counts of a range search: every rank summed its own shards; ONE all-reduce(sum) of the ``[nq]`` int64 vector
+        completes them.  Like :meth:`complete_vectors` it has never run on more than one RCCL rank: the two-rank form is
+        exercised with gloo on host tensors only."""
+        if self.dist is not None:
+            self.dist.all_reduce(counts, op=self.dist.ReduceOp.SUM, group=self.group)
+
+    def search_range_device(self, queries, k: int, thresholds, dfilt, counts: bool = True):
+        """The range search on the device, results left there: every shard runs ``crh_search_range`` with ``row_base`` =
+        shard * STRIDE, the lists merge as in :meth:`search_device` (a shard's cut list is padded, and padding merges as it does
+        there: the merged list is the first ``min(k, count)`` in-range rows of the whole collection), the counts are summed over
+        the local shards and, under backend "dist", completed by :meth:`complete_counts`.  Returns CUDA tensors ``(scores f32
+        [nq, k], GLOBAL rows i64 [nq, k], counts i64 [nq] or None)``."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ffi.use_device(self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        qd = queries if torch.is_tensor(queries) else torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
+        nq = int(qd.shape[0])
+        thr = ffi.range_thresholds(thresholds, nq)
+        local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, dev)
+        part = torch.zeros((len(self.owned), nq), dtype=torch.int64, device=dev) if counts else None
+        for i, s in enumerate(self.owned):           # every local shard writes its own record of the "gathered" buffer
+            on = self.dist is None
+            self.index[s].search_range(qd, k, thr, filters=dfilt, row_base=s * STRIDE, counts=counts, out_scores=all_s[s] if on else loc_s,
+                                       out_rows=all_r[s] if on else loc_r, out_counts=part[i] if counts else None, stream=stream)
+        for s in self.owned:
+            self.index[s].search_finish(stream)
+        if self.dist is not None:
+            self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
+        total = None
+        if counts:
+            total = part.sum(0)
+            self.complete_counts(total)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
+        return out_s, out_r, total
+
+    def search_range(self, queries: np.ndarray, k: int, thresholds, dfilt, counts: bool = True):
+        """:meth:`search` with a score threshold per query: ``(scores [nq, k], shard [nq, k], local row [nq, k], counts int64
+        [nq] or None)``; -1 rows are padding.  One native shard answers directly; several take :meth:`search_range_device`;
+        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
+        nq = int(np.asarray(queries).shape[0]) if not hasattr(queries, "is_cuda") else int(queries.shape[0])
+        thr = ffi.range_thresholds(thresholds, nq)
+        if self.ns == 1:
+            s, r, c = self.index[0].search_range(queries, k, thr, filters=dfilt, counts=counts, **({"stream": self.stream} if self.stream else {}))
+            return s, np.zeros(r.shape, np.int32), r, c
+        if self._merge_host is None:
+            sd, rd, cd = self.search_range_device(queries, k, thr, dfilt, counts)
+            scores, rows, total = sd.cpu().numpy(), rd.cpu().numpy(), (cd.cpu().numpy() if counts else None)
+        else:
+            mine = {s: ix.search_range(queries, k, thr, filters=dfilt, row_base=s * STRIDE, counts=counts) for s, ix in self.index.items()}
+            total = sum(np.asarray(m[2], np.int64) for m in mine.values()) if counts else None
+            if self.dist is None:
+                ss = np.stack([mine[s][0] for s in range(self.ns)])
+                rr = np.stack([mine[s][1] for s in range(self.ns)])
+            else:                                        # the list records travel as in _search_host, the counts in one all-reduce
+                import torch
+                local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, torch.device("cpu"))
+                loc_s.copy_(torch.from_numpy(np.ascontiguousarray(mine[self.rank][0])))
+                loc_r.copy_(torch.from_numpy(np.ascontiguousarray(mine[self.rank][1])))
+                self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
+                ss, rr = all_s.numpy(), all_r.numpy()
+                if counts:
+                    t = torch.from_numpy(np.ascontiguousarray(total, dtype=np.int64))
+                    self.complete_counts(t)
+                    total = t.numpy()
+            scores, rows = self._merge_host(ss, rr)
+        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1), total
+
     def complete_columns(self, packed) -> None:
         """Side columns of a merged candidate table: every rank gathered the rows it owns (zeros elsewhere); ONE all-reduce of
         the packed buffer completes them (``sharded.ShardedIndex.gather_columns``).  Local shards are summed by the caller."""

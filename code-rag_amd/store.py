@@ -384,6 +384,12 @@ class _Collection:
         scores, shard, local = self.shards.search(queries, limit, dfilt)
         return scores, self.slots_of(shard, local)
 
+    def search_range(self, queries: np.ndarray, limit: int, thresholds, dfilt, counts: bool = True):
+        """The same under a score threshold per query (``ShardSet.search_range``): the lists cut after their last in-range hit,
+        and ``counts`` int64 [nq] -- how many rows are in range, however many -- or None."""
+        scores, shard, local, totals = self.shards.search_range(queries, limit, thresholds, dfilt, counts)
+        return scores, self.slots_of(shard, local), totals
+
     def search_multi(self, queries: np.ndarray, limit: int, class_dfilts, query_class) -> tuple[np.ndarray, np.ndarray]:
         """The same for a batch whose queries carry different filters: query ``i`` under ``class_dfilts[query_class[i]]``."""
         scores, shard, local = self.shards.search_multi(queries, limit, class_dfilts, query_class)
@@ -1070,6 +1076,89 @@ class HipVectorStore:
         return out
 
     @staticmethod
+    def _range_args(score_threshold, nq: int, **others) -> np.ndarray:
+        """Checked thresholds of one thresholded call, float32 [nq] (a scalar stands for every query).  ``others``: the arguments
+        a score threshold cannot be combined with in this version, by name; any that is set raises.  ``ValueError`` for the
+        caller alone, before anything is searched."""
+        used = [name for name, v in others.items() if v]
+        if used:
+            raise ValueError(f"score_threshold cannot be combined with {', '.join(used)} (a follow-up: those select from finished "
+                             "top-c lists, the threshold works at the scan)")
+        try:
+            thr = np.asarray(score_threshold, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"score_threshold {score_threshold!r} is not a number or one number per query") from None
+        thr = np.full((nq,), thr, np.float32) if thr.ndim == 0 else thr.reshape(-1)
+        if thr.shape[0] != nq:
+            raise ValueError(f"{thr.shape[0]} score thresholds for {nq} queries")
+        if not np.isfinite(thr).all():
+            raise ValueError("score_threshold must be a finite number")
+        return thr
+
+    def _search_range_sync(self, collection: str, queries: np.ndarray, limit: int, thresholds: np.ndarray, filters, must_not,
+                           counts: bool) -> tuple[list[list[dict[str, Any]]], list[int] | None]:
+        """One thresholded pass + the hit dictionaries of every query, built inside the worker job as in
+        :meth:`_search_hits_sync`: ``(hits per query, in-range count per query or None)``.  ``limit`` 0 asks for the counts
+        alone (the device still selects one row per query: its k is at least 1)."""
+        col = self._col(collection)
+        nq = queries.shape[0]
+        dfilt = col.device_filters(filters, must_not)
+        if dfilt is None or nq == 0 or (limit <= 0 and not counts):       # (a value the collection never stored: nothing is in range)
+            return [[] for _ in range(nq)], ([0] * nq if counts else None)
+        scores, slots, totals = col.search_range(queries, max(int(limit), 1), thresholds, dfilt, counts)
+        keep = (slots >= 0) & (np.arange(slots.shape[1])[None, :] < limit)
+        flat = col.hits(slots[keep].tolist(), scores[keep].tolist())       # (payloads fetched together)
+        out, at = [], 0
+        for n in keep.sum(1).tolist():
+            out.append(flat[at:at + n])
+            at += n
+        return out, ([int(c) for c in totals] if counts else None)
+
+    async def _range_call(self, collection: str, query_vectors, score_threshold, limit: int, filters, must_not, counts: bool, **others):
+        """The common path of every thresholded entry point: argument checks for the caller alone, then a pass of its own --
+        thresholded calls never join the coalescer (their pass differs from a plain one: the threshold moves the scan's cut)."""
+        q = np.asarray(query_vectors, dtype=np.float32)
+        dim = self._col(collection).shards.dim
+        if q.ndim != 2 or (q.shape[0] and q.shape[1] != dim):
+            raise ValueError(f"query dim {q.shape[-1] if q.ndim else 0} != index dim {dim}")
+        if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+            others["per-query filters"] = True
+        thr = self._range_args(score_threshold, q.shape[0], **others)
+        if limit > ffi.MAX_K:
+            raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
+        self.search_passes += (q.shape[0] + 63) // 64
+        return await self._run(self._search_range_sync, collection, q, int(limit), thr, filters, must_not, counts)
+
+    async def search_range_batch(self, collection: str, query_vectors, score_threshold, limit: int = 10,
+                                 filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+        """Batched :meth:`search_range`: ``score_threshold`` is one number or one per query; one ``{"hits", "count"}`` per query."""
+        try:
+            hits, totals = await self._range_call(collection, query_vectors, score_threshold, limit, filters, must_not, True)
+            return [{"hits": h, "count": c} for h, c in zip(hits, totals)]
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_range(self, collection: str, query_vector: list[float], score_threshold: float, limit: int = 10,
+                           filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> dict[str, Any]:
+        """The hits whose cosine is at least ``score_threshold`` (Qdrant's ``query_points(score_threshold=...)``) AND how many
+        such points there are: ``{"hits": [...], "count": int}``.  A point is in range iff it is alive, passes the filter and
+        its score -- the f32 value :meth:`search` reports -- is ``>= score_threshold`` (inclusive).  ``hits`` are the first
+        ``min(limit, count)`` of them in :meth:`search`'s order; ``count`` is exact and not clipped at ``limit`` or at the
+        index's maximum k: "is the top-``limit`` the whole story or the tip of it".  A very low threshold makes
+        every in-range row a candidate on the device; one beyond the candidate workspace's budget fails with the count it met,
+        it never returns a clipped number."""
+        return (await self.search_range_batch(collection, [query_vector], score_threshold, limit, filters, must_not))[0]
+
+    async def count_similar(self, collection: str, query_vector: list[float], score_threshold: float,
+                            filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> int:
+        """How many points are at least ``score_threshold`` similar to ``query_vector`` (:meth:`search_range`'s ``count``
+        without the hits): clone pressure before a refactor, "a one-off or a pattern"."""
+        try:
+            return (await self._range_call(collection, [query_vector], score_threshold, 0, filters, must_not, True))[1][0]
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    @staticmethod
     def _mmr_args(limit: int, diversity: float | None, candidates: int | None) -> tuple[float | None, int | None]:
         """Checked ``(diversity, candidates)`` of one call -- ``(None, None)`` for a plain search.  ``candidates`` defaults to
         ``min(MAX_K, 4 * limit)``.  Raises ``ValueError`` for the caller alone, before the call joins any pass."""
@@ -1111,7 +1200,7 @@ class HipVectorStore:
     async def search(self, collection: str, query_vector: list[float] | None, limit: int = 10,
                      filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
                      diversity: float | None = None, candidates: int | None = None,
-                     group_by: str | None = None, group_size: int = 1) -> list[dict[str, Any]]:
+                     group_by: str | None = None, group_size: int = 1, score_threshold: float | None = None) -> list[dict[str, Any]]:
         """client.py:132-157: descending cosine, ``[{"id", "score", "payload"}]``.  ``query_vector=None`` is the
         filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0.
         A ``filters`` value may be a list / tuple / set (any of them: Qdrant's ``MatchAny``); ``must_not`` (not in the
@@ -1126,8 +1215,17 @@ class HipVectorStore:
         answer is EXACTLY the first ``limit`` rows of the plain order whose rank among the rows of their own value is below
         ``group_size``, still sorted by score, scores and ids unchanged.  Rows without the key (or with None)
         are never capped.  ``candidates`` (default ``min(MAX_K, 4 * limit)``) is how many hits the first round looks at; the
-        store goes on by itself when that does not settle the answer.  Not combinable with ``diversity``."""
+        store goes on by itself when that does not settle the answer.  Not combinable with ``diversity``.
+        ``score_threshold`` (Qdrant's parameter of that name; the reference never sends it): only hits whose score is ``>=`` it
+        are returned -- possibly fewer than ``limit``, possibly none.  Exactly the plain list cut after its last such hit
+        (DESIGN.md 3.18; :meth:`search_range` also says how many there are).  Not combinable with ``diversity`` or ``group_by``;
+        a thresholded call takes a pass of its own."""
         try:
+            if score_threshold is not None:
+                if query_vector is None:
+                    raise ValueError("score_threshold needs a query vector (the filter-only fetch has no scores)")
+                return (await self._range_call(collection, [query_vector], score_threshold, limit, filters, must_not, False,
+                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None))[0][0]
             group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates, query_vector is not None)
             if query_vector is not None and group is None:
                 diversity, candidates = self._mmr_args(limit, diversity, candidates)
@@ -1232,15 +1330,19 @@ class HipVectorStore:
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
                            filters=None, must_not=None, *,
                            diversity: float | None = None, candidates: int | None = None,
-                           group_by: str | None = None, group_size: int = 1) -> list[list[dict[str, Any]]]:
+                           group_by: str | None = None, group_size: int = 1, score_threshold=None) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
         serves up to 64 queries.  ``diversity`` / ``candidates`` / ``group_by`` / ``group_size`` as in :meth:`search`.
         ``filters`` and ``must_not`` may each be a dict for the whole batch, as in :meth:`search`, or a SEQUENCE with one dict
         (or None) per query: every query is then answered under its own filter, exactly as a lone :meth:`search` with that
         filter would answer it, and up to 8 distinct filters share each 64-query pass.  A filter naming a
         value the collection never stored yields an empty list for its own queries only.  Per-query filters cannot be combined
-        with ``diversity`` or ``group_by`` (``ValueError``; a follow-up)."""
+        with ``diversity`` or ``group_by`` (``ValueError``; a follow-up).  ``score_threshold`` as in :meth:`search`, one number or
+        one per query; not combinable with ``diversity``, ``group_by`` or per-query filters."""
         try:
+            if score_threshold is not None:
+                return (await self._range_call(collection, query_vectors, score_threshold, limit, filters, must_not, False,
+                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None))[0]
             if (isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple))) and (diversity is not None or group_by is not None):
                 raise ValueError("per-query filters cannot be combined with diversity or group_by")
             group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates)
@@ -1310,15 +1412,19 @@ class HipVectorStore:
 
     async def search_fused_batch(self, collection: str, query_vector_sets, limit: int = 10,
                                  filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                                 fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None) -> list[list[dict[str, Any]]]:
+                                 fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None,
+                                 score_threshold=None) -> list[list[dict[str, Any]]]:
         """Batched :meth:`search_fused`: ``query_vector_sets`` is a list of sets of query vectors, one set per logical query;
         the sets may differ in size (a shorter one fuses its own lists only, and ``weights`` / the default ``candidates`` go by
         the largest).  All sub-queries of the batch share corpus passes of 64, under ONE filter.  The batch is searched as
         ``len(sets) * m`` queries with ``m`` the largest set: the absent members of shorter sets are searched as zero vectors
         and their lists discarded -- wasted slots of the pass, so sets of very different sizes are better sent apart.
         ``search_passes`` counts ``ceil(len(sets) * m / 64)`` for every call that passes its argument checks, also when the
-        filter names a value the collection never stored and nothing is searched."""
+        filter names a value the collection never stored and nothing is searched.  ``score_threshold`` is accepted to be
+        refused: a fused score is not a cosine, and a threshold on the sub-queries' lists is a follow-up (``ValueError``)."""
         try:
+            if score_threshold is not None:
+                self._range_args(score_threshold, 1, fusion=True)
             q, live, method, rrf_k, weights, candidates = self._fused_args(collection, list(query_vector_sets), limit, fusion, rrf_k, weights, candidates)
             self.search_passes += (q.shape[0] * q.shape[1] + 63) // 64
             return await self._run(self._search_fused_sync, collection, q, live, int(limit), filters, must_not, method, rrf_k, weights, candidates)
@@ -1327,7 +1433,8 @@ class HipVectorStore:
 
     async def search_fused(self, collection: str, query_vectors, limit: int = 10,
                            filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                           fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None) -> list[dict[str, Any]]:
+                           fusion: str = "rrf", rrf_k: int = 60, weights=None, candidates: int | None = None,
+                           score_threshold=None) -> list[dict[str, Any]]:
         """ONE logical query asked in ``m`` ways (``query_vectors`` [m, dim], m <= 16: the original text and its reformulations,
         a HyDE answer, ...): every vector's ``candidates`` best hits, fused on the device into one list of ``limit`` (DESIGN.md
         3.16; Qdrant's ``prefetch=[...]`` + ``FusionQuery``; not in the reference, whose engine searches the original text only).
@@ -1339,7 +1446,7 @@ class HipVectorStore:
         MAX_K``) is the depth of every list.  ``filters`` / ``must_not`` as in :meth:`search`, one filter for all ``m`` vectors.
         A fused call takes a pass of its own (it never joins the coalescer)."""
         return (await self.search_fused_batch(collection, [query_vectors], limit, filters, must_not, fusion=fusion, rrf_k=rrf_k,
-                                              weights=weights, candidates=candidates))[0]
+                                              weights=weights, candidates=candidates, score_threshold=score_threshold))[0]
 
     def _recommend_args(self, collection: str, sets, limit: int, strategy, candidates: int | None):
         """Checked ``(positive ids, negative ids, P, N, strategy, candidates)`` of one recommend call; raises ``ValueError`` for

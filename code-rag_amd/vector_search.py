@@ -70,6 +70,11 @@ def _group_kwargs(max_per_file: int | None) -> dict:
     return {} if max_per_file is None else {"group_by": "file_path", "group_size": max_per_file}
 
 
+def _threshold_kwargs(min_score: float | None) -> dict:
+    """``min_score`` as the store's ``score_threshold`` -- only when given: without it the call is the one issued before."""
+    return {} if min_score is None else {"score_threshold": min_score}
+
+
 def _project(hit: dict, keys: tuple[str, ...]) -> dict:
     payload = hit["payload"]
     row = {"score": hit["score"]}
@@ -100,13 +105,18 @@ class VectorSearcher:
 
     async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
                       must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None,
-                      max_per_file: int | None = None, extra_queries: list[str] | None = None, fusion: str = "rrf"):
+                      max_per_file: int | None = None, extra_queries: list[str] | None = None, fusion: str = "rrf",
+                      min_score: float | None = None):
         """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
         the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given, and
         so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k).  ``extra_queries`` (reformulations of
         ``text``): all texts are embedded in ONE provider batch and the store fuses their hit lists
-        (``HipVectorStore.search_fused``); without them the call is the plain one, keyword for keyword."""
+        (``HipVectorStore.search_fused``); without them the call is the plain one, keyword for keyword.  ``min_score``: the
+        store's ``score_threshold`` -- only hits at least that similar come back; not together with ``extra_queries`` (a fused
+        score is no cosine), ``diversity`` or ``max_per_file`` (the store refuses those)."""
         extra = [t for t in (extra_queries or []) if t and t.strip()]
+        if extra and min_score is not None:
+            raise ValueError("min_score cannot be combined with extra_queries")
         if extra and (diversity is not None or max_per_file is not None):
             raise ValueError("extra_queries cannot be combined with diversity or max_per_file")
         try:
@@ -124,6 +134,7 @@ class VectorSearcher:
             vector = await self.embedder.embed(text)
             kwargs.update(_mmr_kwargs(diversity, candidates))
             kwargs.update(_group_kwargs(max_per_file))
+            kwargs.update(_threshold_kwargs(min_score))
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, **kwargs)
         except EmbeddingError as e:
             logger.error(f"Embedding error: {e}")
@@ -135,7 +146,7 @@ class VectorSearcher:
     async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                           entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                           diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                          extra_queries: list[str] | None = None, fusion: str = "rrf") -> list[dict]:
+                          extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
         ``diversity`` in [0, 1] (not in the reference): ``limit`` maximal-marginal-relevance picks among the ``candidates``
         best hits instead of the plain top-``limit`` (``HipVectorStore.search``).  ``max_per_file`` (the reference applies it
@@ -144,34 +155,38 @@ class VectorSearcher:
         ``extra_queries`` (not in the reference, whose engine searches the original text only, query/engine.py:315-346):
         reformulations of ``query`` -- the planner's sub-queries, a HyDE answer -- embedded with it in one batch; the store
         fuses the hit lists of all of them (``fusion`` = "rrf" or "max", ``HipVectorStore.search_fused``), ``score`` is the fused
-        score and every result also carries ``cosine`` and ``matched``.  Not together with ``diversity`` / ``max_per_file``."""
+        score and every result also carries ``cosine`` and ``matched``.  Not together with ``diversity`` / ``max_per_file``.
+        ``min_score`` (Qdrant's ``score_threshold``; the reference never sends it): only results whose score is at least that --
+        possibly fewer than ``limit``, possibly none ("nothing here is relevant"); a list shorter than ``limit`` is ALL of them.
+        Not together with ``diversity`` / ``max_per_file`` / ``extra_queries``."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion)
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score)
         return [_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                               extra_queries: list[str] | None = None, fusion: str = "rrf") -> list[dict]:
+                               extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
-        ``extra_queries`` / ``fusion`` as in :meth:`search_code`."""
+        ``extra_queries`` / ``fusion`` / ``min_score`` as in :meth:`search_code`."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion)
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score)
         return [_project(h, _SUMMARY_KEYS + _fused_keys(h)) for h in hits]
 
     async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
                                 exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,
-                                max_per_file: int | None = None) -> list[dict]:
+                                max_per_file: int | None = None, min_score: float | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
-        excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``."""
+        excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
+        ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
         on_device = bool(exact_exclude and exclude_file)
@@ -179,7 +194,7 @@ class VectorSearcher:
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch, _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file)
+                                  max_per_file=max_per_file, min_score=min_score)
         kept = []
         for h in hits:
             if exclude_file and h["payload"].get("file_path") == exclude_file:
@@ -218,12 +233,13 @@ class VectorSearcher:
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                                 diversity: float | None = None, candidates: int | None = None,
                                 max_per_file: int | None = None,
-                                filters_per_query: list[dict | None] | None = None) -> list[list[dict]]:
+                                filters_per_query: list[dict | None] | None = None, min_score=None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``filters_per_query``: one filter dict (keys ``language`` / ``entity_type`` / ``project_name``; None = no filter) per
         query -- every query is answered under its own, and the batch still shares corpus passes (up to 8 distinct filters per
         64 queries).  Mutually exclusive with the scalar ``language`` / ``entity_type`` / ``project_name``, where a list already
-        means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet."""
+        means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet.  ``min_score``: one number or one per query, as in
+        :meth:`search_code`; not together with ``filters_per_query`` either."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         if filters_per_query is not None:
             if filters:
@@ -241,7 +257,7 @@ class VectorSearcher:
                 vectors = np.asarray(await self.embedder.embed_batch(texts), dtype=np.float32)
             per_query = await self.qdrant.search_batch(collection=CollectionName.CODE_CHUNKS.value, query_vectors=vectors,
                                                        limit=limit, filters=filters or None, **_mmr_kwargs(diversity, candidates),
-                                                       **_group_kwargs(max_per_file))
+                                                       **_group_kwargs(max_per_file), **_threshold_kwargs(min_score))
         except EmbeddingError as e:
             raise QueryError("Failed to embed search query", cause=e)
         except VectorStoreError as e:

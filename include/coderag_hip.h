@@ -216,6 +216,33 @@ int crh_search_multi(crh_index *h, int nq, const float *queries, int queries_on_
                      const int32_t *query_class, int64_t row_base, float *out_scores, int64_t *out_rows,
                      int out_on_device, void *stream);
 
+/* Score threshold and exact in-range counts.  The reference puts its `limit` hits straight into an LLM prompt however bad they
+ * are (query/vector_search.py:83-110); Qdrant's counterpart is query_points(..., score_threshold=...), which the reference never
+ * sends -- and Qdrant has no count of the points above a score.  The definition is this repository's own and exact (DESIGN.md
+ * 3.18).  With s(q, x) the score crh_search gives row x (canonical f32) and thr = thresholds_host[i], finite:
+ *   IN RANGE  row x is alive, passes the conditions and s(q, x) >= thr as f32 values -- inclusive: a row whose score has
+ *             exactly the threshold's bits is in;
+ *   LIST      the exact top-k of the corpus cut after its last in-range entry (the first min(k, count) in-range rows):
+ *             descending score, ties to the lower row, the tail padded with (-inf, -1);
+ *   COUNT     out_counts[i] = the number of in-range rows, however many: not clipped at k or at CRH_MAX_K.
+ * thresholds_host: host f32 [nq], copied by the call.  out_counts: int64 [nq] in the memory space of the outputs, or NULL for
+ * the list alone -- then a threshold can only RAISE the scan's own nomination threshold: a high one nominates fewer rows than
+ * crh_search_cond, a low one costs nothing extra.  With counts every row at or above thr - margin is listed in the candidate
+ * buffers; they regrow as for any batch, and a threshold so low that one query's candidates exceed the workspace budget ends in
+ * CRH_E_CAPACITY naming that query's candidate count -- never in a wrong or clipped count.
+ * nq may be any count: it is cut into batches of 64 queries (32 at dim 1536) in caller order.  A range batch always runs the
+ * three-launch bf16 scan (over every tile, or over the tile list of a sparse mask), whatever crh_index_set_nomination allows:
+ * the int8 pass, the one-launch scan and the wide scan are not used.  Device outputs and crh_search_finish, row_base, padding,
+ * tie order and crh_search_stats as for crh_search_cond (with counts no tiles are sampled: seed_tiles is 0).  A NaN or infinite
+ * threshold, k outside 1..CRH_MAX_K and bad columns are CRH_E_INVALID with nothing launched.  A threshold above every score, an
+ * empty index and an empty tile list give an all-padding list and count 0. */
+int crh_search_range(crh_index *h, int nq, const float *queries, int queries_on_device, int k,
+                     const float *thresholds_host /* [nq], copied by the call */,
+                     const crh_condition *conds, int n_conds, int64_t row_base,
+                     float *out_scores, int64_t *out_rows,       /* [nq, k] as crh_search_cond */
+                     int64_t *out_counts /* [nq], same memory space as the outputs; NULL: list only */,
+                     int out_on_device, void *stream);
+
 /* (No counterpart in the reference: Qdrant's payload indexes make a filtered query cost about what the matching rows cost,
  * embeddings/client.py:93-113.)  A filtered search of up to 64 queries (32 at dim 1536) whose mask leaves at most one 32-row
  * tile in `max_fraction_den` populated reads only those tiles: their ascending list is made with the mask and kept with it,
