@@ -411,9 +411,10 @@ __global__ __launch_bounds__(64) void k_ln_finalize(const float *__restrict__ pa
 }
 
 // y = bf16(fma(fma(x, rstd, nmr), gamma, beta)): the LayerNorm output itself, from statistics already known -- what the LAST layer
-// of a folded forward needs (the pool reads normalised rows); in place when y == x.  One wave per row, 8-byte accesses.
-__global__ __launch_bounds__(256) void k_ln_apply768(const bf16_t *__restrict__ x, const float *__restrict__ stats, const float *__restrict__ gamma,
-                                                     const float *__restrict__ beta, bf16_t *__restrict__ y, int rows)
+// of a folded forward needs (the pool reads normalised rows); in place when y == x, so neither pointer is __restrict__ (a lane
+// loads its 8 bytes of a chunk before it stores the same 8 bytes; no lane reads what another writes).  One wave per row, 8-byte accesses.
+__global__ __launch_bounds__(256) void k_ln_apply768(const bf16_t *x, const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                     const float *__restrict__ beta, bf16_t *y, int rows)
 {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);

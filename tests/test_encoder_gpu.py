@@ -23,8 +23,10 @@ def _close(torch, got, ref, rel, abs_):
     assert bool((err <= lim).all()), f"max err {err.max().item():.4g} (worst excess {(err - lim).max().item():.4g})"
 
 
-# T >= 3841 rows exercises the per-XCD super-tile order (>= 16 panels), smaller T the linear order; ragged T the row guards
-# everything below a few thousand rows goes to k_gemm_mid (the cost model in crh_encoder.hip), a single row included
+# Random inputs through the DEFAULT path: which kernel a T reaches follows today's cost model (choose_gemm in crh_encoder.hip) and
+# moves whenever a kernel is re-tuned -- tests/test_gemm_matrix_gpu.py is what pins kernels (each one forced, exact cases, tile and
+# short-K edges).  With the constants of this commit (5000, 2304, 768) and (9300, 3072, 768, gelu) run the 256x256 ping-pong kernel
+# and every other shape k_gemm_mid, a single row and (4097, 768, 3072) included; none reaches k_gemm_nt.  Ragged T exercises the row guards.
 @pytest.mark.parametrize("T,N,K,act", [(1, 768, 768, 0), (16, 2304, 768, 0), (9, 3072, 768, 1), (16, 768, 3072, 0), (2, 768, 256, 1), (17, 2304, 768, 0), (64, 3072, 768, 1), (33, 768, 3072, 0), (48, 768, 256, 1), (65, 2304, 768, 0), (200, 3072, 768, 1), (256, 768, 3072, 0), (500, 2304, 768, 0), (513, 768, 768, 0),
                                        (384, 768, 768, 0), (200, 2304, 768, 0), (130, 3072, 768, 1), (256, 768, 3072, 0), (500, 2304, 768, 0), (513, 768, 768, 0),
                                        (5000, 2304, 768, 0), (9300, 3072, 768, 1), (4097, 768, 3072, 0)])
@@ -43,7 +45,9 @@ def test_gemm_bias_act(gpu, T, N, K, act):
     _close(torch, y, ref, rel=2 ** -7, abs_=2e-3)           # one bf16 rounding of the result + f32 accumulation order
 
 
-# k_gemm_mid (64x64 tiles, 4-stage LDS-DMA ring): full and ragged last row tiles, every epilogue
+# Mid-size T with guard rows, full and ragged last row tiles, both activations.  The name is historical: under today's cost model
+# (600, 768, 768), (1000, 2304, 768), (1537 and 4096, 768, 3072) and (577, 128, 256) run k_gemm_mid, (2048, 3072, 768, gelu) and
+# (2049, 3072, 768) run k_gemm_nt, and (4095, 2304, 768, gelu) the ping-pong kernel; tests/test_gemm_matrix_gpu.py pins each kernel.
 @pytest.mark.parametrize("T,N,K,act", [(600, 768, 768, 0), (1000, 2304, 768, 0), (2048, 3072, 768, 1), (1537, 768, 3072, 0), (4096, 768, 3072, 0),
                                        (4095, 2304, 768, 1), (577, 128, 256, 1), (2049, 3072, 768, 0)])
 def test_gemm_mid_shapes(gpu, T, N, K, act):
@@ -107,9 +111,12 @@ def test_gemm256_repeatable(gpu):
 
 @pytest.mark.parametrize("T,N,K,act", [(3000, 768, 3072, 0), (2049, 3072, 768, 1), (64, 768, 3072, 0)])
 def test_gemm_mid_repeatable_and_equal_to_the_other_tiled_kernels(gpu, T, N, K, act):
-    """k_gemm_mid's 4-stage ring is ordered by counted waits and one barrier per step: 30 runs are bit-identical.  And the
-    three tiled kernels add the same products in the same order (one 16x16x32 MFMA chain along K per output block), so
-    k_gemm_nt and the ping-pong kernel (debug variants 0 and 16) give the very same bits where the epilogue is the same (bias only)."""
+    """The rings of the tiled kernels are ordered by counted waits and one barrier per step: 30 runs of the default path are
+    bit-identical (under today's cost model (3000, 768, 3072) and (64, 768, 3072) run k_gemm_mid, (2049, 3072, 768, gelu) runs
+    k_gemm_nt).  And the three tiled kernels add the same products in the same order (one 16x16x32 MFMA chain along K per output
+    block), so k_gemm_nt and the ping-pong kernel (debug variants 0 and 16) give the very same bits as the default path where the
+    epilogue is the same (bias only).  Every other epilogue across the three kernels: test_the_three_kernels_agree_to_the_bit in
+    tests/test_gemm_matrix_gpu.py, which forces the kernel instead of relying on which one a T reaches."""
     torch, ffi, dev = _env()
     g = torch.Generator(device="cpu").manual_seed(T)
     a = torch.randn((T, K), generator=g).to(dev, torch.bfloat16)
@@ -132,8 +139,9 @@ def test_gemm_mid_repeatable_and_equal_to_the_other_tiled_kernels(gpu, T, N, K, 
             assert torch.equal(y.view(torch.int16), outs[0].view(torch.int16)), variant
 
 
+# (6000, 3072): FFN2 inside k_gemm_nt's window of today's cost model (K = 3072: 4865..10240 rows) -- epilogue 2 of that kernel on the default path
 @pytest.mark.parametrize("T,K", [(1, 768), (40, 3072), (64, 768), (129, 3072), (256, 768), (257, 768), (300, 3072), (6000, 768), (22100, 3072), (23040, 768),
-                                 (513, 768), (1000, 3072), (2048, 3072), (4095, 768), (4096, 3072), (16, 3072), (17, 768)])
+                                 (513, 768), (1000, 3072), (2048, 3072), (4095, 768), (4096, 3072), (16, 3072), (17, 768), (6000, 3072)])
 def test_gemm_residual_layernorm(gpu, T, K):
     torch, ffi, dev = _env()
     g = torch.Generator(device="cpu").manual_seed(K)
@@ -153,7 +161,8 @@ def test_gemm_residual_layernorm(gpu, T, K):
 
 
 # ---- LayerNorm folded into the GEMMs around it (round 5; csrc/crh_encoder.hip "LayerNorm folded ...", modeling_roberta.py:329-340,387-398)
-# T picks the kernel: a few rows -> k_gemm_mid, thousands -> k_gemm_nt, tens of thousands -> the 256x256 ping-pong kernel; ragged T the guards
+# T picks the kernel through today's cost model (N = 768, K = 768: k_gemm_mid up to 5440 rows, k_gemm_nt up to 10240, then the ping-pong
+# kernel; the consumer's N = 2304 / 3072 switch far earlier); tests/test_gemm_matrix_gpu.py pins each kernel.  Ragged T: the guards
 @pytest.mark.parametrize("with_stats", [True, False])
 @pytest.mark.parametrize("T,K", [(1, 768), (40, 3072), (257, 768), (1000, 3072), (4095, 768), (6000, 768), (22100, 3072), (23040, 768), (66000, 768)])
 def test_folded_producer_gemm_residual_and_statistics(gpu, T, K, with_stats):
@@ -221,9 +230,12 @@ def test_folded_consumer_gemm_finishes_the_layernorm(gpu, T, N, act):
 
 
 def test_a_rows_folded_results_do_not_depend_on_the_batch_it_sits_in(gpu):
-    """The three tiled kernels build a row's statistics from the same per-lane sums joined the same way: a row's output, its statistics
-    and what the consumer makes of them are bit-identical whether the row is computed among 40 rows (k_gemm_mid), 3 000 (k_gemm_nt)
-    or 30 000 (the ping-pong kernel)."""
+    """A row's output, its statistics and what the consumer makes of them are bit-identical whether the row is computed among 40 rows,
+    3 000 or 30 000.  Under today's cost model the producer (N = 768, K = 768) runs k_gemm_mid at 40 AND at 3 000 rows and the
+    ping-pong kernel at 30 000; the consumer (N = 2304) runs k_gemm_mid, k_gemm_nt and the ping-pong kernel in turn, compared on
+    its first 40 rows.  So this test is about batch size, and compares the producer between two kernels only: that all three
+    build the same bits in every epilogue, statistics included, is test_the_three_kernels_agree_to_the_bit in
+    tests/test_gemm_matrix_gpu.py, where the kernel is forced."""
     torch, ffi, dev = _env()
     g = torch.Generator(device="cpu").manual_seed(5)
     Tbig, K = 30000, 768
