@@ -43,8 +43,9 @@ constexpr int64_t kWorkspaceBudget = 48LL << 30;
 constexpr int kRangeParts = 8;  // workgroups per query in k_range_count (crh_range.hpp)
 constexpr int kSparseDen = 4;   // the sparse route is taken from 1 populated tile in this many down (profiles/sparse_crossover.md)
 
-// A filter in the form the index keeps, compares and uploads: [n conditions, then per condition: column, negate, set size,
-// the set's codes ascending without repeats].  crh_filter lists and crh_condition lists both become one of these.
+// A filter in the form the index keeps, compares and uploads: [n conditions, then per condition: column, mode (0 in, 1 not in,
+// 2 between, 3 not between), set size, the set's codes ascending without repeats -- for a range: 2, lo, hi].  crh_filter lists
+// and crh_condition lists both become one of these.
 using FilterKey = std::vector<int32_t>;
 
 // what build_mask hands a search: the row mask, and -- while the sparse route is enabled -- the ascending list of the tiles
@@ -327,6 +328,12 @@ int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_co
         if (c.n > 0 && !c.codes) return fail(CRH_E_INVALID, "condition %d: codes is NULL with n=%lld", f, (long long)c.n);
         total += c.n;
         if (total > (1LL << 28)) return fail(CRH_E_CAPACITY, "the sets of one filter hold more than 2^28 codes");
+        if (c.negate == CRH_COND_BETWEEN || c.negate == CRH_COND_NOT_BETWEEN) {   // a range: the two bounds as they are (lo > hi: empty)
+            if (c.n != 2) return fail(CRH_E_INVALID, "condition %d: a range condition takes n = 2 bounds, got n=%lld", f, (long long)c.n);
+            const int32_t r[5] = {c.col, c.negate, 2, c.codes[0], c.codes[1]};
+            key.insert(key.end(), r, r + 5);
+            continue;
+        }
         std::vector<int32_t> v;
         v.reserve((size_t)c.n);
         for (int64_t i = 0; i < c.n; ++i)
@@ -355,8 +362,10 @@ size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, F
         fs.neg[f] = key[at + 1];
         fs.cnt[f] = key[at + 2];
         fs.off[f] = (int)at + 3;
-        fs.one[f] = fs.cnt[f] == 1 ? key[at + 3] : 0;
-        *sets = *sets || fs.cnt[f] > 1;
+        const bool range = (fs.neg[f] & 2) != 0;                  // [lo, hi] behind the head; nothing to upload
+        fs.one[f] = fs.cnt[f] == 1 || range ? key[at + 3] : 0;
+        fs.hi[f] = range ? key[at + 4] : 0;
+        *sets = *sets || (fs.cnt[f] > 1 && !range);
         at += 3 + (size_t)fs.cnt[f];
     }
     return at;

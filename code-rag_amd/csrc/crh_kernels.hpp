@@ -203,6 +203,8 @@ __global__ void k_tombstone(uint32_t *alive, const int64_t *__restrict__ rows, i
 // its code in `one` (the equality of crh_filter: a plain compare, a code of -1 included); larger sets are ascending runs of
 // `sets`, cnt codes from off, looked up by binary search (a row costs log2(cnt) cached reads: 15 for 20 000 codes).  An empty
 // set has no member: "in" matches nothing, "not in" everything.
+// neg is the condition's MODE (crh_condition.negate): bit 0 negates, bit 1 (CRH_COND_BETWEEN / _NOT_BETWEEN) makes it a RANGE --
+// the "member" is a row whose value v is not negative and lies in one[f] <= v <= hi[f]; no set is read (cnt is 2: the bounds).
 struct FilterSet {
     int n;
     int col[CRH_MAX_FILTERS];
@@ -210,6 +212,7 @@ struct FilterSet {
     int cnt[CRH_MAX_FILTERS];
     int off[CRH_MAX_FILTERS];
     int one[CRH_MAX_FILTERS];
+    int hi[CRH_MAX_FILTERS];
 };
 __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict__ alive,
                                                      const int32_t *__restrict__ codes, int64_t cap_rows,
@@ -222,7 +225,9 @@ __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict_
         for (int f = 0; f < fs.n; ++f) {
             const int32_t c = codes[(int64_t)fs.col[f] * cap_rows + r];
             bool member;
-            if (fs.cnt[f] == 1) {
+            if (fs.neg[f] & 2) {
+                member = c >= 0 && c >= fs.one[f] && c <= fs.hi[f];
+            } else if (fs.cnt[f] == 1) {
                 member = c == fs.one[f];
             } else {
                 const int32_t *s = sets + fs.off[f];
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict_
                 }
                 member = lo < fs.cnt[f] && s[lo] == c;
             }
-            ok = ok && (member != (fs.neg[f] != 0));
+            ok = ok && (member != ((fs.neg[f] & 1) != 0));
         }
     }
     unsigned long long b = __ballot(ok);
@@ -254,7 +259,9 @@ __device__ __forceinline__ bool filter_row_ok(bool ok, const FilterSet &fs, cons
         for (int f = 0; f < fs.n; ++f) {
             const int32_t c = codes[(int64_t)fs.col[f] * cap_rows + r];
             bool member;
-            if (fs.cnt[f] == 1) {
+            if (fs.neg[f] & 2) {
+                member = c >= 0 && c >= fs.one[f] && c <= fs.hi[f];
+            } else if (fs.cnt[f] == 1) {
                 member = c == fs.one[f];
             } else {
                 const int32_t *s = sets + fs.off[f];
@@ -266,7 +273,7 @@ __device__ __forceinline__ bool filter_row_ok(bool ok, const FilterSet &fs, cons
                 }
                 member = lo < fs.cnt[f] && s[lo] == c;
             }
-            ok = ok && (member != (fs.neg[f] != 0));
+            ok = ok && (member != ((fs.neg[f] & 1) != 0));
         }
     }
     return ok;

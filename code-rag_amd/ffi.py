@@ -25,6 +25,9 @@ FUSE_METHODS = {"rrf": FUSE_RRF, "max": FUSE_MAX}
 MAX_POS, MAX_NEG = 8, 8   # CRH_MAX_POS / CRH_MAX_NEG: live examples of one recommend query (crh_recommend_*)
 RECOMMEND_AVERAGE, RECOMMEND_BEST = 0, 1
 RECOMMEND_STRATEGIES = {"average": RECOMMEND_AVERAGE, "best": RECOMMEND_BEST}
+COND_IN, COND_NOT_IN, COND_BETWEEN, COND_NOT_BETWEEN = 0, 1, 2, 3   # CRH_COND_*: the modes of crh_condition.negate
+RANGE_MODES = {"between": COND_BETWEEN, "not_between": COND_NOT_BETWEEN}
+VALUE_MAX = 2 ** 31 - 1   # largest value a numeric column stores (int32); -1 stands for "absent"
 MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 
@@ -47,6 +50,7 @@ EXPORTS = (
     "crh_fuse_select",
     "crh_recommend_query", "crh_recommend_select",
     "crh_search_range",
+    "crh_span_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -66,7 +70,8 @@ class Filter(C.Structure):
 
 
 class Condition(C.Structure):
-    """``crh_condition``: column ``col`` is (``negate`` = 0) / is not (1) one of the ``n`` int32 codes at ``codes``."""
+    """``crh_condition``: column ``col`` is (``negate`` = 0) / is not (1) one of the ``n`` int32 codes at ``codes``; ``negate`` =
+    ``COND_BETWEEN`` / ``COND_NOT_BETWEEN``: the column's value lies / does not lie in ``codes[0] .. codes[1]`` (``n`` = 2)."""
     _fields_ = [("col", C.c_int32), ("negate", C.c_int32), ("n", C.c_int64), ("codes", C.c_void_p)]
 
 
@@ -191,6 +196,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_mmr_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
     L.crh_index_gather_codes.argtypes = [vp, i32, i64, vp, i64, vp, vp]
     L.crh_group_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_span_select.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.crh_fuse_select.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.crh_recommend_query.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.crh_recommend_select.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -254,8 +260,25 @@ def _filters(filters) -> tuple:
 
 def is_set_condition(item) -> bool:
     """A filter item is ``(column, code)`` -- the equality of ``crh_filter`` -- or a SET condition ``(column, codes, negate)``:
-    the column's code is (``negate`` false) / is not (true) one of ``codes`` (any iterable of ints; ``negate`` may be left out)."""
-    return len(item) == 3 or not isinstance(item[1], (int, np.integer))
+    the column's code is (``negate`` false) / is not (true) one of ``codes`` (any iterable of ints; ``negate`` may be left out)
+    -- or a RANGE condition ``(column, lo, hi, "between" | "not_between")`` (:func:`is_range_condition`), which travels with the
+    set conditions (``crh_condition``)."""
+    return len(item) in (3, 4) or not isinstance(item[1], (int, np.integer))
+
+
+def is_range_condition(item) -> bool:
+    """``(column, lo, hi, "between" | "not_between")``: the column's VALUE (a numeric column stores the value itself, -1 for
+    "absent") lies / does not lie in ``lo .. hi``, both ends inclusive; ``lo > hi`` is an empty range.  A row without the value
+    fails every "between" and passes every "not_between"."""
+    return len(item) == 4
+
+
+def _range_parts(item) -> tuple[int, int, int, int]:
+    """(column, mode, lo, hi) of a range condition, the bounds clipped to what an int32 column can hold."""
+    col, lo, hi, mode = item
+    if not isinstance(mode, str) or mode not in RANGE_MODES:
+        raise NativeError(E_INVALID, f"range condition mode {mode!r} is not one of {sorted(RANGE_MODES)}")
+    return int(col), RANGE_MODES[mode], max(int(lo), 0), min(int(hi), VALUE_MAX)
 
 
 def _conditions(filters) -> tuple:
@@ -266,7 +289,12 @@ def _conditions(filters) -> tuple:
         raise NativeError(E_INVALID, f"at most {MAX_FILTERS} filter conditions are supported")
     arr, keep = (Condition * max(1, len(filters)))(), []
     for i, item in enumerate(filters):
-        if is_set_condition(item):
+        if is_range_condition(item):
+            col, negate, lo, hi = _range_parts(item)
+            if hi < lo:
+                lo, hi = 1, 0                      # (an empty range, whichever bound was clipped)
+            codes = np.asarray([lo, hi], np.int32)
+        elif is_set_condition(item):
             col, codes, negate = item[0], item[1], (bool(item[2]) if len(item) == 3 else False)
             codes = np.ascontiguousarray(sorted(int(c) for c in codes) if not isinstance(codes, np.ndarray) else codes, dtype=np.int32).reshape(-1)
         else:
@@ -281,7 +309,10 @@ def filter_key(filters) -> tuple:
     Conditions are ordered, a set's codes sorted without repeats; ``(col, code)`` and ``(col, [code])`` are the same condition."""
     out = []
     for item in filters or []:
-        if is_set_condition(item):
+        if is_range_condition(item):
+            col, mode, lo, hi = _range_parts(item)
+            out.append((col, mode, (lo, hi) if lo <= hi else (1, 0)))
+        elif is_set_condition(item):
             out.append((int(item[0]), bool(item[2]) if len(item) == 3 else False, tuple(sorted({int(c) for c in item[1]}))))
         else:
             out.append((int(item[0]), False, (int(item[1]),)))
@@ -526,15 +557,19 @@ class Index:
         os.replace(os.path.join(directory, "index.json.tmp"), os.path.join(directory, "index.json"))
         return meta
 
-    def load(self, directory: str) -> dict:
+    def load(self, directory: str, widen=None) -> dict:
         """Fill this EMPTY index from a directory written by :meth:`save` (same dim / dtype / code columns): the files are
-        memory-mapped and moved to HBM chunk by chunk; searches answer with the same ids and identical score bits."""
+        memory-mapped and moved to HBM chunk by chunk; searches answer with the same ids and identical score bits.
+        ``widen(first_row, rows)`` -> int32 ``[extra, rows]``: the snapshot may hold FEWER code columns than this index; its
+        columns come first and every imported chunk is completed with the ``extra`` missing ones (a collection snapshot written
+        before the store kept line numbers on the device)."""
         import json
         with open(os.path.join(directory, "index.json")) as f:
             meta = json.load(f)
         want = {"dim": self.dim, "dtype": "bf16" if self.dtype == DTYPE_BF16 else "f32", "n_code_cols": self.n_code_cols}
+        have_cols = meta.get("n_code_cols")
         for key, val in want.items():
-            if meta.get(key) != val:
+            if meta.get(key) != val and not (key == "n_code_cols" and widen is not None and isinstance(have_cols, int) and 0 <= have_cols < val):
                 raise NativeError(E_INVALID, f"snapshot {directory} has {key}={meta.get(key)!r}, this index {val!r}")
         if meta.get("format") not in (2, self.SNAPSHOT_FORMAT):
             raise NativeError(E_INVALID, f"snapshot {directory} has format={meta.get('format')!r}, this library reads 2 and {self.SNAPSHOT_FORMAT}")
@@ -559,10 +594,15 @@ class Index:
         tiles = mm("tiles.bin", np.uint8, (ntiles, tile_bytes))
         al = mm("alive.u32", np.uint32, (ntiles,))
         master = mm("master.f32", np.float32, (ntiles * 32, self.dim)) if self.dtype == DTYPE_F32 else None
-        codes = mm("codes.i32", np.int32, (self.n_code_cols, ntiles * 32)) if self.n_code_cols else None
+        codes = mm("codes.i32", np.int32, (have_cols, ntiles * 32)) if have_cols else None
         for t0 in range(0, ntiles, self.SNAPSHOT_CHUNK_TILES):
             nt = min(self.SNAPSHOT_CHUNK_TILES, ntiles - t0)
             cbuf = np.ascontiguousarray(codes[:, t0 * 32:(t0 + nt) * 32]) if codes is not None else None
+            if have_cols < self.n_code_cols:             # the missing columns of this chunk's rows (-1 behind the last row)
+                real = min(rows, (t0 + nt) * 32) - t0 * 32
+                extra = np.full((self.n_code_cols - have_cols, nt * 32), -1, np.int32)
+                extra[:, :real] = np.asarray(widen(t0 * 32, real), np.int32).reshape(self.n_code_cols - have_cols, real)
+                cbuf = np.ascontiguousarray(extra if cbuf is None else np.concatenate([cbuf, extra]))
             abuf = np.ascontiguousarray(al[t0:t0 + nt])
             tbuf = tiles[t0:t0 + nt]
             if old_piece_order:
@@ -905,6 +945,35 @@ def group_select(scores, rows, codes, k: int, group_size: int, stream: int = 0):
     info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
     use_device(dev.index)
     check(lib().crh_group_select(nq, c, k, int(group_size), _ptr(scores), _ptr(rows), _ptr(codes), *(_ptr(x) for x in outs), _ptr(info), stream))
+    return outs + (info,)
+
+
+def span_select(scores, rows, file_codes, lo, hi, k: int, max_overlap_permille: int, stream: int = 0):
+    """The overlap-free walk (``crh_span_select``) over candidate lists left on the device: ``scores`` f32 /
+    ``rows`` i64 [nq, c] as a search or merge returns them, ``file_codes`` / ``lo`` / ``hi`` i32 [nq, c] the candidates' file
+    code, first and last line (:meth:`Index.gather_codes` over buffers full of -1).  Returns CUDA tensors ``(pos i32, rows i64,
+    scores f32, file i32, lo i32, hi i32)``, each [nq, k] -- the first ``k`` candidates that repeat at most
+    ``max_overlap_permille`` thousandths of the shorter span of any better kept hit of their file, in list order, tail
+    ``(-1, -1, -inf, -1, -1, -1)`` -- and ``info`` i32 [nq, 2] = (kept in the whole list, real candidates).  Enqueues only."""
+    import torch
+    for x, what in ((scores, "scores"), (rows, "rows"), (file_codes, "file_codes"), (lo, "lo"), (hi, "hi")):
+        if not _is_dev(x):
+            raise NativeError(E_INVALID, f"{what} must be a device tensor")
+    if scores.ndim != 2:
+        raise NativeError(E_INVALID, "scores must be [nq, c]")
+    nq, c = (int(v) for v in scores.shape)
+    _typed(scores, "float32", "scores")
+    _out(rows, "int64", "rows", (nq, c))
+    for x, what in ((file_codes, "file_codes"), (lo, "lo"), (hi, "hi")):
+        _out(x, "int32", what, (nq, c))
+    k = int(k)
+    dev = scores.device
+    outs = tuple(torch.empty((nq, max(k, 0)), dtype=dt, device=dev)
+                 for dt in (torch.int32, torch.int64, torch.float32, torch.int32, torch.int32, torch.int32))
+    info = torch.empty((nq, 2), dtype=torch.int32, device=dev)
+    use_device(dev.index)
+    check(lib().crh_span_select(nq, c, k, int(max_overlap_permille), _ptr(scores), _ptr(rows), _ptr(file_codes), _ptr(lo), _ptr(hi),
+                                *(_ptr(x) for x in outs), _ptr(info), stream))
     return outs + (info,)
 
 

@@ -345,7 +345,7 @@ class VectorSearcher:
 
     async def _run(self, collection: str, query: str, limit: int, filters: dict | None, stage: str, what: str,
                    diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                   min_score: float | None = None):
+                   min_score: float | None = None, max_overlap: float | None = None):
         try:
             vector = await self.embedder.embed(query)
             extra = _only_set_given(diversity=diversity, candidates=candidates)      # (absent unless asked for: the reference's call shape)
@@ -353,6 +353,8 @@ class VectorSearcher:
                 extra.update(group_by="file_path", group_size=max_per_file)
             if min_score is not None:                                                # (the store's score threshold)
                 extra.update(score_threshold=min_score)
+            if max_overlap is not None:                                              # (the store's overlap-free top-k)
+                extra.update(max_overlap=max_overlap)
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, filters=filters, **extra)
         except Exception as e:
             logger.error(f"{what} search failed: {e}")
@@ -361,15 +363,16 @@ class VectorSearcher:
     async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
                           project_name: str | list[str] | None = None, *, diversity: float | None = None,
                           candidates: int | None = None, max_per_file: int | None = None,
-                          min_score: float | None = None) -> list[CodeSearchResult]:
+                          min_score: float | None = None, max_overlap: float | None = None) -> list[CodeSearchResult]:
         """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant).
         ``diversity`` / ``candidates`` (not in the reference): the store's diversity-aware top-k, forwarded only when given;
         ``max_per_file`` likewise: at most that many chunks of one file among the ``limit`` results (the store's grouped search);
         ``min_score`` likewise: only results whose score is at least that (the store's ``score_threshold``), possibly fewer
-        than ``limit``."""
+        than ``limit``; ``max_overlap`` likewise: no result repeats more than that share of a better result's lines (the store's
+        ``max_overlap``)."""
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
                                _only_set(language=language, entity_type=entity_type, project_name=project_name),
-                               "code_search", "Code", diversity, candidates, max_per_file, min_score)
+                               "code_search", "Code", diversity, candidates, max_per_file, min_score, max_overlap)
         return self._format_code_results(hits)
 
     async def search_summaries(self, query: str, limit: int = 10, entity_type: str | None = None, *, diversity: float | None = None,

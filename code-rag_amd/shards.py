@@ -243,7 +243,7 @@ class ShardSet:
                 ix.tombstone(np.asarray(sel, np.int64))
 
     # A filter (``dfilt``) is a list of conditions as ``ffi.Index`` takes them: ``(column, code)`` equalities and
-    # ``(column, codes, negate)`` sets.  It travels to every shard as it is -- in this process or, under backend "dist", in the
+    # ``(column, codes, negate)`` sets and ``(column, lo, hi, "between" | "not_between")`` ranges.  It travels to every shard as it is -- in this process or, under backend "dist", in the
     # same call every rank makes -- so set conditions need nothing of the collectives.
     def _plans(self, dfilt) -> list:
         """``[dfilt]`` -- or, for injected indexes that know equalities only (no ``SET_CONDITIONS``), the disjoint equality
@@ -256,6 +256,8 @@ class ShardSet:
                 opts = [(cond[0], cond[1])]
             elif len(cond) == 3 and cond[2]:
                 raise ValueError("this index takes equality filters only: no 'not in' condition")
+            elif ffi.is_range_condition(cond):
+                raise ValueError("this index takes equality filters only: no range condition")
             else:
                 opts = [(cond[0], int(c)) for c in sorted(set(cond[1]))]
             plans = [p + [o] for p in plans for o in opts]
@@ -537,6 +539,54 @@ class ShardSet:
         _, rows, scores, gcodes, info = ffi.group_select(cs, cr, codes, k, group_size)
         return np.asarray(scores, np.float32), np.asarray(rows, np.int64), np.asarray(gcodes, np.int32), np.asarray(info, np.int32)
 
+    # ------------------------------------------------------------------ overlap-free hit lists (max_overlap)
+    def search_spans_device(self, queries, k: int, candidates: int, cols: tuple[int, int, int], permille: int, dfilt, no_file: int | None = None):
+        """The overlap-free walk on the device, results left there: :meth:`search_device` for ``candidates`` hits per query,
+        every local shard writes the codes of the columns ``cols`` = (file, first line, last line) of the rows it owns into
+        one ``[3, nq, candidates]`` int32 buffer pre-filled with -1 (ONE :meth:`complete_codes` -- all-reduce(MAX) -- finishes
+        the three under backend "dist"), then ``crh_span_select``.  ``no_file``: the file code that names no file (the store's
+        code of "no value"): candidates that carry it have no span.  Returns CUDA tensors ``(pos i32, GLOBAL rows i64, scores
+        f32, file i32, lo i32, hi i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (kept, real)."""
+        import torch
+        cs, cr = self.search_device(queries, candidates, dfilt)
+        stream = torch.cuda.current_stream(cs.device).cuda_stream
+        codes = torch.full((3,) + tuple(cr.shape), -1, dtype=torch.int32, device=cr.device)
+        for s in self.owned:
+            for i, col in enumerate(cols):
+                self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes[i], stream=stream)
+        self.complete_codes(codes)
+        if no_file is not None:
+            codes[0].masked_fill_(codes[0] == int(no_file), -1)
+        return ffi.span_select(cs, cr, codes[0], codes[1], codes[2], k, permille, stream=stream)
+
+    def search_spans(self, queries: np.ndarray, k: int, candidates: int, cols: tuple[int, int, int], permille: int, dfilt, no_file: int | None = None):
+        """One round of the ``max_overlap`` search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], info i32
+        [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits that repeat at most ``permille`` thousandths of the shorter
+        span of any better kept hit of their file; -1 rows are padding; ``info`` = (kept in the whole list, real candidates),
+        what the store's exactness rounds decide on.  Indexes that hold a native handle take :meth:`search_spans_device`;
+        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
+        if all(hasattr(ix, "_handle") for ix in self.index.values()):
+            out = self.search_spans_device(queries, k, candidates, cols, permille, dfilt, no_file)
+            return out[2].cpu().numpy(), out[1].cpu().numpy(), out[6].cpu().numpy()
+        if self.ns == 1:
+            cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
+        else:
+            cs, cr = self._search_host(queries, candidates, dfilt)
+        cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
+        codes = np.full((3,) + cr.shape, -1, np.int32)
+        for s in self.owned:
+            for i, col in enumerate(cols):
+                self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes[i])
+        if self.dist is not None:
+            import torch
+            t = torch.from_numpy(codes)
+            self.complete_codes(t)
+            codes = t.numpy()
+        if no_file is not None:
+            codes[0] = np.where(codes[0] == int(no_file), -1, codes[0])
+        out = ffi.span_select(cs, cr, codes[0], codes[1], codes[2], k, permille)
+        return np.asarray(out[2], np.float32), np.asarray(out[1], np.int64), np.asarray(out[6], np.int32)
+
     # ------------------------------------------------------------------ multi-query fusion (RRF / best match; DESIGN.md 3.16)
     def search_fused_device(self, queries, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
         """Fusion on the device, results left there: ``queries`` [nq, m, dim] -- the ``m`` sub-queries of ``nq`` logical ones --
@@ -705,9 +755,15 @@ class ShardSet:
         for s, ix in self.index.items():
             ix.save(directory if self.ns == 1 else os.path.join(directory, f"shard{s}"))
 
-    def load(self, directory: str) -> None:
+    def load(self, directory: str, widen=None) -> None:
+        """``widen(shard, first_row, rows)`` -> int32 ``[extra columns, rows]``: the snapshot's shards hold fewer code columns
+        than these indexes (a collection snapshot from before the numeric columns); every imported chunk is completed with them."""
         for s, ix in self.index.items():
-            ix.load(directory if self.ns == 1 else os.path.join(directory, f"shard{s}"))
+            sub = directory if self.ns == 1 else os.path.join(directory, f"shard{s}")
+            if widen is None:
+                ix.load(sub)
+            else:
+                ix.load(sub, widen=lambda first, rows, s=s: widen(s, first, rows))
         counts = self._arrays_everyone({s: np.asarray([ix.count()[0]], np.int64) for s, ix in self.index.items()})
         self.rows = [int(counts[s][0]) for s in range(self.ns)]
 

@@ -14,13 +14,15 @@ There is no CPU fallback: without the native library or a gfx950 device ``connec
 from __future__ import annotations
 
 import asyncio
+import math
 import os
 import logging
 import threading
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
 from enum import Enum
-from typing import Any
+from collections.abc import Mapping
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -48,6 +50,53 @@ FILTER_KEYS: dict[str, tuple[str, ...]] = {
                                        "entity_name"),
     CollectionName.SUMMARIES.value: ("file_path", "entity_type", "entity_name", "project_name"),
 }
+
+# Payload keys whose VALUE (a line number) the device holds beside the dictionary codes: range conditions compare them, the
+# overlap-free walk (``max_overlap``) reads them.  Stored behind the columns of FILTER_KEYS, -1 = no usable value.
+NUMERIC_KEYS: dict[str, tuple[str, ...]] = {
+    CollectionName.CODE_CHUNKS.value: ("start_line", "end_line"),
+    CollectionName.SUMMARIES.value: (),
+}
+_RANGE_WORDS = ("gte", "gt", "lte", "lt")
+
+
+def range_bounds(key: str, spec) -> tuple[int, int]:
+    """Qdrant's ``Range(gte, gt, lte, lt)`` -- a mapping or an object with those attributes -- as inclusive integer bounds
+    ``(lo, hi)`` over non-negative ints: ``gt v`` is ``floor(v) + 1``, ``gte v`` ``ceil(v)``, ``lt v`` ``ceil(v) - 1``, ``lte v``
+    ``floor(v)``; a missing (or None) end is open (0 below, ``ffi.VALUE_MAX`` above); ``lo > hi`` is an empty range.
+    ``ValueError`` naming ``key`` for an unknown word or a bound that is no finite-or-infinite number."""
+    if isinstance(spec, Mapping):
+        unknown = [w for w in spec if w not in _RANGE_WORDS]
+        if unknown:
+            raise ValueError(f"range on {key!r}: unknown bound {unknown[0]!r} (use {', '.join(_RANGE_WORDS)})")
+        get = spec.get
+    else:
+        get = lambda w: getattr(spec, w, None)   # noqa: E731
+    lo, hi = 0, ffi.VALUE_MAX
+    for word in _RANGE_WORDS:
+        v = get(word)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+            raise ValueError(f"range on {key!r}: {word}={v!r} is not a number")
+        if v in (math.inf, -math.inf):
+            down = up = (1 << 62) if v > 0 else -(1 << 62)
+        else:
+            down, up = math.floor(v), math.ceil(v)
+        if word == "gte":
+            lo = max(lo, up)
+        elif word == "gt":
+            lo = max(lo, down + 1)
+        elif word == "lte":
+            hi = min(hi, down)
+        else:
+            hi = min(hi, up - 1)
+    return int(lo), int(hi)
+
+
+def _is_range(value) -> bool:
+    return isinstance(value, Mapping)
+
 
 _DTYPES = {"f32": ffi.DTYPE_F32, "fp32": ffi.DTYPE_F32, "float32": ffi.DTYPE_F32, "bf16": ffi.DTYPE_BF16,
            "bfloat16": ffi.DTYPE_BF16}
@@ -81,7 +130,8 @@ class _Collection:
                  group=None, merge_fn=None, compact_dead_fraction: float = 0.25, compact_min_dead: int = 1024):
         self.name = name
         self.keys = FILTER_KEYS.get(name, ())
-        ncols = len(self.keys)
+        self.numeric_keys = NUMERIC_KEYS.get(name, ())
+        ncols = len(self.keys) + len(self.numeric_keys)          # the numeric columns last
         self.shards = ShardSet(nshards, lambda s: ffi.Index(dim, dtype, capacity_rows=capacity, n_code_cols=ncols, device=device),
                                device=device, backend=backend, group=group, merge_fn=merge_fn)
         self.ids = IdTable()
@@ -98,6 +148,7 @@ class _Collection:
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
         self.recommend_rounds = {"queries": 0, "round2": 0, "short": 0}    # recommend: queries asked / sent to round 2 / answered short
+        self.span_rounds = {"queries": 0, "round2": 0, "short": 0}         # search_spans: queries asked / sent to round 2 / answered short
         # One process per shard (backend "dist"): a rank keeps the payload TEXT (content, summary: 4.2 of the 5.2 GB of host
         # tables per 10M chunks) of its OWN rows only -- everybody else stores an empty string there -- and a hit's payload comes
         # from the rank that owns the row (payloads_of: one byte exchange per search, shards.ShardSet.exchange_bytes).
@@ -173,6 +224,21 @@ class _Collection:
                              f"(filterable: {', '.join(self.keys)})")
         return self.keys.index(key)
 
+    def _numeric_column(self, key: str) -> int:
+        return len(self.keys) + self.numeric_keys.index(key)
+
+    def _range_condition(self, key: str, value, negate: bool) -> tuple:
+        """A filter entry on a numeric key as ``(column, lo, hi, "between" | "not_between")``: a ``Range`` mapping, or a plain
+        int (``lo == hi``).  ``ValueError`` naming the key for anything else (a set of values, a string, a float, a bool)."""
+        if _is_range(value):
+            lo, hi = range_bounds(key, value)
+        elif isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+            lo = hi = int(value)
+        else:
+            raise ValueError(f"payload key {key!r} holds numbers: filter it with an int or a range mapping "
+                             f"({', '.join(_RANGE_WORDS)}), not {value!r}")
+        return (self._numeric_column(key), lo, hi, "not_between" if negate else "between")
+
     def _codes_of(self, key: str, values) -> list[int]:
         """Codes of the values the column's dictionary knows (a value that was never stored contributes none)."""
         book = self.payloads.cols[key]
@@ -181,10 +247,18 @@ class _Collection:
     def device_filters(self, filters: dict[str, Any] | None, must_not: dict[str, Any] | None = None) -> list[tuple] | None:
         """dict(s) -> the conditions of ``ffi.Index``: ``(column, code)`` for a plain value, ``(column, codes, False)`` for a
         list / tuple / set of values (any of them), ``(column, codes, True)`` for a ``must_not`` entry (none of them; one
-        value or a collection).  None when a plain value or a whole any-of collection was never stored (nothing can match);
-        a ``must_not`` entry whose values were never stored excludes nothing and is dropped."""
+        value or a collection); on a numeric key (``numeric_keys``) ``(column, lo, hi, "between")`` for a range mapping or a
+        plain int and ``(column, lo, hi, "not_between")`` under ``must_not``.  None when a plain value or a whole any-of
+        collection was never stored (nothing can match); a ``must_not`` entry whose values were never stored excludes nothing
+        and is dropped."""
         out: list[tuple] = []
         for key, value in (filters or {}).items():
+            if key in self.numeric_keys:
+                out.append(self._range_condition(key, value, False))
+                continue
+            if _is_range(value):
+                raise ValueError(f"payload key {key!r} is dictionary-coded: a range needs one of the numeric keys "
+                                 f"({', '.join(self.numeric_keys) or 'this collection has none'})")
             col = self._column(key)
             if isinstance(value, _COLLECTIONS):
                 codes = self._codes_of(key, value)
@@ -197,6 +271,12 @@ class _Collection:
                     return None
                 out.append((col, code))
         for key, value in (must_not or {}).items():
+            if key in self.numeric_keys:
+                out.append(self._range_condition(key, value, True))      # (rows without the value pass, as under Qdrant's must_not)
+                continue
+            if _is_range(value):
+                raise ValueError(f"payload key {key!r} is dictionary-coded: a range needs one of the numeric keys "
+                                 f"({', '.join(self.numeric_keys) or 'this collection has none'})")
             col = self._column(key)
             codes = self._codes_of(key, value if isinstance(value, _COLLECTIONS) else [value])
             if codes:
@@ -276,7 +356,7 @@ class _Collection:
         self.payloads.extend(stored)
         orphans: dict[int, tuple[int, int]] = {}
         try:
-            codes = self.payloads.device_codes(self.keys, n0, n0 + n) if self.keys else None
+            codes = self.device_codes(n0, n0 + n)
             if lazy:
                 per_shard = {}
                 embed_failure = None
@@ -349,6 +429,16 @@ class _Collection:
         if stale.size:
             self.remove_slots(stale)                          # (a slot that is already dead is tombstoned again: the device ignores it)
             self.maybe_compact()
+
+    def device_codes(self, lo: int, hi: int):
+        """[hi - lo, columns] int32 of the slots [lo, hi) as the index stores them: the dictionary codes of ``keys``, then the
+        values of ``numeric_keys`` (None for a collection without columns)."""
+        if not self.keys and not self.numeric_keys:
+            return None
+        codes = self.payloads.device_codes(self.keys, lo, hi)
+        if not self.numeric_keys:
+            return codes
+        return np.ascontiguousarray(np.concatenate([codes, self.payloads.numeric_codes(self.numeric_keys, lo, hi)], axis=1))
 
     def hit(self, slot: int, score: float) -> dict[str, Any]:
         return {"id": self.ids.get(slot), "score": score, "payload": self.payloads_of([slot])[0]}
@@ -468,6 +558,39 @@ class _Collection:
             both = sorted(held + list(zip(s[real].tolist(), r[real].tolist())), key=lambda t: (-t[0], t[1]))[:limit]
             out_s[qi, :len(both)] = np.asarray([t[0] for t in both], np.float32)       # (a Python float holds an f32 exactly)
             out_r[qi, :len(both)] = [t[1] for t in both]
+        shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
+        return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
+
+    def search_spans(self, queries: np.ndarray, limit: int, candidates: int, permille: int, dfilt) -> tuple[np.ndarray, np.ndarray]:
+        """(scores [nq, limit], slots [nq, limit]) of the EXACT overlap-free top-``limit``: the first ``limit``
+        rows, in the order of the plain search, that repeat at most ``permille`` thousandths of the shorter span of any better
+        KEPT row of their file; rows without a file, a start line or an end line are always kept.  Whether a row is kept
+        depends on the rows before it only, so the walk over an exact top-c list is a prefix of the corpus-wide walk.  Round 1
+        runs at ``candidates``; a query is done when its walk kept ``limit`` rows or its list came back short (the filter has
+        no more rows); the others go on together at ``MAX_K``; what is still short then is returned SHORT -- its kept hits are
+        exactly the first kept hits of the corpus-wide walk, only fewer than ``limit``.  ``self.span_rounds`` counts the queries
+        asked, those sent to round 2 and those answered short."""
+        if not self.numeric_keys:
+            raise ValueError(f"collection {self.name!r} keeps no line numbers on the device: max_overlap needs them")
+        cols = (self._column("file_path"), self._numeric_column("start_line"), self._numeric_column("end_line"))
+        nq = int(queries.shape[0])
+        out_s, out_r = np.full((nq, limit), -np.inf, np.float32), np.full((nq, limit), -1, np.int64)
+        stats = self.span_rounds
+        stats["queries"] += nq
+        todo = np.arange(nq)
+        for rnd, c in enumerate((candidates, ffi.MAX_K)):
+            if rnd == 1:
+                stats["round2"] += int(todo.size)
+            s, r, info = self.shards.search_spans(queries[todo], limit, c, cols, permille, dfilt, no_file=NONE_CODE)
+            done = (info[:, 0] >= limit) | (info[:, 1] < c)
+            last = c >= ffi.MAX_K                    # (no deeper round: what is not done comes back short)
+            take = done | last
+            out_s[todo[take]], out_r[todo[take]] = s[take], r[take]
+            if last:
+                stats["short"] += int((~done).sum())
+            todo = todo[~take]
+            if not todo.size:
+                break
         shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
         return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
 
@@ -599,7 +722,9 @@ class _Collection:
             with open(os.path.join(tmp, "collection.json"), "w") as f:
                 # format 4: says where the payload tables are ("text_tables": "per_rank" = tables{rank}/ hold the text of that
                 # rank's rows only, written by one process per shard; "root" = one complete table)
-                json.dump({"name": self.name, "keys": list(self.keys), "format": 4, "slots": self.payloads.n, "shards": self.shards.ns,
+                # format 5: "numeric_keys" -- the shards' codes.i32 hold len(keys) + len(numeric_keys) columns, the numeric ones last
+                json.dump({"name": self.name, "keys": list(self.keys), "numeric_keys": list(self.numeric_keys), "format": 5,
+                           "slots": self.payloads.n, "shards": self.shards.ns,
                            "shard_rows": list(self.shards.rows), "degrees": self._degrees,
                            "text_tables": "per_rank" if self.partial else "root"}, f, default=repr)
         self.shards.barrier()
@@ -616,7 +741,14 @@ class _Collection:
             raise ValueError(f"snapshot of {self.name} codes the payload keys {meta['keys']}, this store {list(self.keys)}")
         if int(meta.get("shards", 1)) != self.shards.ns:
             raise ValueError(f"snapshot of {self.name} has {meta.get('shards', 1)} shards, this store {self.shards.ns}")
-        self.shards.load(directory)
+        # format <= 4 knows no numeric columns: its codes.i32 hold len(keys) columns, and every imported chunk is widened with
+        # the numeric ones, rebuilt from the payload table's int columns of the same rows (the tables are read first for that)
+        snap_numeric = tuple(meta.get("numeric_keys", ())) if int(meta.get("format", 0)) >= 5 else ()
+        if snap_numeric not in ((), self.numeric_keys):
+            raise ValueError(f"snapshot of {self.name} stores the numeric keys {list(snap_numeric)}, this store {list(self.numeric_keys)}")
+        widen = snap_numeric != self.numeric_keys
+        if not widen:
+            self.shards.load(directory)
         n = int(meta["slots"])
         self.ids.load(directory, n)
         per_rank = os.path.join(directory, f"tables{self.shards.rank}") if self.partial else None
@@ -629,6 +761,19 @@ class _Collection:
         self.payloads.load(per_rank if layout == "per_rank" else directory)
         self.row_shard = np.fromfile(os.path.join(directory, "rows.shard.i32"), np.int32)
         self.row_local = np.fromfile(os.path.join(directory, "rows.local.i64"), np.int64)
+        if widen:
+            values = self.payloads.numeric_codes(self.numeric_keys, 0, self.payloads.n)          # [slots, numeric columns]
+            slot_of = {}
+            for s in self.shards.owned if self.shards.ns > 1 else ():
+                m = np.flatnonzero(self.row_shard == s)
+                slot_of[s] = np.empty((m.size,), np.int64)
+                slot_of[s][self.row_local[m]] = m
+
+            def columns(s: int, first: int, rows: int) -> np.ndarray:
+                """int32 [numeric columns, rows]: the values of shard ``s``'s local rows first .. first + rows."""
+                slots = np.arange(first, first + rows) if self.shards.ns == 1 else slot_of[s][first:first + rows]
+                return np.ascontiguousarray(values[slots].T)
+            self.shards.load(directory, widen=columns)
         if self.payloads.n != n or sum(self.shards.rows) != n or list(self.shards.rows) != [int(v) for v in meta["shard_rows"]]:
             raise ValueError(f"snapshot of {self.name}: {self.shards.rows} rows in the shards, {n} ids, {self.payloads.n} payloads")
         self.slot_of = [np.zeros((0,), np.int64) for _ in range(self.shards.ns)]
@@ -665,8 +810,20 @@ def ffi_index_tensor(vecs, keep):
 _COLLECTIONS = (list, tuple, set, frozenset)
 
 
+class SpanCut(NamedTuple):
+    """What travels in the ``group`` slot of a search pass for ``max_overlap``: the overlap a hit may share with a better one,
+    in thousandths (the coalescer keys passes by it, as it does by ``(group_by, group_size)``)."""
+    permille: int
+
+
 def _value_key(v) -> str:
-    """A filter value as part of a coalescing key: collections compare as sets of their members."""
+    """A filter value as part of a coalescing key: collections compare as sets of their members, range mappings as the
+    inclusive bounds they stand for (``{"gt": 3}`` and ``{"gte": 4}`` select the same points) -- and as nothing else does."""
+    if _is_range(v):
+        try:
+            return "range" + repr(range_bounds("", v))
+        except ValueError:                     # (a malformed range: its own key; the call fails where the filter is built)
+            return "range?" + repr(sorted((str(k), repr(x)) for k, x in v.items()))
     return repr(sorted(repr(x) for x in v)) if isinstance(v, _COLLECTIONS) else "=" + repr(v)
 
 
@@ -713,14 +870,17 @@ class _RawClient:
     @staticmethod
     def _conditions(flt) -> list[tuple[str, str, Any, bool]]:
         """Duck-typed qdrant ``Filter(must=[...], must_not=[...])`` of ``FieldCondition(key, match=MatchValue | MatchText |
-        MatchAny | MatchExcept)`` -> (key, kind, value, negate); kind: "value", "text", "any" (value: the list)."""
+        MatchAny | MatchExcept)`` or ``FieldCondition(key, range=Range(gte, gt, lte, lt))`` -> (key, kind, value, negate); kind:
+        "value", "text", "any" (value: the list), "range" (value: the inclusive ``(lo, hi)`` of :func:`range_bounds`)."""
         out = []
         for negate, conds in ((False, getattr(flt, "must", None)), (True, getattr(flt, "must_not", None))):
             if conds is not None and not isinstance(conds, (list, tuple)):
                 conds = [conds]                      # (qdrant accepts a single condition in place of a list)
             for cond in (conds or []):
                 m = getattr(cond, "match", None)
-                if getattr(m, "text", None) is not None:
+                if m is None and getattr(cond, "range", None) is not None:
+                    out.append((cond.key, "range", range_bounds(cond.key, cond.range), negate))
+                elif getattr(m, "text", None) is not None:
                     out.append((cond.key, "text", m.text, negate))
                 elif getattr(m, "any", None) is not None:
                     out.append((cond.key, "any", list(m.any), negate))
@@ -737,6 +897,16 @@ class _RawClient:
         files, not rows), and however many codes that is, the device takes them as one set."""
         out: list[tuple] = []
         for key, kind, value, negate in conds:
+            if key in col.numeric_keys:
+                if kind == "range":
+                    out.append((col._numeric_column(key), value[0], value[1], "not_between" if negate else "between"))
+                elif kind == "value" and isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+                    out.append(col._range_condition(key, value, negate))
+                else:
+                    return None                      # (MatchValue(None), MatchAny, MatchText on a line number: the host walk, as before)
+                continue
+            if kind == "range":
+                raise ValueError(f"payload key {key!r} is not numeric: a Range needs one of {', '.join(col.numeric_keys) or '(none)'}")
             if key not in col.keys:
                 return None
             book = col.payloads.cols[key]
@@ -760,7 +930,8 @@ class _RawClient:
             for key, kind, value, negate in conds:
                 have = col.payloads.value(int(t), key)
                 hit = ((isinstance(have, str) and str(value) in have) if kind == "text" else
-                       (have in value) if kind == "any" else have == value)
+                       (have in value) if kind == "any" else
+                       (type(have) is int and max(value[0], 0) <= have <= min(value[1], ffi.VALUE_MAX)) if kind == "range" else have == value)
                 ok = ok and (hit != negate)
             if ok:
                 slots.append(int(t))
@@ -1015,8 +1186,8 @@ class HipVectorStore:
         per = _per_query(filters, must_not, nq)
         if per is not None:
             if diversity is not None or group is not None:
-                raise ValueError("per-query filters cannot be combined with diversity or group_by (a follow-up: the candidate "
-                                 "lists behind both are per filter)")
+                raise ValueError("per-query filters cannot be combined with diversity, group_by or max_overlap (a follow-up: the "
+                                 "candidate lists behind them are per filter)")
             classes: dict[tuple, int] = {}
             pairs, qclass = [], []
             for f, m in zip(*per):                                       # distinct filters -> classes, by the coalescer's normalisation
@@ -1031,7 +1202,9 @@ class HipVectorStore:
         dfilt = col.device_filters(filters, must_not)
         if dfilt is None or limit <= 0 or ((diversity is not None or group is not None) and nq == 0):
             return col, np.full((nq, max(limit, 0)), -np.inf, np.float32), np.full((nq, max(limit, 0)), -1, np.int64)
-        if group is not None:
+        if isinstance(group, SpanCut):
+            scores, slots = col.search_spans(queries, limit, candidates, group.permille, dfilt)
+        elif group is not None:
             scores, slots = col.search_grouped(queries, limit, candidates, group[0], group[1], dfilt)
         elif diversity is None:
             scores, slots = col.search(queries, limit, dfilt)
@@ -1197,10 +1370,57 @@ class HipVectorStore:
             raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and <= {ffi.MAX_K}")
         return (group_by, int(group_size)), candidates
 
+    def _span_args(self, collection: str, limit: int, max_overlap, candidates: int | None, diversity: float | None, group: tuple | None,
+                   has_vector: bool = True, per_query: bool = False) -> tuple[SpanCut, int]:
+        """Checked ``(SpanCut(permille), candidates)`` of one ``max_overlap`` call: a float in [0, 1] becomes
+        ``round(max_overlap * 1000)``; ``candidates`` defaults to ``min(MAX_K, 4 * limit)``, bounds as for the grouped search.
+        Raises ``ValueError`` for the caller alone, before the call joins any pass."""
+        try:
+            share = float(max_overlap)
+        except (TypeError, ValueError):
+            raise ValueError(f"max_overlap {max_overlap!r} is not a number") from None
+        if isinstance(max_overlap, bool) or not 0.0 <= share <= 1.0:          # (NaN fails both comparisons)
+            raise ValueError(f"max_overlap {max_overlap!r} outside [0, 1]")
+        used = [name for name, v in (("diversity", diversity is not None), ("group_by", group is not None), ("per-query filters", per_query)) if v]
+        if used:
+            raise ValueError(f"max_overlap cannot be combined with {', '.join(used)}")
+        if not has_vector:
+            raise ValueError("max_overlap needs a query vector (the filter-only fetch has no order to walk)")
+        if not self._col(collection).numeric_keys:
+            raise ValueError(f"collection {collection!r} keeps no line numbers on the device: max_overlap needs them")
+        if candidates is None:
+            candidates = min(ffi.MAX_K, 4 * max(int(limit), 1))
+        candidates = int(candidates)
+        if candidates < limit or candidates < 1 or candidates > ffi.MAX_K:
+            raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and <= {ffi.MAX_K}")
+        return SpanCut(int(round(share * 1000))), candidates
+
+    async def chunks_at(self, collection: str, file_path: str, line: int, last_line: int | None = None, limit: int = 64) -> list[dict[str, Any]]:
+        """The payloads of the alive points of ``file_path`` whose span meets the lines ``line .. last_line`` (``last_line``
+        None: the one line) -- ``start_line <= last`` and ``end_line >= first`` -- in insertion order, at most ``limit``: "which
+        chunk covers line 120 of this file", the chunks under a stack frame or an editor selection.  One filter-only device call
+        (two range conditions and the file's code); no vector is involved.  Points without line numbers never match."""
+        try:
+            first = int(line)
+            last = first if last_line is None else int(last_line)
+            if isinstance(line, bool) or isinstance(last_line, bool) or first < 0 or last < first:
+                raise ValueError(f"chunks_at needs 0 <= line <= last_line, got {line!r} .. {last_line!r}")
+
+            def fetch():
+                col = self._col(collection)
+                if not col.numeric_keys:
+                    raise ValueError(f"collection {collection!r} keeps no line numbers on the device")
+                slots = col.matching_slots({"file_path": file_path, "start_line": {"lte": last}, "end_line": {"gte": first}}, limit=int(limit))
+                return col.payloads_of(slots)
+            return await self._run(fetch)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to fetch the chunks at {file_path}:{line}", cause=e)
+
     async def search(self, collection: str, query_vector: list[float] | None, limit: int = 10,
                      filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
                      diversity: float | None = None, candidates: int | None = None,
-                     group_by: str | None = None, group_size: int = 1, score_threshold: float | None = None) -> list[dict[str, Any]]:
+                     group_by: str | None = None, group_size: int = 1, score_threshold: float | None = None,
+                     max_overlap: float | None = None) -> list[dict[str, Any]]:
         """client.py:132-157: descending cosine, ``[{"id", "score", "payload"}]``.  ``query_vector=None`` is the
         filter-only fetch the context builder issues (quirk Q7): first ``limit`` matching points, score 0.0.
         A ``filters`` value may be a list / tuple / set (any of them: Qdrant's ``MatchAny``); ``must_not`` (not in the
@@ -1219,14 +1439,26 @@ class HipVectorStore:
         ``score_threshold`` (Qdrant's parameter of that name; the reference never sends it): only hits whose score is ``>=`` it
         are returned -- possibly fewer than ``limit``, possibly none.  Exactly the plain list cut after its last such hit
         (DESIGN.md 3.18; :meth:`search_range` also says how many there are).  Not combinable with ``diversity`` or ``group_by``;
-        a thresholded call takes a pass of its own."""
+        a thresholded call takes a pass of its own.
+        A ``filters`` / ``must_not`` value on ``start_line`` / ``end_line`` may be an int or a mapping with any of ``gte``, ``gt``,
+        ``lte``, ``lt`` (Qdrant's ``Range``): a numeric range, evaluated on the device; under ``must_not`` points without the
+        value pass.
+        ``max_overlap`` in [0, 1] (no counterpart in the reference or in Qdrant): the exact top-``limit`` in which no hit repeats
+        more than that share of a better hit's lines -- a method next to its class, a ``_part2`` next to ``_part1`` (DESIGN.md
+        3.19).  A hit is dropped iff a better KEPT hit of the same file shares more than ``max_overlap`` of the SHORTER of the
+        two spans with it; hits without a file or line numbers are never dropped; scores, ids and order are unchanged.
+        ``candidates`` as for ``group_by``; a list that 1024 candidates cannot complete comes back short, never wrong.  Not
+        combinable with ``diversity``, ``group_by``, ``score_threshold`` or per-query filters.  ``None`` is the plain search."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
                     raise ValueError("score_threshold needs a query vector (the filter-only fetch has no scores)")
                 return (await self._range_call(collection, [query_vector], score_threshold, limit, filters, must_not, False,
-                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None))[0][0]
+                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None,
+                                               max_overlap=max_overlap is not None))[0][0]
             group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates, query_vector is not None)
+            if max_overlap is not None:
+                group, candidates = self._span_args(collection, limit, max_overlap, candidates, diversity, group, query_vector is not None)
             if query_vector is not None and group is None:
                 diversity, candidates = self._mmr_args(limit, diversity, candidates)
             if query_vector is None:
@@ -1330,7 +1562,8 @@ class HipVectorStore:
     async def search_batch(self, collection: str, query_vectors, limit: int = 10,
                            filters=None, must_not=None, *,
                            diversity: float | None = None, candidates: int | None = None,
-                           group_by: str | None = None, group_size: int = 1, score_threshold=None) -> list[list[dict[str, Any]]]:
+                           group_by: str | None = None, group_size: int = 1, score_threshold=None,
+                           max_overlap: float | None = None) -> list[list[dict[str, Any]]]:
         """Batched form of :meth:`search` (not in the reference, which sends one query per RPC): one corpus scan
         serves up to 64 queries.  ``diversity`` / ``candidates`` / ``group_by`` / ``group_size`` as in :meth:`search`.
         ``filters`` and ``must_not`` may each be a dict for the whole batch, as in :meth:`search`, or a SEQUENCE with one dict
@@ -1338,14 +1571,19 @@ class HipVectorStore:
         filter would answer it, and up to 8 distinct filters share each 64-query pass.  A filter naming a
         value the collection never stored yields an empty list for its own queries only.  Per-query filters cannot be combined
         with ``diversity`` or ``group_by`` (``ValueError``; a follow-up).  ``score_threshold`` as in :meth:`search`, one number or
-        one per query; not combinable with ``diversity``, ``group_by`` or per-query filters."""
+        one per query; not combinable with ``diversity``, ``group_by`` or per-query filters.  ``max_overlap`` as in :meth:`search`;
+        not combinable with ``diversity``, ``group_by``, ``score_threshold`` or per-query filters."""
         try:
             if score_threshold is not None:
                 return (await self._range_call(collection, query_vectors, score_threshold, limit, filters, must_not, False,
-                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None))[0]
-            if (isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple))) and (diversity is not None or group_by is not None):
+                                               diversity=diversity is not None, group_by=group_by is not None, candidates=candidates is not None,
+                                               max_overlap=max_overlap is not None))[0]
+            per_query = isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple))
+            if per_query and (diversity is not None or group_by is not None):
                 raise ValueError("per-query filters cannot be combined with diversity or group_by")
             group, candidates = self._group_args(collection, limit, group_by, group_size, diversity, candidates)
+            if max_overlap is not None:
+                group, candidates = self._span_args(collection, limit, max_overlap, candidates, diversity, group, per_query=per_query)
             if group is None:
                 diversity, candidates = self._mmr_args(limit, diversity, candidates)
             elif limit > ffi.MAX_K:

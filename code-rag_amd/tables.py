@@ -455,6 +455,18 @@ class PayloadTable:
             out[:, c] = np.maximum(self.cols[key].codes[lo:hi], 0)
         return out
 
+    def numeric_codes(self, keys: Sequence[str], lo: int, hi: int) -> np.ndarray:
+        """[hi - lo, len(keys)] int32 VALUES of the slots [lo, hi) for the device's numeric columns (``INT_KEYS``): a payload
+        value that is an ``int`` (not a ``bool``) with ``0 <= v < 2**31`` is stored as it is, anything else -- absent, None,
+        negative, a float, a string, too large -- as -1, which no range condition matches."""
+        out = np.full((hi - lo, len(keys)), -1, np.int32)
+        for c, key in enumerate(keys):
+            col = self.cols[key]
+            vals, kind = col.vals[lo:hi], col.kind[lo:hi]
+            ok = (kind == K_VALUE) & (vals >= 0) & (vals < (1 << 31))
+            out[ok, c] = vals[ok]
+        return out
+
     def compact(self, keep: np.ndarray) -> None:
         keep = np.asarray(keep, np.int64)
         new_of = np.full((self.n,), -1, np.int64)

@@ -75,6 +75,12 @@ def _threshold_kwargs(min_score: float | None) -> dict:
     return {} if min_score is None else {"score_threshold": min_score}
 
 
+def _overlap_kwargs(max_overlap: float | None) -> dict:
+    """``max_overlap`` as the store's keyword of that name (no hit repeats more than that share of a better hit's lines) -- only
+    when given: without it the call is the one issued before."""
+    return {} if max_overlap is None else {"max_overlap": max_overlap}
+
+
 def _project(hit: dict, keys: tuple[str, ...]) -> dict:
     payload = hit["payload"]
     row = {"score": hit["score"]}
@@ -106,19 +112,20 @@ class VectorSearcher:
     async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
                       must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None,
                       max_per_file: int | None = None, extra_queries: list[str] | None = None, fusion: str = "rrf",
-                      min_score: float | None = None):
+                      min_score: float | None = None, max_overlap: float | None = None):
         """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
         the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given, and
         so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k).  ``extra_queries`` (reformulations of
         ``text``): all texts are embedded in ONE provider batch and the store fuses their hit lists
         (``HipVectorStore.search_fused``); without them the call is the plain one, keyword for keyword.  ``min_score``: the
         store's ``score_threshold`` -- only hits at least that similar come back; not together with ``extra_queries`` (a fused
-        score is no cosine), ``diversity`` or ``max_per_file`` (the store refuses those)."""
+        score is no cosine), ``diversity`` or ``max_per_file`` (the store refuses those).  ``max_overlap``: the store's overlap-free
+        top-k; not together with ``extra_queries``, and the store refuses it beside ``diversity``, ``max_per_file`` or ``min_score``."""
         extra = [t for t in (extra_queries or []) if t and t.strip()]
         if extra and min_score is not None:
             raise ValueError("min_score cannot be combined with extra_queries")
-        if extra and (diversity is not None or max_per_file is not None):
-            raise ValueError("extra_queries cannot be combined with diversity or max_per_file")
+        if extra and (diversity is not None or max_per_file is not None or max_overlap is not None):
+            raise ValueError("extra_queries cannot be combined with diversity, max_per_file or max_overlap")
         try:
             kwargs = {} if filters is _NO_FILTER_KWARG else {"filters": filters}
             if must_not:
@@ -135,6 +142,7 @@ class VectorSearcher:
             kwargs.update(_mmr_kwargs(diversity, candidates))
             kwargs.update(_group_kwargs(max_per_file))
             kwargs.update(_threshold_kwargs(min_score))
+            kwargs.update(_overlap_kwargs(max_overlap))
             return await self.qdrant.search(collection=collection, query_vector=vector, limit=limit, **kwargs)
         except EmbeddingError as e:
             logger.error(f"Embedding error: {e}")
@@ -146,7 +154,8 @@ class VectorSearcher:
     async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                           entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                           diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                          extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None) -> list[dict]:
+                          extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
+                          max_overlap: float | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
         ``diversity`` in [0, 1] (not in the reference): ``limit`` maximal-marginal-relevance picks among the ``candidates``
         best hits instead of the plain top-``limit`` (``HipVectorStore.search``).  ``max_per_file`` (the reference applies it
@@ -158,13 +167,18 @@ class VectorSearcher:
         score and every result also carries ``cosine`` and ``matched``.  Not together with ``diversity`` / ``max_per_file``.
         ``min_score`` (Qdrant's ``score_threshold``; the reference never sends it): only results whose score is at least that --
         possibly fewer than ``limit``, possibly none ("nothing here is relevant"); a list shorter than ``limit`` is ALL of them.
-        Not together with ``diversity`` / ``max_per_file`` / ``extra_queries``."""
+        Not together with ``diversity`` / ``max_per_file`` / ``extra_queries``.
+        ``max_overlap`` in [0, 1] (not in the reference, which returns a class, its method and the method's ``_part2`` for one
+        good query): no result repeats more than that share of a better result's lines (``HipVectorStore.search``, DESIGN.md
+        3.19); the list still holds ``limit`` results.  Not together with ``diversity`` / ``max_per_file`` / ``min_score`` /
+        ``extra_queries``."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score)
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
+                                  max_overlap=max_overlap)
         return [_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
@@ -182,11 +196,13 @@ class VectorSearcher:
 
     async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
                                 exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,
-                                max_per_file: int | None = None, min_score: float | None = None) -> list[dict]:
+                                max_per_file: int | None = None, min_score: float | None = None,
+                                max_overlap: float | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
-        ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet."""
+        ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet.  ``max_overlap`` as in
+        :meth:`search_code`: no chunk repeats more than that share of a better chunk's lines."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
         on_device = bool(exact_exclude and exclude_file)
@@ -194,7 +210,7 @@ class VectorSearcher:
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch, _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file, min_score=min_score)
+                                  max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
         kept = []
         for h in hits:
             if exclude_file and h["payload"].get("file_path") == exclude_file:
@@ -228,18 +244,34 @@ class VectorSearcher:
             raise QueryError("Failed to find similar code", cause=e)
         return [_transform_similar_code_result(h) for h in hits]
 
+    async def chunks_at(self, file_path: str, line: int, last_line: int | None = None) -> list[dict]:
+        """The code chunks of ``file_path`` that cover line ``line`` -- or any line of ``line .. last_line`` -- in the result shape
+        of :meth:`search_code` with ``score`` 0.0, in indexing order: what a stack frame, a diff hunk or the selection of an
+        editor points at (not in the reference, whose ``ContextBuilder`` fetches a file's chunks and compares in Python).
+        Nothing is embedded: one filter-only device call (``HipVectorStore.chunks_at``)."""
+        if not file_path:
+            raise QueryError("chunks_at needs a file path")
+        try:
+            payloads = await self.qdrant.chunks_at(collection=CollectionName.CODE_CHUNKS.value, file_path=file_path, line=line, last_line=last_line)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to fetch the chunks at a line", cause=e)
+        return [_project({"score": 0.0, "payload": p}, _CODE_KEYS) for p in payloads]
+
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                                 diversity: float | None = None, candidates: int | None = None,
                                 max_per_file: int | None = None,
-                                filters_per_query: list[dict | None] | None = None, min_score=None) -> list[list[dict]]:
+                                filters_per_query: list[dict | None] | None = None, min_score=None,
+                                max_overlap: float | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``filters_per_query``: one filter dict (keys ``language`` / ``entity_type`` / ``project_name``; None = no filter) per
         query -- every query is answered under its own, and the batch still shares corpus passes (up to 8 distinct filters per
         64 queries).  Mutually exclusive with the scalar ``language`` / ``entity_type`` / ``project_name``, where a list already
         means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet.  ``min_score``: one number or one per query, as in
-        :meth:`search_code`; not together with ``filters_per_query`` either."""
+        :meth:`search_code`; not together with ``filters_per_query`` either.  ``max_overlap`` as in :meth:`search_code`; not
+        together with ``filters_per_query``, ``diversity``, ``max_per_file`` or ``min_score``."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         if filters_per_query is not None:
             if filters:
@@ -257,7 +289,8 @@ class VectorSearcher:
                 vectors = np.asarray(await self.embedder.embed_batch(texts), dtype=np.float32)
             per_query = await self.qdrant.search_batch(collection=CollectionName.CODE_CHUNKS.value, query_vectors=vectors,
                                                        limit=limit, filters=filters or None, **_mmr_kwargs(diversity, candidates),
-                                                       **_group_kwargs(max_per_file), **_threshold_kwargs(min_score))
+                                                       **_group_kwargs(max_per_file), **_threshold_kwargs(min_score),
+                                                       **_overlap_kwargs(max_overlap))
         except EmbeddingError as e:
             raise QueryError("Failed to embed search query", cause=e)
         except VectorStoreError as e:

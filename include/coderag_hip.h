@@ -62,7 +62,20 @@ typedef struct crh_filter {
  * under Filter(must_not=[...]) / MatchExcept(**{"except": [...]}).  The reference itself only ever sends MatchValue
  * (embeddings/client.py:171-176) and filters the rest on the host (query/vector_search.py:199-215).
  * An empty set has no member: "in" matches no row, "not in" every row.  A row whose code is -1 (key absent from its payload)
- * is a member of no set: it fails every "in" and passes every "not in"; negative codes in `codes` are ignored. */
+ * is a member of no set: it fails every "in" and passes every "not in"; negative codes in `codes` are ignored.
+ *
+ * `negate` is the condition's MODE.  0 = in and 1 = not in, as above; every other non-zero value but the two below keeps the
+ * meaning "not in".  CRH_COND_BETWEEN (2) is a numeric RANGE over a column that stores values instead of dictionary codes (line
+ * numbers: Qdrant's FieldCondition(key, range=Range(gte, lte)); the reference has no counterpart): n must be 2 and the row's value
+ * v satisfies codes[0] <= v <= codes[1], both ends inclusive; codes[0] > codes[1] is an empty range.  CRH_COND_NOT_BETWEEN (3) is
+ * its complement (the same Range under must_not).  A row whose value is negative (-1: absent) is inside no range: it fails every
+ * BETWEEN and passes every NOT_BETWEEN whatever the bounds -- the set rule.  Mode 2 or 3 with n != 2 is CRH_E_INVALID.  A range
+ * uploads nothing; every entry point that takes crh_condition (search_cond / _multi / _range, match_rows_cond, tombstone_cond)
+ * takes ranges, with the mask cache and the sparse route as for sets.  sizeof(crh_condition) is 24 as before. */
+#define CRH_COND_IN 0
+#define CRH_COND_NOT_IN 1
+#define CRH_COND_BETWEEN 2
+#define CRH_COND_NOT_BETWEEN 3
 typedef struct crh_condition {
     int32_t col;
     int32_t negate;
@@ -417,6 +430,30 @@ int crh_index_gather_codes(crh_index *h, int col, int64_t n, const int64_t *rows
 int crh_group_select(int nq, int c, int k, int group_size, const float *scores_dev, const int64_t *rows_dev,
                      const int32_t *codes_dev, int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev,
                      int32_t *out_codes_dev, int32_t *out_info_dev, void *stream);
+
+/* ---- overlap-free hit lists on the device (max_overlap).  The reference's chunker emits an entity for a class and one for each
+ * of its methods and splits long entities into parts that share trailing lines (embeddings/indexer.py:85-133), so a good query
+ * returns the same lines two or three times; the reference has no answer and Qdrant no counterpart.  The definition is this
+ * repository's own and exact.
+ *
+ * nq candidate lists of c entries (scores f32 / rows int64 as crh_search or crh_merge_topk* return them, rows < 0 = padding, at
+ * the end) with, per candidate, file_codes / lo / hi int32 [nq, c] as crh_index_gather_codes completes them over buffers
+ * pre-filled with -1: the code of its file, its first and its last line.  A real candidate HAS A SPAN iff file_code >= 0, lo >= 0
+ * and hi >= lo; its length is hi - lo + 1.  The walk, in list order: padding is skipped; a candidate without a span is kept; a
+ * candidate i with a span is REDUNDANT iff some earlier KEPT candidate j with a span and the same file code has
+ *   ov = min(hi_i, hi_j) - max(lo_i, lo_j) + 1 > 0   and   (int64)ov * 1000 > (int64)max_overlap_permille * min(len_i, len_j);
+ * otherwise it is kept.  Integer arithmetic only, nothing rounded.  The first k kept candidates are written in list order, each
+ * [nq, k]: out_pos (int32 position in the list), out_rows, out_scores (the score's bits, unchanged), out_file, out_lo, out_hi
+ * (the candidate's three values as given); the tail is (-1, -1, -inf, -1, -1, -1).  out_info int32 [nq, 2] = (kept: kept
+ * candidates of the WHOLE list, not clipped at k; real: non-padding candidates).  max_overlap_permille = 1000 returns the first k
+ * candidates unchanged, 0 drops on any shared line; the first j outputs of a k-output call are the j-output call.
+ * 1 <= k <= c <= CRH_MAX_K, nq >= 0, 0 <= max_overlap_permille <= 1000, anything else CRH_E_INVALID with nothing launched.  Needs
+ * no index handle (launches on the current device, like crh_group_select).  Deterministic; enqueues only; writes every output
+ * slot. */
+int crh_span_select(int nq, int c, int k, int max_overlap_permille, const float *scores_dev, const int64_t *rows_dev,
+                    const int32_t *file_codes_dev, const int32_t *lo_dev, const int32_t *hi_dev, /* each [nq, c] */
+                    int32_t *out_pos_dev, int64_t *out_rows_dev, float *out_scores_dev, int32_t *out_file_dev, int32_t *out_lo_dev,
+                    int32_t *out_hi_dev, /* each [nq, k] */ int32_t *out_info_dev /* [nq, 2] */, void *stream);
 
 /* ---- multi-query fusion on the device (reciprocal-rank fusion / best match).  The reference's planner writes reformulations of
  * a question (QueryPlan.sub_queries[].query_text, query/query_planner.py:66-91) and its engine searches the original text only
