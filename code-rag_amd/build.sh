@@ -24,7 +24,7 @@ for src in csrc/*.hip; do
   dobjs+=("build/debug/$base.o")
 done
 # host-side native tokenizer (plain C++, no GPU code): lib/libcoderag_tok.so
-g++ -O2 -std=c++17 -shared -fPIC -pthread csrc_host/bpe_tokenizer.cpp -o lib/libcoderag_tok.so &
+g++ -O2 -std=c++17 -shared -fPIC -pthread csrc_host/bpe_tokenizer.cpp csrc_host/lex_terms.cpp -o lib/libcoderag_tok.so &
 pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
 g++ -shared -fPIC -o lib/libcoderag_hip.so "${objs[@]}"

@@ -2138,4 +2138,24 @@ int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_co
     return match_key(h, key, limit, rows_out_host, n_out);
 }
 
+// The validity words of a search under these conditions, for a structure beside the index (crh_lex): the mask build_mask
+// hands a search -- the alive words without a condition -- copied out in stream order.
+int crh_index_row_mask(crh_index *h, const crh_condition *conds, int n_conds, uint32_t *out_mask_dev, int64_t n_words, void *stream)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    const int64_t ntiles = ceil_div(h->count, kTileRows);
+    if (n_words < ntiles) return fail(CRH_E_INVALID, "row_mask: n_words=%lld, the index has %lld tiles", (long long)n_words, (long long)ntiles);
+    if (ntiles == 0) return CRH_OK;
+    if (!out_mask_dev) return fail(CRH_E_INVALID, "out_mask_dev is NULL");
+    DeviceGuard g(h->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CRH_TRY(ensure_workspace0(h));
+    MaskRef m;
+    CRH_TRY(build_mask(h, h->ws, key, &m, st));
+    CRH_HIP(hipMemcpyAsync(out_mask_dev, m.mask, (size_t)ntiles * 4, hipMemcpyDeviceToDevice, st));
+    return CRH_OK;
+}
+
 }  // extern "C"

@@ -30,6 +30,7 @@ RANGE_MODES = {"between": COND_BETWEEN, "not_between": COND_NOT_BETWEEN}
 VALUE_MAX = 2 ** 31 - 1   # largest value a numeric column stores (int32); -1 stands for "absent"
 MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
+LEX_MAX_QUERY_TERMS = 32   # CRH_LEX_MAX_QUERY_TERMS: distinct term ids of one crh_lex_search query
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -51,6 +52,8 @@ EXPORTS = (
     "crh_recommend_query", "crh_recommend_select",
     "crh_search_range",
     "crh_span_select",
+    "crh_index_row_mask", "crh_lex_create", "crh_lex_destroy", "crh_lex_clear", "crh_lex_count", "crh_lex_append", "crh_lex_stats",
+    "crh_lex_search",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -200,6 +203,14 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_fuse_select.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.crh_recommend_query.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.crh_recommend_select.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_index_row_mask.argtypes = [vp, C.POINTER(Condition), i32, vp, i64, vp]
+    L.crh_lex_create.argtypes = [i32, i64, C.POINTER(vp)]
+    L.crh_lex_destroy.argtypes = [vp]
+    L.crh_lex_clear.argtypes = [vp]
+    L.crh_lex_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.crh_lex_append.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.crh_lex_stats.argtypes = [vp, vp, i64, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.crh_lex_search.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, vp, i64, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -870,6 +881,124 @@ class Index:
     def match_rows(self, filters=None, limit: int = 1) -> np.ndarray:
         out = np.empty((max(limit, 1),), dtype=np.int64)
         return out[: self._match(filters, limit, out.ctypes.data)].copy()
+
+    def row_mask(self, filters=None, out=None, stream: int = 0):
+        """The validity words a search under ``filters`` uses (``crh_index_row_mask``): alive AND filter, one uint32 per 32-row
+        tile -- an int32 CUDA tensor of ``ceil(rows / 32)`` words (given or allocated).  This is how tombstones and filters
+        reach a :class:`Lex`.  Enqueues on ``stream``."""
+        import torch
+        words = (self.count()[0] + 31) // 32
+        if out is None:
+            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.device}")
+        _typed(out, "int32", "out")
+        if not _is_dev(out) or out.ndim != 1 or int(out.shape[0]) < words:
+            raise NativeError(E_INVALID, f"out must be a device tensor of at least {words} words")
+        carr, nc, keep = _conditions(filters)
+        check(lib().crh_index_row_mask(self._handle(), carr, nc, _ptr(out), int(out.shape[0]), stream))
+        del keep
+        return out
+
+
+def lex_queries(queries, idf) -> tuple:
+    """Per-query ascending distinct term ids and their idf as the CSR ``crh_lex_search`` takes: (q_off int64, terms uint32, idf
+    float32).  More than ``LEX_MAX_QUERY_TERMS`` ids in a query, ids that do not ascend strictly, or an idf list of another
+    length are refused here, before anything reaches the library."""
+    if len(queries) != len(idf):
+        raise NativeError(E_INVALID, f"{len(queries)} queries but {len(idf)} idf lists")
+    off, ts, ws = [0], [], []
+    for q, (t, w) in enumerate(zip(queries, idf)):
+        t, w = np.asarray(t, dtype=np.uint32).reshape(-1), np.asarray(w, dtype=np.float32).reshape(-1)
+        if t.size > LEX_MAX_QUERY_TERMS:
+            raise NativeError(E_INVALID, f"query {q} has {t.size} terms, at most {LEX_MAX_QUERY_TERMS} are searched")
+        if t.size != w.size:
+            raise NativeError(E_INVALID, f"query {q} has {t.size} terms but {w.size} idf values")
+        if t.size > 1 and not (t[1:] > t[:-1]).all():
+            raise NativeError(E_INVALID, f"the term ids of query {q} are not strictly ascending")
+        ts.append(t)
+        ws.append(w)
+        off.append(off[-1] + t.size)
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts), dtype=dt) if parts else np.zeros(0, dt)   # noqa: E731
+    return np.asarray(off, np.int64), cat(ts, np.uint32), cat(ws, np.float32)
+
+
+class Lex:
+    """Owning wrapper of one ``crh_lex`` handle: the forward index of term ids beside one :class:`Index` (same rows, same
+    numbering), searched with exact BM25 on the device."""
+
+    def __init__(self, capacity_rows: int = 0, device: int = 0):
+        self.device = device
+        h = C.c_void_p()
+        check(lib().crh_lex_create(device, int(capacity_rows), C.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.crh_lex_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _handle(self):
+        if not self._h:
+            raise NativeError(E_INVALID, "lex handle is closed")
+        return self._h
+
+    def clear(self) -> None:
+        check(lib().crh_lex_clear(self._handle()))
+
+    def count(self) -> tuple[int, int]:
+        """(rows, entries)."""
+        r, e = C.c_int64(0), C.c_int64(0)
+        check(lib().crh_lex_count(self._handle(), C.byref(r), C.byref(e)))
+        return int(r.value), int(e.value)
+
+    def append(self, row_off, terms, tf, dl) -> None:
+        """``n`` rows behind the existing ones: CSR ``row_off`` int64 [n + 1] from 0, ``terms`` uint32 / ``tf`` uint8 per entry
+        (a row's ids strictly ascending, tf >= 1), ``dl`` int32 per row (>= the sum of the row's tf).  All or nothing."""
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64).reshape(-1)
+        terms = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1)
+        tf = np.ascontiguousarray(tf, dtype=np.uint8).reshape(-1)
+        dl = np.ascontiguousarray(dl, dtype=np.int32).reshape(-1)
+        n = int(dl.size)
+        if row_off.size != n + 1 or terms.size != tf.size or (n and int(row_off[-1]) != terms.size):
+            raise NativeError(E_INVALID, f"append: row_off {row_off.size}, terms {terms.size}, tf {tf.size}, dl {n} do not make a CSR")
+        check(lib().crh_lex_append(self._handle(), n, row_off.ctypes.data, terms.ctypes.data, tf.ctypes.data, dl.ctypes.data))
+
+    def stats(self, terms, mask=None) -> tuple:
+        """``(df int64 per term, rows, sum_dl)`` over the rows whose bit is set in ``mask`` (a device tensor of validity words as
+        :meth:`Index.row_mask` returns it, complete on its stream; None: every row).  Synchronous."""
+        terms = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1)
+        df = np.zeros(terms.size, np.int64)
+        rows, total = C.c_int64(0), C.c_int64(0)
+        self._check_mask(mask)
+        check(lib().crh_lex_stats(self._handle(), _ptr(mask), terms.size, terms.ctypes.data, df.ctypes.data, C.byref(rows), C.byref(total)))
+        return df, int(rows.value), int(total.value)
+
+    def _check_mask(self, mask) -> None:
+        if mask is None:
+            return
+        _typed(mask, "int32", "mask")
+        if not _is_dev(mask) or int(mask.numel()) < (self.count()[0] + 31) // 32:
+            raise NativeError(E_INVALID, "mask must be a device tensor of one word per 32-row tile")
+
+    def search(self, queries, idf, k: int, k1: float = 1.2, b: float = 0.75, avgdl: float = 1.0, mask=None, row_base: int = 0,
+               out_scores=None, out_rows=None, out_count=None, stream: int = 0):
+        """Exact BM25 top-``k`` (``crh_lex_search``): ``queries`` per query its distinct term ids ascending, ``idf`` the f32 idf
+        of each.  Returns CUDA tensors ``(scores f32 [nq, k], rows i64 [nq, k], count i64 [nq])``; tail (-inf, -1); ``count``
+        is the number of qualifying rows, never clipped.  Waits on ``stream``."""
+        import torch
+        q_off, terms, w = lex_queries(queries, idf)
+        nq, k = len(queries), int(k)
+        if not 1 <= k <= MAX_K:
+            raise NativeError(E_INVALID, f"k={k} outside 1..{MAX_K}")
+        self._check_mask(mask)
+        dev = f"cuda:{self.device}"
+        out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev) if out_scores is None else _out(out_scores, "float32", "out_scores", (nq, k))
+        out_rows = torch.empty((nq, k), dtype=torch.int64, device=dev) if out_rows is None else _out(out_rows, "int64", "out_rows", (nq, k))
+        out_count = torch.empty((nq,), dtype=torch.int64, device=dev) if out_count is None else _out(out_count, "int64", "out_count", (nq,))
+        check(lib().crh_lex_search(self._handle(), nq, q_off.ctypes.data, terms.ctypes.data, w.ctypes.data, float(k1), float(b), float(avgdl), k,
+                                   _ptr(mask), int(row_base), _ptr(out_scores), _ptr(out_rows), _ptr(out_count), stream))
+        return out_scores, out_rows, out_count
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

@@ -336,6 +336,11 @@ def _only_set_given(**kw: Any) -> dict[str, Any]:
     return {k: v for k, v in kw.items() if v is not None}
 
 
+def _mode_given(mode: str) -> dict[str, Any]:
+    """``mode`` as a keyword -- only when it is not the default: a semantic search is the call issued before."""
+    return {} if mode == "semantic" else {"mode": mode}
+
+
 class VectorSearcher:
     """Dataclass-returning searcher (indexer.py:162-257); every failure -> ``IndexingError`` (quirk Q5)."""
 
@@ -345,8 +350,20 @@ class VectorSearcher:
 
     async def _run(self, collection: str, query: str, limit: int, filters: dict | None, stage: str, what: str,
                    diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                   min_score: float | None = None, max_overlap: float | None = None):
+                   min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic"):
         try:
+            if mode != "semantic":                                                   # (the store's keyword / fused searches)
+                if mode not in ("lexical", "hybrid"):
+                    raise ValueError(f"unknown search mode {mode!r} (one of 'semantic', 'lexical', 'hybrid')")
+                used = [k for k, v in (("diversity", diversity), ("max_per_file", max_per_file), ("min_score", min_score),
+                                       ("max_overlap", max_overlap)) if v is not None]
+                if used:
+                    raise ValueError(f"mode={mode!r} cannot be combined with {', '.join(used)}")
+                if mode == "lexical":
+                    return await self.qdrant.search_lexical(collection=collection, text=query, limit=limit, filters=filters)
+                vector = await self.embedder.embed(query)
+                return await self.qdrant.search_hybrid(collection=collection, query_vector=vector, text=query, limit=limit, filters=filters,
+                                                       **_only_set_given(candidates=candidates))
             vector = await self.embedder.embed(query)
             extra = _only_set_given(diversity=diversity, candidates=candidates)      # (absent unless asked for: the reference's call shape)
             if max_per_file is not None:                                             # (the store's exact per-file cap)
@@ -363,8 +380,11 @@ class VectorSearcher:
     async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
                           project_name: str | list[str] | None = None, *, diversity: float | None = None,
                           candidates: int | None = None, max_per_file: int | None = None,
-                          min_score: float | None = None, max_overlap: float | None = None) -> list[CodeSearchResult]:
-        """``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant).
+                          min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic") -> list[CodeSearchResult]:
+        """``mode`` (not in the reference): "semantic" (the default: everything below), "lexical" (the store's exact keyword
+        search of ``query``, nothing embedded) or "hybrid" (both, fused by reciprocal rank); the keyword modes take the
+        filters and ``candidates`` only.
+        ``language`` / ``project_name`` may be a list: any of them (one device condition, ``MatchAny`` on Qdrant).
         ``diversity`` / ``candidates`` (not in the reference): the store's diversity-aware top-k, forwarded only when given;
         ``max_per_file`` likewise: at most that many chunks of one file among the ``limit`` results (the store's grouped search);
         ``min_score`` likewise: only results whose score is at least that (the store's ``score_threshold``), possibly fewer
@@ -372,14 +392,14 @@ class VectorSearcher:
         ``max_overlap``)."""
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
                                _only_set(language=language, entity_type=entity_type, project_name=project_name),
-                               "code_search", "Code", diversity, candidates, max_per_file, min_score, max_overlap)
+                               "code_search", "Code", diversity, candidates, max_per_file, min_score, max_overlap, **_mode_given(mode))
         return self._format_code_results(hits)
 
     async def search_summaries(self, query: str, limit: int = 10, entity_type: str | None = None, *, diversity: float | None = None,
                                candidates: int | None = None, max_per_file: int | None = None,
-                               min_score: float | None = None) -> list[SummarySearchResult]:
+                               min_score: float | None = None, mode: str = "semantic") -> list[SummarySearchResult]:
         hits = await self._run(CollectionName.SUMMARIES.value, query, limit, _only_set(entity_type=entity_type),
-                               "summary_search", "Summaries", diversity, candidates, max_per_file, min_score)
+                               "summary_search", "Summaries", diversity, candidates, max_per_file, min_score, **_mode_given(mode))
         return self._format_summary_results(hits)
 
     @staticmethod

@@ -625,6 +625,92 @@ class ShardSet:
             cs[dead], cr[dead] = -np.inf, -1
         return tuple(np.asarray(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights))
 
+    # ------------------------------------------------------------------ keyword search (BM25)
+    # ``lex`` = {shard: ffi.Lex}: the forward indexes beside the owned shards, rows numbered like the shards' (the collection
+    # builds and keeps them).  Tombstones and filters reach them as the validity words of ``Index.row_mask`` only.
+    def _native(self) -> bool:
+        return all(hasattr(ix, "_handle") for ix in self.index.values())
+
+    def _stream(self) -> int:
+        if not self._native():
+            return 0
+        import torch
+        ffi.use_device(self.device)
+        return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+
+    def lex_stats(self, lex: dict, terms) -> tuple[np.ndarray, int, int]:
+        """``(df int64 per term, N, sum_dl)`` over the ALIVE rows of every shard, summed: the statistics of the whole
+        collection, whatever filter a search runs under."""
+        terms = np.ascontiguousarray(terms, dtype=np.uint32)
+        df, rows, total = np.zeros(terms.size, np.int64), 0, 0
+        for s, ix in self.index.items():
+            if self.rows[s] == 0:
+                continue
+            mask = ix.row_mask(None)                 # (default stream, like the synchronous crh_lex_stats behind it)
+            d, r, t = lex[s].stats(terms, mask)
+            df, rows, total = df + d, rows + r, total + t
+        return df, rows, total
+
+    def lex_search_device(self, lex: dict, queries, idf, k: int, k1: float, b: float, avgdl: float, dfilt):
+        """Exact BM25 top-k over all shards, results left where the indexes live: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k],
+        counts i64 [nq])`` -- per shard ``crh_index_row_mask`` + ``crh_lex_search`` with ``row_base`` = shard * STRIDE, then
+        ``crh_merge_topk_strided``; the counts are summed.  Injected host-side indexes (CPU test tier) return numpy arrays."""
+        nq, native = len(queries), self._native()
+        stream = self._stream()
+        if native:
+            import torch
+            dev = torch.device("cuda", self.device)
+            all_s = torch.full((self.ns, nq, k), float("-inf"), dtype=torch.float32, device=dev)
+            all_r = torch.full((self.ns, nq, k), -1, dtype=torch.int64, device=dev)
+            counts = torch.zeros((nq,), dtype=torch.int64, device=dev)
+        else:
+            all_s, all_r = np.full((self.ns, nq, k), -np.inf, np.float32), np.full((self.ns, nq, k), -1, np.int64)
+            counts = np.zeros((nq,), np.int64)
+        for s, ix in self.index.items():
+            if self.rows[s] == 0:
+                continue
+            mask = ix.row_mask(dfilt, stream=stream)
+            out = {"out_scores": all_s[s], "out_rows": all_r[s]} if native else {}      # (every shard writes its own part of the table)
+            ps, pr, pc = lex[s].search(queries, idf, k, k1, b, avgdl, mask=mask, row_base=s * STRIDE, stream=stream, **out)
+            if not native:
+                all_s[s], all_r[s] = ps, pr
+            counts += pc
+        if self.ns == 1:
+            return all_s[0], all_r[0], counts
+        if not native:
+            ms, mr = self._merge_host(all_s, all_r)
+            return ms, mr, counts
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
+        return out_s, out_r, counts
+
+    def lex_search(self, lex: dict, queries, idf, k: int, k1: float, b: float, avgdl: float, dfilt):
+        """:meth:`lex_search_device` as host arrays."""
+        return tuple(_host(a) for a in self.lex_search_device(lex, queries, idf, k, k1, b, avgdl, dfilt))
+
+    def search_hybrid(self, lex: dict, vectors: np.ndarray, queries, idf, k: int, candidates: int, k1: float, b: float, avgdl: float,
+                      dfilt, rrf_k: int = 60, weights=None):
+        """Dense + keyword, fused: the dense top-``candidates`` (:meth:`search_device`) and the BM25 top-``candidates``
+        (:meth:`lex_search_device`) of every query under the same filter, as ``[nq, 2, candidates]``, into ``crh_fuse_select``
+        with ``m = 2`` and reciprocal-rank fusion.  Returns host arrays: the fusion's ``(GLOBAL rows, fused, cos, lists, first,
+        info)`` and the two candidate tables ``(dense scores, dense rows, lexical scores, lexical rows)``."""
+        nq = len(queries)
+        if self._native():
+            import torch
+            ds, dr = self.search_device(vectors, candidates, dfilt)
+            ls, lr, _ = self.lex_search_device(lex, queries, idf, candidates, k1, b, avgdl, dfilt)
+            cs, cr = torch.stack([ds, ls], dim=1).contiguous(), torch.stack([dr, lr], dim=1).contiguous()
+            fused = ffi.fuse_select(cs, cr, 2, k, "rrf", rrf_k, weights, stream=self._stream())
+        else:
+            vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+            ds, dr = self.index[0].search(vectors, candidates, filters=dfilt) if self.ns == 1 else self._search_host(vectors, candidates, dfilt)
+            ls, lr, _ = self.lex_search_device(lex, queries, idf, candidates, k1, b, avgdl, dfilt)
+            cs = np.stack([np.asarray(ds, np.float32), np.asarray(ls, np.float32)], axis=1).reshape(nq, 2, candidates)
+            cr = np.stack([np.asarray(dr, np.int64), np.asarray(lr, np.int64)], axis=1).reshape(nq, 2, candidates)
+            fused = ffi.fuse_select(cs, cr, 2, k, "rrf", rrf_k, weights)
+        return tuple(_host(a) for a in fused), tuple(_host(a) for a in (ds, dr, ls, lr))
+
     # ------------------------------------------------------------------ recommend by example (DESIGN.md 3.17)
     def rows_alive(self, shard: np.ndarray, local: np.ndarray) -> np.ndarray:
         """Whether every row (shard, local) is alive, from the owners' validity words (one all-reduce under backend "dist")."""
@@ -770,6 +856,11 @@ class ShardSet:
     def close(self) -> None:
         for ix in self.index.values():
             ix.close()
+
+
+def _host(a) -> np.ndarray:
+    """A device tensor or a host array as a host array."""
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
 def shard_sizes(rows: Sequence[int]) -> str:

@@ -26,7 +26,7 @@ from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import ffi
+from . import ffi, lexical
 from .errors import VectorStoreError
 from .settings import get_settings
 from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet
@@ -144,6 +144,11 @@ class _Collection:
         self._side_books = None
         self._degrees: dict[str, int] | None = None
         self._device = device
+        # keyword side, DERIVED like the side columns: shard -> ffi.Lex of its rows, built from the payload
+        # tables on the first lexical call, extended lazily, dropped by compact() and load(); never part of a snapshot
+        self._lex: dict[int, Any] = {}
+        self._lex_df: tuple | None = None    # (mutation state, {term id: df}, N, sum_dl) of the alive rows of the whole collection
+        self.lex_stats_calls = 0             # crh_lex_stats rounds run so far (repeated queries reuse the counts)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
@@ -653,6 +658,86 @@ class _Collection:
         shard = np.where(out[0] >= 0, out[0] // SHARD_STRIDE, 0).astype(np.int32)
         return (self.slots_of(shard, np.where(out[0] >= 0, out[0] % SHARD_STRIDE, -1)),) + out[1:]
 
+    # -- keyword search
+    def _lex_ready(self) -> dict[int, Any]:
+        """The forward indexes of the owned shards, brought up to date: rows appended since the last lexical call are cut into
+        terms (``lexical.terms_batch``) and appended.  A collection that is never searched lexically never comes here."""
+        if self.shards.backend == "dist":
+            raise VectorStoreError("lexical search is not available with shard_backend='dist' yet (its collection statistics need "
+                                   "an all-reduce)")
+        for s in self.shards.owned:
+            lex = self._lex.get(s)
+            if lex is None:
+                lex = self._lex[s] = ffi.Lex(capacity_rows=self.shards.rows[s], device=self._device)
+            have, want = lex.count()[0], self.shards.rows[s]
+            for a in range(have, want, 65536):
+                b = min(want, a + 65536)
+                slots = np.arange(a, b) if self.shards.ns == 1 else self.slot_of[s][a:b]
+                texts = [lexical.point_text(self.payloads.get(int(t))) if t >= 0 else b"" for t in slots]   # (-1: a dead row without a slot)
+                lex.append(*lexical.terms_batch(texts))
+        return self._lex
+
+    def _lex_drop(self) -> None:
+        for lex in self._lex.values():
+            lex.close()
+        self._lex, self._lex_df = {}, None
+
+    def _lex_weights(self, lex: dict, term_lists) -> tuple[list, list, np.float32]:
+        """Per query ``(term ids, idf)`` and ``avgdl``: the statistics are those of the ALIVE rows of the whole collection
+        (Lucene's and Qdrant's convention: not of the filtered subset), kept until the next upsert, delete or compaction --
+        only terms not counted yet go to ``crh_lex_stats``.  A text with more than 32 distinct terms keeps the 32 with the
+        smallest df, ties to the lower id."""
+        state = (tuple(self.shards.rows), self.shards.count()[1], self.compactions)
+        if self._lex_df is None or self._lex_df[0] != state:
+            self._lex_df = (state, {}, None, None)
+        _, known, n_rows, sum_dl = self._lex_df
+        every = np.unique(np.concatenate([np.zeros(0, np.uint32)] + [np.asarray(t, np.uint32) for t in term_lists]))
+        new = np.asarray([t for t in every.tolist() if t not in known], np.uint32)
+        if new.size or n_rows is None:
+            df, n_rows, sum_dl = self.shards.lex_stats(lex, new)
+            self.lex_stats_calls += 1
+            known.update(zip(new.tolist(), df.tolist()))
+            self._lex_df = (state, known, n_rows, sum_dl)
+        queries, weights = [], []
+        avgdl = np.float32(1.0)
+        for t in term_lists:
+            t = np.asarray(t, np.uint32)
+            t, _ = lexical.rarest(t, [known[v] for v in t.tolist()])
+            idf, avgdl = lexical.bm25_weights([known[v] for v in t.tolist()], n_rows, sum_dl)
+            queries.append(t)
+            weights.append(idf)
+        return queries, weights, avgdl
+
+    def _global_slots(self, rows: np.ndarray) -> np.ndarray:
+        shard = np.where(rows >= 0, rows // SHARD_STRIDE, 0).astype(np.int32)
+        return self.slots_of(shard, np.where(rows >= 0, rows % SHARD_STRIDE, -1))
+
+    def search_lexical(self, texts, limit: int, dfilt, k1: float = 1.2, b: float = 0.75):
+        """Exact BM25 top-``limit`` of every text: (scores f32 [nq, limit], slots i64 [nq, limit], counts i64 [nq]); -1 slots
+        are padding, ``counts`` the rows that hold at least one of the text's terms under the filter, however many."""
+        lex = self._lex_ready()
+        queries, idf, avgdl = self._lex_weights(lex, [lexical.query_terms(t) for t in texts])
+        scores, rows, counts = self.shards.lex_search(lex, queries, idf, limit, k1, b, float(avgdl), dfilt)
+        return scores, self._global_slots(rows), counts
+
+    def search_hybrid(self, vectors: np.ndarray, texts, limit: int, candidates: int, dfilt, rrf_k: int, weights, k1: float = 1.2, b: float = 0.75):
+        """Dense + keyword under one filter, fused by reciprocal rank on the device (``ShardSet.search_hybrid``): per query the
+        fused ``(slots, fused score, cosine or nan, lexical score or nan, lists bits)``, each [nq, limit].  The cosine and the
+        BM25 score of a hit are looked up in the two candidate lists -- nan when that list did not hold the row."""
+        lex = self._lex_ready()
+        queries, idf, avgdl = self._lex_weights(lex, [lexical.query_terms(t) for t in texts])
+        (rows, fused, _, lists, _, _), (ds, dr, ls, lr) = self.shards.search_hybrid(lex, vectors, queries, idf, limit, candidates, k1, b,
+                                                                                     float(avgdl), dfilt, rrf_k, weights)
+        def looked_up(cs, cr):
+            out = np.full(rows.shape, np.nan, np.float32)
+            for q in range(rows.shape[0]):
+                where = {int(r): float(v) for r, v in zip(cr[q], cs[q]) if r >= 0}
+                for j, r in enumerate(rows[q].tolist()):
+                    if r in where:
+                        out[q, j] = where[r]
+            return out
+        return self._global_slots(rows), fused, looked_up(ds, dr), looked_up(ls, lr), lists
+
     # -- compaction
     def maybe_compact(self) -> bool:
         rows, alive = self.shards.count()
@@ -691,6 +776,7 @@ class _Collection:
             for s, side in self._side.items():
                 side.select(np.flatnonzero(maps[s][: side.rows] >= 0))
             self.compactions += 1
+        self._lex_drop()                      # (derived: rebuilt from the payload tables on the next lexical call)
         return int(before - keep.size)
 
     # -- persistence
@@ -784,9 +870,11 @@ class _Collection:
                 so[self.row_local[m]] = m
                 self.slot_of[s] = so
         self._side = {}
+        self._lex_drop()
         self._degrees = meta.get("degrees")
 
     def close(self) -> None:
+        self._lex_drop()
         self.shards.close()
 
 
@@ -1685,6 +1773,134 @@ class HipVectorStore:
         A fused call takes a pass of its own (it never joins the coalescer)."""
         return (await self.search_fused_batch(collection, [query_vectors], limit, filters, must_not, fusion=fusion, rrf_k=rrf_k,
                                               weights=weights, candidates=candidates, score_threshold=score_threshold))[0]
+
+    # ------------------------------------------------------------------ keyword and hybrid search (DESIGN.md 3.20)
+    @staticmethod
+    def _lexical_args(texts, limit: int, filters, must_not, k1: float, b: float) -> tuple[list, int, float, float]:
+        """Checked ``(texts, limit, k1, b)`` of a lexical call; ``ValueError`` for the caller alone, before anything runs."""
+        texts = list(texts)
+        if not all(isinstance(t, (str, bytes)) for t in texts):
+            raise ValueError("a lexical query is a text (str or bytes)")
+        if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+            raise ValueError("lexical and hybrid searches take one filter for the whole batch, not per-query filters")
+        limit, k1, b = int(limit), float(k1), float(b)
+        if limit > ffi.MAX_K:
+            raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
+        if not (math.isfinite(k1) and k1 >= 0.0 and 0.0 <= b <= 1.0):
+            raise ValueError(f"BM25 needs k1 >= 0 and 0 <= b <= 1, got k1={k1} b={b}")
+        return texts, limit, k1, b
+
+    def _search_lexical_sync(self, collection: str, texts: list, limit: int, filters, must_not, k1: float, b: float):
+        """One lexical pass + the hit dictionaries of every text, built inside the worker job (:meth:`_search_hits_sync`):
+        ``(hits per text, qualifying rows per text)``.  ``limit`` 0 asks for the counts alone."""
+        col = self._col(collection)
+        dfilt = col.device_filters(filters, must_not)
+        if col.shards.backend == "dist":
+            col._lex_ready()                                             # (raises: not available there yet)
+        if dfilt is None or not texts:
+            return [[] for _ in texts], [0] * len(texts)
+        scores, slots, counts = col.search_lexical(texts, max(limit, 1), dfilt, k1, b)
+        keep = (slots >= 0) & (np.arange(slots.shape[1])[None, :] < limit)
+        flat = col.hits(slots[keep].tolist(), scores[keep].tolist())
+        out, at = [], 0
+        for n in keep.sum(1).tolist():
+            out.append(flat[at:at + n])
+            at += n
+        return out, [int(c) for c in counts]
+
+    async def search_lexical_batch(self, collection: str, texts, limit: int = 10, filters: dict[str, Any] | None = None,
+                                   must_not: dict[str, Any] | None = None, *, k1: float = 1.2, b: float = 0.75) -> list[list[dict[str, Any]]]:
+        """Batched :meth:`search_lexical`: one list of hits per text, all texts under ONE filter, 64 texts per pass over the
+        forward index."""
+        try:
+            texts, limit, k1, b = self._lexical_args(texts, limit, filters, must_not, k1, b)
+            return (await self._run(self._search_lexical_sync, collection, texts, limit, filters, must_not, k1, b))[0]
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_lexical(self, collection: str, text: str, limit: int = 10, filters: dict[str, Any] | None = None,
+                             must_not: dict[str, Any] | None = None, *, k1: float = 1.2, b: float = 0.75) -> list[dict[str, Any]]:
+        """Exact keyword search (BM25) over the points' ``entity_name`` / ``content`` / ``summary``: where is
+        ``parse_retry_after``, who mentions ``HTTPServerError`` (Qdrant's sparse BM25 vectors).  ``text`` is cut
+        like the stored text -- identifiers into their sub-words AND kept whole -- and a point qualifies iff it is alive,
+        passes the filter and holds at least one of the terms.  Hits ``{"id", "score", "payload"}`` by descending BM25 score
+        (idf and average length those of the whole collection's alive points), ties to the earlier row.  A text with more than
+        32 distinct terms is searched by its 32 rarest.  The keyword index is built from the payloads on the first such call
+        and kept up to date lazily; not available with ``shard_backend="dist"`` yet."""
+        return (await self.search_lexical_batch(collection, [text], limit, filters, must_not, k1=k1, b=b))[0]
+
+    async def lexical_count(self, collection: str, text: str, filters: dict[str, Any] | None = None,
+                            must_not: dict[str, Any] | None = None) -> int:
+        """How many alive points under the filter hold at least one term of ``text``: exact, not clipped at any ``limit``."""
+        try:
+            texts, _, k1, b = self._lexical_args([text], 0, filters, must_not, 1.2, 0.75)
+            return (await self._run(self._search_lexical_sync, collection, texts, 0, filters, must_not, k1, b))[1][0]
+        except Exception as e:
+            raise VectorStoreError(f"Failed to count in {collection}", cause=e)
+
+    def _search_hybrid_sync(self, collection: str, queries: np.ndarray, texts: list, limit: int, candidates: int, rrf_k: int, weights,
+                            filters, must_not, k1: float, b: float) -> list[list[dict[str, Any]]]:
+        col = self._col(collection)
+        dfilt = col.device_filters(filters, must_not)
+        if col.shards.backend == "dist":
+            col._lex_ready()
+        if dfilt is None or limit <= 0 or not texts:
+            return [[] for _ in texts]
+        slots, fused, cos, lexs, lists = col.search_hybrid(queries, texts, limit, candidates, dfilt, rrf_k, weights, k1, b)
+        keep = slots >= 0
+        flat = col.hits(slots[keep].tolist(), fused[keep].tolist())
+        for h, cv, lv, bits in zip(flat, cos[keep].tolist(), lexs[keep].tolist(), lists[keep].tolist()):
+            h["cosine"] = None if math.isnan(cv) else cv
+            h["lexical_score"] = None if math.isnan(lv) else lv
+            h["matched"] = tuple(name for j, name in enumerate(("vector", "lexical")) if bits >> j & 1)
+        out, at = [], 0
+        for n in keep.sum(1).tolist():
+            out.append(flat[at:at + n])
+            at += n
+        return out
+
+    async def search_hybrid_batch(self, collection: str, query_vectors, texts, limit: int = 10, candidates: int | None = None,
+                                  rrf_k: int = 60, weights=None, filters: dict[str, Any] | None = None,
+                                  must_not: dict[str, Any] | None = None, *, fusion: str = "rrf", k1: float = 1.2, b: float = 0.75,
+                                  diversity=None, group_by=None, max_overlap=None, score_threshold=None) -> list[list[dict[str, Any]]]:
+        """Batched :meth:`search_hybrid`: query ``i`` is ``(query_vectors[i], texts[i])``; all under ONE filter."""
+        try:
+            used = [name for name, v in (("diversity", diversity), ("group_by", group_by), ("max_overlap", max_overlap),
+                                         ("score_threshold", score_threshold)) if v is not None]
+            if used:
+                raise ValueError(f"a hybrid search cannot be combined with {', '.join(used)} (a follow-up: those select from one "
+                                 "candidate list, the fusion from two)")
+            if ffi.fuse_method(fusion) != ffi.FUSE_RRF:
+                raise ValueError("a hybrid search fuses by rank (fusion='rrf'): a cosine and a BM25 score are on different scales")
+            texts, limit, k1, b = self._lexical_args(texts, limit, filters, must_not, k1, b)
+            q = np.asarray(query_vectors, dtype=np.float32)
+            dim = self._col(collection).shards.dim
+            q = q.reshape(0, dim) if q.size == 0 else q
+            if q.ndim != 2 or q.shape[1] != dim or q.shape[0] != len(texts):
+                raise ValueError(f"{len(texts)} texts need query vectors [{len(texts)}, {dim}], got shape {tuple(q.shape)}")
+            rrf_k = int(rrf_k)
+            if rrf_k < 0 or rrf_k > 2**31 - 1:
+                raise ValueError(f"rrf_k {rrf_k} must be >= 0")
+            weights = ffi.fuse_weights(weights, 2, ffi.FUSE_RRF)
+            candidates = min(ffi.MAX_K // 2, 4 * max(limit, 1)) if candidates is None else int(candidates)
+            if candidates < limit or candidates < 1 or 2 * candidates > ffi.MAX_K:
+                raise ValueError(f"candidates {candidates} must be >= limit ({limit}) and 2 lists x candidates <= {ffi.MAX_K}")
+            self.search_passes += (q.shape[0] + 63) // 64
+            return await self._run(self._search_hybrid_sync, collection, q, texts, limit, candidates, rrf_k, weights, filters, must_not, k1, b)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_hybrid(self, collection: str, query_vector, text: str, limit: int = 10, candidates: int | None = None,
+                            rrf_k: int = 60, weights=None, filters: dict[str, Any] | None = None,
+                            must_not: dict[str, Any] | None = None, **kw) -> list[dict[str, Any]]:
+        """Dense and keyword search fused (Qdrant's ``query_points(prefetch=[dense, sparse], query=FusionQuery(RRF))``): the
+        ``candidates`` best hits of ``query_vector`` and the ``candidates`` best BM25 hits of ``text`` (default ``4 * limit``;
+        ``2 * candidates <= MAX_K``) under the same filter, fused on the device by reciprocal rank (``rrf_k``, ``weights`` =
+        ``(vector, lexical)``, default 1 each) into ``limit`` hits.  A hit carries ``score`` (fused), ``cosine`` and
+        ``lexical_score`` -- each None when that list did not hold the point -- and ``matched``, a subset of ``("vector",
+        "lexical")``.  ``fusion="max"`` is refused (the scales differ); not combinable with ``diversity``, ``group_by``,
+        ``max_overlap``, ``score_threshold`` or per-query filter lists."""
+        return (await self.search_hybrid_batch(collection, [query_vector], [text], limit, candidates, rrf_k, weights, filters, must_not, **kw))[0]
 
     def _recommend_args(self, collection: str, sets, limit: int, strategy, candidates: int | None):
         """Checked ``(positive ids, negative ids, P, N, strategy, candidates)`` of one recommend call; raises ``ValueError`` for

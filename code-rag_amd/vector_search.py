@@ -90,8 +90,16 @@ def _project(hit: dict, keys: tuple[str, ...]) -> dict:
 
 
 def _fused_keys(hit: dict) -> tuple[str, ...]:
-    """The two extra result keys of a fused hit (``HipVectorStore.search_fused``); none for a plain one."""
+    """The extra result keys of a fused hit (``HipVectorStore.search_fused``: two; ``search_hybrid``: three); none for a plain one."""
+    if "lexical_score" in hit:
+        return ("cosine", "lexical_score", "matched")
     return ("cosine", "matched") if "matched" in hit else ()
+
+
+def _mode_kwargs(mode: str) -> dict:
+    """``mode`` as a keyword of :meth:`VectorSearcher._lookup` -- only when it is not the default: a semantic call is the
+    one issued before."""
+    return {} if mode == "semantic" else {"mode": mode}
 
 
 def _transform_similar_code_result(hit: dict) -> dict:
@@ -112,8 +120,10 @@ class VectorSearcher:
     async def _lookup(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str,
                       must_not: dict | None = None, diversity: float | None = None, candidates: int | None = None,
                       max_per_file: int | None = None, extra_queries: list[str] | None = None, fusion: str = "rrf",
-                      min_score: float | None = None, max_overlap: float | None = None):
-        """Embed, search, map the two error kinds.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
+                      min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic"):
+        """Embed, search, map the two error kinds.  ``mode``: "semantic" (the calls below, unchanged), "lexical" (nothing is
+        embedded: ``HipVectorStore.search_lexical`` of the text) or "hybrid" (``HipVectorStore.search_hybrid`` of the text's
+        vector and the text); the two keyword modes take ``filters`` / ``must_not`` / ``candidates`` only.  ``filters=_NO_FILTER_KWARG`` omits the keyword altogether, as
         the reference's ``find_similar_code`` does (vector_search.py:193-197); ``must_not`` is passed only when given, and
         so are ``diversity`` / ``candidates`` (the store's diversity-aware top-k).  ``extra_queries`` (reformulations of
         ``text``): all texts are embedded in ONE provider batch and the store fuses their hit lists
@@ -122,6 +132,10 @@ class VectorSearcher:
         score is no cosine), ``diversity`` or ``max_per_file`` (the store refuses those).  ``max_overlap``: the store's overlap-free
         top-k; not together with ``extra_queries``, and the store refuses it beside ``diversity``, ``max_per_file`` or ``min_score``."""
         extra = [t for t in (extra_queries or []) if t and t.strip()]
+        if mode != "semantic":
+            return await self._lookup_keyword(text, collection, limit, filters, embed_fail, store_fail, must_not, candidates, mode,
+                                              diversity=diversity, max_per_file=max_per_file, extra_queries=extra or None,
+                                              min_score=min_score, max_overlap=max_overlap)
         if extra and min_score is not None:
             raise ValueError("min_score cannot be combined with extra_queries")
         if extra and (diversity is not None or max_per_file is not None or max_overlap is not None):
@@ -151,12 +165,44 @@ class VectorSearcher:
             logger.error(f"Vector store error: {e}")
             raise QueryError(store_fail, cause=e)
 
+    async def _lookup_keyword(self, text: str, collection: str, limit: int, filters: Any, embed_fail: str, store_fail: str, must_not,
+                              candidates, mode: str, **others):
+        """``mode`` "lexical" / "hybrid" of :meth:`_lookup`: the store's keyword and fused searches.  A hybrid hit's
+        ``cosine`` / ``lexical_score`` / ``matched`` travel in its payload copy, like a fused hit's."""
+        if mode not in ("lexical", "hybrid"):
+            raise ValueError(f"unknown search mode {mode!r} (one of 'semantic', 'lexical', 'hybrid')")
+        used = [k for k, v in others.items() if v is not None]
+        if used:
+            raise ValueError(f"mode={mode!r} cannot be combined with {', '.join(used)}")
+        try:
+            kwargs = {} if filters is _NO_FILTER_KWARG else {"filters": filters}
+            if must_not:
+                kwargs["must_not"] = must_not
+            if mode == "lexical":
+                return await self.qdrant.search_lexical(collection=collection, text=text, limit=limit, **kwargs)
+            vector = await self.embedder.embed(text)
+            if candidates is not None:
+                kwargs["candidates"] = candidates
+            hits = await self.qdrant.search_hybrid(collection=collection, query_vector=vector, text=text, limit=limit, **kwargs)
+            for h in hits:
+                h["payload"] = dict(h["payload"], cosine=h["cosine"], lexical_score=h["lexical_score"], matched=h["matched"])
+            return hits
+        except EmbeddingError as e:
+            logger.error(f"Embedding error: {e}")
+            raise QueryError(embed_fail, cause=e)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError(store_fail, cause=e)
+
     async def search_code(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                           entity_type: str | None = None, project_name: str | list[str] | None = None, *,
                           diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                           extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
-                          max_overlap: float | None = None) -> list[dict]:
-        """vector_search.py:60-116.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
+                          max_overlap: float | None = None, mode: str = "semantic") -> list[dict]:
+        """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
+        "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
+        -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
+        ``lexical_score`` and ``matched``.  The keyword modes take the filters and ``candidates`` only.  ``language`` / ``project_name`` may be a list: any of them (one device condition).
         ``diversity`` in [0, 1] (not in the reference): ``limit`` maximal-marginal-relevance picks among the ``candidates``
         best hits instead of the plain top-``limit`` (``HipVectorStore.search``).  ``max_per_file`` (the reference applies it
         after the fetch, query/reranker.py:122-145, and comes back short): at most that many chunks of one file among the
@@ -178,20 +224,22 @@ class VectorSearcher:
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
-                                  max_overlap=max_overlap)
+                                  max_overlap=max_overlap, **_mode_kwargs(mode))
         return [_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
-                               extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None) -> list[dict]:
+                               extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
+                               mode: str = "semantic") -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
-        ``extra_queries`` / ``fusion`` / ``min_score`` as in :meth:`search_code`."""
+        ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
-                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score)
+                                  max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
+                                  **_mode_kwargs(mode))
         return [_project(h, _SUMMARY_KEYS + _fused_keys(h)) for h in hits]
 
     async def find_similar_code(self, code_snippet: str, limit: int = DEFAULT_SEARCH_LIMIT, exclude_file: str | None = None,
@@ -264,8 +312,10 @@ class VectorSearcher:
                                 diversity: float | None = None, candidates: int | None = None,
                                 max_per_file: int | None = None,
                                 filters_per_query: list[dict | None] | None = None, min_score=None,
-                                max_overlap: float | None = None) -> list[list[dict]]:
+                                max_overlap: float | None = None, mode: str = "semantic") -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
+        ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
+        ``candidates`` only).
         ``filters_per_query``: one filter dict (keys ``language`` / ``entity_type`` / ``project_name``; None = no filter) per
         query -- every query is answered under its own, and the batch still shares corpus passes (up to 8 distinct filters per
         64 queries).  Mutually exclusive with the scalar ``language`` / ``entity_type`` / ``project_name``, where a list already
@@ -279,6 +329,9 @@ class VectorSearcher:
             if len(filters_per_query) != len(queries):
                 raise QueryError(f"filters_per_query has {len(filters_per_query)} entries for {len(queries)} queries")
             filters = [({k: v for k, v in f.items() if v} or None) if f else None for f in filters_per_query]
+        if mode != "semantic":
+            return await self._batch_keyword(queries, limit, filters or None, candidates, mode, diversity=diversity, max_per_file=max_per_file,
+                                             filters_per_query=filters_per_query, min_score=min_score, max_overlap=max_overlap)
         try:
             if isinstance(queries, np.ndarray) or (hasattr(queries, "shape") and not isinstance(queries, (list, tuple))):
                 vectors = queries
@@ -296,3 +349,29 @@ class VectorSearcher:
         except VectorStoreError as e:
             raise QueryError("Failed to search code", cause=e)
         return [[_project(h, _CODE_KEYS) for h in hits] for hits in per_query]
+
+    async def _batch_keyword(self, queries, limit: int, filters, candidates, mode: str, **others) -> list[list[dict]]:
+        if mode not in ("lexical", "hybrid"):
+            raise QueryError(f"unknown search mode {mode!r} (one of 'semantic', 'lexical', 'hybrid')")
+        used = [k for k, v in others.items() if v is not None]
+        if used:
+            raise QueryError(f"mode={mode!r} cannot be combined with {', '.join(used)}")
+        texts = list(queries) if isinstance(queries, (list, tuple)) else None
+        if texts is None or any((not isinstance(t, str) or not t.strip()) for t in texts):
+            raise QueryError(f"mode={mode!r} needs the query texts")
+        try:
+            col = CollectionName.CODE_CHUNKS.value
+            if mode == "lexical":
+                per_query = await self.qdrant.search_lexical_batch(collection=col, texts=texts, limit=limit, filters=filters)
+            else:
+                vectors = np.asarray(await self.embedder.embed_batch(texts), dtype=np.float32)
+                kw = {} if candidates is None else {"candidates": candidates}
+                per_query = await self.qdrant.search_hybrid_batch(collection=col, query_vectors=vectors, texts=texts, limit=limit, filters=filters, **kw)
+                for hits in per_query:
+                    for h in hits:
+                        h["payload"] = dict(h["payload"], cosine=h["cosine"], lexical_score=h["lexical_score"], matched=h["matched"])
+        except EmbeddingError as e:
+            raise QueryError("Failed to embed search query", cause=e)
+        except VectorStoreError as e:
+            raise QueryError("Failed to search code", cause=e)
+        return [[_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits] for hits in per_query]

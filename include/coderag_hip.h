@@ -539,6 +539,58 @@ int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters,
 int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t limit,
                               int64_t *rows_out_host, int64_t *n_out);
 
+/* ---- exact BM25 keyword search on the device.  Qdrant's counterpart is a sparse (BM25) vector searched beside the dense one,
+ * query_points(prefetch=[dense, sparse], query=FusionQuery(RRF)); the fusion half is crh_fuse_select.  The definitions are this
+ * repository's own and exact.
+ *
+ * The validity words a search of `h` under these conditions uses -- alive AND filter, one u32 per 32-row tile, bit i = row
+ * 32 t + i -- copied to out_mask_dev (n_words >= ceil(rows / 32), anything less is CRH_E_INVALID; words behind the last tile are
+ * not written).  n_conds = 0 gives the alive words.  Built (or found) by the same routine and mask cache a search uses;
+ * enqueues on `stream`.  This is how tombstones and filters reach a crh_lex. */
+int crh_index_row_mask(crh_index *h, const crh_condition *conds, int n_conds, uint32_t *out_mask_dev, int64_t n_words, void *stream);
+
+/* A crh_lex is a FORWARD index whose rows are numbered like the rows of the crh_index it accompanies: per row its distinct term
+ * ids (u32, strictly ascending) with their frequencies tf (u8, 1..255, saturated) and its length dl (int32, the number of terms
+ * before de-duplication) -- CSR: row_off int64 [rows + 1], 5 bytes per entry.  What a term is, is the caller's business (the
+ * store hashes sub-words of identifiers).  Buffers grow by doubling on append; a search releases nothing. */
+typedef struct crh_lex crh_lex; /* opaque */
+#define CRH_LEX_MAX_QUERY_TERMS 32
+
+int crh_lex_create(int device, int64_t capacity_rows, crh_lex **out);
+int crh_lex_destroy(crh_lex *l);
+int crh_lex_clear(crh_lex *l); /* forget every row, keep the buffers */
+int crh_lex_count(crh_lex *l, int64_t *rows_out, int64_t *entries_out);
+
+/* n rows behind the existing ones, all host pointers: row_off [n + 1] starting at 0, terms / tf one per entry, dl one per row.
+ * CRH_E_INVALID, with nothing stored, when offsets do not start at 0 or decrease, a row's ids are not strictly ascending, a tf is
+ * 0, or a dl is smaller than the sum of the row's tf.  A row without entries is allowed.  Synchronous. */
+int crh_lex_append(crh_lex *l, int64_t n, const int64_t *row_off_host, const uint32_t *terms_host, const uint8_t *tf_host,
+                   const int32_t *dl_host);
+
+/* Over the rows whose bit is set in mask_dev (words as crh_index_row_mask writes them, complete before the call; NULL: every
+ * row): df_out_host[i] = the number of such rows holding terms_host[i] (nt >= 0 terms, repeats allowed), *rows_out their number,
+ * *sum_dl_out the sum of their dl.  Integers only.  Synchronous (runs on the default stream). */
+int crh_lex_stats(crh_lex *l, const uint32_t *mask_dev, int64_t nt, const uint32_t *terms_host, int64_t *df_out_host,
+                  int64_t *rows_out, int64_t *sum_dl_out);
+
+/* BM25, exact.  Query q's terms are q_terms_host[q_off_host[q] .. q_off_host[q + 1]) -- at most CRH_LEX_MAX_QUERY_TERMS ids,
+ * strictly ascending -- with q_idf_host beside them.  With c = (float)tf and len = (float)dl, every operation rounded to f32 on
+ * its own (no fused multiply-add, divisions correctly rounded):
+ *     norm    = k1 * ((1.0f - b) + b * (len / avgdl))
+ *     contrib = idf_t * ((c * (k1 + 1.0f)) / (c + norm))
+ *     score   = +0.0f, then + contrib for each of the query's terms the row holds, in ASCENDING term id.
+ * idf and avgdl are inputs: the host derives them from crh_lex_stats, so device and host never disagree about a logarithm.  A
+ * row QUALIFIES for a query iff its mask bit is set (mask_dev NULL: every row) and it holds at least one of the query's terms.
+ * Outputs [nq, k]: the qualifying rows by descending score (order-preserving integer image of f32), ties to the lower row,
+ * row_base added; the tail is (-inf, -1); every slot is written.  out_count_dev int64 [nq] = the number of qualifying rows,
+ * exact, never clipped at k.  A query without terms returns an empty list and 0.
+ * 1 <= k <= CRH_MAX_K, nq >= 0 (run in passes of 64 queries), avgdl finite and > 0; more than CRH_LEX_MAX_QUERY_TERMS terms or
+ * ids that do not ascend are CRH_E_INVALID with nothing launched.  Deterministic; waits on `stream` (the candidate lists are sized
+ * to what a first pass over the index counted). */
+int crh_lex_search(crh_lex *l, int nq, const int64_t *q_off_host, const uint32_t *q_terms_host, const float *q_idf_host, float k1,
+                   float b, float avgdl, int k, const uint32_t *mask_dev, int64_t row_base, float *out_scores_dev,
+                   int64_t *out_rows_dev, int64_t *out_count_dev, void *stream);
+
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
  * the HF RobertaModel it wraps).  All pointers are device pointers; activations bf16,
