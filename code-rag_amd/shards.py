@@ -278,356 +278,14 @@ class ShardSet:
         return sh, lo
 
     # ------------------------------------------------------------------ query
-    def search(self, queries: np.ndarray, k: int, dfilt) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """Exact top-k over all shards: (scores [nq, k], shard [nq, k], local row [nq, k]); -1 rows are padding."""
-        if self.ns == 1:
-            s, r = self.index[0].search(queries, k, filters=dfilt, **({"stream": self.stream} if self.stream else {}))
-            return s, np.zeros(r.shape, np.int32), r
-        if self._merge_host is not None:            # injected host-side index + merge (CPU test tier)
-            scores, rows = self._search_host(queries, k, dfilt)
-        else:
-            sd, rd = self.search_device(queries, k, dfilt)
-            scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
-        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
-
-    def search_multi(self, queries: np.ndarray, k: int, class_filters, query_class) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """:meth:`search` for a batch whose queries carry different filters (``ffi.Index.search_multi``): query ``i`` under
-        ``class_filters[query_class[i]]``.  The same per-shard plan as :meth:`search` -- every shard answers the whole batch
-        under the same classes, [one all-gather,] one merge."""
-        multi = (list(class_filters), np.asarray(query_class, np.int32))
-        if self.ns == 1:
-            s, r = self.index[0].search_multi(queries, k, *multi, **({"stream": self.stream} if self.stream else {}))
-            return s, np.zeros(r.shape, np.int32), r
-        if self._merge_host is not None:
-            scores, rows = self._search_host(queries, k, None, multi)
-        else:
-            sd, rd = self.search_device(queries, k, None, multi)
-            scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
-        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
-
-    @staticmethod
-    def _shard_search(ix, queries, k, dfilt, multi, **kw):
-        """One shard's part of a search: under one filter, or -- ``multi`` = (class_filters, query_class) -- under every query's own."""
-        if multi is None:
-            return ix.search(queries, k, filters=dfilt, **kw)
-        return ix.search_multi(queries, k, multi[0], multi[1], **kw)
-
-    def _search_host(self, queries, k, dfilt, multi=None):
-        nq = int(queries.shape[0])
-        mine = {s: self._shard_search(ix, queries, k, dfilt, multi, row_base=s * STRIDE) for s, ix in self.index.items()}
-        if self.dist is None:
-            parts = mine
-        else:                                        # the same single all-gather of [scores | rows] records as on the device
-            import torch
-            local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, torch.device("cpu"))
-            ms, mr = mine[self.rank]
-            loc_s.copy_(torch.from_numpy(np.ascontiguousarray(ms)))
-            loc_r.copy_(torch.from_numpy(np.ascontiguousarray(mr)))
-            self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
-            return self._merge_host(all_s.numpy(), all_r.numpy())
-        ss = np.stack([parts[s][0] for s in range(self.ns)])
-        rr = np.stack([parts[s][1] for s in range(self.ns)])
-        return self._merge_host(ss, rr)
-
-    def search_device(self, queries, k: int, dfilt, multi=None):
-        """The same on the device, results left there: (scores f32 [nq, k], GLOBAL rows i64 [nq, k]) CUDA tensors -- per-shard
-        ``crh_search`` with ``row_base`` = shard * STRIDE, [one all-gather of the records,] ``crh_merge_topk_strided``.
-        ``multi`` = (class_filters, query_class): every query under its own filter (``crh_search_multi``), ``dfilt`` unused."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        ffi.use_device(self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        qd = queries if torch.is_tensor(queries) else torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
-        nq = int(qd.shape[0])
-        local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, dev)
-        if self.dist is None:
-            for s, ix in self.index.items():         # every shard writes its own record of the "gathered" buffer
-                self._shard_search(ix, qd, k, dfilt, multi, row_base=s * STRIDE, out_scores=all_s[s], out_rows=all_r[s], stream=stream)
-            for ix in self.index.values():
-                ix.search_finish(stream)
-        else:
-            ix = self.index[self.rank]
-            self._shard_search(ix, qd, k, dfilt, multi, row_base=self.rank * STRIDE, out_scores=loc_s, out_rows=loc_r, stream=stream)
-            ix.search_finish(stream)
-            self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
-        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
-        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
-        return out_s, out_r
-
-    # ------------------------------------------------------------------ score threshold and in-range counts (DESIGN.md 3.18)
-    def complete_counts(self, counts) -> None:
-        """In-range counts of a range search: every rank summed its own shards; ONE all-reduce(sum) of the ``[nq]`` int64 vector
-        completes them.  Like :meth:`complete_vectors` it has never run on more than one RCCL rank: the two-rank form is
-        exercised with gloo on host tensors only."""
-        if self.dist is not None:
-            self.dist.all_reduce(counts, op=self.dist.ReduceOp.SUM, group=self.group)
-
-    def search_range_device(self, queries, k: int, thresholds, dfilt, counts: bool = True):
-        """The range search on the device, results left there: every shard runs ``crh_search_range`` with ``row_base`` =
-        shard * STRIDE, the lists merge as in :meth:`search_device` (a shard's cut list is padded, and padding merges as it does
-        there: the merged list is the first ``min(k, count)`` in-range rows of the whole collection), the counts are summed over
-        the local shards and, under backend "dist", completed by :meth:`complete_counts`.  Returns CUDA tensors ``(scores f32
-        [nq, k], GLOBAL rows i64 [nq, k], counts i64 [nq] or None)``."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        ffi.use_device(self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        qd = queries if torch.is_tensor(queries) else torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
-        nq = int(qd.shape[0])
-        thr = ffi.range_thresholds(thresholds, nq)
-        local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, dev)
-        part = torch.zeros((len(self.owned), nq), dtype=torch.int64, device=dev) if counts else None
-        for i, s in enumerate(self.owned):           # every local shard writes its own record of the "gathered" buffer
-            on = self.dist is None
-            self.index[s].search_range(qd, k, thr, filters=dfilt, row_base=s * STRIDE, counts=counts, out_scores=all_s[s] if on else loc_s,
-                                       out_rows=all_r[s] if on else loc_r, out_counts=part[i] if counts else None, stream=stream)
-        for s in self.owned:
-            self.index[s].search_finish(stream)
-        if self.dist is not None:
-            self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
-        total = None
-        if counts:
-            total = part.sum(0)
-            self.complete_counts(total)
-        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
-        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
-        return out_s, out_r, total
-
-    def search_range(self, queries: np.ndarray, k: int, thresholds, dfilt, counts: bool = True):
-        """:meth:`search` with a score threshold per query: ``(scores [nq, k], shard [nq, k], local row [nq, k], counts int64
-        [nq] or None)``; -1 rows are padding.  One native shard answers directly; several take :meth:`search_range_device`;
-        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
-        nq = int(np.asarray(queries).shape[0]) if not hasattr(queries, "is_cuda") else int(queries.shape[0])
-        thr = ffi.range_thresholds(thresholds, nq)
-        if self.ns == 1:
-            s, r, c = self.index[0].search_range(queries, k, thr, filters=dfilt, counts=counts, **({"stream": self.stream} if self.stream else {}))
-            return s, np.zeros(r.shape, np.int32), r, c
-        if self._merge_host is None:
-            sd, rd, cd = self.search_range_device(queries, k, thr, dfilt, counts)
-            scores, rows, total = sd.cpu().numpy(), rd.cpu().numpy(), (cd.cpu().numpy() if counts else None)
-        else:
-            mine = {s: ix.search_range(queries, k, thr, filters=dfilt, row_base=s * STRIDE, counts=counts) for s, ix in self.index.items()}
-            total = sum(np.asarray(m[2], np.int64) for m in mine.values()) if counts else None
-            if self.dist is None:
-                ss = np.stack([mine[s][0] for s in range(self.ns)])
-                rr = np.stack([mine[s][1] for s in range(self.ns)])
-            else:                                        # the list records travel as in _search_host, the counts in one all-reduce
-                import torch
-                local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, torch.device("cpu"))
-                loc_s.copy_(torch.from_numpy(np.ascontiguousarray(mine[self.rank][0])))
-                loc_r.copy_(torch.from_numpy(np.ascontiguousarray(mine[self.rank][1])))
-                self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
-                ss, rr = all_s.numpy(), all_r.numpy()
-                if counts:
-                    t = torch.from_numpy(np.ascontiguousarray(total, dtype=np.int64))
-                    self.complete_counts(t)
-                    total = t.numpy()
-            scores, rows = self._merge_host(ss, rr)
-        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1), total
-
-    def complete_columns(self, packed) -> None:
-        """Side columns of a merged candidate table: every rank gathered the rows it owns (zeros elsewhere); ONE all-reduce of
-        the packed buffer completes them (``sharded.ShardedIndex.gather_columns``).  Local shards are summed by the caller."""
-        if self.dist is not None:
-            self.dist.all_reduce(packed, op=self.dist.ReduceOp.SUM, group=self.group)
-
-    # ------------------------------------------------------------------ diversity-aware top-k (MMR; DESIGN.md)
-    def complete_vectors(self, vecs) -> None:
-        """Candidate vectors of a merged list: every rank gathered the rows it owns (zeros elsewhere); ONE all-reduce(sum)
-        completes them, as :meth:`complete_columns` does for the side columns.  It moves ``nq * candidates * dim * 4`` bytes
-        (3 MB for one 768-wide query at 1024 candidates) and has never run on more than one RCCL rank: the two-rank form is
-        exercised with gloo on host tensors only."""
-        if self.dist is not None:
-            self.dist.all_reduce(vecs, op=self.dist.ReduceOp.SUM, group=self.group)
-
-    def search_mmr_device(self, queries, k: int, candidates: int, diversity: float, dfilt):
-        """Diversity-aware top-k on the device, results left there: :meth:`search_device` for ``candidates`` hits per query,
-        every local shard gathers the stored vectors of the rows it owns into one ``[nq, candidates, dim]`` buffer (a row has
-        one owner and the others contribute zeros: the local shards' gathers are summed, and under backend "dist" one
-        all-reduce(sum) of ``nq * candidates * dim * 4`` bytes completes the buffer -- :meth:`complete_vectors`; never run on
-        more than one RCCL rank), then ``crh_mmr_select``.  Returns CUDA tensors ``(pos i32, GLOBAL rows i64, scores f32,
-        obj f32)``, each [nq, k]; ``scores`` are the hits' cosines, -1 rows are padding."""
-        import torch
-        cs, cr = self.search_device(queries, candidates, dfilt)
-        stream = torch.cuda.current_stream(cs.device).cuda_stream
-        vecs = None
-        for s in self.owned:
-            part = self.index[s].gather_vectors(cr, row_base=s * STRIDE, stream=stream)
-            if vecs is None:
-                vecs = part
-            else:
-                vecs += part
-        self.complete_vectors(vecs)
-        return ffi.mmr_select(cs, cr, vecs, k, diversity, stream=stream)
-
-    def search_mmr(self, queries: np.ndarray, k: int, candidates: int, diversity: float, dfilt) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """:meth:`search` with diversity: (scores [nq, k], shard [nq, k], local row [nq, k]) of the MMR picks among the
-        ``candidates`` best hits of every query; -1 rows are padding.  Indexes that hold a native handle take
-        :meth:`search_mmr_device`; injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
-        if all(hasattr(ix, "_handle") for ix in self.index.values()):
-            _, rd, sd, _ = self.search_mmr_device(queries, k, candidates, diversity, dfilt)
-            scores, rows = sd.cpu().numpy(), rd.cpu().numpy()
-        else:
-            if self.ns == 1:
-                cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
-            else:
-                cs, cr = self._search_host(queries, candidates, dfilt)
-            cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
-            vecs = sum(self.index[s].gather_vectors(cr, row_base=s * STRIDE) for s in self.owned)
-            if self.dist is not None:
-                import torch
-                t = torch.from_numpy(np.ascontiguousarray(vecs, dtype=np.float32))
-                self.complete_vectors(t)
-                vecs = t.numpy()
-            _, rows, scores, _ = ffi.mmr_select(cs, cr, vecs, k, diversity)
-            scores, rows = np.asarray(scores), np.asarray(rows)
-        return scores, np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
-
-    # ------------------------------------------------------------------ per-group cap (group_by / group_size; DESIGN.md 3.13)
-    def complete_codes(self, codes) -> None:
-        """Group codes of a merged candidate list: the buffer starts full of -1 and every rank wrote the codes of the rows it
-        owns (stored codes are >= -1, a row has one owner); ONE all-reduce(MAX) of ``nq * candidates`` int32 completes it.
-        Like :meth:`complete_vectors` it has never run on more than one RCCL rank: the two-rank form is exercised with gloo
-        on host tensors only."""
-        if self.dist is not None:
-            self.dist.all_reduce(codes, op=self.dist.ReduceOp.MAX, group=self.group)
-
-    def search_grouped_device(self, queries, k: int, candidates: int, col: int, group_size: int, dfilt, ungrouped: int | None = None):
-        """The capped walk on the device, results left there: :meth:`search_device` for ``candidates`` hits per query, every
-        local shard writes the column-``col`` codes of the rows it owns into one ``[nq, candidates]`` int32 buffer pre-filled
-        with -1 (:meth:`complete_codes` finishes it under backend "dist"), then ``crh_group_select``.  ``ungrouped``: a code
-        that names no group (the store's code of "no value"): candidates that carry it are never capped.  Returns CUDA tensors
-        ``(pos i32, GLOBAL rows i64, scores f32, codes i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (kept, real)."""
-        import torch
-        cs, cr = self.search_device(queries, candidates, dfilt)
-        stream = torch.cuda.current_stream(cs.device).cuda_stream
-        codes = torch.full(tuple(cr.shape), -1, dtype=torch.int32, device=cr.device)
-        for s in self.owned:
-            self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes, stream=stream)
-        self.complete_codes(codes)
-        if ungrouped is not None:
-            codes.masked_fill_(codes == int(ungrouped), -1)
-        return ffi.group_select(cs, cr, codes, k, group_size, stream=stream)
-
-    def search_grouped(self, queries: np.ndarray, k: int, candidates: int, col: int, group_size: int, dfilt, ungrouped: int | None = None):
-        """One round of the grouped search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], codes i32 [nq, k],
-        info i32 [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits whose rank in their column-``col`` group is below
-        ``group_size`` (a candidate whose code is negative or ``ungrouped`` is never capped and comes back with code -1); -1 rows
-        are padding; ``info`` = (kept in the whole list, real candidates), what the store's exactness
-        rounds decide on.  Indexes that hold a native handle take :meth:`search_grouped_device`; injected host-side indexes
-        (CPU test tier) run the same steps on numpy arrays."""
-        if all(hasattr(ix, "_handle") for ix in self.index.values()):
-            _, rd, sd, cd, info = self.search_grouped_device(queries, k, candidates, col, group_size, dfilt, ungrouped)
-            return sd.cpu().numpy(), rd.cpu().numpy(), cd.cpu().numpy(), info.cpu().numpy()
-        if self.ns == 1:
-            cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
-        else:
-            cs, cr = self._search_host(queries, candidates, dfilt)
-        cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
-        codes = np.full(cr.shape, -1, np.int32)
-        for s in self.owned:
-            self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes)
-        if self.dist is not None:
-            import torch
-            t = torch.from_numpy(codes)
-            self.complete_codes(t)
-            codes = t.numpy()
-        if ungrouped is not None:
-            codes = np.where(codes == int(ungrouped), -1, codes).astype(np.int32)
-        _, rows, scores, gcodes, info = ffi.group_select(cs, cr, codes, k, group_size)
-        return np.asarray(scores, np.float32), np.asarray(rows, np.int64), np.asarray(gcodes, np.int32), np.asarray(info, np.int32)
-
-    # ------------------------------------------------------------------ overlap-free hit lists (max_overlap; DESIGN.md 3.19)
-    def search_spans_device(self, queries, k: int, candidates: int, cols: tuple[int, int, int], permille: int, dfilt, no_file: int | None = None):
-        """The overlap-free walk on the device, results left there: :meth:`search_device` for ``candidates`` hits per query,
-        every local shard writes the codes of the columns ``cols`` = (file, first line, last line) of the rows it owns into
-        one ``[3, nq, candidates]`` int32 buffer pre-filled with -1 (ONE :meth:`complete_codes` -- all-reduce(MAX) -- finishes
-        the three under backend "dist"), then ``crh_span_select``.  ``no_file``: the file code that names no file (the store's
-        code of "no value"): candidates that carry it have no span.  Returns CUDA tensors ``(pos i32, GLOBAL rows i64, scores
-        f32, file i32, lo i32, hi i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (kept, real)."""
-        import torch
-        cs, cr = self.search_device(queries, candidates, dfilt)
-        stream = torch.cuda.current_stream(cs.device).cuda_stream
-        codes = torch.full((3,) + tuple(cr.shape), -1, dtype=torch.int32, device=cr.device)
-        for s in self.owned:
-            for i, col in enumerate(cols):
-                self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes[i], stream=stream)
-        self.complete_codes(codes)
-        if no_file is not None:
-            codes[0].masked_fill_(codes[0] == int(no_file), -1)
-        return ffi.span_select(cs, cr, codes[0], codes[1], codes[2], k, permille, stream=stream)
-
-    def search_spans(self, queries: np.ndarray, k: int, candidates: int, cols: tuple[int, int, int], permille: int, dfilt, no_file: int | None = None):
-        """One round of the ``max_overlap`` search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], info i32
-        [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits that repeat at most ``permille`` thousandths of the shorter
-        span of any better kept hit of their file; -1 rows are padding; ``info`` = (kept in the whole list, real candidates),
-        what the store's exactness rounds decide on.  Indexes that hold a native handle take :meth:`search_spans_device`;
-        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
-        if all(hasattr(ix, "_handle") for ix in self.index.values()):
-            out = self.search_spans_device(queries, k, candidates, cols, permille, dfilt, no_file)
-            return out[2].cpu().numpy(), out[1].cpu().numpy(), out[6].cpu().numpy()
-        if self.ns == 1:
-            cs, cr = self.index[0].search(queries, candidates, filters=dfilt)
-        else:
-            cs, cr = self._search_host(queries, candidates, dfilt)
-        cs, cr = np.asarray(cs, np.float32), np.asarray(cr, np.int64)
-        codes = np.full((3,) + cr.shape, -1, np.int32)
-        for s in self.owned:
-            for i, col in enumerate(cols):
-                self.index[s].gather_codes(cr, col, row_base=s * STRIDE, out=codes[i])
-        if self.dist is not None:
-            import torch
-            t = torch.from_numpy(codes)
-            self.complete_codes(t)
-            codes = t.numpy()
-        if no_file is not None:
-            codes[0] = np.where(codes[0] == int(no_file), -1, codes[0])
-        out = ffi.span_select(cs, cr, codes[0], codes[1], codes[2], k, permille)
-        return np.asarray(out[2], np.float32), np.asarray(out[1], np.int64), np.asarray(out[6], np.int32)
-
-    # ------------------------------------------------------------------ multi-query fusion (RRF / best match; DESIGN.md 3.16)
-    def search_fused_device(self, queries, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
-        """Fusion on the device, results left there: ``queries`` [nq, m, dim] -- the ``m`` sub-queries of ``nq`` logical ones --
-        are searched as ``nq * m`` plain queries (:meth:`search_device`, ``candidates`` hits each: the merged lists carry
-        GLOBAL rows), then ``crh_fuse_select`` turns every ``m`` lists into one.  ``live`` (bool [nq, m], host): the real
-        members of ragged sets; the lists of the others are overwritten with padding before the fusion.  Under backend "dist"
-        every rank holds the same merged lists and fuses them itself: no collective is added.  Returns CUDA tensors ``(GLOBAL
-        rows i64, fused f32, cos f32, lists i32, first i32)``, each [nq, k], and ``info`` i32 [nq, 2] = (distinct, real)."""
-        import torch
-        nq, m = int(queries.shape[0]), int(queries.shape[1])
-        flat = queries.reshape(nq * m, int(queries.shape[2]))
-        cs, cr = self.search_device(flat, candidates, dfilt)
-        stream = torch.cuda.current_stream(cs.device).cuda_stream
-        if live is not None:
-            dead = torch.from_numpy(~np.asarray(live, bool).reshape(nq * m)).to(cs.device)
-            cs.masked_fill_(dead[:, None], float("-inf"))
-            cr.masked_fill_(dead[:, None], -1)
-        return ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights, stream=stream)
-
-    def search_fused(self, queries: np.ndarray, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
-        """:meth:`search_fused_device` as host arrays: ``(GLOBAL rows i64, fused f32, cos f32, lists i32, first i32)``, each
-        [nq, k], and ``info`` i32 [nq, 2]; -1 rows are padding.  Indexes that hold a native handle take the device form;
-        injected host-side indexes (CPU test tier) run the same steps on numpy arrays."""
-        if all(hasattr(ix, "_handle") for ix in self.index.values()):
-            return tuple(t.cpu().numpy() for t in self.search_fused_device(queries, k, candidates, dfilt, method, rrf_k, weights, live))
-        queries = np.asarray(queries, np.float32)
-        nq, m = int(queries.shape[0]), int(queries.shape[1])
-        flat = np.ascontiguousarray(queries.reshape(nq * m, queries.shape[2]))
-        if self.ns == 1:
-            cs, cr = self.index[0].search(flat, candidates, filters=dfilt)
-        else:
-            cs, cr = self._search_host(flat, candidates, dfilt)
-        cs, cr = np.array(cs, np.float32), np.array(cr, np.int64)
-        if live is not None:
-            dead = ~np.asarray(live, bool).reshape(nq * m)
-            cs[dead], cr[dead] = -np.inf, -1
-        return tuple(np.asarray(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights))
-
-    # ------------------------------------------------------------------ keyword search (BM25; DESIGN.md 3.20)
-    # ``lex`` = {shard: ffi.Lex}: the forward indexes beside the owned shards, rows numbered like the shards' (the collection
-    # builds and keeps them).  Tombstones and filters reach them as the validity words of ``Index.row_mask`` only.
+    # Every search feature is ONE pipeline on arrays "where the indexes live" -- CUDA tensors for native indexes, numpy arrays
+    # for the injected host-side indexes of the CPU test tier (whose ``ffi.*_select`` are numpy restatements):
+    #   1. the top-c candidate lists with GLOBAL rows (_candidates: per-shard search, [one all-gather,] merge);
+    #   2. optionally the lists of absent members overwritten with padding (_mask_lists);
+    #   3. the candidates' codes or vectors gathered from the owning shards into a pre-filled buffer and completed by one
+    #      all-reduce (_gather_codes, _gather_everywhere; reduce);
+    #   4. one ``ffi.*_select``;  5. ``_host``.
+    # Only the helpers of this first part know which kind of array they hold; no feature below does.
     def _native(self) -> bool:
         return all(hasattr(ix, "_handle") for ix in self.index.values())
 
@@ -638,6 +296,231 @@ class ShardSet:
         ffi.use_device(self.device)
         return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
 
+    def _local(self, a: np.ndarray):
+        """A host array where the indexes live."""
+        if not self._native():
+            return a
+        import torch
+        return torch.from_numpy(a).to(torch.device("cuda", self.device))
+
+    def _full(self, shape, value, dtype: str):
+        """A buffer full of ``value`` where the indexes live."""
+        if not self._native():
+            return np.full(shape, value, dtype)
+        import torch
+        return torch.full(shape, value, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
+
+    def reduce(self, x, op: str):
+        """The one all-reduce (``op``: "SUM" | "MAX") of a buffer every rank filled for the rows it owns, in place; nothing to
+        do without ``dist``.  A host array travels as the tensor that shares its memory (gloo).  Candidate vectors (zeros
+        elsewhere, SUM: ``nq * candidates * dim * 4`` bytes, 3 MB for one 768-wide query at 1024 candidates), codes (-1 elsewhere,
+        stored codes are >= -1: MAX), in-range counts and the re-rank's side columns (SUM) are completed by it.  On more than one
+        RCCL rank it has never run: the two-rank form is exercised with gloo on host tensors only."""
+        if self.dist is not None:
+            import torch
+            self.dist.all_reduce(x if torch.is_tensor(x) else torch.from_numpy(x), op=getattr(self.dist.ReduceOp, op), group=self.group)
+        return x
+
+    @staticmethod
+    def _shard_search(ix, queries, k, dfilt, multi, thr, **kw):
+        """One shard's part of a search: under one filter; or -- ``multi`` = (class_filters, query_class) -- under every query's
+        own; or -- ``thr`` -- with a score threshold per query (``counts`` among ``kw``)."""
+        if thr is not None:
+            return ix.search_range(queries, k, thr, filters=dfilt, **kw)
+        if multi is None:
+            return ix.search(queries, k, filters=dfilt, **kw)
+        return ix.search_multi(queries, k, multi[0], multi[1], **kw)
+
+    def _scan(self, queries, k: int, dfilt, multi=None, thr=None, counts: bool = False):
+        """The per-shard dispatch and the exchange-and-merge of every search: each owned shard searches with ``row_base`` =
+        shard * STRIDE (``crh_search`` / ``crh_search_multi`` / ``crh_search_range``), under backend "dist" ONE all-gather moves
+        the ``[scores | rows]`` records, and the lists merge (a cut list's padding merges like any other: the merged list of a
+        range search is the first ``min(k, count)`` in-range rows of the whole collection).  ``counts``: the in-range counts
+        are summed over the owned shards and completed by :meth:`reduce`.  Native shards write their own record of the
+        gathered buffer on the current stream; injected host indexes return theirs.  Returns ``(scores f32 [nq, k], GLOBAL rows
+        i64 [nq, k], counts i64 [nq] or None)`` where the indexes live."""
+        native, on = self._native(), self.dist is None
+        if native:
+            import torch
+            dev, stream = torch.device("cuda", self.device), self._stream()
+            if not torch.is_tensor(queries):
+                queries = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
+        elif not on:
+            import torch
+            dev = torch.device("cpu")
+        nq = int(queries.shape[0])
+        if native or not on:
+            local, loc_s, loc_r, gathered, all_s, all_r = ffi.topk_exchange_buffers(torch, self.ns, nq, k, dev)
+        part = torch.zeros((len(self.owned), nq), dtype=torch.int64, device=dev) if native and counts else None
+        got = {}
+        for i, s in enumerate(self.owned):
+            kw = {"row_base": s * STRIDE}
+            if thr is not None:
+                kw["counts"] = counts
+            if native:                               # every shard writes its own record of the "gathered" buffer
+                kw.update(out_scores=all_s[s] if on else loc_s, out_rows=all_r[s] if on else loc_r, stream=stream)
+                if thr is not None:
+                    kw["out_counts"] = part[i] if counts else None
+            got[s] = self._shard_search(self.index[s], queries, k, dfilt, multi, thr, **kw)
+        if native:
+            for s in self.owned:
+                self.index[s].search_finish(stream)
+        elif on:
+            all_s, all_r = (np.stack([got[s][j] for s in range(self.ns)]) for j in (0, 1))
+        else:
+            loc_s.copy_(torch.from_numpy(np.ascontiguousarray(got[self.rank][0])))
+            loc_r.copy_(torch.from_numpy(np.ascontiguousarray(got[self.rank][1])))
+        if not on:
+            self.dist.all_gather_into_tensor(gathered.view(-1), local, group=self.group)
+            if not native:
+                all_s, all_r = all_s.numpy(), all_r.numpy()
+        total = None
+        if counts:
+            total = self.reduce(part.sum(0) if native else sum(np.asarray(got[s][2], np.int64) for s in self.owned), "SUM")
+        return self._merge(all_s, all_r, stream if native else 0) + (total,)
+
+    def _merge(self, all_s, all_r, stream: int):
+        """Per-shard lists ``[ns, nq, k]`` (padding -inf / -1) -> the merged ``(scores, rows)`` [nq, k], ties to the lower GLOBAL
+        row: ``crh_merge_topk_strided`` on ``stream``, or the injected host merge."""
+        if not self._native():
+            s, r = self._merge_host(all_s, all_r)
+            return np.asarray(s, np.float32), np.asarray(r, np.int64)
+        import torch
+        out_s = torch.empty(tuple(all_s.shape[1:]), dtype=torch.float32, device=all_s.device)
+        out_r = torch.empty(tuple(all_r.shape[1:]), dtype=torch.int64, device=all_r.device)
+        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
+        return out_s, out_r
+
+    def _plain(self, queries, k: int, dfilt, multi=None, thr=None, counts: bool = False) -> tuple:
+        """A plain, mixed-filter or thresholded search as host arrays: ``(scores [nq, k], shard [nq, k], local row [nq, k])``
+        and, with ``thr``, ``counts int64 [nq] or None``; -1 rows are padding.  ONE shard answers directly -- no row base, no
+        merge, no torch allocation: the coalescer's and the benchmark's path."""
+        ranged = () if thr is None else (counts,)
+        if self.ns == 1:
+            kw = {"counts": counts} if ranged else {}
+            if self.stream:
+                kw["stream"] = self.stream
+            out = self._shard_search(self.index[0], queries, k, dfilt, multi, thr, **kw)
+            return (out[0], np.zeros(out[1].shape, np.int32), out[1]) + tuple(out[2:])
+        scores, rows, total = self._scan(queries, k, dfilt, multi, thr, *ranged)
+        return (_host(scores),) + split_global(_host(rows)) + ((_host(total) if counts else None,) if ranged else ())
+
+    def search(self, queries: np.ndarray, k: int, dfilt) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Exact top-k over all shards: (scores [nq, k], shard [nq, k], local row [nq, k]); -1 rows are padding."""
+        return self._plain(queries, k, dfilt)
+
+    def search_multi(self, queries: np.ndarray, k: int, class_filters, query_class) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search` for a batch whose queries carry different filters (``ffi.Index.search_multi``): query ``i`` under
+        ``class_filters[query_class[i]]``.  The same per-shard plan as :meth:`search` -- every shard answers the whole batch
+        under the same classes, [one all-gather,] one merge."""
+        return self._plain(queries, k, None, multi=(list(class_filters), np.asarray(query_class, np.int32)))
+
+    def search_range(self, queries: np.ndarray, k: int, thresholds, dfilt, counts: bool = True):
+        """:meth:`search` with a score threshold per query: ``(scores [nq, k], shard [nq, k], local row [nq,
+        k], counts int64 [nq] or None)``; -1 rows are padding."""
+        return self._plain(queries, k, dfilt, thr=ffi.range_thresholds(thresholds, len(queries)), counts=counts)
+
+    def search_device(self, queries, k: int, dfilt, multi=None):
+        """:meth:`search` on the device, results left there: (scores f32 [nq, k], GLOBAL rows i64 [nq, k]) CUDA tensors -- per-shard
+        ``crh_search`` with ``row_base`` = shard * STRIDE, [one all-gather of the records,] ``crh_merge_topk_strided``, at one
+        shard too.  ``multi`` = (class_filters, query_class): every query under its own filter (``crh_search_multi``), ``dfilt``
+        unused.  What the device re-rank starts from."""
+        return self._scan(queries, k, dfilt, multi)[:2]
+
+    def _candidates(self, queries, c: int, dfilt):
+        """The top-``c`` lists of ``queries`` with GLOBAL rows, where the indexes live: ``(scores f32 [nq, c], rows i64 [nq, c])``.
+        Native shards take :meth:`search_device`, one shard included; ONE injected index answers directly."""
+        if self._native() or self.ns > 1:
+            return self._scan(queries, c, dfilt)[:2]
+        s, r = self.index[0].search(queries, c, filters=dfilt)
+        return np.array(s, np.float32), np.array(r, np.int64)
+
+    def _mask_lists(self, cs, cr, dead: np.ndarray) -> None:
+        """Overwrite the lists of the absent members of ragged sets (``dead``: host bool, one per list) with padding, in place."""
+        dead = self._local(dead)[:, None]
+        _put(cs, dead, float("-inf"))
+        _put(cr, dead, -1)
+
+    def _gather_codes(self, rows, cols, none_code: int | None = None):
+        """Codes of the payload column(s) ``cols`` of a table of GLOBAL rows: int32 of ``rows``' shape -- one plane per column
+        for a tuple of columns -- pre-filled with -1, every owned shard writes the rows it owns, ONE :meth:`reduce` (MAX)
+        completes all planes.  ``none_code``: the store's code of "no value" in the (first) column becomes -1 too."""
+        one = isinstance(cols, (int, np.integer))
+        codes = self._full((() if one else (len(cols),)) + tuple(rows.shape), -1, "int32")
+        stream = self._stream()
+        for s in self.owned:
+            for i, col in enumerate([cols] if one else cols):
+                self.index[s].gather_codes(rows, col, row_base=s * STRIDE, out=codes if one else codes[i], stream=stream)
+        self.reduce(codes, "MAX")
+        if none_code is not None:
+            first = codes if one else codes[0]
+            _put(first, first == int(none_code), -1)
+        return codes
+
+    def _gather_everywhere(self, rows, stream: int = 0):
+        """Stored vectors of a table of GLOBAL rows, f32 ``rows.shape + (dim,)``: a row has one owner and the others contribute
+        zeros (padding too), so the owned shards' gathers are summed and ONE :meth:`reduce` (SUM) completes the buffer."""
+        vecs = None
+        for s in self.owned:
+            part = self.index[s].gather_vectors(rows, row_base=s * STRIDE, stream=stream)
+            if vecs is None:
+                vecs = part
+            else:
+                vecs += part
+        return self.reduce(vecs, "SUM")
+
+    # ------------------------------------------------------------------ diversity-aware top-k (MMR; DESIGN.md 3.12)
+    def search_mmr(self, queries: np.ndarray, k: int, candidates: int, diversity: float, dfilt) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search` with diversity: (scores [nq, k], shard [nq, k], local row [nq, k]) of the ``crh_mmr_select`` picks among
+        the ``candidates`` best hits of every query, over their gathered stored vectors; ``scores`` are the picks' cosines, -1
+        rows are padding."""
+        cs, cr = self._candidates(queries, candidates, dfilt)
+        stream = self._stream()
+        _, rows, scores, _ = ffi.mmr_select(cs, cr, self._gather_everywhere(cr, stream), k, diversity, stream=stream)
+        return (_host(scores),) + split_global(_host(rows))
+
+    # ------------------------------------------------------------------ per-group cap (group_by / group_size; DESIGN.md 3.13)
+    def search_grouped(self, queries: np.ndarray, k: int, candidates: int, col: int, group_size: int, dfilt, ungrouped: int | None = None):
+        """One round of the grouped search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], codes i32 [nq, k],
+        info i32 [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits whose rank in their column-``col`` group is below
+        ``group_size`` (``crh_group_select`` over the gathered codes; a candidate whose code is negative or ``ungrouped`` -- the
+        store's code of "no value" -- is never capped and comes back with code -1); -1 rows are padding; ``info`` = (kept in the
+        whole list, real candidates), what the store's exactness rounds decide on."""
+        cs, cr = self._candidates(queries, candidates, dfilt)
+        codes = self._gather_codes(cr, col, ungrouped)
+        _, rows, scores, gcodes, info = ffi.group_select(cs, cr, codes, k, group_size, stream=self._stream())
+        return _host(scores), _host(rows), _host(gcodes), _host(info)
+
+    # ------------------------------------------------------------------ overlap-free hit lists (max_overlap; DESIGN.md 3.19)
+    def search_spans(self, queries: np.ndarray, k: int, candidates: int, cols: tuple[int, int, int], permille: int, dfilt, no_file: int | None = None):
+        """One round of the ``max_overlap`` search as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], info i32
+        [nq, 2])`` -- the first ``k`` of the ``candidates`` best hits that repeat at most ``permille`` thousandths of the shorter
+        span of any better kept hit of their file (``crh_span_select`` over the gathered codes of ``cols`` = (file, first line,
+        last line): three planes, ONE all-reduce; a candidate whose file code is ``no_file`` -- the store's code of "no value" --
+        has no span); -1 rows are padding; ``info`` = (kept in the whole list, real candidates), what the store's exactness
+        rounds decide on."""
+        cs, cr = self._candidates(queries, candidates, dfilt)
+        codes = self._gather_codes(cr, cols, no_file)
+        out = ffi.span_select(cs, cr, codes[0], codes[1], codes[2], k, permille, stream=self._stream())
+        return _host(out[2]), _host(out[1]), _host(out[6])
+
+    # ------------------------------------------------------------------ multi-query fusion (RRF / best match; DESIGN.md 3.16)
+    def search_fused(self, queries: np.ndarray, k: int, candidates: int, dfilt, method: str = "rrf", rrf_k: int = 60, weights=None, live=None):
+        """Fusion as host arrays: ``queries`` [nq, m, dim] -- the ``m`` sub-queries of ``nq`` logical ones -- are searched as
+        ``nq * m`` plain queries, ``candidates`` hits each, then ``crh_fuse_select`` turns every ``m`` lists into one.  ``live``
+        (bool [nq, m], host): the real members of ragged sets; the lists of the others are overwritten with padding before the
+        fusion.  Under backend "dist" every rank holds the same merged lists and fuses them itself: no collective is added.
+        Returns ``(GLOBAL rows i64, fused f32, cos f32, lists i32, first i32)``, each [nq, k], and ``info`` i32 [nq, 2] =
+        (distinct, real); -1 rows are padding."""
+        nq, m = int(queries.shape[0]), int(queries.shape[1])
+        cs, cr = self._candidates(queries.reshape(nq * m, int(queries.shape[2])), candidates, dfilt)
+        if live is not None:
+            self._mask_lists(cs, cr, ~np.asarray(live, bool).reshape(nq * m))
+        return tuple(_host(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights, stream=self._stream()))
+
+    # ------------------------------------------------------------------ keyword search (BM25; DESIGN.md 3.20)
+    # ``lex`` = {shard: ffi.Lex}: the forward indexes beside the owned shards, rows numbered like the shards' (the collection
+    # builds and keeps them).  Tombstones and filters reach them as the validity words of ``Index.row_mask`` only.
     def lex_stats(self, lex: dict, terms) -> tuple[np.ndarray, int, int]:
         """``(df int64 per term, N, sum_dl)`` over the ALIVE rows of every shard, summed: the statistics of the whole
         collection, whatever filter a search runs under."""
@@ -651,64 +534,39 @@ class ShardSet:
             df, rows, total = df + d, rows + r, total + t
         return df, rows, total
 
-    def lex_search_device(self, lex: dict, queries, idf, k: int, k1: float, b: float, avgdl: float, dfilt):
-        """Exact BM25 top-k over all shards, results left where the indexes live: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k],
-        counts i64 [nq])`` -- per shard ``crh_index_row_mask`` + ``crh_lex_search`` with ``row_base`` = shard * STRIDE, then
-        ``crh_merge_topk_strided``; the counts are summed.  Injected host-side indexes (CPU test tier) return numpy arrays."""
-        nq, native = len(queries), self._native()
-        stream = self._stream()
-        if native:
-            import torch
-            dev = torch.device("cuda", self.device)
-            all_s = torch.full((self.ns, nq, k), float("-inf"), dtype=torch.float32, device=dev)
-            all_r = torch.full((self.ns, nq, k), -1, dtype=torch.int64, device=dev)
-            counts = torch.zeros((nq,), dtype=torch.int64, device=dev)
-        else:
-            all_s, all_r = np.full((self.ns, nq, k), -np.inf, np.float32), np.full((self.ns, nq, k), -1, np.int64)
-            counts = np.zeros((nq,), np.int64)
+    def _lex_lists(self, lex: dict, queries, idf, k: int, k1: float, b: float, avgdl: float, dfilt):
+        """Exact BM25 top-k over all shards, where the indexes live: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], counts i64
+        [nq])`` -- per shard ``crh_index_row_mask`` + ``crh_lex_search`` with ``row_base`` = shard * STRIDE into its own part of
+        one table full of padding, then the merge of :meth:`_scan` (none at one shard); the counts are summed."""
+        nq, stream = len(queries), self._stream()
+        all_s, all_r = self._full((self.ns, nq, k), float("-inf"), "float32"), self._full((self.ns, nq, k), -1, "int64")
+        counts = self._full((nq,), 0, "int64")
         for s, ix in self.index.items():
             if self.rows[s] == 0:
                 continue
             mask = ix.row_mask(dfilt, stream=stream)
-            out = {"out_scores": all_s[s], "out_rows": all_r[s]} if native else {}      # (every shard writes its own part of the table)
-            ps, pr, pc = lex[s].search(queries, idf, k, k1, b, avgdl, mask=mask, row_base=s * STRIDE, stream=stream, **out)
-            if not native:
-                all_s[s], all_r[s] = ps, pr
+            mine_s, mine_r = all_s[s], all_r[s]      # (every shard writes its own part of the table)
+            ps, pr, pc = lex[s].search(queries, idf, k, k1, b, avgdl, mask=mask, row_base=s * STRIDE, stream=stream, out_scores=mine_s, out_rows=mine_r)
+            if ps is not mine_s:                     # (a host-side index returns its lists)
+                mine_s[...], mine_r[...] = ps, pr
             counts += pc
         if self.ns == 1:
             return all_s[0], all_r[0], counts
-        if not native:
-            ms, mr = self._merge_host(all_s, all_r)
-            return ms, mr, counts
-        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
-        ffi.merge_topk(all_s, all_r, out_s, out_r, stream)
-        return out_s, out_r, counts
+        return self._merge(all_s, all_r, stream) + (counts,)
 
     def lex_search(self, lex: dict, queries, idf, k: int, k1: float, b: float, avgdl: float, dfilt):
-        """:meth:`lex_search_device` as host arrays."""
-        return tuple(_host(a) for a in self.lex_search_device(lex, queries, idf, k, k1, b, avgdl, dfilt))
+        """Exact BM25 top-k over all shards as host arrays: ``(scores f32 [nq, k], GLOBAL rows i64 [nq, k], counts i64 [nq])``."""
+        return tuple(_host(a) for a in self._lex_lists(lex, queries, idf, k, k1, b, avgdl, dfilt))
 
     def search_hybrid(self, lex: dict, vectors: np.ndarray, queries, idf, k: int, candidates: int, k1: float, b: float, avgdl: float,
                       dfilt, rrf_k: int = 60, weights=None):
-        """Dense + keyword, fused: the dense top-``candidates`` (:meth:`search_device`) and the BM25 top-``candidates``
-        (:meth:`lex_search_device`) of every query under the same filter, as ``[nq, 2, candidates]``, into ``crh_fuse_select``
-        with ``m = 2`` and reciprocal-rank fusion.  Returns host arrays: the fusion's ``(GLOBAL rows, fused, cos, lists, first,
-        info)`` and the two candidate tables ``(dense scores, dense rows, lexical scores, lexical rows)``."""
-        nq = len(queries)
-        if self._native():
-            import torch
-            ds, dr = self.search_device(vectors, candidates, dfilt)
-            ls, lr, _ = self.lex_search_device(lex, queries, idf, candidates, k1, b, avgdl, dfilt)
-            cs, cr = torch.stack([ds, ls], dim=1).contiguous(), torch.stack([dr, lr], dim=1).contiguous()
-            fused = ffi.fuse_select(cs, cr, 2, k, "rrf", rrf_k, weights, stream=self._stream())
-        else:
-            vectors = np.ascontiguousarray(vectors, dtype=np.float32)
-            ds, dr = self.index[0].search(vectors, candidates, filters=dfilt) if self.ns == 1 else self._search_host(vectors, candidates, dfilt)
-            ls, lr, _ = self.lex_search_device(lex, queries, idf, candidates, k1, b, avgdl, dfilt)
-            cs = np.stack([np.asarray(ds, np.float32), np.asarray(ls, np.float32)], axis=1).reshape(nq, 2, candidates)
-            cr = np.stack([np.asarray(dr, np.int64), np.asarray(lr, np.int64)], axis=1).reshape(nq, 2, candidates)
-            fused = ffi.fuse_select(cs, cr, 2, k, "rrf", rrf_k, weights)
+        """Dense + keyword, fused: the dense top-``candidates`` and the BM25 top-``candidates`` (:meth:`_lex_lists`) of every
+        query under the same filter, as ``[nq, 2, candidates]``, into ``crh_fuse_select`` with ``m = 2`` and reciprocal-rank
+        fusion.  Returns host arrays: the fusion's ``(GLOBAL rows, fused, cos, lists, first, info)`` and the two candidate
+        tables ``(dense scores, dense rows, lexical scores, lexical rows)``."""
+        ds, dr = self._candidates(vectors, candidates, dfilt)
+        ls, lr, _ = self._lex_lists(lex, queries, idf, candidates, k1, b, avgdl, dfilt)
+        fused = ffi.fuse_select(_pair(ds, ls), _pair(dr, lr), 2, k, "rrf", rrf_k, weights, stream=self._stream())
         return tuple(_host(a) for a in fused), tuple(_host(a) for a in (ds, dr, ls, lr))
 
     # ------------------------------------------------------------------ recommend by example (DESIGN.md 3.17)
@@ -728,99 +586,34 @@ class ShardSet:
             out = t.cpu().numpy()
         return out.astype(bool)
 
-    def _gather_everywhere(self, rows_dev, stream):
-        """Stored vectors of a table of GLOBAL rows, completed across the shards as :meth:`search_mmr_device` does."""
-        vecs = None
-        for s in self.owned:
-            part = self.index[s].gather_vectors(rows_dev, row_base=s * STRIDE, stream=stream)
-            if vecs is None:
-                vecs = part
-            else:
-                vecs += part
-        self.complete_vectors(vecs)
-        return vecs
-
-    def recommend_device(self, example_rows, P: int, N: int, k: int, candidates: int, dfilt, strategy: str = "average", n_pos=None, n_neg=None):
-        """Recommend by example on the device, results left there.  ``example_rows`` (host int64 [nq, P + N]): the GLOBAL rows
-        of every query's examples, positives first, -1 for an unused slot; ``n_pos`` / ``n_neg`` (host int [nq] or None) the
-        live counts of ragged sets.  The examples' stored vectors are gathered across the shards (:meth:`complete_vectors`
-        under backend "dist").  ``"average"``: ``crh_recommend_query`` makes one query per set, :meth:`search_device` answers it
-        with ``candidates`` hits and ``crh_recommend_select`` drops the example rows.  ``"best"``: the ``nq * P`` positives are
-        searched as plain device queries (``candidates`` hits each; the lists of absent positives are overwritten with
-        padding), the candidates' vectors gathered, and ``crh_recommend_select`` applies the veto, ranks and counts the settled
-        prefix.  Returns CUDA tensors ``(GLOBAL rows i64, score f32, neg f32, best i32)``, each [nq, k], ``info`` i32 [nq, 4] =
-        (kept, settled, distinct, vetoed) and ``full`` bool [nq]: whether any of the query's lists came back full."""
-        import torch
-        code = ffi.recommend_strategy(strategy)
-        dev = torch.device("cuda", self.device)
-        ffi.use_device(self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        er = torch.from_numpy(np.ascontiguousarray(example_rows, dtype=np.int64)).to(dev)
-        nq, E = int(er.shape[0]), P + N
-        examples = self._gather_everywhere(er, stream)                    # [nq, P + N, dim]
-        bf16 = self.dtype == ffi.DTYPE_BF16
-        if code == ffi.RECOMMEND_AVERAGE:
-            q = ffi.recommend_query(examples, P, N, n_pos, n_neg, stream=stream)
-            cs, cr = self.search_device(q, candidates, dfilt)
-            cs, cr = cs.view(nq, 1, candidates), cr.view(nq, 1, candidates)
-            vecs = None
-        else:
-            cs, cr = self.search_device(examples[:, :P].reshape(nq * P, self.dim), candidates, dfilt)
-            if n_pos is not None:
-                dead = torch.from_numpy((np.arange(P)[None, :] >= np.asarray(n_pos).reshape(nq, 1)).reshape(nq * P)).to(dev)
-                cs.masked_fill_(dead[:, None], float("-inf"))
-                cr.masked_fill_(dead[:, None], -1)
-            vecs = self._gather_everywhere(cr, stream).view(nq, P * candidates, self.dim)
-            cs, cr = cs.view(nq, P, candidates), cr.view(nq, P, candidates)
-        full = (cr[:, :, -1] >= 0).any(1)
-        return ffi.recommend_select(cs, cr, vecs, examples, er, P, N, k, strategy, bf16, n_pos, n_neg, stream=stream) + (full,)
-
-    def _read_global(self, rows: np.ndarray) -> np.ndarray:
-        """``read_rows`` of a table of GLOBAL rows on host arrays (zeros for padding and for rows of shards owned elsewhere,
-        which :meth:`complete_vectors` adds)."""
-        rows = np.asarray(rows, np.int64)
-        out = np.zeros(rows.shape + (self.dim,), np.float32)
-        flat_r, flat_o = rows.reshape(-1), out.reshape(-1, self.dim)
-        for i in np.flatnonzero(flat_r >= 0):
-            s, lo = int(flat_r[i] // STRIDE), int(flat_r[i] % STRIDE)
-            if s in self.index:
-                flat_o[i] = self.index[s].read_rows(lo, 1)[0]
-        if self.dist is not None:
-            import torch
-            t = torch.from_numpy(out)
-            self.complete_vectors(t)
-        return out
-
     def recommend(self, example_rows, P: int, N: int, k: int, candidates: int, dfilt, strategy: str = "average", n_pos=None, n_neg=None):
-        """:meth:`recommend_device` as host arrays: ``(GLOBAL rows i64, score f32, neg f32, best i32)``, each [nq, k], ``info``
-        i32 [nq, 4] and ``full`` bool [nq]; -1 rows are padding.  Indexes that hold a native handle take the device form;
-        injected host-side indexes (CPU test tier) run the same steps on numpy arrays out of ``search`` and ``read_rows``."""
-        if all(hasattr(ix, "_handle") for ix in self.index.values()):
-            return tuple(t.cpu().numpy() for t in self.recommend_device(example_rows, P, N, k, candidates, dfilt, strategy, n_pos, n_neg))
+        """Recommend by example as host arrays.  ``example_rows`` (host int64 [nq, P + N]): the GLOBAL rows of every query's
+        examples, positives first, -1 for an unused slot; ``n_pos`` / ``n_neg`` (host int [nq] or None) the live counts of ragged
+        sets.  The examples' stored vectors are gathered across the shards.  ``"average"``: ``crh_recommend_query`` makes one
+        query per set, its ``candidates`` best hits are searched and ``crh_recommend_select`` drops the example rows.
+        ``"best"``: the ``nq * P`` positives are searched as plain queries (``candidates`` hits each; the lists of absent
+        positives are overwritten with padding), the candidates' vectors gathered, and ``crh_recommend_select`` applies the
+        veto, ranks and counts the settled prefix.  Returns ``(GLOBAL rows i64, score f32, neg f32, best i32)``, each [nq, k],
+        ``info`` i32 [nq, 4] = (kept, settled, distinct, vetoed) and ``full`` bool [nq]: whether any of the query's lists came
+        back full; -1 rows are padding."""
         code = ffi.recommend_strategy(strategy)
-        er = np.ascontiguousarray(example_rows, dtype=np.int64)
+        stream = self._stream()
+        er = self._local(np.ascontiguousarray(example_rows, dtype=np.int64))
         nq = int(er.shape[0])
-        examples = self._read_global(er)
-
-        def search(queries):
-            if self.ns == 1:
-                s, r = self.index[0].search(queries, candidates, filters=dfilt)
-            else:
-                s, r = self._search_host(queries, candidates, dfilt)
-            return np.array(s, np.float32), np.array(r, np.int64)
-        bf16 = self.dtype == ffi.DTYPE_BF16
+        examples = self._gather_everywhere(er, stream)                    # [nq, P + N, dim]
         if code == ffi.RECOMMEND_AVERAGE:
-            cs, cr = search(np.asarray(ffi.recommend_query(examples, P, N, n_pos, n_neg), np.float32))
-            cs, cr, vecs = cs.reshape(nq, 1, candidates), cr.reshape(nq, 1, candidates), None
+            m, vecs = 1, None
+            cs, cr = self._candidates(ffi.recommend_query(examples, P, N, n_pos, n_neg, stream=stream), candidates, dfilt)
         else:
-            cs, cr = search(np.ascontiguousarray(examples[:, :P].reshape(nq * P, self.dim)))
+            m = P
+            cs, cr = self._candidates(examples[:, :P].reshape(nq * P, self.dim), candidates, dfilt)
             if n_pos is not None:
-                dead = (np.arange(P)[None, :] >= np.asarray(n_pos).reshape(nq, 1)).reshape(nq * P)
-                cs[dead], cr[dead] = -np.inf, -1
-            vecs = self._read_global(cr).reshape(nq, P * candidates, self.dim)
-            cs, cr = cs.reshape(nq, P, candidates), cr.reshape(nq, P, candidates)
+                self._mask_lists(cs, cr, (np.arange(P)[None, :] >= np.asarray(n_pos).reshape(nq, 1)).reshape(nq * P))
+            vecs = self._gather_everywhere(cr, stream).reshape(nq, P * candidates, self.dim)
+        cs, cr = cs.reshape(nq, m, candidates), cr.reshape(nq, m, candidates)
         full = (cr[:, :, -1] >= 0).any(1)
-        return tuple(np.asarray(a) for a in ffi.recommend_select(cs, cr, vecs, examples, er, P, N, k, strategy, bf16, n_pos, n_neg)) + (full,)
+        picked = ffi.recommend_select(cs, cr, vecs, examples, er, P, N, k, strategy, self.dtype == ffi.DTYPE_BF16, n_pos, n_neg, stream=stream)
+        return tuple(_host(a) for a in tuple(picked) + (full,))
 
     # ------------------------------------------------------------------ maintenance
     def compact(self) -> dict[int, np.ndarray]:
@@ -861,6 +654,27 @@ class ShardSet:
 def _host(a) -> np.ndarray:
     """A device tensor or a host array as a host array."""
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _put(a, mask, value) -> None:
+    """``a[mask] = value`` in place, ``mask`` broadcast: on a device tensor (nothing waits for the device) or a host array."""
+    if hasattr(a, "masked_fill_"):
+        a.masked_fill_(mask, value)
+    else:
+        np.copyto(a, value, where=mask)
+
+
+def _pair(a, b):
+    """Two ``[nq, c]`` tables as one contiguous ``[nq, 2, c]``, where they live."""
+    if hasattr(a, "cpu"):
+        import torch
+        return torch.stack([a, b], dim=1).contiguous()
+    return np.stack([a, b], axis=1)
+
+
+def split_global(rows: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """GLOBAL rows (host) as ``(shard int32, local row int64)``; padding (-1) as ``(0, -1)``."""
+    return np.where(rows >= 0, rows // STRIDE, 0).astype(np.int32), np.where(rows >= 0, rows % STRIDE, -1)
 
 
 def shard_sizes(rows: Sequence[int]) -> str:

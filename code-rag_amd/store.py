@@ -29,7 +29,7 @@ import numpy as np
 from . import ffi, lexical
 from .errors import VectorStoreError
 from .settings import get_settings
-from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet
+from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet, split_global
 from .tables import DICT_KEYS, NONE as NONE_CODE, TEXT_KEYS, IdTable, PayloadTable
 
 logger = logging.getLogger(__name__)
@@ -185,6 +185,10 @@ class _Collection:
                 out[m] = self.slot_of[s][local[m]]
         return out
 
+    def _global_slots(self, rows: np.ndarray) -> np.ndarray:
+        """Slots of a table of GLOBAL rows (``shard * SHARD_STRIDE + local row``, as the shards' candidate lists carry them)."""
+        return self.slots_of(*split_global(rows))
+
     def side_columns(self) -> dict[int, Any]:
         """Per-shard side data for the device re-rank (ranking/device.py), extended lazily as rows are appended; the
         dictionaries behind the file / merge-key / node codes are shared by the shards (candidates of different shards are
@@ -214,7 +218,7 @@ class _Collection:
                 total = cols
             else:
                 total.packed += cols.packed
-        self.shards.complete_columns(total.packed)
+        self.shards.reduce(total.packed, "SUM")
         return total
 
     def set_degrees(self, total_degree: dict[str, int]) -> None:
@@ -563,8 +567,7 @@ class _Collection:
             both = sorted(held + list(zip(s[real].tolist(), r[real].tolist())), key=lambda t: (-t[0], t[1]))[:limit]
             out_s[qi, :len(both)] = np.asarray([t[0] for t in both], np.float32)       # (a Python float holds an f32 exactly)
             out_r[qi, :len(both)] = [t[1] for t in both]
-        shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
-        return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
+        return out_s, self._global_slots(out_r)
 
     def search_spans(self, queries: np.ndarray, limit: int, candidates: int, permille: int, dfilt) -> tuple[np.ndarray, np.ndarray]:
         """(scores [nq, limit], slots [nq, limit]) of the EXACT overlap-free top-``limit``: the first ``limit``
@@ -596,15 +599,13 @@ class _Collection:
             todo = todo[~take]
             if not todo.size:
                 break
-        shard = np.where(out_r >= 0, out_r // SHARD_STRIDE, 0).astype(np.int32)
-        return out_s, self.slots_of(shard, np.where(out_r >= 0, out_r % SHARD_STRIDE, -1))
+        return out_s, self._global_slots(out_r)
 
     def search_fused(self, queries: np.ndarray, limit: int, candidates: int, dfilt, method: str, rrf_k: int, weights, live=None):
         """The fused top-``limit`` of every logical query of ``queries`` [nq, m, dim] (``ShardSet.search_fused``):
         (slots i64, fused f32, cos f32, lists i32), each [nq, limit]; -1 slots are padding."""
         rows, fused, cos, lists, _, _ = self.shards.search_fused(queries, limit, candidates, dfilt, method, rrf_k, weights, live)
-        shard = np.where(rows >= 0, rows // SHARD_STRIDE, 0).astype(np.int32)
-        return self.slots_of(shard, np.where(rows >= 0, rows % SHARD_STRIDE, -1)), fused, cos, lists
+        return self._global_slots(rows), fused, cos, lists
 
     def example_rows(self, slots: np.ndarray) -> np.ndarray:
         """GLOBAL rows of a table of example slots (-1 stays -1)."""
@@ -655,8 +656,7 @@ class _Collection:
                 todo = todo[~done]
                 if not todo.size:
                     break
-        shard = np.where(out[0] >= 0, out[0] // SHARD_STRIDE, 0).astype(np.int32)
-        return (self.slots_of(shard, np.where(out[0] >= 0, out[0] % SHARD_STRIDE, -1)),) + out[1:]
+        return (self._global_slots(out[0]),) + out[1:]
 
     # -- keyword search
     def _lex_ready(self) -> dict[int, Any]:
@@ -707,10 +707,6 @@ class _Collection:
             queries.append(t)
             weights.append(idf)
         return queries, weights, avgdl
-
-    def _global_slots(self, rows: np.ndarray) -> np.ndarray:
-        shard = np.where(rows >= 0, rows // SHARD_STRIDE, 0).astype(np.int32)
-        return self.slots_of(shard, np.where(rows >= 0, rows % SHARD_STRIDE, -1))
 
     def search_lexical(self, texts, limit: int, dfilt, k1: float = 1.2, b: float = 0.75):
         """Exact BM25 top-``limit`` of every text: (scores f32 [nq, limit], slots i64 [nq, limit], counts i64 [nq]); -1 slots
@@ -1328,12 +1324,25 @@ class HipVectorStore:
         (``_Collection.search_grouped``); the first j rows of its answer are the j-row answer, so the prefixes hold again."""
         per = [int(limits)] * queries.shape[0] if isinstance(limits, (int, np.integer)) else [int(v) for v in limits]
         col, scores, slots = self._search_sync(collection, queries, max(per, default=0), filters, must_not, diversity, candidates, group)
-        picked = [[(int(r), float(s)) for s, r in zip(srow[:max(lim, 0)], rrow[:max(lim, 0)]) if r >= 0] for lim, srow, rrow in zip(per, scores, slots)]
-        flat = col.hits([t for one in picked for t, _ in one], [sc for one in picked for _, sc in one])      # (payloads fetched together)
+        return self._hit_lists(col, slots, scores, per)
+
+    @staticmethod
+    def _hit_lists(col: _Collection, slots: np.ndarray, scores: np.ndarray, limit=None, decorate=None) -> list[list[dict[str, Any]]]:
+        """The hit dictionaries of every query of a ``[nq, k]`` table of slots (-1: padding) and its scores: ONE flat
+        ``col.hits`` call (payloads fetched together), split by the queries' own counts.  ``limit``: how much of its row a
+        query keeps -- one int, or one per query; ``decorate(hits, keep)`` adds a feature's own fields to the flat list, ``keep``
+        being the bool ``[nq, k]`` mask of the entries that became hits, in order.  Like its callers it runs inside the worker
+        job, under the store's lock (:meth:`_search_hits_sync`)."""
+        keep = slots >= 0
+        if limit is not None:
+            keep &= np.arange(slots.shape[1])[None, :] < np.asarray(limit).reshape(-1, 1)
+        flat = col.hits(slots[keep].tolist(), scores[keep].tolist())
+        if decorate is not None:
+            decorate(flat, keep)
         out, at = [], 0
-        for one in picked:
-            out.append(flat[at:at + len(one)])
-            at += len(one)
+        for n in keep.sum(1).tolist():
+            out.append(flat[at:at + n])
+            at += n
         return out
 
     @staticmethod
@@ -1367,13 +1376,7 @@ class HipVectorStore:
         if dfilt is None or nq == 0 or (limit <= 0 and not counts):       # (a value the collection never stored: nothing is in range)
             return [[] for _ in range(nq)], ([0] * nq if counts else None)
         scores, slots, totals = col.search_range(queries, max(int(limit), 1), thresholds, dfilt, counts)
-        keep = (slots >= 0) & (np.arange(slots.shape[1])[None, :] < limit)
-        flat = col.hits(slots[keep].tolist(), scores[keep].tolist())       # (payloads fetched together)
-        out, at = [], 0
-        for n in keep.sum(1).tolist():
-            out.append(flat[at:at + n])
-            at += n
-        return out, ([int(c) for c in totals] if counts else None)
+        return self._hit_lists(col, slots, scores, limit), ([int(c) for c in totals] if counts else None)
 
     async def _range_call(self, collection: str, query_vectors, score_threshold, limit: int, filters, must_not, counts: bool, **others):
         """The common path of every thresholded entry point: argument checks for the caller alone, then a pass of its own --
@@ -1725,16 +1728,12 @@ class HipVectorStore:
         if dfilt is None or limit <= 0 or nq == 0:
             return [[] for _ in range(nq)]
         slots, fused, cos, lists = col.search_fused(queries, limit, candidates, dfilt, method, rrf_k, weights, live)
-        keep = slots >= 0
-        flat = col.hits(slots[keep].tolist(), fused[keep].tolist())              # (payloads fetched together)
-        for h, cv, bits in zip(flat, cos[keep].tolist(), lists[keep].tolist()):
-            h["cosine"] = cv
-            h["matched"] = [j for j in range(ffi.MAX_LISTS) if bits >> j & 1]
-        out, at = [], 0
-        for n in keep.sum(1).tolist():
-            out.append(flat[at:at + n])
-            at += n
-        return out
+
+        def decorate(hits, keep):
+            for h, cv, bits in zip(hits, cos[keep].tolist(), lists[keep].tolist()):
+                h["cosine"] = cv
+                h["matched"] = [j for j in range(ffi.MAX_LISTS) if bits >> j & 1]
+        return self._hit_lists(col, slots, fused, decorate=decorate)
 
     async def search_fused_batch(self, collection: str, query_vector_sets, limit: int = 10,
                                  filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
@@ -1800,13 +1799,7 @@ class HipVectorStore:
         if dfilt is None or not texts:
             return [[] for _ in texts], [0] * len(texts)
         scores, slots, counts = col.search_lexical(texts, max(limit, 1), dfilt, k1, b)
-        keep = (slots >= 0) & (np.arange(slots.shape[1])[None, :] < limit)
-        flat = col.hits(slots[keep].tolist(), scores[keep].tolist())
-        out, at = [], 0
-        for n in keep.sum(1).tolist():
-            out.append(flat[at:at + n])
-            at += n
-        return out, [int(c) for c in counts]
+        return self._hit_lists(col, slots, scores, limit), [int(c) for c in counts]
 
     async def search_lexical_batch(self, collection: str, texts, limit: int = 10, filters: dict[str, Any] | None = None,
                                    must_not: dict[str, Any] | None = None, *, k1: float = 1.2, b: float = 0.75) -> list[list[dict[str, Any]]]:
@@ -1847,17 +1840,13 @@ class HipVectorStore:
         if dfilt is None or limit <= 0 or not texts:
             return [[] for _ in texts]
         slots, fused, cos, lexs, lists = col.search_hybrid(queries, texts, limit, candidates, dfilt, rrf_k, weights, k1, b)
-        keep = slots >= 0
-        flat = col.hits(slots[keep].tolist(), fused[keep].tolist())
-        for h, cv, lv, bits in zip(flat, cos[keep].tolist(), lexs[keep].tolist(), lists[keep].tolist()):
-            h["cosine"] = None if math.isnan(cv) else cv
-            h["lexical_score"] = None if math.isnan(lv) else lv
-            h["matched"] = tuple(name for j, name in enumerate(("vector", "lexical")) if bits >> j & 1)
-        out, at = [], 0
-        for n in keep.sum(1).tolist():
-            out.append(flat[at:at + n])
-            at += n
-        return out
+
+        def decorate(hits, keep):
+            for h, cv, lv, bits in zip(hits, cos[keep].tolist(), lexs[keep].tolist(), lists[keep].tolist()):
+                h["cosine"] = None if math.isnan(cv) else cv
+                h["lexical_score"] = None if math.isnan(lv) else lv
+                h["matched"] = tuple(name for j, name in enumerate(("vector", "lexical")) if bits >> j & 1)
+        return self._hit_lists(col, slots, fused, decorate=decorate)
 
     async def search_hybrid_batch(self, collection: str, query_vectors, texts, limit: int = 10, candidates: int | None = None,
                                   rrf_k: int = 60, weights=None, filters: dict[str, Any] | None = None,
@@ -1955,18 +1944,12 @@ class HipVectorStore:
         n_pos, n_neg = np.asarray([len(p) for p in pos], np.int32), np.asarray([len(n) for n in neg], np.int32)
         ragged = bool((n_pos != P).any() or (n_neg != N).any())
         got, score, nscore, best = col.recommend(slots, P, N, limit, candidates, dfilt, strategy, n_pos if ragged else None, n_neg if ragged else None)
-        keep = got >= 0
-        hits = col.hits(got[keep].tolist(), score[keep].tolist())            # (payloads fetched together)
-        if strategy == "best":
-            qi = np.nonzero(keep)[0]
-            for h, q, nv, b in zip(hits, qi.tolist(), nscore[keep].tolist(), best[keep].tolist()):
+
+        def decorate(hits, keep):
+            for h, q, nv, b in zip(hits, np.nonzero(keep)[0].tolist(), nscore[keep].tolist(), best[keep].tolist()):
                 h["negative_score"] = nv
                 h["matched_positive"] = pos[q][b]
-        out, at = [], 0
-        for n in keep.sum(1).tolist():
-            out.append(hits[at:at + n])
-            at += n
-        return out
+        return self._hit_lists(col, got, score, decorate=decorate if strategy == "best" else None)
 
     async def recommend_batch(self, collection: str, example_sets, limit: int = 10, strategy: str = "average",
                               filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None,
@@ -2061,8 +2044,7 @@ class HipVectorStore:
                     s = torch.full((nq, limit), float("-inf"), dtype=torch.float32, device=dev)
                     r = torch.full((nq, limit), -1, dtype=torch.int64, device=dev)
                 out = reranker.rank(s, r, col.gather_side(r), plans)
-                rows = r.cpu().numpy()
-                slots = col.slots_of(np.where(rows >= 0, rows // SHARD_STRIDE, 0), np.where(rows >= 0, rows % SHARD_STRIDE, -1))
+                slots = col._global_slots(r.cpu().numpy())
                 wanted = set()
                 for qi in range(nq):
                     c = int(out.count[qi])

@@ -47,6 +47,27 @@ class FakeIndex:
     def read_rows(self, first, n):
         return self.x[first:first + n].copy()
 
+    def gather_vectors(self, rows, row_base=0, out=None, stream=0):
+        """``crh_index_gather_vectors`` on host arrays: the stored row where this index owns it, zeros elsewhere (padding too)."""
+        rows = np.asarray(rows, np.int64)
+        r = rows - row_base
+        own = (rows >= 0) & (r >= 0) & (r < len(self.x))
+        got = np.zeros(rows.shape + (self.dim,), np.float32)
+        got[own] = self.x[r[own]]
+        return got
+
+    def gather_codes(self, rows, col, row_base=0, out=None, stream=0):
+        """``crh_index_gather_codes`` on host arrays: column ``col`` of the rows this index owns written into ``out`` (full of
+        -1 when allocated here), every other position untouched; tombstoned rows included."""
+        assert 0 <= col < self.n_code_cols
+        rows = np.asarray(rows, np.int64)
+        if out is None:
+            out = np.full(rows.shape, -1, np.int32)
+        r = rows - row_base
+        own = (rows >= 0) & (r >= 0) & (r < len(self.x))
+        out[own] = self.codes[r[own], col]
+        return out
+
     def match_rows(self, filters=None, limit=1):
         ok = self.alive.astype(bool).copy()
         for col, code in (filters or []):
@@ -100,3 +121,20 @@ class FakeIndex:
 
     def close(self):
         self.closed = True
+
+
+def fake_device(monkeypatch=None, index=FakeIndex, **stand_ins):
+    """``coderag_amd.ffi`` without a device: ``index`` for ``ffi.Index``, the library and device queries answered by constants,
+    ``stand_ins`` (name -> value) for anything else, such as the numpy restatement of a selector.  Returns ``ffi``.  Without a
+    ``monkeypatch`` the attributes are set for good: the form for a spawned worker process."""
+    import coderag_amd  # noqa: F401
+    from coderag_amd import ffi
+    put = (lambda name, val: setattr(ffi, name, val)) if monkeypatch is None else (lambda name, val: monkeypatch.setattr(ffi, name, val))
+    put("Index", index)
+    put("lib", lambda: object())
+    put("device_count", lambda: 1)
+    put("device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
+    put("use_device", lambda d: None)
+    for name, val in stand_ins.items():
+        put(name, val)
+    return ffi

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import search as orc
-from tests.fake_index import FakeIndex
+from tests.fake_index import FakeIndex, fake_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -98,14 +98,8 @@ def _corpus(n=240, dim=768):
 
 @pytest.mark.parametrize("shards", [1, 3])
 def test_store_translates_values_must_not_and_raw_filters(monkeypatch, shards):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
     from coderag_amd.store import HipVectorStore
-    monkeypatch.setattr(ffi, "Index", SetFakeIndex)
-    monkeypatch.setattr(ffi, "lib", lambda: object())
-    monkeypatch.setattr(ffi, "device_count", lambda: 1)
-    monkeypatch.setattr(ffi, "device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    monkeypatch.setattr(ffi, "use_device", lambda d: None)
+    fake_device(monkeypatch, SetFakeIndex)
     rng, vecs, payloads, ids = _corpus()
     q = rng.standard_normal(768).astype(np.float32)
 

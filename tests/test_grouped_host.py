@@ -13,6 +13,7 @@ import pytest
 
 from oracle import search as orc
 from tests import group_cases
+from tests.fake_index import fake_device
 from tests.test_filter_sets_host import SetFakeIndex, _corpus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,19 +21,12 @@ U32 = np.uint32
 
 
 class GroupFakeIndex(SetFakeIndex):
-    """SetFakeIndex + ``gather_codes`` with the semantics of ``crh_index_gather_codes`` on host arrays."""
+    """SetFakeIndex that counts the ``gather_codes`` calls (the gather itself is ``FakeIndex``'s)."""
     gathers = 0
 
-    def gather_codes(self, rows, col, row_base=0, out=None, stream=0):
+    def gather_codes(self, *args, **kw):
         GroupFakeIndex.gathers += 1
-        assert 0 <= col < self.n_code_cols
-        rows = np.asarray(rows, np.int64)
-        if out is None:
-            out = np.full(rows.shape, -1, np.int32)
-        r = rows - row_base
-        own = (rows >= 0) & (r >= 0) & (r < len(self.x))
-        out[own] = self.codes[r[own], col]           # (tombstoned rows included; every other position untouched)
-        return out
+        return super().gather_codes(*args, **kw)
 
 
 # ------------------------------------------------------------------ the restatement itself
@@ -131,13 +125,7 @@ def test_new_entries_are_exported_and_check_their_arguments():
 
 # ------------------------------------------------------------------ store plumbing over the fake index
 def _fake_device(monkeypatch):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
-    monkeypatch.setattr(ffi, "Index", GroupFakeIndex)
-    monkeypatch.setattr(ffi, "lib", lambda: object())
-    monkeypatch.setattr(ffi, "device_count", lambda: 1)
-    monkeypatch.setattr(ffi, "device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    monkeypatch.setattr(ffi, "use_device", lambda d: None)
+    ffi = fake_device(monkeypatch, GroupFakeIndex)
     monkeypatch.setattr(ffi, "group_select", group_cases.group_select)
     return ffi
 
@@ -324,10 +312,10 @@ def _gloo_worker(rank: int, world: int, port: int, out_dir: str) -> None:
     codes = np.stack([lang, which], axis=1).astype(np.int32)
     sh.append({rank: raw[shard == rank]}, codes, shard=shard)
     assert all(r > 0 for r in sh.rows) and sh.index[rank].count()[0] == sh.rows[rank]
-    # complete_codes alone: each rank wrote its own positions of a buffer full of -1
+    # the all-reduce(MAX) alone: each rank wrote its own positions of a buffer full of -1
     t = torch.full((4, 6), -1, dtype=torch.int32)
     t[rank::2] = torch.arange(24, dtype=torch.int32).reshape(4, 6)[rank::2] - 1          # (a stored code may be -1 or 0)
-    sh.complete_codes(t)
+    sh.reduce(t, "MAX")
     assert torch.equal(t, torch.arange(24, dtype=torch.int32).reshape(4, 6) - 1)
     gid = np.empty(len(raw), np.int64)                                  # global row of every input row
     for s in range(world):

@@ -13,23 +13,19 @@ import pytest
 
 from oracle import search as orc
 from tests import mmr_cases
+from tests.fake_index import fake_device
 from tests.test_filter_sets_host import SetFakeIndex, _corpus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class MmrFakeIndex(SetFakeIndex):
-    """SetFakeIndex + ``gather_vectors`` with the semantics of ``crh_index_gather_vectors`` on host arrays."""
+    """SetFakeIndex that counts the ``gather_vectors`` calls (the gather itself is ``FakeIndex``'s)."""
     gathers = 0
 
-    def gather_vectors(self, rows, row_base=0, out=None, stream=0):
+    def gather_vectors(self, *args, **kw):
         MmrFakeIndex.gathers += 1
-        rows = np.asarray(rows, np.int64)
-        r = rows - row_base
-        own = (rows >= 0) & (r >= 0) & (r < len(self.x))
-        got = np.zeros(rows.shape + (self.dim,), np.float32)
-        got[own] = self.x[r[own]]
-        return got
+        return super().gather_vectors(*args, **kw)
 
 
 # ------------------------------------------------------------------ the restatement itself
@@ -93,13 +89,7 @@ def test_new_entries_are_exported_and_check_their_arguments():
 
 # ------------------------------------------------------------------ store plumbing over the fake index
 def _fake_device(monkeypatch):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
-    monkeypatch.setattr(ffi, "Index", MmrFakeIndex)
-    monkeypatch.setattr(ffi, "lib", lambda: object())
-    monkeypatch.setattr(ffi, "device_count", lambda: 1)
-    monkeypatch.setattr(ffi, "device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    monkeypatch.setattr(ffi, "use_device", lambda d: None)
+    ffi = fake_device(monkeypatch, MmrFakeIndex)
     monkeypatch.setattr(ffi, "mmr_select", mmr_cases.mmr_select)
     return ffi
 

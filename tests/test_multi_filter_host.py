@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import search as orc
-from tests.fake_index import FakeIndex
+from tests.fake_index import FakeIndex, fake_device
 
 
 class MultiFakeIndex(FakeIndex):
@@ -143,13 +143,7 @@ def _corpus(n=400, dim=768):
 
 
 def _fake_store(monkeypatch):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
-    monkeypatch.setattr(ffi, "Index", MultiFakeIndex)
-    monkeypatch.setattr(ffi, "lib", lambda: object())
-    monkeypatch.setattr(ffi, "device_count", lambda: 1)
-    monkeypatch.setattr(ffi, "device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    monkeypatch.setattr(ffi, "use_device", lambda d: None)
+    fake_device(monkeypatch, MultiFakeIndex)
     MultiFakeIndex.multi_calls = []
     MultiFakeIndex.plain_calls = 0
 

@@ -12,6 +12,7 @@ import pytest
 
 from oracle import search as orc
 from tests import range_cases
+from tests.fake_index import fake_device
 from tests.test_filter_sets_host import _corpus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,13 +87,7 @@ def test_new_entry_is_exported_and_checks_its_arguments():
 
 # ------------------------------------------------------------------ store plumbing over the fake index
 def _fake_device(monkeypatch):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
-    monkeypatch.setattr(ffi, "Index", range_cases.RangeFakeIndex)
-    monkeypatch.setattr(ffi, "lib", lambda: object())
-    monkeypatch.setattr(ffi, "device_count", lambda: 1)
-    monkeypatch.setattr(ffi, "device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    monkeypatch.setattr(ffi, "use_device", lambda d: None)
+    ffi = fake_device(monkeypatch, range_cases.RangeFakeIndex)
     return ffi
 
 

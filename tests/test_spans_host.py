@@ -17,6 +17,7 @@ import pytest
 
 from oracle import search as orc
 from tests import span_cases
+from tests.fake_index import fake_device
 from tests.test_filter_sets_host import SetFakeIndex
 from tests.test_grouped_host import GroupFakeIndex
 
@@ -243,16 +244,7 @@ def test_numeric_coding_of_odd_payload_values():
 
 # ------------------------------------------------------------------ store plumbing over the fake index
 def _fake_device(monkeypatch=None):
-    import coderag_amd  # noqa: F401
-    from coderag_amd import ffi
-    patch = (lambda name, val: monkeypatch.setattr(ffi, name, val)) if monkeypatch is not None else (lambda name, val: setattr(ffi, name, val))
-    patch("Index", SpanFakeIndex)
-    patch("lib", lambda: object())
-    patch("device_count", lambda: 1)
-    patch("device_info", lambda d=0: {"name": "fake", "arch": "gfx950", "hbm_bytes": 0, "cu_count": 256})
-    patch("use_device", lambda d: None)
-    patch("span_select", span_cases.span_select)
-    return ffi
+    return fake_device(monkeypatch, SpanFakeIndex, span_select=span_cases.span_select)
 
 
 def _pairs(hits):
