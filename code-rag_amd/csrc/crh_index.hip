@@ -44,8 +44,9 @@ constexpr int kRangeParts = 8;  // workgroups per query in k_range_count (crh_ra
 constexpr int kSparseDen = 4;   // the sparse route is taken from 1 populated tile in this many down (profiles/sparse_crossover.md)
 
 // A filter in the form the index keeps, compares and uploads: [n conditions, then per condition: column, mode (0 in, 1 not in,
-// 2 between, 3 not between), set size, the set's codes ascending without repeats -- for a range: 2, lo, hi].  crh_filter lists
-// and crh_condition lists both become one of these.
+// 2 between, 3 not between, 4 words, 5 not words), set size, the set's codes ascending without repeats -- for a range: 2, lo, hi;
+// for a row bitmap the "column" is the caller's tag and the set is 4 values: the device pointer's low and high half, n's low and
+// high half].  crh_filter lists and crh_condition lists both become one of these.
 using FilterKey = std::vector<int32_t>;
 
 // what build_mask hands a search: the row mask, and -- while the sparse route is enabled -- the ascending list of the tiles
@@ -314,7 +315,7 @@ void key_from_filters(const crh_filter *filters, int nfilt, FilterKey &key)
 
 // crh_condition list -> key: arguments checked, every set sorted, repeats and negative codes dropped (no row's code is a
 // negative member: -1 means "key absent", which is in no set)
-int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_conds, bool need_one, FilterKey &key)
+int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_conds, bool need_one, FilterKey &key, bool words_ok = false)
 {
     if (n_conds < (need_one ? 1 : 0) || n_conds > CRH_MAX_FILTERS)
         return fail(CRH_E_INVALID, "n_conds=%d outside %d..%d%s", n_conds, need_one ? 1 : 0, CRH_MAX_FILTERS, need_one ? " (a delete needs a filter)" : "");
@@ -323,6 +324,17 @@ int key_from_conditions(const crh_index *h, const crh_condition *conds, int n_co
     int64_t total = 0;
     for (int f = 0; f < n_conds; ++f) {
         const crh_condition &c = conds[f];
+        if (c.negate == CRH_COND_WORDS || c.negate == CRH_COND_NOT_WORDS) {   // a row bitmap: the pointer and n as they are, col is a tag
+            if (!words_ok) return fail(CRH_E_INVALID, "condition %d: a row-bitmap condition (mode %d) is not taken by this entry point", f, c.negate);
+            if (c.n < ceil_div(h->count, kTileRows))
+                return fail(CRH_E_INVALID, "condition %d: a row bitmap of n=%lld words, the index has %lld tiles", f, (long long)c.n,
+                            (long long)ceil_div(h->count, kTileRows));
+            if (!c.codes && h->count > 0) return fail(CRH_E_INVALID, "condition %d: the row bitmap is NULL", f);
+            const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(c.codes), n = (uint64_t)c.n;
+            const int32_t r[7] = {c.col, c.negate, 4, (int32_t)(uint32_t)ptr, (int32_t)(uint32_t)(ptr >> 32), (int32_t)(uint32_t)n, (int32_t)(uint32_t)(n >> 32)};
+            key.insert(key.end(), r, r + 7);
+            continue;
+        }
         if (c.col < 0 || c.col >= h->ncols) return fail(CRH_E_INVALID, "condition %d: column %d out of range (index has %d code columns)", f, c.col, h->ncols);
         if (c.n < 0) return fail(CRH_E_INVALID, "condition %d: set size %lld is negative", f, (long long)c.n);
         if (c.n > 0 && !c.codes) return fail(CRH_E_INVALID, "condition %d: codes is NULL with n=%lld", f, (long long)c.n);
@@ -354,7 +366,8 @@ size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, F
     const int nfilt = key[at++];
     fs.n = nfilt;
     for (int f = 0; f < nfilt; ++f) {
-        if (key[at] < 0 || key[at] >= h->ncols) {
+        const bool words = (key[at + 1] & 4) != 0;                 // a row bitmap: no column, [pointer lo, hi, n lo, hi] behind the head
+        if (!words && (key[at] < 0 || key[at] >= h->ncols)) {
             *bad_col = key[at];
             return 0;
         }
@@ -363,9 +376,9 @@ size_t filterset_from_key(const crh_index *h, const FilterKey &key, size_t at, F
         fs.cnt[f] = key[at + 2];
         fs.off[f] = (int)at + 3;
         const bool range = (fs.neg[f] & 2) != 0;                  // [lo, hi] behind the head; nothing to upload
-        fs.one[f] = fs.cnt[f] == 1 || range ? key[at + 3] : 0;
-        fs.hi[f] = range ? key[at + 4] : 0;
-        *sets = *sets || (fs.cnt[f] > 1 && !range);
+        fs.one[f] = fs.cnt[f] == 1 || range || words ? key[at + 3] : 0;
+        fs.hi[f] = range || words ? key[at + 4] : 0;
+        *sets = *sets || (fs.cnt[f] > 1 && !range && !words);
         at += 3 + (size_t)fs.cnt[f];
     }
     return at;
@@ -1958,7 +1971,7 @@ int crh_search_cond(crh_index *h, int nq, const float *queries, int queries_on_d
     CRH_TRY(search_args(h, nq, queries, k, out_scores, out_rows));
     if (nq == 0) return CRH_OK;
     FilterKey key;
-    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
     return search_key(h, nq, queries, queries_on_device, k, key, row_base, out_scores, out_rows, out_on_device, stream);
 }
 
@@ -1993,7 +2006,7 @@ int crh_search_range(crh_index *h, int nq, const float *queries, int queries_on_
     if (nq < 0) return fail(CRH_E_INVALID, "nq < 0");
     if (k <= 0 || k > CRH_MAX_K) return fail(CRH_E_INVALID, "k=%d outside 1..%d", k, CRH_MAX_K);
     FilterKey key;
-    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
     if (nq == 0) return CRH_OK;
     if (!queries || !out_scores || !out_rows) return fail(CRH_E_INVALID, "NULL query or output pointer");
     if (!thresholds_host) return fail(CRH_E_INVALID, "thresholds_host is NULL");
@@ -2133,7 +2146,7 @@ int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_co
     if (!h || !n_out) return fail(CRH_E_INVALID, "NULL argument");
     *n_out = 0;
     FilterKey key;
-    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
     if (limit <= 0 || h->count == 0) return CRH_OK;   // (rows_out_host == NULL: count only, up to `limit`)
     return match_key(h, key, limit, rows_out_host, n_out);
 }
@@ -2144,7 +2157,7 @@ int crh_index_row_mask(crh_index *h, const crh_condition *conds, int n_conds, ui
 {
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
     FilterKey key;
-    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key));
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
     const int64_t ntiles = ceil_div(h->count, kTileRows);
     if (n_words < ntiles) return fail(CRH_E_INVALID, "row_mask: n_words=%lld, the index has %lld tiles", (long long)n_words, (long long)ntiles);
     if (ntiles == 0) return CRH_OK;

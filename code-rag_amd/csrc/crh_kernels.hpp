@@ -205,6 +205,8 @@ __global__ void k_tombstone(uint32_t *alive, const int64_t *__restrict__ rows, i
 // set has no member: "in" matches nothing, "not in" everything.
 // neg is the condition's MODE (crh_condition.negate): bit 0 negates, bit 1 (CRH_COND_BETWEEN / _NOT_BETWEEN) makes it a RANGE --
 // the "member" is a row whose value v is not negative and lies in one[f] <= v <= hi[f]; no set is read (cnt is 2: the bounds).
+// Bit 2 (CRH_COND_WORDS / _NOT_WORDS) makes it a ROW BITMAP: one[f] / hi[f] are the low / high half of a device pointer to u32
+// validity words, the "member" is a row whose bit is set; col[f] is the caller's tag and no code is read.
 struct FilterSet {
     int n;
     int col[CRH_MAX_FILTERS];
@@ -223,6 +225,12 @@ __global__ __launch_bounds__(256) void k_filter_mask(const uint32_t *__restrict_
     bool ok = r < count;
     if (ok) {
         for (int f = 0; f < fs.n; ++f) {
+            if (fs.neg[f] & 4) {
+                const uint32_t *words = reinterpret_cast<const uint32_t *>(((uint64_t)(uint32_t)fs.hi[f] << 32) | (uint64_t)(uint32_t)fs.one[f]);
+                const bool member = ((words[r >> 5] >> (r & 31)) & 1u) != 0u;
+                ok = ok && (member != ((fs.neg[f] & 1) != 0));
+                continue;
+            }
             const int32_t c = codes[(int64_t)fs.col[f] * cap_rows + r];
             bool member;
             if (fs.neg[f] & 2) {

@@ -26,11 +26,14 @@ MAX_POS, MAX_NEG = 8, 8   # CRH_MAX_POS / CRH_MAX_NEG: live examples of one reco
 RECOMMEND_AVERAGE, RECOMMEND_BEST = 0, 1
 RECOMMEND_STRATEGIES = {"average": RECOMMEND_AVERAGE, "best": RECOMMEND_BEST}
 COND_IN, COND_NOT_IN, COND_BETWEEN, COND_NOT_BETWEEN = 0, 1, 2, 3   # CRH_COND_*: the modes of crh_condition.negate
+COND_WORDS, COND_NOT_WORDS = 4, 5   # a row bitmap in device memory (RowWords) instead of a column
 RANGE_MODES = {"between": COND_BETWEEN, "not_between": COND_NOT_BETWEEN}
 VALUE_MAX = 2 ** 31 - 1   # largest value a numeric column stores (int32); -1 stands for "absent"
 MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass of crh_search_multi
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 LEX_MAX_QUERY_TERMS = 32   # CRH_LEX_MAX_QUERY_TERMS: distinct term ids of one crh_lex_search query
+TEXT_MAX_PATTERNS, TEXT_MAX_PATTERN_BYTES = 8, 64   # CRH_TEXT_MAX_PATTERNS / CRH_TEXT_MAX_PATTERN_BYTES of one crh_text_match
+TEXT_ALL, TEXT_ANY = 0, 1   # CRH_TEXT_ALL / CRH_TEXT_ANY
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -54,6 +57,7 @@ EXPORTS = (
     "crh_span_select",
     "crh_index_row_mask", "crh_lex_create", "crh_lex_destroy", "crh_lex_clear", "crh_lex_count", "crh_lex_append", "crh_lex_stats",
     "crh_lex_search",
+    "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -211,6 +215,12 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_lex_append.argtypes = [vp, i64, vp, vp, vp, vp]
     L.crh_lex_stats.argtypes = [vp, vp, i64, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.crh_lex_search.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, vp, i64, vp, vp, vp, vp]
+    L.crh_text_create.argtypes = [i32, i64, i64, C.POINTER(vp)]
+    L.crh_text_destroy.argtypes = [vp]
+    L.crh_text_clear.argtypes = [vp]
+    L.crh_text_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.crh_text_append.argtypes = [vp, i64, vp, vp]
+    L.crh_text_match.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, C.POINTER(i64), vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -269,19 +279,54 @@ def _filters(filters) -> tuple:
     return arr, len(filters)
 
 
+class RowWords:
+    """A ROW-BITMAP condition (``CRH_COND_WORDS`` / ``CRH_COND_NOT_WORDS``): the row passes iff its bit is set (``negate``: clear)
+    in validity words somebody else computed (:meth:`Text.match`).  ``words`` maps ``id(index)`` to that index's int32 device
+    tensor of at least ``ceil(rows / 32)`` words -- one filter serves every shard of a collection, each :class:`Index` takes
+    its own words -- or is ONE tensor for whichever index is asked.  The library cannot look into the buffer: conditions are
+    equal iff pointer, length, mode and ``tag`` are, so whoever rewrites a buffer takes a new tag (:func:`next_words_tag`).
+    Travels with the set conditions (``crh_condition``); ``len()`` is 5, unlike every tuple form."""
+    __slots__ = ("tag", "words", "negate")
+
+    def __init__(self, tag: int, words, negate: bool = False):
+        self.tag, self.words, self.negate = int(tag), words, bool(negate)
+
+    def __len__(self) -> int:
+        return 5
+
+    def words_of(self, owner):
+        w = self.words.get(id(owner)) if isinstance(self.words, dict) else self.words
+        if w is None:
+            raise NativeError(E_INVALID, "row-bitmap condition: no words for this index")
+        _typed(w, "int32", "row bitmap")
+        if not _is_dev(w):
+            raise NativeError(E_INVALID, "row-bitmap condition: the words must be a device tensor")
+        return w
+
+
+_words_tag = 0
+
+
+def next_words_tag() -> int:
+    """A tag no earlier :class:`RowWords` of this process carries (positive, wraps far beyond any cache's memory)."""
+    global _words_tag
+    _words_tag = _words_tag % (2 ** 31 - 2) + 1
+    return _words_tag
+
+
 def is_set_condition(item) -> bool:
     """A filter item is ``(column, code)`` -- the equality of ``crh_filter`` -- or a SET condition ``(column, codes, negate)``:
     the column's code is (``negate`` false) / is not (true) one of ``codes`` (any iterable of ints; ``negate`` may be left out)
     -- or a RANGE condition ``(column, lo, hi, "between" | "not_between")`` (:func:`is_range_condition`), which travels with the
     set conditions (``crh_condition``)."""
-    return len(item) in (3, 4) or not isinstance(item[1], (int, np.integer))
+    return isinstance(item, RowWords) or len(item) in (3, 4) or not isinstance(item[1], (int, np.integer))
 
 
 def is_range_condition(item) -> bool:
     """``(column, lo, hi, "between" | "not_between")``: the column's VALUE (a numeric column stores the value itself, -1 for
     "absent") lies / does not lie in ``lo .. hi``, both ends inclusive; ``lo > hi`` is an empty range.  A row without the value
     fails every "between" and passes every "not_between"."""
-    return len(item) == 4
+    return not isinstance(item, RowWords) and len(item) == 4
 
 
 def _range_parts(item) -> tuple[int, int, int, int]:
@@ -292,14 +337,19 @@ def _range_parts(item) -> tuple[int, int, int, int]:
     return int(col), RANGE_MODES[mode], max(int(lo), 0), min(int(hi), VALUE_MAX)
 
 
-def _conditions(filters) -> tuple:
-    """Any mix of the two item forms as ``crh_condition``s: (array, n, the numpy sets the array points into -- keep them alive
-    for the call)."""
+def _conditions(filters, owner=None) -> tuple:
+    """Any mix of the item forms as ``crh_condition``s: (array, n, the numpy sets the array points into -- keep them alive
+    for the call).  ``owner``: the :class:`Index` asking, whose words a :class:`RowWords` hands over."""
     filters = list(filters or [])
     if len(filters) > MAX_FILTERS:
         raise NativeError(E_INVALID, f"at most {MAX_FILTERS} filter conditions are supported")
     arr, keep = (Condition * max(1, len(filters)))(), []
     for i, item in enumerate(filters):
+        if isinstance(item, RowWords):
+            w = item.words_of(owner)
+            keep.append(w)
+            arr[i].col, arr[i].negate, arr[i].n, arr[i].codes = item.tag, COND_NOT_WORDS if item.negate else COND_WORDS, int(w.numel()), int(w.data_ptr())
+            continue
         if is_range_condition(item):
             col, negate, lo, hi = _range_parts(item)
             if hi < lo:
@@ -320,7 +370,9 @@ def filter_key(filters) -> tuple:
     Conditions are ordered, a set's codes sorted without repeats; ``(col, code)`` and ``(col, [code])`` are the same condition."""
     out = []
     for item in filters or []:
-        if is_range_condition(item):
+        if isinstance(item, RowWords):
+            out.append((item.tag, COND_NOT_WORDS if item.negate else COND_WORDS, ()))
+        elif is_range_condition(item):
             col, mode, lo, hi = _range_parts(item)
             out.append((col, mode, (lo, hi) if lo <= hi else (1, 0)))
         elif is_set_condition(item):
@@ -492,7 +544,7 @@ class Index:
         n = C.c_int64(0)
         Index.device_calls += 1
         if _has_sets(filters):
-            carr, nc, keep = _conditions(filters)
+            carr, nc, keep = _conditions(filters, self)
             check(lib().crh_index_tombstone_cond(self._handle(), carr, nc, C.byref(n)))
             del keep
         else:
@@ -718,7 +770,7 @@ class Index:
             if _is_dev(out_scores) != _is_dev(out_rows):
                 raise NativeError(E_INVALID, "out_scores and out_rows must live in the same memory space")
         if _has_sets(filters):
-            carr, nc, keep = _conditions(filters)
+            carr, nc, keep = _conditions(filters, self)
             check(lib().crh_search_cond(self._handle(), nq, _ptr(queries), _is_dev(queries), k, carr, nc, row_base,
                                         _ptr(out_scores), _ptr(out_rows), _is_dev(out_scores), stream))
             del keep
@@ -795,7 +847,7 @@ class Index:
             off.append(len(flat))
         carr, keep = (Condition * max(1, len(flat)))(), []
         for i, item in enumerate(flat):
-            one, _, kp = _conditions([item])
+            one, _, kp = _conditions([item], self)
             carr[i] = one[0]
             keep.append(kp)
         off = np.asarray(off, dtype=np.int32)
@@ -838,7 +890,7 @@ class Index:
                 raise NativeError(E_INVALID, "out_counts given with counts=False")
             if _is_dev(out_scores) != _is_dev(out_rows) or (counts and _is_dev(out_counts) != _is_dev(out_scores)):
                 raise NativeError(E_INVALID, "out_scores, out_rows and out_counts must live in the same memory space")
-        carr, nc, keep = _conditions(filters)
+        carr, nc, keep = _conditions(filters, self)
         check(lib().crh_search_range(self._handle(), nq, _ptr(queries), _is_dev(queries), k, thr.ctypes.data, carr, nc, row_base,
                                      _ptr(out_scores), _ptr(out_rows), _ptr(out_counts) if counts else None, _is_dev(out_scores), stream))
         del keep
@@ -870,7 +922,7 @@ class Index:
         n = C.c_int64(0)
         Index.device_calls += 1
         if _has_sets(filters):
-            carr, nc, keep = _conditions(filters)
+            carr, nc, keep = _conditions(filters, self)
             check(lib().crh_index_match_rows_cond(self._handle(), carr, nc, limit, out, C.byref(n)))
             del keep
         else:
@@ -893,7 +945,7 @@ class Index:
         _typed(out, "int32", "out")
         if not _is_dev(out) or out.ndim != 1 or int(out.shape[0]) < words:
             raise NativeError(E_INVALID, f"out must be a device tensor of at least {words} words")
-        carr, nc, keep = _conditions(filters)
+        carr, nc, keep = _conditions(filters, self)
         check(lib().crh_index_row_mask(self._handle(), carr, nc, _ptr(out), int(out.shape[0]), stream))
         del keep
         return out
@@ -999,6 +1051,81 @@ class Lex:
         check(lib().crh_lex_search(self._handle(), nq, q_off.ctypes.data, terms.ctypes.data, w.ctypes.data, float(k1), float(b), float(avgdl), k,
                                    _ptr(mask), int(row_base), _ptr(out_scores), _ptr(out_rows), _ptr(out_count), stream))
         return out_scores, out_rows, out_count
+
+
+def text_patterns(patterns) -> tuple:
+    """Byte patterns as the CSR ``crh_text_match`` takes: (n, pat_off int64, bytes uint8).  1..``TEXT_MAX_PATTERNS`` patterns of
+    1..``TEXT_MAX_PATTERN_BYTES`` bytes each are the library's limits; it is the library that refuses what breaks them."""
+    pats = [bytes(p) for p in patterns]
+    off = np.zeros(len(pats) + 1, np.int64)
+    np.cumsum([len(p) for p in pats], out=off[1:])
+    return len(pats), off, np.frombuffer(b"".join(pats) or b"\0", dtype=np.uint8).copy()
+
+
+class Text:
+    """Owning wrapper of one ``crh_text`` handle: the text arena beside one :class:`Index` (same rows, same numbering), matched
+    against literal byte patterns on the device."""
+    match_calls = 0       # crh_text_match calls issued by all handles (tests count the greps of a job)
+
+    def __init__(self, capacity_rows: int = 0, capacity_bytes: int = 0, device: int = 0):
+        self.device = device
+        h = C.c_void_p()
+        check(lib().crh_text_create(device, int(capacity_rows), int(capacity_bytes), C.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.crh_text_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _handle(self):
+        if not self._h:
+            raise NativeError(E_INVALID, "text handle is closed")
+        return self._h
+
+    def clear(self) -> None:
+        check(lib().crh_text_clear(self._handle()))
+
+    def count(self) -> tuple[int, int]:
+        """(rows, bytes)."""
+        r, b = C.c_int64(0), C.c_int64(0)
+        check(lib().crh_text_count(self._handle(), C.byref(r), C.byref(b)))
+        return int(r.value), int(b.value)
+
+    def append(self, row_off, data) -> None:
+        """``n`` rows behind the existing ones: ``row_off`` int64 [n + 1] from 0, ``data`` their bytes (bytes-like or uint8
+        array of ``row_off[n]`` bytes).  All or nothing."""
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64).reshape(-1)
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        n = int(row_off.size) - 1
+        if n < 0 or (n and int(row_off[-1]) != data.size):
+            raise NativeError(E_INVALID, f"append: row_off {row_off.size} entries ending at {int(row_off[-1]) if n >= 0 else None}, {data.size} bytes")
+        check(lib().crh_text_append(self._handle(), n, row_off.ctypes.data, data.ctypes.data if data.size else None))
+
+    def match(self, patterns, fold_case: bool = False, any_of: bool = False, mask=None, out=None, count: bool = True, stream: int = 0):
+        """Which rows hold the byte ``patterns`` (``crh_text_match``): all of them, or -- ``any_of`` -- at least one; ``fold_case``
+        folds ASCII letters only.  ``mask``: device validity words as :meth:`Index.row_mask` returns them, complete on
+        ``stream`` (None: every row).  Returns ``(words int32 device tensor [ceil(rows / 32)], count or None)``; with ``count``
+        the call waits on ``stream``."""
+        import torch
+        n, off, data = text_patterns(patterns)
+        words = (self.count()[0] + 31) // 32
+        if mask is not None:
+            _typed(mask, "int32", "mask")
+            if not _is_dev(mask) or int(mask.numel()) < words:
+                raise NativeError(E_INVALID, "mask must be a device tensor of one word per 32-row tile")
+        if out is None:
+            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.device}")
+        _typed(out, "int32", "out")
+        if not _is_dev(out) or out.ndim != 1 or int(out.shape[0]) < words:
+            raise NativeError(E_INVALID, f"out must be a device tensor of at least {words} words")
+        c = C.c_int64(0)
+        Text.match_calls += 1
+        check(lib().crh_text_match(self._handle(), n, off.ctypes.data, data.ctypes.data, int(bool(fold_case)), TEXT_ANY if any_of else TEXT_ALL,
+                                   _ptr(mask), _ptr(out), C.byref(c) if count else None, stream))
+        return out, (int(c.value) if count else None)
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

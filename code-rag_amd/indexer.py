@@ -380,7 +380,8 @@ class VectorSearcher:
     async def search_code(self, query: str, limit: int = 10, language: str | list[str] | None = None, entity_type: str | None = None,
                           project_name: str | list[str] | None = None, *, diversity: float | None = None,
                           candidates: int | None = None, max_per_file: int | None = None,
-                          min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic") -> list[CodeSearchResult]:
+                          min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic",
+                          contains: str | list[str] | None = None) -> list[CodeSearchResult]:
         """``mode`` (not in the reference): "semantic" (the default: everything below), "lexical" (the store's exact keyword
         search of ``query``, nothing embedded) or "hybrid" (both, fused by reciprocal rank); the keyword modes take the
         filters and ``candidates`` only.
@@ -389,9 +390,12 @@ class VectorSearcher:
         ``max_per_file`` likewise: at most that many chunks of one file among the ``limit`` results (the store's grouped search);
         ``min_score`` likewise: only results whose score is at least that (the store's ``score_threshold``), possibly fewer
         than ``limit``; ``max_overlap`` likewise: no result repeats more than that share of a better result's lines (the store's
-        ``max_overlap``)."""
-        hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit,
-                               _only_set(language=language, entity_type=entity_type, project_name=project_name),
+        ``max_overlap``); ``contains`` likewise: a literal string, or a list of them, every result's ``content`` must hold (the
+        store's text condition, matched exactly on the device)."""
+        filters = _only_set(language=language, entity_type=entity_type, project_name=project_name)
+        if contains is not None:
+            filters = dict(filters or {}, content={"contains": contains})
+        hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit, filters,
                                "code_search", "Code", diversity, candidates, max_per_file, min_score, max_overlap, **_mode_given(mode))
         return self._format_code_results(hits)
 

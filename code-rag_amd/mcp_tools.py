@@ -31,7 +31,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
     async def semantic_search(query: str, limit: int = 5, entity_type: str | None = None, diversity: float | None = None,
                               candidates: int | None = None, max_per_file: int | None = None, extra_queries: list[str] | None = None,
                               fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None,
-                              min_score: float | None = None, max_overlap: float | None = None, mode: str | None = None) -> ToolResult:
+                              min_score: float | None = None, max_overlap: float | None = None, mode: str | None = None,
+                              contains: str | list[str] | None = None, contains_case: bool | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -43,7 +44,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                           score=h.get("score"), summary=h.get("summary"))) for h in hits]
                 return ToolResult(success=True, data=data, message=f"Found {len(data)} matches like {len(like_ids)} example(s).")
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
-                                       ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score), ("max_overlap", max_overlap), ("mode", mode)) if v is not None}   # (only when asked for)
+                                       ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score), ("max_overlap", max_overlap), ("mode", mode),
+                                       ("contains", contains or None), ("contains_case", contains_case if contains else None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -88,5 +90,10 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             "like_ids": {"type": "array", "description": "Ids of results to find more of (up to 8): the answer is built from these "
                                                          "stored examples instead of the query text", "required": False},
             "unlike_ids": {"type": "array", "description": "With like_ids: ids of results to steer away from (up to 8)", "required": False},
+            "contains": {"type": "string", "description": "A literal string (or a list of up to 8) every result's code must contain, "
+                                                          "punctuation included: 'retry_after=', '.unwrap()', '#include <hip/'",
+                         "required": False},
+            "contains_case": {"type": "boolean", "description": "With contains: false ignores the case of ASCII letters (default: true)",
+                              "required": False},
         },
     }

@@ -30,7 +30,7 @@ from . import ffi, lexical
 from .errors import VectorStoreError
 from .settings import get_settings
 from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet, split_global
-from .tables import DICT_KEYS, NONE as NONE_CODE, TEXT_KEYS, IdTable, PayloadTable
+from .tables import DICT_KEYS, NONE as NONE_CODE, TEXT_KEYS as _TEXT_COLUMNS, IdTable, PayloadTable
 
 logger = logging.getLogger(__name__)
 
@@ -58,6 +58,16 @@ NUMERIC_KEYS: dict[str, tuple[str, ...]] = {
     CollectionName.SUMMARIES.value: (),
 }
 _RANGE_WORDS = ("gte", "gt", "lte", "lt")
+# Payload keys whose TEXT can be filtered by literal substring (``{"contains": ...}``): Qdrant's
+# ``FieldCondition(key, match=MatchText(text))`` on a field without a full-text index.  Matched on the device by ``crh_text_match``
+# over an arena derived from the payload tables on first use; never a device column, never part of a snapshot.
+TEXT_KEYS: dict[str, tuple[str, ...]] = {
+    CollectionName.CODE_CHUNKS.value: ("content",),
+    CollectionName.SUMMARIES.value: ("summary",),
+}
+_TEXT_WORDS = ("contains", "any", "case")
+_ASCII_LOWER = bytes(c + 32 if 65 <= c <= 90 else c for c in range(256))   # the device's folding: ASCII letters only
+_TEXT_CACHE = 8          # match results a collection keeps (a repeated query under the same text filter does not grep again)
 
 
 def range_bounds(key: str, spec) -> tuple[int, int]:
@@ -94,8 +104,58 @@ def range_bounds(key: str, spec) -> tuple[int, int]:
     return int(lo), int(hi)
 
 
+def _is_text(value) -> bool:
+    """A filter value that asks for a substring match: a mapping with the key ``"contains"``."""
+    return isinstance(value, Mapping) and "contains" in value
+
+
 def _is_range(value) -> bool:
-    return isinstance(value, Mapping)
+    return isinstance(value, Mapping) and "contains" not in value
+
+
+class TextSpec(NamedTuple):
+    """A ``{"contains": ...}`` filter value, checked: the distinct patterns as sorted UTF-8 bytes, any-of / all-of, and whether
+    case matters (``case=False`` folds ASCII letters only).  Equal specs select the same rows."""
+    patterns: tuple
+    any_of: bool
+    case: bool
+
+
+def text_spec(key: str, spec) -> TextSpec:
+    """``{"contains": str | [str, ...], "any": bool = False, "case": bool = True}`` as a :class:`TextSpec`.  ``ValueError``
+    naming ``key`` for an unknown word, a pattern that is no ``str``, an empty pattern, one over 64 bytes of UTF-8, no pattern
+    at all or more than 8, and flags that are not bools."""
+    unknown = [w for w in spec if w not in _TEXT_WORDS]
+    if unknown:
+        raise ValueError(f"text filter on {key!r}: unknown word {unknown[0]!r} (use {', '.join(_TEXT_WORDS)})")
+    pats = spec["contains"]
+    pats = [pats] if isinstance(pats, str) else list(pats) if isinstance(pats, (list, tuple)) else None
+    if pats is None or not all(isinstance(p, str) for p in pats):
+        raise ValueError(f"text filter on {key!r}: 'contains' takes a str or a list of str, not {spec['contains']!r}")
+    if not 1 <= len(pats) <= ffi.TEXT_MAX_PATTERNS:
+        raise ValueError(f"text filter on {key!r}: {len(pats)} patterns (1..{ffi.TEXT_MAX_PATTERNS} are matched in one pass)")
+    raw = [p.encode("utf-8", "surrogatepass") for p in pats]
+    for p, b in zip(pats, raw):
+        if not 1 <= len(b) <= ffi.TEXT_MAX_PATTERN_BYTES:
+            raise ValueError(f"text filter on {key!r}: the pattern {p[:80]!r} has {len(b)} bytes of UTF-8 (1..{ffi.TEXT_MAX_PATTERN_BYTES})")
+    flags = []
+    for word, default in (("any", False), ("case", True)):
+        v = spec.get(word, default)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"text filter on {key!r}: {word}={v!r} is not a bool")
+        flags.append(bool(v))
+    if not flags[1]:
+        raw = [b.translate(_ASCII_LOWER) for b in raw]     # (what the device compares: folded patterns are equal patterns)
+    return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1])
+
+
+def has_text_condition(filters, must_not=None) -> bool:
+    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``{"contains": ...}`` value?"""
+    for f in (filters, must_not):
+        for d in (f if isinstance(f, (list, tuple)) else [f]):
+            if isinstance(d, Mapping) and any(_is_text(v) for v in d.values()):
+                return True
+    return False
 
 
 _DTYPES = {"f32": ffi.DTYPE_F32, "fp32": ffi.DTYPE_F32, "float32": ffi.DTYPE_F32, "bf16": ffi.DTYPE_BF16,
@@ -131,6 +191,7 @@ class _Collection:
         self.name = name
         self.keys = FILTER_KEYS.get(name, ())
         self.numeric_keys = NUMERIC_KEYS.get(name, ())
+        self.text_keys = TEXT_KEYS.get(name, ())
         ncols = len(self.keys) + len(self.numeric_keys)          # the numeric columns last
         self.shards = ShardSet(nshards, lambda s: ffi.Index(dim, dtype, capacity_rows=capacity, n_code_cols=ncols, device=device),
                                device=device, backend=backend, group=group, merge_fn=merge_fn)
@@ -149,6 +210,11 @@ class _Collection:
         self._lex: dict[int, Any] = {}
         self._lex_df: tuple | None = None    # (mutation state, {term id: df}, N, sum_dl) of the alive rows of the whole collection
         self.lex_stats_calls = 0             # crh_lex_stats rounds run so far (repeated queries reuse the counts)
+        # substring side, DERIVED the same way: text key -> shard -> ffi.Text of its rows, built from the payload
+        # tables on the first text filter, extended lazily, dropped by compact() and load(); never part of a snapshot
+        self._text: dict[str, dict[int, Any]] = {}
+        self._text_cache: dict[tuple, tuple] = {}    # (key, spec, other conditions, collection state) -> (tag, words per index, count)
+        self.text_match_calls = 0            # text conditions resolved by a grep so far (repeated filters reuse the words)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
@@ -261,7 +327,10 @@ class _Collection:
         collection was never stored (nothing can match); a ``must_not`` entry whose values were never stored excludes nothing
         and is dropped."""
         out: list[tuple] = []
+        texts: list[tuple] = []                                          # (key, TextSpec, negate): resolved once the others are known
         for key, value in (filters or {}).items():
+            if self._text_entry(key, value, False, texts):
+                continue
             if key in self.numeric_keys:
                 out.append(self._range_condition(key, value, False))
                 continue
@@ -280,6 +349,8 @@ class _Collection:
                     return None
                 out.append((col, code))
         for key, value in (must_not or {}).items():
+            if self._text_entry(key, value, True, texts):
+                continue
             if key in self.numeric_keys:
                 out.append(self._range_condition(key, value, True))      # (rows without the value pass, as under Qdrant's must_not)
                 continue
@@ -290,7 +361,79 @@ class _Collection:
             codes = self._codes_of(key, value if isinstance(value, _COLLECTIONS) else [value])
             if codes:
                 out.append((col, codes, True))
+        if texts:
+            if len(out) + len(texts) > ffi.MAX_FILTERS:
+                raise ValueError(f"{len(out) + len(texts)} filter conditions, the device takes {ffi.MAX_FILTERS} (a text condition is one)")
+            others = list(out)                                           # every text condition greps under the OTHER kinds' rows
+            out += [self._text_condition(key, spec, negate, others) for key, spec, negate in texts]
         return out
+
+    # -- substring filters
+    def _text_entry(self, key: str, value, negate: bool, texts: list) -> bool:
+        """Files a filter entry that concerns a text key under ``texts`` and says so; ``ValueError`` naming the key for
+        ``contains`` on another key and for anything but ``contains`` on a text key."""
+        if key not in self.text_keys:
+            if _is_text(value):
+                raise ValueError(f"collection {self.name!r} cannot match text in payload key {key!r} "
+                                 f"(text keys: {', '.join(self.text_keys) or 'none'})")
+            return False
+        if not _is_text(value):
+            raise ValueError(f"payload key {key!r} holds text: filter it with a mapping {{'contains': str or list of str}}, not {value!r}")
+        texts.append((key, text_spec(key, value), negate))
+        return True
+
+    def _text_ready(self, key: str) -> dict[int, Any]:
+        """The text arenas of ``key`` for the owned shards, brought up to date: the UTF-8 of the rows appended since the last
+        text filter is appended.  A value that is absent or no ``str`` is empty text.  A collection that is never filtered by
+        text never comes here."""
+        if self.shards.backend == "dist":
+            raise VectorStoreError("text filters are not available with shard_backend='dist' yet (a rank holds the text of its own rows only)")
+        arenas = self._text.setdefault(key, {})
+        for s in self.shards.owned:
+            arena = arenas.get(s)
+            if arena is None:
+                arena = arenas[s] = ffi.Text(capacity_rows=self.shards.rows[s], device=self._device)
+            have, want = arena.count()[0], self.shards.rows[s]
+            for a in range(have, want, 65536):
+                b = min(want, a + 65536)
+                slots = np.arange(a, b) if self.shards.ns == 1 else self.slot_of[s][a:b]
+                vals = [self.payloads.value(int(t), key) if t >= 0 else None for t in slots]                  # (-1: a dead row without a slot)
+                raw = [v.encode("utf-8", "surrogatepass") if isinstance(v, str) else b"" for v in vals]
+                off = np.zeros(len(raw) + 1, np.int64)
+                np.cumsum([len(r) for r in raw], out=off[1:])
+                arena.append(off, b"".join(raw))
+        return arenas
+
+    def _text_drop(self) -> None:
+        for arenas in self._text.values():
+            for arena in arenas.values():
+                arena.close()
+        self._text, self._text_cache = {}, {}
+
+    def _text_condition(self, key: str, spec: TextSpec, negate: bool, others: list) -> "ffi.RowWords":
+        """A text condition as the row-bitmap condition of the device filter.  Per owned shard: the words of the OTHER
+        conditions (``crh_index_row_mask``; none: the alive words), ``crh_text_match`` under them -- a tile they leave empty
+        costs no read of its text -- and the result as ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  The last few results
+        are kept, keyed by what they were computed from; every result lives in buffers of its own under a tag of its own."""
+        arenas = self._text_ready(key)
+        state = (tuple(self.shards.rows), self.shards.count()[1], self.compactions)
+        ck = (key, spec, ffi.filter_key(others), state)
+        hit = self._text_cache.pop(ck, None)
+        if hit is None:
+            words, total = {}, 0
+            stream = self.shards._stream()
+            for s in self.shards.owned:
+                ix = self.shards.index[s]
+                mask = ix.row_mask(others, stream=stream)
+                w, n = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, stream=stream)
+                words[id(ix)] = w
+                total += n
+            self.text_match_calls += 1
+            hit = (ffi.next_words_tag(), words, total)
+            while len(self._text_cache) >= _TEXT_CACHE:
+                self._text_cache.pop(next(iter(self._text_cache)))       # (the least recently used: hits are re-inserted below)
+        self._text_cache[ck] = hit
+        return ffi.RowWords(hit[0], hit[1], negate)
 
     def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None, must_not: dict[str, Any] | None = None) -> np.ndarray:
         """Alive slots matching every condition, in insertion order -- resolved on the device from the code columns."""
@@ -310,6 +453,8 @@ class _Collection:
     def delete(self, filters: dict[str, Any], must_not: dict[str, Any] | None = None) -> int:
         """client.py:159-169: every point matching the AND of the conditions.  An empty filter matches every point, as
         ``Filter(must=[])`` does."""
+        if has_text_condition(filters, must_not):
+            raise ValueError("delete takes no text condition ({'contains': ...}): fetch the matching points (search_text) and delete by id or file")
         dfilt = self.device_filters(filters, must_not)
         if dfilt is None:
             return 0
@@ -359,7 +504,7 @@ class _Collection:
         shard = self.shards.route(n)
         if self.partial:                                      # the text of rows other ranks own stays with them
             owned = np.isin(shard, self.shards.owned)
-            stored = [p if o else {k: ("" if k in TEXT_KEYS and isinstance(v, str) else v) for k, v in p.items()} for p, o in zip(payloads, owned)]
+            stored = [p if o else {k: ("" if k in _TEXT_COLUMNS and isinstance(v, str) else v) for k, v in p.items()} for p, o in zip(payloads, owned)]
         else:
             stored = payloads
         self.payloads.extend(stored)
@@ -463,7 +608,7 @@ class _Collection:
         mine = set(self.shards.owned)
         # only the TEXT fields travel (everything else is replicated and keeps its Python type: tuples, None, numbers)
         local = [self.payloads.get(t) for t in slots]
-        parts = [json.dumps({k: p[k] for k in TEXT_KEYS if isinstance(p.get(k), str)}, ensure_ascii=False).encode("utf-8", "surrogatepass")
+        parts = [json.dumps({k: p[k] for k in _TEXT_COLUMNS if isinstance(p.get(k), str)}, ensure_ascii=False).encode("utf-8", "surrogatepass")
                  if int(self.row_shard[t]) in mine else None for t, p in zip(slots, local)]
         out = []
         for p, b in zip(local, self.shards.exchange_bytes(parts)):
@@ -773,6 +918,7 @@ class _Collection:
                 side.select(np.flatnonzero(maps[s][: side.rows] >= 0))
             self.compactions += 1
         self._lex_drop()                      # (derived: rebuilt from the payload tables on the next lexical call)
+        self._text_drop()                     # (likewise: on the next text filter)
         return int(before - keep.size)
 
     # -- persistence
@@ -867,10 +1013,12 @@ class _Collection:
                 self.slot_of[s] = so
         self._side = {}
         self._lex_drop()
+        self._text_drop()
         self._degrees = meta.get("degrees")
 
     def close(self) -> None:
         self._lex_drop()
+        self._text_drop()
         self.shards.close()
 
 
@@ -903,6 +1051,11 @@ class SpanCut(NamedTuple):
 def _value_key(v) -> str:
     """A filter value as part of a coalescing key: collections compare as sets of their members, range mappings as the
     inclusive bounds they stand for (``{"gt": 3}`` and ``{"gte": 4}`` select the same points) -- and as nothing else does."""
+    if _is_text(v):
+        try:
+            return "text" + repr(tuple(text_spec("", v)))
+        except (ValueError, TypeError):        # (a malformed text filter: its own key; the call fails where the filter is built)
+            return "text?" + repr(sorted((str(k), repr(x)) for k, x in v.items()))
     if _is_range(v):
         try:
             return "range" + repr(range_bounds("", v))
@@ -1269,6 +1422,9 @@ class HipVectorStore:
         nq = queries.shape[0]
         per = _per_query(filters, must_not, nq)
         if per is not None:
+            if has_text_condition(filters, must_not):
+                raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...}): a text condition is "
+                                 "one grep for the whole batch -- pass ONE filter dict")
             if diversity is not None or group is not None:
                 raise ValueError("per-query filters cannot be combined with diversity, group_by or max_overlap (a follow-up: the "
                                  "candidate lists behind them are per filter)")
@@ -1539,7 +1695,13 @@ class HipVectorStore:
         3.19).  A hit is dropped iff a better KEPT hit of the same file shares more than ``max_overlap`` of the SHORTER of the
         two spans with it; hits without a file or line numbers are never dropped; scores, ids and order are unchanged.
         ``candidates`` as for ``group_by``; a list that 1024 candidates cannot complete comes back short, never wrong.  Not
-        combinable with ``diversity``, ``group_by``, ``score_threshold`` or per-query filters.  ``None`` is the plain search."""
+        combinable with ``diversity``, ``group_by``, ``score_threshold`` or per-query filters.  ``None`` is the plain search.
+        A ``filters`` / ``must_not`` value on a TEXT key (``TEXT_KEYS``: ``content`` of the code chunks, ``summary`` of the
+        summaries) is a mapping ``{"contains": str | [str, ...], "any": False, "case": True}``: the points whose text holds the
+        literal string(s) -- all of them, or with ``any`` at least one; ``case=False`` folds ASCII letters only; under
+        ``must_not`` the points that do not (a point without the text passes).  Exact substring match on the device (Qdrant's
+        ``MatchText`` on a field without a full-text index), combinable with everything a filter combines with
+        except per-query filter lists.  1..8 patterns of 1..64 bytes of UTF-8 each."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -1586,7 +1748,8 @@ class HipVectorStore:
         name = collection.value if isinstance(collection, CollectionName) else collection
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
-        if self._coalesce_filters and diversity is None and group is None:
+        if self._coalesce_filters and diversity is None and group is None and not has_text_condition(filters, must_not):
+            # (a text condition is one grep per pass, not one per query: such calls are keyed by their filter below)
             # plain calls of one collection travel together whatever their filters: each entry carries its own
             key = (name, "any filter")
             self._search_pending.setdefault(key, []).append((vec, int(limit), fut, filters, must_not))
@@ -1828,6 +1991,59 @@ class HipVectorStore:
         try:
             texts, _, k1, b = self._lexical_args([text], 0, filters, must_not, 1.2, 0.75)
             return (await self._run(self._search_lexical_sync, collection, texts, 0, filters, must_not, k1, b))[1][0]
+        except Exception as e:
+            raise VectorStoreError(f"Failed to count in {collection}", cause=e)
+
+    # ------------------------------------------------------------------ literal text search
+    def _search_text_sync(self, collection: str, contains, limit: int, filters, must_not, any_of: bool, case: bool) -> dict[str, Any]:
+        """The text condition joined to the filter, the exact count and the first ``limit`` matching points in insertion order
+        (``crh_index_match_rows_cond``), with their ``match_line``; ``limit`` 0 asks for the count alone."""
+        col = self._col(collection)
+        if not col.text_keys:
+            raise ValueError(f"collection {col.name!r} has no text key to search")
+        key = col.text_keys[0]
+        if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+            raise ValueError("a text search takes one filter, not per-query filters")
+        if key in (filters or {}):
+            raise ValueError(f"the filter already holds a condition on {key!r}: give the strings in `contains`")
+        spec = {"contains": contains, "any": any_of, "case": case}
+        dfilt = col.device_filters({**(filters or {}), key: spec}, must_not)
+        if dfilt is None:
+            return {"hits": [], "count": 0}
+        count = int(col.shards.count_matching(dfilt))
+        if limit <= 0 or count == 0:
+            return {"hits": [], "count": count}
+        sh, lo = col.shards.match_rows(dfilt, int(limit))
+        slots = np.sort(col.slots_of(sh, lo))[: int(limit)]
+        hits = col.hits(slots, [0.0] * len(slots))
+        pats = text_spec(key, spec).patterns
+        for hit in hits:
+            text, start = hit["payload"].get(key), hit["payload"].get("start_line")
+            raw = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else b""
+            where = [p for p in ((raw if case else raw.translate(_ASCII_LOWER)).find(pat) for pat in pats) if p >= 0]
+            first = type(start) is int and where
+            hit["match_line"] = start + raw.count(b"\n", 0, min(where)) if first else None
+        return {"hits": hits, "count": count}
+
+    async def search_text(self, collection: str, contains, limit: int = 10, filters: dict[str, Any] | None = None,
+                          must_not: dict[str, Any] | None = None, *, any: bool = False, case: bool = True) -> dict[str, Any]:   # noqa: A002
+        """Literal text search -- grep over the stored chunks: the points whose text (``content`` of the code chunks, ``summary``
+        of the summaries) holds the string ``contains``, or every string of a list (``any``: at least one), under ``filters`` /
+        ``must_not`` as in :meth:`search`.  ``case=False`` folds ASCII letters only.  Returns ``{"hits": [...], "count": int}``:
+        ``hits`` are the first ``limit`` matching points in insertion order (``{"id", "score": 0.0, "payload", "match_line"}``),
+        ``count`` how many points match, exact and not clipped at ``limit``.  ``match_line`` is ``start_line`` plus the number of
+        newlines before the first occurrence of any of the strings (None for a point without an int ``start_line``).  Matched
+        on the device; 1..8 strings of 1..64 bytes of UTF-8 each."""
+        try:
+            return await self._run(self._search_text_sync, collection, contains, int(limit), filters, must_not, any, case)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def count_text(self, collection: str, contains, filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                         any: bool = False, case: bool = True) -> int:   # noqa: A002
+        """How many points :meth:`search_text` matches: exact."""
+        try:
+            return (await self._run(self._search_text_sync, collection, contains, 0, filters, must_not, any, case))["count"]
         except Exception as e:
             raise VectorStoreError(f"Failed to count in {collection}", cause=e)
 

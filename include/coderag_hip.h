@@ -64,18 +64,30 @@ typedef struct crh_filter {
  * An empty set has no member: "in" matches no row, "not in" every row.  A row whose code is -1 (key absent from its payload)
  * is a member of no set: it fails every "in" and passes every "not in"; negative codes in `codes` are ignored.
  *
- * `negate` is the condition's MODE.  0 = in and 1 = not in, as above; every other non-zero value but the two below keeps the
+ * `negate` is the condition's MODE.  0 = in and 1 = not in, as above; every other non-zero value but the four below keeps the
  * meaning "not in".  CRH_COND_BETWEEN (2) is a numeric RANGE over a column that stores values instead of dictionary codes (line
  * numbers: Qdrant's FieldCondition(key, range=Range(gte, lte)); the reference has no counterpart): n must be 2 and the row's value
  * v satisfies codes[0] <= v <= codes[1], both ends inclusive; codes[0] > codes[1] is an empty range.  CRH_COND_NOT_BETWEEN (3) is
  * its complement (the same Range under must_not).  A row whose value is negative (-1: absent) is inside no range: it fails every
  * BETWEEN and passes every NOT_BETWEEN whatever the bounds -- the set rule.  Mode 2 or 3 with n != 2 is CRH_E_INVALID.  A range
  * uploads nothing; every entry point that takes crh_condition (search_cond / _multi / _range, match_rows_cond, tombstone_cond)
- * takes ranges, with the mask cache and the sparse route as for sets.  sizeof(crh_condition) is 24 as before. */
+ * takes ranges, with the mask cache and the sparse route as for sets.  sizeof(crh_condition) is 24 as before.
+ *
+ * CRH_COND_WORDS (4) is a ROW BITMAP somebody else computed (crh_text_match: the rows whose text holds a string): `codes` is a
+ * DEVICE pointer to n u32 validity words (bit i of word t = row 32 t + i, as crh_index_row_mask writes them), cast to const
+ * int32_t *; the words must be complete on the search's stream before the call and stay untouched until the search has finished;
+ * n must be at least ceil(count / 32), anything less -- or a NULL pointer with rows in the index -- is CRH_E_INVALID.  `col` is no
+ * column here but a caller-chosen TAG.  The row passes iff its bit is set; CRH_COND_NOT_WORDS (5) iff it is clear.  Like every mode
+ * the pass is ANDed with `alive` and the other conditions, the mask is kept and the sparse route taken as for sets, also when it is
+ * the only condition.  The mask cache cannot look into the buffer: two such conditions are EQUAL iff pointer, n, mode and tag are
+ * all equal, so whoever rewrites a buffer must change the tag.  Taken by crh_search_cond, crh_search_range,
+ * crh_index_match_rows_cond and crh_index_row_mask; crh_search_multi and crh_index_tombstone_cond answer CRH_E_INVALID. */
 #define CRH_COND_IN 0
 #define CRH_COND_NOT_IN 1
 #define CRH_COND_BETWEEN 2
 #define CRH_COND_NOT_BETWEEN 3
+#define CRH_COND_WORDS 4
+#define CRH_COND_NOT_WORDS 5
 typedef struct crh_condition {
     int32_t col;
     int32_t negate;
@@ -590,6 +602,43 @@ int crh_lex_stats(crh_lex *l, const uint32_t *mask_dev, int64_t nt, const uint32
 int crh_lex_search(crh_lex *l, int nq, const int64_t *q_off_host, const uint32_t *q_terms_host, const float *q_idf_host, float k1,
                    float b, float avgdl, int k, const uint32_t *mask_dev, int64_t row_base, float *out_scores_dev,
                    int64_t *out_rows_dev, int64_t *out_count_dev, void *stream);
+
+/* ---- literal substring match on the device.  Qdrant's counterpart is FieldCondition(key, match=MatchText(text)) on a field
+ * without a full-text index: an exact substring match.  The definitions are this repository's own and exact.
+ *
+ * A crh_text is an ARENA whose rows are numbered like the rows of the crh_index it accompanies: row_off int64 [rows + 1] and the
+ * rows' bytes one behind the other, both in device memory.  What the bytes are is the caller's business (the store keeps the
+ * UTF-8 of a chunk's content).  Buffers grow by doubling on append; a match releases nothing. */
+typedef struct crh_text crh_text; /* opaque */
+#define CRH_TEXT_MAX_PATTERNS 8
+#define CRH_TEXT_MAX_PATTERN_BYTES 64
+#define CRH_TEXT_ALL 0 /* a row matches iff it holds every pattern */
+#define CRH_TEXT_ANY 1 /* ... at least one pattern */
+
+int crh_text_create(int device, int64_t capacity_rows, int64_t capacity_bytes, crh_text **out);
+int crh_text_destroy(crh_text *t);
+int crh_text_clear(crh_text *t); /* forget every row, keep the buffers */
+int crh_text_count(crh_text *t, int64_t *rows_out, int64_t *bytes_out);
+
+/* n rows behind the existing ones, host pointers: row_off [n + 1] starting at 0, bytes_host row_off[n] bytes.  CRH_E_INVALID,
+ * with nothing stored, when n < 0 or the offsets do not start at 0 or decrease.  A row without bytes is allowed.  Synchronous. */
+int crh_text_append(crh_text *t, int64_t n, const int64_t *row_off_host, const uint8_t *bytes_host);
+
+/* Which rows hold the patterns.  Pattern p is pat_bytes_host[pat_off_host[p] .. pat_off_host[p + 1]): 1..CRH_TEXT_MAX_PATTERNS
+ * patterns of 1..CRH_TEXT_MAX_PATTERN_BYTES bytes each (repeats allowed).
+ *   A row MATCHES pattern p iff p's bytes occur contiguously inside that row's own bytes; a match never spans two rows.
+ *   fold_case != 0 maps ASCII A..Z to a..z, on the text and on the pattern; every other byte compares as itself ('@', '[', '`',
+ *   '{', NUL and all bytes >= 0x80: no Unicode case folding).
+ *   combine: CRH_TEXT_ALL / CRH_TEXT_ANY.
+ * Bit r of out_words_dev (u32 [ceil(rows / 32)], every word written) is set iff the row's bit is set in mask_dev (words as
+ * crh_index_row_mask writes them, complete on `stream` before the call; NULL: every row < rows) and the row matches; bits at or
+ * past `rows` are 0.  A tile whose mask word is 0 costs no read of its text.  out_count_host (int64, may be NULL) receives the
+ * number of set bits, exact; with it the call waits for `stream`, without it it only enqueues.  Any violation of the limits, a
+ * NULL pointer or an unknown `combine` is CRH_E_INVALID with nothing launched; an arena without rows is CRH_OK, count 0, no
+ * launch.  Deterministic. */
+int crh_text_match(crh_text *t, int n_pat, const int64_t *pat_off_host, const uint8_t *pat_bytes_host, int fold_case, int combine,
+                   const uint32_t *mask_dev /* or NULL */, uint32_t *out_words_dev, int64_t *out_count_host /* or NULL */,
+                   void *stream);
 
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
