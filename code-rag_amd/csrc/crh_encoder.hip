@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef CRH_ATTN_PERMLANE
 #define CRH_ATTN_PERMLANE 1
@@ -441,7 +442,66 @@ constexpr int BM = 256, BN = 128, BK = 64, STAGES = 3, GEMM_WAVES = 8;
 // wave's ds_read_b128 of 16 rows x 4 chunks spreads over all 16 slots of the 256-B bank row (conflict-free)
 __device__ __forceinline__ int lds_off(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
-// EPI: 0 bias, 1 bias + erf-GELU, 2 bias + residual.  M arbitrary (guarded), N % 128 == 0, K % 64 == 0.
+// ---- the epilogues of the three tiled kernels (k_gemm_nt, k_gemm_mid, g256::k_gemm_pp): the ONE place that says what they compute.
+// EPI: 0 bias, 1 bias + erf-GELU, 2 bias + residual; the LayerNorm-folded forms (round 5):
+//   3 / 4  "LN in": A holds UN-normalised rows r, W the weights scaled by the LayerNorm gain (W' = gamma (.) W), and the epilogue
+//          finishes the normalisation per row m: y = rstd_m (acc - mu_m c_n) + b'_n = fma(acc, rstd_m, fma(nmr_m, c_n, b'_n)) with
+//          rstats[m] = (rstd_m, nmr_m = -mu_m rstd_m), aux0 = c_n = sum_k W'_nk, bias = b'_n = b_n + sum_k beta_k W_nk; 4 adds erf-GELU.
+//   5      "residual + stats out": out = bf16(acc + bias_n + h), h the residual -- normalised on the fly when rstats is given:
+//          out = bf16(fma(fma(r, rstd_m, nmr_m), aux0_n /*gamma*/, acc + bias_n)) with bias = this GEMM's bias + the LayerNorm's beta
+//          (folded on the host), else out = bf16((acc + bias_n) + r), which is epilogue 2.  `out` is the UN-normalised input of
+//          the next LayerNorm; per (row, 32-column slot) the mean and the sum of squared deviations of the rounded outputs go to
+//          partials[m][n / 32] (LnAcc / ln_join_row above; k_ln_finalize turns a row's N / 32 pairs into (rstd, nmr)).
+constexpr int EPI_BIAS = 0, EPI_GELU = 1, EPI_RES = 2, EPI_LNIN = 3, EPI_LNIN_GELU = 4, EPI_RES_STATS = 5, kEpilogues = 6;
+constexpr bool epi_ln_in(int e) { return e == EPI_LNIN || e == EPI_LNIN_GELU; }
+constexpr bool epi_gelu(int e) { return e == EPI_GELU || e == EPI_LNIN_GELU; }
+constexpr bool epi_residual(int e) { return e == EPI_RES || e == EPI_RES_STATS; }
+constexpr bool epi_stats(int e) { return e == EPI_RES_STATS; }
+
+// One accumulator fragment (4 consecutive n of one row m) through epilogue EPI -> the packed, once-rounded bf16 quad.
+// b = bias, st = the row's (rstd, nmr), cv = colsum (3 / 4) or gain (5), r = the residual, res_ln = epilogue 5 normalises its
+// residual.  What an epilogue does not use is never read.  (Explicit fma: the file is compiled with -ffp-contract=off.)
+template <int EPI>
+__device__ __forceinline__ u32x2 epi_frag(const f32x4 &acc, const float4 &b, const float2 &st, const float4 &cv, const u32x2 &r, const bool res_ln)
+{
+    const float bb[4] = {b.x, b.y, b.z, b.w};
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = acc[j] + bb[j];
+    if (epi_ln_in(EPI)) {
+        const float cc[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(acc[j], st.x, __builtin_fmaf(st.y, cc[j], bb[j]));
+    }
+    if (epi_gelu(EPI)) {
+        const f32x2_t ga = gelu_erf2(f32x2_t{v[0], v[1]}), gb = gelu_erf2(f32x2_t{v[2], v[3]});
+        v[0] = ga.x;
+        v[1] = ga.y;
+        v[2] = gb.x;
+        v[3] = gb.y;
+    }
+    if (epi_residual(EPI)) {
+        const float h[4] = {bf2f(r.x & 0xffffu), bf2f(r.x >> 16), bf2f(r.y & 0xffffu), bf2f(r.y >> 16)};
+        if (epi_stats(EPI) && res_ln) {
+            const float gg[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(__builtin_fmaf(h[j], st.x, st.y), gg[j], v[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] += h[j];
+        }
+    }
+    u32x2 o;
+    o.x = pack2(v[0], v[1]);
+    o.y = pack2(v[2], v[3]);
+    return o;
+}
+// epilogue 5: the ROUNDED values of a fragment into the statistics of its row's 32-column slot
+__device__ __forceinline__ void ln_acc_frag(LnAcc &a, bool first, u32x2 o)
+{
+    ln_acc4(a, first, bf2f(o.x & 0xffffu), bf2f(o.x >> 16), bf2f(o.y & 0xffffu), bf2f(o.y >> 16));
+}
+// EPI: the epilogues above.  M arbitrary (guarded), N % 128 == 0, K % 64 == 0.
 // 256x128x64 tiles, 8 waves (4 along M x 2 along N, 64x64 each), one workgroup per CU.
 //  * Staging by LDS-DMA (global_load_lds_dwordx4): one wave-instruction moves 1 KiB = 8 tile rows straight into LDS
 //    (destination = wave-uniform base + lane*16, a lane-linear image); the XOR swizzle the fragment reads expect is applied
@@ -669,7 +729,7 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_gemm_nt(const bf16_t *__res
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) bv[nt] = *reinterpret_cast<const float4 *>(bias + n0 + wn * 64 + nt * 16 + 4 * g);
         u32x2 rv[4][4];
-        if (EPI == 2 || EPI == 5) {
+        if (epi_residual(EPI)) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -679,11 +739,11 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_gemm_nt(const bf16_t *__res
                     rv[nt][mt] = *reinterpret_cast<const u32x2 *>(R + (size_t)m * N + n0 + wn * 64 + nt * 16 + 4 * g);
                 }
         }
-        // EPI 3 / 4 ("LN in", crh_gemm256.hpp): per-row (rstd, -mu rstd) of the A rows and the column sums of the gain-scaled weights
+        // "LN in": per-row (rstd, -mu rstd) of the A rows and the column sums of the gain-scaled weights
         float2 st[4];
         float4 cv[4];
-        const bool res_ln = EPI == 5 && rstats != nullptr;   // epilogue 5: the residual is normalised on the fly (cv = the gain)
-        if (EPI == 3 || EPI == 4 || res_ln) {
+        const bool res_ln = epi_stats(EPI) && rstats != nullptr;   // epilogue 5: the residual is normalised on the fly (cv = the gain)
+        if (epi_ln_in(EPI) || res_ln) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 int m = m0 + wm * 64 + mt * 16 + c16;
@@ -698,48 +758,16 @@ __global__ __launch_bounds__(GEMM_WAVES * 64) void k_gemm_nt(const bf16_t *__res
 #pragma unroll
             for (int mh = 0; mh < 2; ++mh) {
                 const int mt = half * 2 + mh;
-                LnAcc la[2];   // EPI 5: the row's two 32-column slots of this wave
+                LnAcc la[2];   // epilogue 5: the row's two 32-column slots of this wave
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
-                    float v0 = acc[nt][mt][0] + bv[nt].x, v1 = acc[nt][mt][1] + bv[nt].y, v2 = acc[nt][mt][2] + bv[nt].z,
-                          v3 = acc[nt][mt][3] + bv[nt].w;
-                    if (EPI == 3 || EPI == 4) {
-                        v0 = __builtin_fmaf(acc[nt][mt][0], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].x, bv[nt].x));
-                        v1 = __builtin_fmaf(acc[nt][mt][1], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].y, bv[nt].y));
-                        v2 = __builtin_fmaf(acc[nt][mt][2], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].z, bv[nt].z));
-                        v3 = __builtin_fmaf(acc[nt][mt][3], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].w, bv[nt].w));
-                    }
-                    if (EPI == 1 || EPI == 4) {
-                        const f32x2_t ga = gelu_erf2(f32x2_t{v0, v1}), gb = gelu_erf2(f32x2_t{v2, v3});
-                        v0 = ga.x;
-                        v1 = ga.y;
-                        v2 = gb.x;
-                        v3 = gb.y;
-                    }
-                    if (EPI == 2 || EPI == 5) {
-                        const float h0 = bf2f(rv[nt][mt].x & 0xffffu), h1 = bf2f(rv[nt][mt].x >> 16), h2 = bf2f(rv[nt][mt].y & 0xffffu),
-                                    h3 = bf2f(rv[nt][mt].y >> 16);
-                        if (res_ln) {
-                            v0 = __builtin_fmaf(__builtin_fmaf(h0, st[mt].x, st[mt].y), cv[nt].x, v0);
-                            v1 = __builtin_fmaf(__builtin_fmaf(h1, st[mt].x, st[mt].y), cv[nt].y, v1);
-                            v2 = __builtin_fmaf(__builtin_fmaf(h2, st[mt].x, st[mt].y), cv[nt].z, v2);
-                            v3 = __builtin_fmaf(__builtin_fmaf(h3, st[mt].x, st[mt].y), cv[nt].w, v3);
-                        } else {
-                            v0 += h0;
-                            v1 += h1;
-                            v2 += h2;
-                            v3 += h3;
-                        }
-                    }
-                    u32x2 o;
-                    o.x = pack2(v0, v1);
-                    o.y = pack2(v2, v3);
-                    if (EPI == 5) ln_acc4(la[nt >> 1], (nt & 1) == 0, bf2f(o.x & 0xffffu), bf2f(o.x >> 16), bf2f(o.y & 0xffffu), bf2f(o.y >> 16));
+                    const u32x2 o = epi_frag<EPI>(acc[nt][mt], bv[nt], st[mt], cv[nt], rv[nt][mt], res_ln);
+                    if (epi_stats(EPI)) ln_acc_frag(la[nt >> 1], (nt & 1) == 0, o);
                     const int row = mh * 16 + c16;           // row of the 32-row image
                     const int chunk = nt * 2 + (g >> 1);     // 16-byte chunk of the 128-byte row holding cols nt*16 + 4g ..
                     *reinterpret_cast<u32x2 *>(cimg + row * 128 + ((chunk ^ (row & 7)) << 4) + (g & 1) * 8) = o;
                 }
-                if (EPI == 5) {
+                if (epi_stats(EPI)) {
                     const float2 p0 = ln_join_row(ln_acc_done8(la[0])), p1 = ln_join_row(ln_acc_done8(la[1]));
                     const int m = m0 + wm * 64 + mt * 16 + c16;
                     if (g == 0 && m < M)
@@ -1366,34 +1394,24 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mid(const bf16_t *__restrict__ 
         }
     }
     // a lane holds, per (nt, mt), the 4 consecutive n = n0 + wn*32 + nt*16 + 4g + {0..3} of row m = m0 + wm*32 + mt*16 + c16
-    const bool res_ln = EPI == 5 && rstats != nullptr;
+    const bool res_ln = epi_stats(EPI) && rstats != nullptr;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const int m = m0 + wm * 32 + mt * 16 + c16;
         const int mc = m < M ? m : M - 1;          // (rows past M compute on a valid row and store nothing: the row joins below need every lane)
         float2 st = float2{1.f, 0.f};
-        if (EPI == 3 || EPI == 4 || res_ln) st = *reinterpret_cast<const float2 *>(rstats + 2 * (size_t)mc);
-        LnAcc la;      // EPI 5: the row's 32-column slot of this wave
+        if (epi_ln_in(EPI) || res_ln) st = *reinterpret_cast<const float2 *>(rstats + 2 * (size_t)mc);
+        LnAcc la;      // epilogue 5: the row's 32-column slot of this wave
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
             const int n = n0 + wn * 32 + nt * 16 + 4 * g;
             const float4 b4 = *reinterpret_cast<const float4 *>(bias + n);
-            float o0 = acc[nt][mt][0] + b4.x, o1 = acc[nt][mt][1] + b4.y, o2 = acc[nt][mt][2] + b4.z, o3 = acc[nt][mt][3] + b4.w;
-            if (EPI == 3 || EPI == 4) {      // "LN in" (crh_gemm256.hpp): the same two fma per element as the other tiled kernels
-                const float4 c4 = *reinterpret_cast<const float4 *>(aux0 + n);
-                o0 = __builtin_fmaf(acc[nt][mt][0], st.x, __builtin_fmaf(st.y, c4.x, b4.x));
-                o1 = __builtin_fmaf(acc[nt][mt][1], st.x, __builtin_fmaf(st.y, c4.y, b4.y));
-                o2 = __builtin_fmaf(acc[nt][mt][2], st.x, __builtin_fmaf(st.y, c4.z, b4.z));
-                o3 = __builtin_fmaf(acc[nt][mt][3], st.x, __builtin_fmaf(st.y, c4.w, b4.w));
-            }
-            if (EPI == 1 || EPI == 4) {
-                const f32x2_t ga = gelu_erf2(f32x2_t{o0, o1}), gb = gelu_erf2(f32x2_t{o2, o3});
-                o0 = ga.x;
-                o1 = ga.y;
-                o2 = gb.x;
-                o3 = gb.y;
-            }
-            if (EPI == 2 || EPI == 5) {
+            u32x2 o;
+            if constexpr (epi_stats(EPI)) {
+                // Epilogue 5 keeps its OWN copy of epi_frag<5>'s arithmetic here: the gain is fetched inside the branch that uses it.
+                // Through epi_frag the fetch needs a branch of its own ahead of the call (10 instructions more per tile, FFN2 at T = 300
+                // 2 % slower: profiles/gemm_refactor.md).  A change to epi_frag's residual path must be repeated in these lines.
+                float o0 = acc[nt][mt][0] + b4.x, o1 = acc[nt][mt][1] + b4.y, o2 = acc[nt][mt][2] + b4.z, o3 = acc[nt][mt][3] + b4.w;
                 const u32x2 r2 = *reinterpret_cast<const u32x2 *>(R + (size_t)mc * N + n);
                 const float h0 = bf2f(r2.x & 0xffffu), h1 = bf2f(r2.x >> 16), h2 = bf2f(r2.y & 0xffffu), h3 = bf2f(r2.y >> 16);
                 if (res_ln) {
@@ -1408,14 +1426,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mid(const bf16_t *__restrict__ 
                     o2 += h2;
                     o3 += h3;
                 }
+                o.x = pack2(o0, o1);
+                o.y = pack2(o2, o3);
+                ln_acc_frag(la, nt == 0, o);
+            } else {
+                u32x2 r2;
+                float4 c4;   // colsum ("LN in")
+                if (epi_residual(EPI)) r2 = *reinterpret_cast<const u32x2 *>(R + (size_t)mc * N + n);
+                if (epi_ln_in(EPI)) c4 = *reinterpret_cast<const float4 *>(aux0 + n);
+                o = epi_frag<EPI>(acc[nt][mt], b4, st, c4, r2, false);
             }
-            u32x2 o;
-            o.x = pack2(o0, o1);
-            o.y = pack2(o2, o3);
-            if (EPI == 5) ln_acc4(la, nt == 0, bf2f(o.x & 0xffffu), bf2f(o.x >> 16), bf2f(o.y & 0xffffu), bf2f(o.y >> 16));
             if (m < M) *reinterpret_cast<u32x2 *>(C + (size_t)m * N + n) = o;
         }
-        if (EPI == 5) {
+        if (epi_stats(EPI)) {
             const float2 p = ln_join_row(ln_acc_done8(la));
             if (g == 0 && m < M) *reinterpret_cast<float2 *>(partials + ((size_t)m * (N >> 5) + ((n0 >> 5) + wn)) * 2) = p;
         }
@@ -1438,10 +1461,13 @@ namespace {
 // label's gridDim/8 workgroups stride through that share: size the grid by the BUSIEST label.  (Sizing it by the total --
 // min(tiles, CUs) -- gave T = 5120, N = 768 a grid of 120: 15 workgroups per label for the 18 tiles of a 3-panel label,
 // i.e. two rounds, 93 us against 50 at both T = 4096 and T = 6144.)
+int64_t busiest_label(int64_t panels, int64_t nb)     // tiles of the XCD label with the most (also what the cost model of choose_gemm counts)
+{
+    return panels >= 16 ? crh::ceil_div(panels, 8) * nb : crh::ceil_div(panels * nb, 8);
+}
 unsigned xcd_grid(int64_t panels, int64_t nb, int64_t max_per_label)
 {
-    const int64_t busiest = panels >= 16 ? crh::ceil_div(panels, 8) * nb : crh::ceil_div(panels * nb, 8);
-    return (unsigned)(8 * std::max<int64_t>(1, std::min(busiest, max_per_label)));
+    return (unsigned)(8 * std::max<int64_t>(1, std::min(busiest_label(panels, nb), max_per_label)));
 }
 unsigned gemm_grid(int T, int N)
 {
@@ -1453,16 +1479,6 @@ unsigned gemm_grid(int T, int N)
     return xcd_grid(crh::ceil_div(T, BM), N / BN, persistent ? crh::current_device_cus() / 8 : INT32_MAX);
 }
 
-template <int EPI>
-int launch_mid(const void *x, const void *w, const float *bias, const void *res, void *y, int T, int N, int K, hipStream_t st,
-               const float *aux0 = nullptr, const float *rstats = nullptr, float *partials = nullptr)
-{
-    const int64_t tiles = crh::ceil_div(T, 64) * (N / 64);
-    hipLaunchKernelGGL((k_gemm_mid<EPI>), dim3((unsigned)(crh::ceil_div(tiles, 8) * 8)), dim3(256), 0, st, (const bf16_t *)x, (const bf16_t *)w, bias,
-                       (const bf16_t *)res, (bf16_t *)y, T, N, K, aux0, rstats, partials);
-    CRH_HIP(hipGetLastError());
-    return CRH_OK;
-}
 // ---- which tiled kernel?  Three kernels compete and the winner flips with the shape (measured per
 // GEMM, tools/gemm_mid_sweep.py): a launch costs (rounds of its busiest XCD label) x (one tile's walk through K), so
 // k_gemm_nt wins while its 256x128 tiles fill the chip in one round, the 256x256 ping-pong kernel wherever halving the
@@ -1488,9 +1504,7 @@ GemmKernel choose_gemm(int T, int N, int K, int act)
     if (pp_ok && pp_mode == 2) return GEMM_PP;
     const double kf = K / 768.0;
     auto tiled = [&](int bm, int bn, double per_round) {
-        const int64_t panels = crh::ceil_div(T, bm), nb = N / bn;
-        const int64_t busiest = panels >= 16 ? crh::ceil_div(panels, 8) * nb : crh::ceil_div(panels * nb, 8);
-        const int64_t rounds = crh::ceil_div(busiest, 32);
+        const int64_t rounds = crh::ceil_div(busiest_label(crh::ceil_div(T, bm), N / bn), 32);
         return per_round * (1.0 + 0.85 * (double)(rounds - 1));
     };
     const double nt = tiled(BM, BN, 11.0 * kf + 6.0 + (act ? 2.0 : 0.0));
@@ -1503,48 +1517,68 @@ unsigned gemm256_grid(int T, int N)
 {
     return xcd_grid(crh::ceil_div(T, g256::BM), N / g256::BN, crh::current_device_cus() / 8);
 }
-int launch_gemm256(int epi, const void *x, const void *w, const float *bias, const void *res, void *y, int T, int N, int K, hipStream_t st,
-                   const float *aux0 = nullptr, const float *rstats = nullptr, float *partials = nullptr)
+constexpr size_t kGemmLds = (size_t)STAGES * (BM + BN) * BK * 2;  // 144 KB of the CU's 160 KB
+
+// f(std::integral_constant<int, epi>{}): how a runtime epilogue number reaches a template parameter
+template <class F>
+int with_epi(int epi, F &&f)
 {
-    static OncePerDevice once;
-    if (once.need()) {
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<0>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<1>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<2>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<4>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<5>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-    }
-    const dim3 grid(gemm256_grid(T, N)), block(g256::WAVES * 64);
-    const bf16_t *xa = (const bf16_t *)x, *wa = (const bf16_t *)w, *ra = (const bf16_t *)res;
-    bf16_t *ya = (bf16_t *)y;
     switch (epi) {
-    case 0: hipLaunchKernelGGL((g256::k_gemm_pp<0>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    case 1: hipLaunchKernelGGL((g256::k_gemm_pp<1>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    case 2: hipLaunchKernelGGL((g256::k_gemm_pp<2>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    case 3: hipLaunchKernelGGL((g256::k_gemm_pp<3>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    case 4: hipLaunchKernelGGL((g256::k_gemm_pp<4>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    case 5: hipLaunchKernelGGL((g256::k_gemm_pp<5>), grid, block, g256::kLds, st, xa, wa, bias, ra, ya, T, N, K, aux0, rstats, partials); break;
-    default: return fail(CRH_E_INTERNAL, "gemm256: epilogue %d", epi);
+    case EPI_BIAS: return f(std::integral_constant<int, EPI_BIAS>{});
+    case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{});
+    case EPI_RES: return f(std::integral_constant<int, EPI_RES>{});
+    case EPI_LNIN: return f(std::integral_constant<int, EPI_LNIN>{});
+    case EPI_LNIN_GELU: return f(std::integral_constant<int, EPI_LNIN_GELU>{});
+    case EPI_RES_STATS: return f(std::integral_constant<int, EPI_RES_STATS>{});
+    default: return fail(CRH_E_INTERNAL, "gemm: epilogue %d", epi);
     }
+}
+// dynamic LDS above 64 KiB: lds_attr sets one kernel's attribute, for_each_epi calls f for each of the six epilogues
+template <class Kern>
+int lds_attr(Kern kern, int bytes)
+{
+    CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return CRH_OK;
+}
+template <class F>
+int for_each_epi(F &&f)
+{
+    for (int e = 0; e < kEpilogues; ++e) CRH_TRY(with_epi(e, f));
+    return CRH_OK;
+}
+// the one place a tiled GEMM kernel is launched from
+template <class Kern>
+int launch_kernel(Kern kern, unsigned grid, unsigned block, size_t lds, const void *x, const void *w, const float *bias, const void *res, void *y,
+                  int T, int N, int K, hipStream_t st, const float *aux0, const float *rstats, float *partials)
+{
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)res, (bf16_t *)y, T, N, K,
+                       aux0, rstats, partials);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }
-
-constexpr size_t kGemmLds = (size_t)STAGES * (BM + BN) * BK * 2;  // 144 KB of the CU's 160 KB
-
-int gemm_lds_attr()
+// One GEMM with epilogue `epi` by the tiled kernel choose_gemm picks (`forced`: that kernel; the caller has checked its shape).
+int launch_gemm(int epi, const void *x, const void *w, const float *bias, const void *res, void *y, int T, int N, int K, hipStream_t st,
+                const float *aux0 = nullptr, const float *rstats = nullptr, float *partials = nullptr, const GemmKernel *forced = nullptr)
 {
-    static OncePerDevice once;
-    if (once.need()) {
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<3, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<5, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds));
+    const GemmKernel which = forced ? *forced : choose_gemm(T, N, K, epi_gelu(epi));
+    if (which == GEMM_PP) {
+        static OncePerDevice once;
+        if (once.need())
+            CRH_TRY(for_each_epi([](auto E) { return lds_attr(g256::k_gemm_pp<decltype(E)::value>, g256::kLds); }));
+    } else if (which == GEMM_NT) {
+        static OncePerDevice once;
+        if (once.need())
+            CRH_TRY(for_each_epi([](auto E) { return lds_attr(k_gemm_nt<decltype(E)::value, 0>, (int)kGemmLds); }));
     }
-    return CRH_OK;
+    return with_epi(epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        if (which == GEMM_MID)
+            return launch_kernel(k_gemm_mid<EPI>, (unsigned)(crh::ceil_div(crh::ceil_div(T, 64) * (N / 64), 8) * 8), 256, 0, x, w, bias, res, y, T, N, K, st,
+                                 aux0, rstats, partials);
+        if (which == GEMM_PP)
+            return launch_kernel(g256::k_gemm_pp<EPI>, gemm256_grid(T, N), g256::WAVES * 64, g256::kLds, x, w, bias, res, y, T, N, K, st, aux0, rstats, partials);
+        return launch_kernel(k_gemm_nt<EPI, 0>, gemm_grid(T, N), GEMM_WAVES * 64, kGemmLds, x, w, bias, res, y, T, N, K, st, aux0, rstats, partials);
+    });
 }
 }  // namespace
 
@@ -1556,17 +1590,7 @@ int crh_gemm_bf16_bias(const void *x, const void *w, const float *bias, void *y,
     if (T <= 0 || N <= 0 || K <= 0 || N % BN || K % BK) return fail(CRH_E_INVALID, "gemm: shape T=%d N=%d K=%d (need N%%128==0, K%%64==0)", T, N, K);
     if (act != 0 && act != 1) return fail(CRH_E_INVALID, "gemm: act=%d (0 none, 1 gelu)", act);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const GemmKernel which = choose_gemm(T, N, K, act);
-    if (which == GEMM_MID) return act == 1 ? launch_mid<1>(x, w, bias, nullptr, y, T, N, K, st) : launch_mid<0>(x, w, bias, nullptr, y, T, N, K, st);
-    if (which == GEMM_PP) return launch_gemm256(act, x, w, bias, nullptr, y, T, N, K, st);
-    const dim3 grid(gemm_grid(T, N));
-    CRH_TRY(gemm_lds_attr());
-    if (act == 1)
-        hipLaunchKernelGGL((k_gemm_nt<1, 0>), grid, dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-    else
-        hipLaunchKernelGGL((k_gemm_nt<0, 0>), grid, dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-    CRH_HIP(hipGetLastError());
-    return CRH_OK;
+    return launch_gemm(act ? EPI_GELU : EPI_BIAS, x, w, bias, nullptr, y, T, N, K, st);
 }
 
 #ifdef CRH_ENABLE_DEBUG   // libcoderag_hip_debug.so only (build.sh): never exported by the product library
@@ -1574,76 +1598,36 @@ int crh_gemm_bf16_bias(const void *x, const void *w, const float *bias, void *y,
 int crh_debug_gemm_variant(const void *x, const void *w, const float *bias, void *y, int T, int N, int K, int variant, void *stream)
 {
     if (!x || !w || !bias || !y || T <= 0 || N % BN || K % BK) return fail(CRH_E_INVALID, "debug gemm: bad arguments");
-    const dim3 grid(gemm_grid(T, N));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    CRH_TRY(gemm_lds_attr());
-#define CRH_DBG_LAUNCH(V)                                                                                                   \
-    do {                                                                                                                    \
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_nt<0, V>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmLds)); \
-        hipLaunchKernelGGL((k_gemm_nt<0, V>), grid, dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias,  \
-                           (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);                                                 \
-    } while (0)
+    const bool pp = variant >= 16 && variant <= 20;   // 0-8: k_gemm_nt, 16-20: the 256x256 ping-pong kernel regardless of the tile count
+    if (pp && !pp_allowed(T, N, K)) return fail(CRH_E_INVALID, "debug gemm: variants 16-20 need N%%256==0, K%%128==0, K>=256, byte offsets < 4 GiB");
+    const GemmKernel kernel = pp ? GEMM_PP : GEMM_NT;
+    // an instantiation with a DBG mask: bias epilogue, its LDS attribute set on every call
+    auto ablate = [&](auto kern) {
+        const int lds = pp ? g256::kLds : (int)kGemmLds;
+        CRH_TRY(lds_attr(kern, lds));
+        return launch_kernel(kern, pp ? gemm256_grid(T, N) : gemm_grid(T, N), pp ? g256::WAVES * 64 : GEMM_WAVES * 64, lds, x, w, bias, nullptr, y, T, N, K, st,
+                             nullptr, nullptr, nullptr);
+    };
     switch (variant) {
-    case 16:   // the 256x256 ping-pong kernel regardless of the tile count (results are valid)
-        if (N % g256::BN || K % (2 * g256::BK) || K < 4 * g256::BK || (int64_t)T * K * 2 >= (1LL << 32))
-            return fail(CRH_E_INVALID, "debug gemm: variant 16 needs N%%256==0, K%%128==0, K>=256, T*K*2 < 4 GiB");
-        return launch_gemm256(0, x, w, bias, nullptr, y, T, N, K, st);
-    case 19:   // EPI 2 (bias + residual, residual = y's previous contents) without the LayerNorm: isolates the residual epilogue
-        if (N % g256::BN || K % (2 * g256::BK) || K < 4 * g256::BK || (int64_t)T * K * 2 >= (1LL << 32)) return fail(CRH_E_INVALID, "debug gemm: bad shape");
-        return launch_gemm256(2, x, w, bias, y, y, T, N, K, st);
-    case 20: {   // no epilogue + 1.5x LDS-DMA + extra fragment reads (what a two-pass half-height schedule would load)
-        if (N % g256::BN || K % (2 * g256::BK) || K < 4 * g256::BK || (int64_t)T * K * 2 >= (1LL << 32)) return fail(CRH_E_INVALID, "debug gemm: bad shape");
-        const dim3 grid256(gemm256_grid(T, N)), block(g256::WAVES * 64);
-        CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<0, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-        hipLaunchKernelGGL((g256::k_gemm_pp<0, 6>), grid256, block, g256::kLds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-        CRH_HIP(hipGetLastError());
-        return CRH_OK;
-    }
-    case 17:
-    case 18: {   // ablations of the ping-pong kernel's epilogue: 17 = no global stores, 18 = no epilogue
-        if (N % g256::BN || K % (2 * g256::BK) || K < 4 * g256::BK || (int64_t)T * K * 2 >= (1LL << 32)) return fail(CRH_E_INVALID, "debug gemm: bad shape");
-        const dim3 grid256(gemm256_grid(T, N)), block(g256::WAVES * 64);
-        if (variant == 17) {
-            CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-            hipLaunchKernelGGL((g256::k_gemm_pp<0, 1>), grid256, block, g256::kLds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-        } else {
-            CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g256::k_gemm_pp<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, g256::kLds));
-            hipLaunchKernelGGL((g256::k_gemm_pp<0, 2>), grid256, block, g256::kLds, st, (const bf16_t *)x, (const bf16_t *)w, bias, (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-        }
-        CRH_HIP(hipGetLastError());
-        return CRH_OK;
-    }
-    case 0: CRH_DBG_LAUNCH(0); break;
-    case 1: CRH_DBG_LAUNCH(1); break;
-    case 2: CRH_DBG_LAUNCH(2); break;
-    case 4: CRH_DBG_LAUNCH(4); break;
-    case 5: CRH_DBG_LAUNCH(5); break;
-    case 6: CRH_DBG_LAUNCH(6); break;
-    case 8: CRH_DBG_LAUNCH(8); break;
+    case 0:
+    case 16:   // (results are valid)
+        return launch_gemm(EPI_BIAS, x, w, bias, nullptr, y, T, N, K, st, nullptr, nullptr, nullptr, &kernel);
+    case 19:   // bias + residual (residual = y's previous contents) without the LayerNorm: isolates the residual epilogue
+        return launch_gemm(EPI_RES, x, w, bias, y, y, T, N, K, st, nullptr, nullptr, nullptr, &kernel);
+    case 1: return ablate(k_gemm_nt<EPI_BIAS, 1>);
+    case 2: return ablate(k_gemm_nt<EPI_BIAS, 2>);
+    case 4: return ablate(k_gemm_nt<EPI_BIAS, 4>);
+    case 5: return ablate(k_gemm_nt<EPI_BIAS, 5>);
+    case 6: return ablate(k_gemm_nt<EPI_BIAS, 6>);
+    case 8: return ablate(k_gemm_nt<EPI_BIAS, 8>);
+    case 17: return ablate(g256::k_gemm_pp<EPI_BIAS, 1>);   // no global stores in the epilogue
+    case 18: return ablate(g256::k_gemm_pp<EPI_BIAS, 2>);   // no epilogue
+    case 20: return ablate(g256::k_gemm_pp<EPI_BIAS, 6>);   // no epilogue + 1.5x LDS-DMA + extra fragment reads (what a two-pass half-height schedule would load)
     default: return fail(CRH_E_INVALID, "debug gemm: variant %d", variant);
     }
-#undef CRH_DBG_LAUNCH
-    CRH_HIP(hipGetLastError());
-    return CRH_OK;
 }
 #endif  // CRH_ENABLE_DEBUG
-
-// One GEMM of any tiled kernel with epilogue `epi` (0 bias, 2 bias + residual)
-static int launch_tiled(int epi, const void *x, const void *w, const float *bias, const void *res, void *y, int T, int N, int K, hipStream_t st)
-{
-    const GemmKernel which = choose_gemm(T, N, K, 0);
-    if (which == GEMM_MID) return epi == 2 ? launch_mid<2>(x, w, bias, res, y, T, N, K, st) : launch_mid<0>(x, w, bias, nullptr, y, T, N, K, st);
-    if (which == GEMM_PP) return launch_gemm256(epi, x, w, bias, res, y, T, N, K, st);
-    CRH_TRY(gemm_lds_attr());
-    if (epi == 2)
-        hipLaunchKernelGGL((k_gemm_nt<2, 0>), dim3(gemm_grid(T, N)), dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias,
-                           (const bf16_t *)res, (bf16_t *)y, T, N, K);
-    else
-        hipLaunchKernelGGL((k_gemm_nt<0, 0>), dim3(gemm_grid(T, N)), dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias,
-                           (const bf16_t *)nullptr, (bf16_t *)y, T, N, K);
-    CRH_HIP(hipGetLastError());
-    return CRH_OK;
-}
 
 int crh_gemm_bf16_bias_res_ln(const void *x, const void *w, const float *bias, const void *residual, const float *gamma,
                               const float *beta, float eps, void *y, int T, int N, int K, void *stream)
@@ -1661,8 +1645,7 @@ int crh_gemm_bf16_bias_res_ln(const void *x, const void *w, const float *bias, c
     //   K  > 1024 (FFN2): residual added to the f32 accumulator in the GEMM epilogue, one rounding, plain LayerNorm after.
     // (y == residual with K <= 1024 cannot take the first form -- the GEMM would overwrite the residual -- and falls to the second.)
     const bool ln_side = K <= 1024 && y != residual;
-    const int epi = ln_side ? 0 : 2;
-    CRH_TRY(launch_tiled(epi, x, w, bias, residual, y, T, N, K, st));
+    CRH_TRY(launch_gemm(ln_side ? EPI_BIAS : EPI_RES, x, w, bias, ln_side ? nullptr : residual, y, T, N, K, st));
     if (ln_side)
         hipLaunchKernelGGL(k_layernorm768_res, dim3((unsigned)ceil_div(T, 4)), dim3(256), 0, st, (bf16_t *)y, (const bf16_t *)residual, gamma, beta, eps, T);
     else
@@ -1678,7 +1661,7 @@ int crh_gemm_bf16_bias_res32_ln(const void *x, const void *w, const float *bias,
     if (N != 768) return fail(CRH_E_INVALID, "gemm_res32_ln: N=%d (the LayerNorm is built for 768)", N);
     if (T <= 0 || K <= 0 || K % BK) return fail(CRH_E_INVALID, "gemm_res32_ln: shape T=%d K=%d", T, K);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    CRH_TRY(launch_tiled(0, x, w, bias, nullptr, y, T, N, K, st));      // bias-only epilogue at every K: the residual joins in f32, below
+    CRH_TRY(launch_gemm(EPI_BIAS, x, w, bias, nullptr, y, T, N, K, st));      // bias-only epilogue at every K: the residual joins in f32, below
     hipLaunchKernelGGL(k_layernorm768_res32, dim3((unsigned)ceil_div(T, 4)), dim3(256), 0, st, (bf16_t *)y, residual_f32, gamma, beta, eps, T);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
@@ -1692,21 +1675,7 @@ int crh_gemm_bf16_lnin(const void *x, const float *row_stats, const void *w_scal
     if (T <= 0 || N <= 0 || K <= 0 || N % BN || K % BK) return fail(CRH_E_INVALID, "gemm_lnin: shape T=%d N=%d K=%d (need N%%128==0, K%%64==0)", T, N, K);
     if (act != 0 && act != 1) return fail(CRH_E_INVALID, "gemm_lnin: act=%d (0 none, 1 gelu)", act);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const GemmKernel which = choose_gemm(T, N, K, act);
-    if (which == GEMM_MID)
-        return act == 1 ? launch_mid<4>(x, w_scaled, bias_folded, nullptr, y, T, N, K, st, colsum, row_stats)
-                        : launch_mid<3>(x, w_scaled, bias_folded, nullptr, y, T, N, K, st, colsum, row_stats);
-    if (which == GEMM_PP) return launch_gemm256(3 + act, x, w_scaled, bias_folded, nullptr, y, T, N, K, st, colsum, row_stats, nullptr);
-    const dim3 grid(gemm_grid(T, N));
-    CRH_TRY(gemm_lds_attr());
-    if (act == 1)
-        hipLaunchKernelGGL((k_gemm_nt<4, 0>), grid, dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w_scaled, bias_folded,
-                           (const bf16_t *)nullptr, (bf16_t *)y, T, N, K, colsum, row_stats);
-    else
-        hipLaunchKernelGGL((k_gemm_nt<3, 0>), grid, dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w_scaled, bias_folded,
-                           (const bf16_t *)nullptr, (bf16_t *)y, T, N, K, colsum, row_stats);
-    CRH_HIP(hipGetLastError());
-    return CRH_OK;
+    return launch_gemm(act ? EPI_LNIN_GELU : EPI_LNIN, x, w_scaled, bias_folded, nullptr, y, T, N, K, st, colsum, row_stats);
 }
 
 int crh_gemm_bf16_res_lnstats(const void *x, const void *w, const float *bias, const void *residual, const float *res_stats,
@@ -1718,17 +1687,7 @@ int crh_gemm_bf16_res_lnstats(const void *x, const void *w, const float *bias, c
     if (T <= 0 || K <= 0 || K % BK) return fail(CRH_E_INVALID, "gemm_res_lnstats: shape T=%d K=%d", T, K);
     if (y == residual) return fail(CRH_E_INVALID, "gemm_res_lnstats: the output must not overwrite the residual");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const GemmKernel which = choose_gemm(T, N, K, 0);
-    if (which == GEMM_MID) {
-        CRH_TRY(launch_mid<5>(x, w, bias, residual, y, T, N, K, st, res_gamma, res_stats, partials));
-    } else if (which == GEMM_PP) {
-        CRH_TRY(launch_gemm256(5, x, w, bias, residual, y, T, N, K, st, res_gamma, res_stats, partials));
-    } else {
-        CRH_TRY(gemm_lds_attr());
-        hipLaunchKernelGGL((k_gemm_nt<5, 0>), dim3(gemm_grid(T, N)), dim3(GEMM_WAVES * 64), kGemmLds, st, (const bf16_t *)x, (const bf16_t *)w, bias,
-                           (const bf16_t *)residual, (bf16_t *)y, T, N, K, res_gamma, res_stats, partials);
-        CRH_HIP(hipGetLastError());
-    }
+    CRH_TRY(launch_gemm(EPI_RES_STATS, x, w, bias, residual, y, T, N, K, st, res_gamma, res_stats, partials));
     static_assert(kLnSlots == 768 / 32, "k_ln_finalize is built for 768 columns");
     hipLaunchKernelGGL(k_ln_finalize, dim3((unsigned)ceil_div(T, 64)), dim3(64), 0, st, (const float *)partials, stats_out, T, eps);
     CRH_HIP(hipGetLastError());

@@ -1,7 +1,7 @@
 // crh_gemm256.hpp -- the large-T encoder GEMM: C[M,N] = epi(A[M,K] . W[N,K]^T + bias), 256x256x64 tiles, two wave
 // groups per CU running half a phase apart ("ping-pong"): while one group's four waves issue MFMAs, the other group's
 // four (their SIMD partners) read fragments from LDS and issue the LDS-DMA of a later k-tile, then the roles swap.
-// Included by crh_encoder.hip (types, gelu_erf, pack2, bf2f come from there).
+// Included by crh_encoder.hip (types, pack2, bf2f, gelu_erf2 and the epilogue definition -- EPI_*, epi_frag, ln_acc_frag -- come from there).
 //
 // Geometry.  8 waves; group grp = wave >> 2 owns tile rows [grp*128, +128), column wc = wave & 3 owns tile columns
 // [wc*64, +64): 128 x 64 outputs per wave = acc[nt 0..3][mt 0..7] (C^T fragments: a lane holds 4 consecutive n of one m).
@@ -41,15 +41,7 @@ constexpr int R_AH0 = 0, R_WH0 = 1, R_WH1 = 2, R_AH1 = 3;
 
 __device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
-// EPI: 0 bias, 1 bias + erf-GELU, 2 bias + residual; the LayerNorm-folded forms (round 5):
-//   3 / 4  "LN in": A holds UN-normalised rows r, W the weights scaled by the LayerNorm gain (W' = gamma (.) W), and the epilogue
-//          finishes the normalisation per row m: y = rstd_m (acc - mu_m c_n) + b'_n = fma(acc, rstd_m, fma(nmr_m, c_n, b'_n)) with
-//          rstats[m] = (rstd_m, nmr_m = -mu_m rstd_m), aux0 = c_n = sum_k W'_nk, bias = b'_n = b_n + sum_k beta_k W_nk; 4 adds erf-GELU.
-//   5      "residual + stats out": out = bf16(acc + bias_n + h), h the residual -- normalised on the fly when rstats is given:
-//          out = bf16(fma(fma(r, rstd_m, nmr_m), aux0_n /*gamma*/, acc + bias_n)) with bias = this GEMM's bias + the LayerNorm's beta
-//          (folded on the host), else out = bf16((acc + bias_n) + r), which is epilogue 2.  `out` is the UN-normalised input of
-//          the next LayerNorm; per (row, 32-column slot) the mean and the sum of squared deviations of the rounded outputs go to
-//          partials[m][n / 32] (crh_encoder.hip: LnAcc / ln_join_row; k_ln_finalize turns a row's N / 32 pairs into (rstd, nmr)).
+// EPI: the epilogues named and explained in crh_encoder.hip (EPI_BIAS .. EPI_RES_STATS, epi_frag).
 // M arbitrary (guarded), N % 256 == 0, K % 128 == 0, K >= 256.
 // DBG (timing ablations, wrong results): 1 = no global stores in the epilogue, 2 = no epilogue at all, 4 = 1.5x the LDS-DMA
 // (one more half-tile every other phase, into the idle epilogue images) and 4 more fragment reads per phase -- the load a
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
     // its own range of panels) walk the row panels from the last to the first: every label starts on the rows it wrote last, which
     // are still in its L2 / the last-level cache, instead of on the ones written first and evicted since (+0.3-0.7 % of the encoder
     // leg on two of three devices, level on the third: profiles/r05_ffn2_panel_order.txt).  Order only: a tile's bits do not change.
-    constexpr bool kLastFirst = EPI == 2 || EPI == 5;
+    constexpr bool kLastFirst = epi_residual(EPI);
     auto tile_origin = [&](int ts, int &tm0, int &tn0) {
         const int u = jx + ts * bpx;
         if (!by_panel) {
@@ -251,7 +243,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
     // after the advance, to this one in phases 2-3
     int m0 = 0, n0 = 0;   // origin of the tile being computed
     float4 bv[4];         // its bias fragment, fetched under the tile's last 16 MFMAs (FW1 is dead by then)
-    float b_lin = 0.f, g_lin = 1.f;   // EPI 5: bias and LayerNorm gain of column n0 + wc*64 + lane
+    float b_lin = 0.f, g_lin = 1.f;   // epilogue 5: bias and LayerNorm gain of column n0 + wc*64 + lane
     auto extra_load = [&](const bool dma) __attribute__((always_inline)) {
         if (!(DBG & 4)) return;
         if (dma && c_more) {
@@ -297,7 +289,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
         stage(R_WH0, B);
         extra_load(false);
         if (last && !(DBG & 2)) {
-            if (EPI == 5) {   // one column per lane (2 registers; the epilogue spreads them through a 512-byte LDS table)
+            if (epi_stats(EPI)) {   // one column per lane (2 registers; the epilogue spreads them through a 512-byte LDS table)
                 b_lin = bias[n0 + wc * 64 + lane];
                 g_lin = rstats != nullptr ? aux0[n0 + wc * 64 + lane] : 1.0f;
             } else {
@@ -333,8 +325,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
                 for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(acc[i][j]));
             continue;
         }
-        if constexpr (EPI == 5) {
-            // ---- epilogue 5 (header comment): out = bf16(acc + bias + h), h = the residual, normalised on the fly when rstats is given;
+        if constexpr (epi_stats(EPI)) {
+            // ---- epilogue 5: out = bf16(acc + bias + h), h = the residual, normalised on the fly when rstats is given;
             // statistics of the rounded outputs per (row, 32-column slot).  Registers are what bounds this epilogue (the 128
             // accumulators stay live while it runs): bias and gain live lane-linear in one register each and a 4-column fragment
             // is read from a small LDS table per (q, nt); the residual rows and their statistics come in two batches of four m-tiles.
@@ -376,22 +368,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
                     const float4 b4 = *reinterpret_cast<const float4 *>(smem + tq + nt * 64), g4 = *reinterpret_cast<const float4 *>(smem + tq + 256 + nt * 64);
-                    const float bb[4] = {b4.x, b4.y, b4.z, b4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
 #pragma unroll
                     for (int mh = 0; mh < 2; ++mh) {
                         const int mt = q * 2 + mh;
-                        const u32x2 r2 = rq[mt >> 2][nt][mt & 3];
-                        const float2 s2 = sq[mt >> 2][mt & 3];
-                        const float h0 = bf2f(r2.x & 0xffffu), h1 = bf2f(r2.x >> 16), h2 = bf2f(r2.y & 0xffffu), h3 = bf2f(r2.y >> 16);
                         // (without statistics: rstd = 1, nmr = 0, gain = 1 -- fma(h, 1, 0) = h and fma(h, 1, v) = v + h: epilogue 2's bits)
-                        const float v0 = __builtin_fmaf(__builtin_fmaf(h0, s2.x, s2.y), gg[0], acc[nt][mt][0] + bb[0]);
-                        const float v1 = __builtin_fmaf(__builtin_fmaf(h1, s2.x, s2.y), gg[1], acc[nt][mt][1] + bb[1]);
-                        const float v2 = __builtin_fmaf(__builtin_fmaf(h2, s2.x, s2.y), gg[2], acc[nt][mt][2] + bb[2]);
-                        const float v3 = __builtin_fmaf(__builtin_fmaf(h3, s2.x, s2.y), gg[3], acc[nt][mt][3] + bb[3]);
-                        u32x2 o;
-                        o.x = pack2(v0, v1);
-                        o.y = pack2(v2, v3);
-                        ln_acc4(la[mh][nt >> 1], (nt & 1) == 0, bf2f(o.x & 0xffffu), bf2f(o.x >> 16), bf2f(o.y & 0xffffu), bf2f(o.y >> 16));
+                        const u32x2 o = epi_frag<EPI>(acc[nt][mt], b4, sq[mt >> 2][mt & 3], g4, rq[mt >> 2][nt][mt & 3], true);
+                        ln_acc_frag(la[mh][nt >> 1], (nt & 1) == 0, o);
                         const int row = mh * 16 + c16;
                         const int chunk = nt * 2 + (g >> 1);
                         *reinterpret_cast<u32x2 *>(cimg + row * 128 + ((chunk ^ (row & 7)) << 4) + (g & 1) * 8) = o;
@@ -415,11 +397,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
             after_epi = (m0 + BM <= M) ? 3 : 0;
             continue;
         }
-        // epilogues 3 / 4 ("LN in"): per-row (rstd, -mu rstd) of the A rows and the column sums of the gain-scaled weights
-        constexpr bool kLnIn = EPI == 3 || EPI == 4;
+        // "LN in": per-row (rstd, -mu rstd) of the A rows and the column sums of the gain-scaled weights
         float2 st[8];
         float4 cv[4];
-        if (kLnIn) {
+        if (epi_ln_in(EPI)) {
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) {
                 int m = m0 + grp * 128 + mt * 16 + c16;
@@ -442,7 +423,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
                     rv[batch][nt][mi] = *reinterpret_cast<const u32x2 *>(R + (size_t)m * N + n0 + wc * 64 + nt * 16 + 4 * g);
                 }
         };
-        if (EPI == 2) load_res(0);
+        if (EPI == EPI_RES) load_res(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -450,31 +431,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
 #pragma unroll
                 for (int mh = 0; mh < 2; ++mh) {
                     const int mt = q * 2 + mh;
-                    float v0 = acc[nt][mt][0] + bv[nt].x, v1 = acc[nt][mt][1] + bv[nt].y, v2 = acc[nt][mt][2] + bv[nt].z,
-                          v3 = acc[nt][mt][3] + bv[nt].w;
-                    if (kLnIn) {
-                        v0 = __builtin_fmaf(acc[nt][mt][0], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].x, bv[nt].x));
-                        v1 = __builtin_fmaf(acc[nt][mt][1], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].y, bv[nt].y));
-                        v2 = __builtin_fmaf(acc[nt][mt][2], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].z, bv[nt].z));
-                        v3 = __builtin_fmaf(acc[nt][mt][3], st[mt].x, __builtin_fmaf(st[mt].y, cv[nt].w, bv[nt].w));
-                    }
-                    if (EPI == 1 || EPI == 4) {
-                        const f32x2_t ga = gelu_erf2(f32x2_t{v0, v1}), gb = gelu_erf2(f32x2_t{v2, v3});
-                        v0 = ga.x;
-                        v1 = ga.y;
-                        v2 = gb.x;
-                        v3 = gb.y;
-                    }
-                    if (EPI == 2) {
-                        const u32x2 r2 = rv[mt >> 2][nt][mt & 3];
-                        v0 += bf2f(r2.x & 0xffffu);
-                        v1 += bf2f(r2.x >> 16);
-                        v2 += bf2f(r2.y & 0xffffu);
-                        v3 += bf2f(r2.y >> 16);
-                    }
-                    u32x2 o;
-                    o.x = pack2(v0, v1);
-                    o.y = pack2(v2, v3);
+                    const u32x2 o = epi_frag<EPI>(acc[nt][mt], bv[nt], st[mt], cv[nt], rv[mt >> 2][nt][mt & 3], false);
                     const int row = mh * 16 + c16;
                     const int chunk = nt * 2 + (g >> 1);
                     *reinterpret_cast<u32x2 *>(cimg + row * 128 + ((chunk ^ (row & 7)) << 4) + (g & 1) * 8) = o;
@@ -489,14 +446,14 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_pp(const bf16_t *__restrict
                     // stores are acknowledged sooner, and the next tile's counted waits stall less on them (-8 % on those
                     // GEMMs); the N = 768 outputs are re-read at once by the LayerNorm and keep the default policy
                     u32x4 *dst = reinterpret_cast<u32x4 *>(C + (size_t)m * N + n0 + wc * 64 + chunk * 8);
-                    if (EPI == 2)
+                    if (EPI == EPI_RES)
                         *dst = v;
                     else
                         __builtin_nontemporal_store(v, dst);
                 }
                 if (DBG & 1) asm volatile("" ::"v"(v));
             }
-            if (EPI == 2 && q == 0) load_res(1);
+            if (EPI == EPI_RES && q == 0) load_res(1);
         }
         after_epi = (m0 + BM <= M) ? 3 : 0;   // a ragged tile may have skipped stores: fall back to the tighter wait
     }

@@ -242,37 +242,57 @@ class HipUniXcoder:
     # ------------------------------------------------------------------ kernels
     def forward_ids(self, ids):
         """ids: int32 CUDA tensor [B, L], L % 16 == 0, padded with the pad id.  Returns f32 [B, 768] sentence embeddings."""
-        torch, L_ = self._torch, ffi.lib()
+        L_ = ffi.lib()
         ffi.use_device(self.device.index)      # (worker threads start on device 0)
         B, L = ids.shape
+        cfg, H = self.cfg, self.cfg.hidden_size
+        st = self._torch.cuda.current_stream(self.device).cuda_stream
+        pids = int(ids.data_ptr())
+        return self._forward(
+            B, B * L, L, st,
+            lambda px, pkm: L_.crh_embed_ln(pids, *self._emb_ptrs, cfg.layer_norm_eps, cfg.pad_token_id, px, pkm, B, L, H, st),
+            lambda pqkv, pkm, pctx: L_.crh_attn_fwd_varlen(pqkv, pkm, pctx, B, L, cfg.num_heads, st),
+            lambda px, pkm, psent: L_.crh_masked_mean_pool(px, pkm, psent, B, L, H, st))
+
+    def _forward(self, B, T, Lmax, st, embed, attention, pool):
+        """The body of both forwards: the activation buffers of T tokens in B rows of up to ``Lmax``, then embed -> the twelve
+        layers in the form ``cfg`` asks for -> pool.  ``embed(px, pkm)``, ``attention(pqkv, pkm, pctx)`` and ``pool(px, pkm, psent)``
+        are the padded or the packed entry points, bound by the caller; each returns the library's status."""
+        torch = self._torch
         cfg, H, F = self.cfg, self.cfg.hidden_size, self.cfg.intermediate_size
-        T = B * L
-        st = torch.cuda.current_stream(self.device).cuda_stream
         bf = torch.bfloat16
         x = torch.empty((T, H), dtype=bf, device=self.device)
         x1 = torch.empty((T, H), dtype=bf, device=self.device)
         qkv = torch.empty((T, 3 * H), dtype=bf, device=self.device)
         ctx = torch.empty((T, H), dtype=bf, device=self.device)
         hid = torch.empty((T, F), dtype=bf, device=self.device)
-        kmask = torch.empty((B, (L + 63) // 64), dtype=torch.int64, device=self.device)
+        kmask = torch.empty((B, (Lmax + 63) // 64), dtype=torch.int64, device=self.device)
         sent = torch.empty((B, H), dtype=torch.float32, device=self.device)
         px, px1, pqkv, pctx, phid, pkm, psent = (int(t.data_ptr()) for t in (x, x1, qkv, ctx, hid, kmask, sent))
+        check = ffi.check
+        check(embed(px, pkm))
+        layers = self._layers_folded if cfg.ln_fold else self._layers_res32 if cfg.residual_f32 else self._layers_default
+        layers(px, px1, pqkv, pctx, phid, T, st, lambda: check(attention(pqkv, pkm, pctx)), x0=x)
+        check(pool(px, pkm, psent))
+        return sent
+
+    def _layers_default(self, px, px1, pqkv, pctx, phid, T, st, attention, x0=None) -> None:
+        """The twelve layers in the default form: a bf16 residual stream, each LayerNorm right behind its GEMM
+        (``crh_gemm_bf16_bias_res_ln``).  ``px`` holds the embedding LayerNorm's output on entry and the last LayerNorm's on exit."""
+        L_ = ffi.lib()
+        cfg, H, F = self.cfg, self.cfg.hidden_size, self.cfg.intermediate_size
         eps, check = cfg.layer_norm_eps, ffi.check
-        gemm, gemm_ln, attn = L_.crh_gemm_bf16_bias, L_.crh_gemm_bf16_bias_res_ln, L_.crh_attn_fwd_varlen
-        check(L_.crh_embed_ln(int(ids.data_ptr()), *self._emb_ptrs, eps, cfg.pad_token_id, px, pkm, B, L, H, st))
-        if cfg.ln_fold or cfg.residual_f32:
-            layers = self._layers_folded if cfg.ln_fold else self._layers_res32
-            layers(px, px1, pqkv, pctx, phid, T, st, lambda: check(attn(pqkv, pkm, pctx, B, L, cfg.num_heads, st)), x0=x)
-            check(L_.crh_masked_mean_pool(px, pkm, psent, B, L, H, st))
-            return sent
+        gemm, gemm_ln = L_.crh_gemm_bf16_bias, L_.crh_gemm_bf16_bias_res_ln
         for ly in self._layer_ptrs:
+            # (a launch loop re-takes the interpreter lock microseconds after every ctypes call: a thread that waits for it -- the
+            # store's worker answering a query beside this indexing run -- would otherwise get it only at the 5 ms switch
+            # interval, per hop; yielding once per layer costs a microsecond and lets it in within a layer's ~1 ms)
+            _yield_gil()
             check(gemm(px, ly["qkv_w"], ly["qkv_b"], pqkv, T, 3 * H, H, 0, st))
-            check(attn(pqkv, pkm, pctx, B, L, cfg.num_heads, st))
+            attention()
             check(gemm_ln(pctx, ly["o_w"], ly["o_b"], px, ly["ln1_g"], ly["ln1_b"], eps, px1, T, H, H, st))
             check(gemm(px1, ly["f1_w"], ly["f1_b"], phid, T, F, H, 1, st))
             check(gemm_ln(phid, ly["f2_w"], ly["f2_b"], px1, ly["ln2_g"], ly["ln2_b"], eps, px, T, H, F, st))
-        check(L_.crh_masked_mean_pool(px, pkm, psent, B, L, H, st))
-        return sent
 
     def _layers_res32(self, px, px1, pqkv, pctx, phid, T, st, attention, x0=None) -> None:
         """The twelve layers with the residual stream in f32 (EncoderConfig.residual_f32): the same GEMMs and attention on bf16
@@ -332,39 +352,19 @@ class HipUniXcoder:
         take the row offsets (``crh_*_packed``).  Same arithmetic per token as :meth:`forward_ids`.  The kernels clamp every row to
         the T tokens of the buffers and a device-side check of ``row_off`` reports a bad array as ``NativeError(E_INVALID)`` at the
         next packed call -- or right here with ``verify=True`` (which waits for the stream)."""
-        torch, L_ = self._torch, ffi.lib()
+        L_ = ffi.lib()
         ffi.use_device(self.device.index)
         B, T = int(row_off.shape[0]) - 1, int(ids.shape[0])
-        cfg, H, F = self.cfg, self.cfg.hidden_size, self.cfg.intermediate_size
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        bf = torch.bfloat16
-        x = torch.empty((T, H), dtype=bf, device=self.device)
-        x1 = torch.empty((T, H), dtype=bf, device=self.device)
-        qkv = torch.empty((T, 3 * H), dtype=bf, device=self.device)
-        ctx = torch.empty((T, H), dtype=bf, device=self.device)
-        hid = torch.empty((T, F), dtype=bf, device=self.device)
-        kmask = torch.empty((B, (Lmax + 63) // 64), dtype=torch.int64, device=self.device)
-        sent = torch.empty((B, H), dtype=torch.float32, device=self.device)
-        px, px1, pqkv, pctx, phid, pkm, psent, poff = (int(t.data_ptr()) for t in (x, x1, qkv, ctx, hid, kmask, sent, row_off))
-        eps, check = cfg.layer_norm_eps, ffi.check
-        gemm, gemm_ln = L_.crh_gemm_bf16_bias, L_.crh_gemm_bf16_bias_res_ln
-        check(L_.crh_embed_ln_packed(int(ids.data_ptr()), poff, *self._emb_ptrs, eps, cfg.pad_token_id, px, pkm, B, T, Lmax, H, st))
-        if cfg.ln_fold or cfg.residual_f32:
-            layers = self._layers_folded if cfg.ln_fold else self._layers_res32
-            layers(px, px1, pqkv, pctx, phid, T, st, lambda: check(L_.crh_attn_fwd_packed(pqkv, poff, pkm, pctx, B, T, Lmax, cfg.num_heads, st)), x0=x)
-        for ly in (() if (cfg.ln_fold or cfg.residual_f32) else self._layer_ptrs):
-            # (a launch loop re-takes the interpreter lock microseconds after every ctypes call: a thread that waits for it -- the
-            # store's worker answering a query beside this indexing run -- would otherwise get it only at the 5 ms switch
-            # interval, per hop; yielding once per layer costs a microsecond and lets it in within a layer's ~1 ms)
-            _yield_gil()
-            check(gemm(px, ly["qkv_w"], ly["qkv_b"], pqkv, T, 3 * H, H, 0, st))
-            check(L_.crh_attn_fwd_packed(pqkv, poff, pkm, pctx, B, T, Lmax, cfg.num_heads, st))
-            check(gemm_ln(pctx, ly["o_w"], ly["o_b"], px, ly["ln1_g"], ly["ln1_b"], eps, px1, T, H, H, st))
-            check(gemm(px1, ly["f1_w"], ly["f1_b"], phid, T, F, H, 1, st))
-            check(gemm_ln(phid, ly["f2_w"], ly["f2_b"], px1, ly["ln2_g"], ly["ln2_b"], eps, px, T, H, F, st))
-        check(L_.crh_masked_mean_pool_packed(px, poff, pkm, psent, B, T, Lmax, H, st))
+        cfg, H = self.cfg, self.cfg.hidden_size
+        st = self._torch.cuda.current_stream(self.device).cuda_stream
+        pids, poff = int(ids.data_ptr()), int(row_off.data_ptr())
+        sent = self._forward(
+            B, T, Lmax, st,
+            lambda px, pkm: L_.crh_embed_ln_packed(pids, poff, *self._emb_ptrs, cfg.layer_norm_eps, cfg.pad_token_id, px, pkm, B, T, Lmax, H, st),
+            lambda pqkv, pkm, pctx: L_.crh_attn_fwd_packed(pqkv, poff, pkm, pctx, B, T, Lmax, cfg.num_heads, st),
+            lambda px, pkm, psent: L_.crh_masked_mean_pool_packed(px, poff, pkm, psent, B, T, Lmax, H, st))
         if verify:      # the sync point of a forward: the verdict of the device-side check of row_off (crh_encoder_finish)
-            check(L_.crh_encoder_finish(st))
+            ffi.check(L_.crh_encoder_finish(st))
         return sent
 
     def pack_rows(self, id_rows, rows):

@@ -31,8 +31,8 @@ import torch
 
 KERNELS = ("mid", "nt", "pp")       # the order the children run in
 TILE = {"nt": (256, 128), "mid": (64, 64), "pp": (256, 256)}
-# choose_gemm (csrc/crh_encoder.hip): CODERAG_HIP_MID=2 -> k_gemm_mid whenever N % 64 == 0; CODERAG_HIP_GEMM256=2 -> the ping-pong
-# kernel whenever pp_allowed(); both 0 -> k_gemm_nt
+# choose_gemm, asked by every entry's one launch_gemm call (csrc/crh_encoder.hip): CODERAG_HIP_MID=2 -> k_gemm_mid whenever
+# N % 64 == 0; CODERAG_HIP_GEMM256=2 -> the ping-pong kernel whenever pp_allowed(); both 0 -> k_gemm_nt
 ENV = {"nt": {"CODERAG_HIP_GEMM256": "0", "CODERAG_HIP_MID": "0"},
        "mid": {"CODERAG_HIP_MID": "2"},
        "pp": {"CODERAG_HIP_GEMM256": "2", "CODERAG_HIP_MID": "0"}}
