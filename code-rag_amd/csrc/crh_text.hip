@@ -1,4 +1,5 @@
-// crh_text.hip -- literal substring match over the chunks' text in HBM (gfx950 / CDNA4 only).
+// crh_text.hip -- literal substring match (k_text_match) and regular-expression match by byte DFA (k_text_regex, described where it
+// stands) over the chunks' text in HBM (gfx950 / CDNA4 only).
 //
 // Replaces what Qdrant answers for FieldCondition(key, match=MatchText(text)) on a field WITHOUT a full-text index: an exact
 // substring match ("chunks that contain `retry_after=`").  The definition is THIS repository's (tests/text_cases.py
@@ -201,6 +202,111 @@ __global__ __launch_bounds__(kTextWaves * 64) void k_text_match(const TextArgs a
     if (lane == 0 && found) atomicAdd(a.count, (unsigned long long)found);
 }
 
+// ---- k_text_regex: a byte DFA walked over every row
+//
+// One wave per PAIR of 32-row tiles, one lane per row; pairs are strided over the waves of the grid as the tiles are above.  A pair
+// whose two mask words are 0 stores zeros and reads no byte.  The DFA's image -- the class map (256 bytes) and the table with one
+// more column than the caller's, the SKIP column whose entry is the state itself -- is copied from the handle's buffer to dynamic
+// LDS once per workgroup; the LDS request is the size of THIS DFA, so a small one keeps full occupancy.  A lane streams its own
+// row with 16-byte aligned loads from `off[r] & ~15` to below `off[r + 1]` (so at most 15 bytes behind the row's end are read: the
+// arena's last row stays inside kTextSlack), the next load issued before the current 16 bytes are walked.  A byte outside
+// [begin, end) takes the SKIP class, so the walk has no branch and the predicate is off the dependent chain: per byte the chain is
+// one multiply-add and one LDS byte read.  The wave loops while any lane has bytes left and is not in the (absorbing) accept
+// state; then every lane feeds END.  A wave takes as long as its longest row; one very long row is a serial walk.  The two result
+// words are the halves of one ballot, ANDed with the mask words, stored by lane 0 -- the second only if that tile exists; the
+// count is one integer atomic per wave.
+constexpr int kRegexClassMap = 256;                     // bytes of the class map in front of the table in the image
+constexpr int kRegexImageMax = kRegexClassMap + CRH_REGEX_MAX_TABLE_BYTES + CRH_REGEX_MAX_STATES;   // (the SKIP column: one byte per state)
+
+struct RegexArgs {
+    const int64_t *row_off;
+    const uint8_t *bytes;
+    int64_t rows;
+    const uint32_t *mask;        // one word per tile, or nullptr: every row
+    uint32_t *out;               // one word per tile
+    unsigned long long *count;   // += set bits
+    const uint32_t *image;       // image_words dwords: class map, then table [n_states][ncols]
+    int image_words;
+    int ncols;                   // the caller's n_classes + 1: column ncols - 1 is SKIP
+    int end_class;
+    int accept;
+};
+
+template <int J>
+__device__ __forceinline__ void regex_classes(const text_u32x4 &w, int lo, int hi, uint32_t skip, const uint8_t *lds, uint32_t (&c)[kTextLane])
+{
+    const uint32_t d = J / 4 == 0 ? w.x : J / 4 == 1 ? w.y : J / 4 == 2 ? w.z : w.w;
+    const uint32_t cls = lds[(d >> (8 * (J % 4))) & 0xffu];
+    c[J] = (J >= lo && J < hi) ? cls : skip;
+    if constexpr (J + 1 < kTextLane) regex_classes<J + 1>(w, lo, hi, skip, lds, c);
+}
+
+__global__ __launch_bounds__(kTextWaves * 64) void k_text_regex(const RegexArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t regex_lds[];
+    for (int i = threadIdx.x; i < a.image_words; i += kTextWaves * 64) regex_lds[i] = a.image[i];
+    __syncthreads();
+    const uint8_t *lmap = reinterpret_cast<const uint8_t *>(regex_lds);
+    const uint8_t *ltab = lmap + kRegexClassMap;
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ntiles = (a.rows + 31) / 32, npairs = (ntiles + 1) / 2;
+    const uint32_t ncols = (uint32_t)a.ncols, skip = ncols - 1u, accept = (uint32_t)a.accept;
+    unsigned int found = 0u;   // set bits this wave has written (wave-uniform)
+
+    for (int64_t pr = (int64_t)blockIdx.x * kTextWaves + wave; pr < npairs; pr += (int64_t)gridDim.x * kTextWaves) {
+        const int64_t t0 = pr * 2, r0 = pr * 64;
+        const bool second = t0 + 1 < ntiles;                              // (wave-uniform) does the pair's second tile exist?
+        uint32_t m0 = a.mask ? a.mask[t0] : 0xffffffffu;
+        uint32_t m1 = second ? (a.mask ? a.mask[t0 + 1] : 0xffffffffu) : 0u;
+        const int64_t left = a.rows - r0;                                 // >= 1
+        if (left < 32) m0 &= (1u << (int)left) - 1u;
+        if (left < 64) m1 &= left <= 32 ? 0u : (1u << (int)(left - 32)) - 1u;
+        m0 = __builtin_amdgcn_readfirstlane(m0);
+        m1 = __builtin_amdgcn_readfirstlane(m1);
+        if ((m0 | m1) == 0u) {                                            // (wave-uniform) nothing of the pair is read
+            if (lane == 0) {
+                a.out[t0] = 0u;
+                if (second) a.out[t0 + 1] = 0u;
+            }
+            continue;
+        }
+        const bool active = (((lane < 32 ? m0 : m1) >> (lane & 31)) & 1u) != 0u;   // (a set bit is a row below `rows`)
+        int64_t begin = 0, end = 0;
+        if (active) {
+            begin = a.row_off[r0 + lane];
+            end = a.row_off[r0 + lane + 1];
+        }
+        int64_t p = begin < end ? begin & ~(int64_t)(kTextLane - 1) : end;
+        uint32_t s = 0u;
+        text_u32x4 cur = p < end ? *reinterpret_cast<const text_u32x4 *>(a.bytes + p) : text_u32x4{0u, 0u, 0u, 0u};
+        while (__ballot(p < end && s != accept) != 0ull) {
+            const int64_t pn = p + kTextLane;
+            // (unconditional, so that nothing waits for it before the walk: a lane without a next chunk reloads the arena's first)
+            const text_u32x4 nxt = *reinterpret_cast<const text_u32x4 *>(a.bytes + (pn < end ? pn : 0));
+            // the lane's bytes of this chunk that lie inside its row: [lo, hi) of 0..16 (none once p >= end)
+            const int64_t dlo = begin - p, dhi = end - p;
+            const int lo = dlo > 0 ? (int)dlo : 0;
+            const int hi = dhi >= kTextLane ? kTextLane : dhi > 0 ? (int)dhi : 0;
+            uint32_t c[kTextLane];
+            regex_classes<0>(cur, lo, hi, skip, lmap, c);                 // (independent of the state: off the chain)
+#pragma unroll
+            for (int j = 0; j < kTextLane; ++j) s = ltab[__umul24(s, ncols) + c[j]];   // (s < 256, ncols <= 258)
+            p = pn;
+            cur = nxt;
+        }
+        s = ltab[__umul24(s, ncols) + (uint32_t)a.end_class];
+        const unsigned long long hit = __ballot(active && s == accept);
+        const uint32_t w0 = (uint32_t)hit & m0, w1 = (uint32_t)(hit >> 32) & m1;
+        if (lane == 0) {
+            a.out[t0] = w0;
+            if (second) a.out[t0 + 1] = w1;
+        }
+        found += (unsigned int)(__popc(w0) + __popc(w1));
+    }
+    if (lane == 0 && found) atomicAdd(a.count, (unsigned long long)found);
+}
+
 int text_alloc(void **p, int64_t bytes)
 {
     hipError_t e = hipMalloc(p, (size_t)std::max<int64_t>(bytes, 1));
@@ -241,7 +347,9 @@ struct crh_text {
     int64_t cap_off = 0, cap_bytes = 0;   // in bytes: of row_off (8 per entry), of bytes (without the slack)
     uint8_t *row_off = nullptr;           // int64 [rows + 1]
     uint8_t *bytes = nullptr;             // nbytes, then kTextSlack zeros
-    unsigned long long *count = nullptr;  // the match's counter
+    unsigned long long *count = nullptr;  // the match's / the regex's counter
+    uint8_t *regex_image = nullptr;       // kRegexImageMax bytes, allocated by the first crh_text_regex
+    std::vector<uint8_t> regex_host;      // the image the last crh_text_regex uploaded (the copy's source outlives the call)
 };
 
 using namespace crh;
@@ -278,7 +386,7 @@ int crh_text_destroy(crh_text *t)
     if (!t) return CRH_OK;
     DeviceGuard g(t->device);
     (void)hipDeviceSynchronize();
-    void *bufs[] = {t->row_off, t->bytes, t->count};
+    void *bufs[] = {t->row_off, t->bytes, t->count, t->regex_image};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete t;
@@ -383,6 +491,75 @@ int crh_text_match(crh_text *t, int n_pat, const int64_t *pat_off_host, const ui
     case 4: text_launch<4>(a, fold, blocks, st); break;
     default: text_launch<8>(a, fold, blocks, st); break;
     }
+    CRH_HIP(hipGetLastError());
+    if (out_count_host) {
+        unsigned long long c = 0ull;
+        CRH_HIP(hipMemcpyAsync(&c, t->count, 8, hipMemcpyDeviceToHost, st));
+        CRH_HIP(hipStreamSynchronize(st));
+        *out_count_host = (int64_t)c;
+    }
+    return CRH_OK;
+}
+
+int crh_text_regex(crh_text *t, int n_states, int n_classes, const uint8_t *class_of_host, int end_class, const uint8_t *trans_host,
+                   int accept_state, const uint32_t *mask_dev, uint32_t *out_words_dev, int64_t *out_count_host, void *stream)
+{
+    if (!t) return fail(CRH_E_INVALID, "text handle is NULL");
+    if (out_count_host) *out_count_host = 0;
+    if (n_states < 1 || n_states > CRH_REGEX_MAX_STATES) return fail(CRH_E_INVALID, "text_regex: n_states=%d outside 1..%d", n_states, CRH_REGEX_MAX_STATES);
+    if (n_classes < 2 || n_classes > 257) return fail(CRH_E_INVALID, "text_regex: n_classes=%d outside 2..257", n_classes);
+    if ((int64_t)n_states * n_classes > CRH_REGEX_MAX_TABLE_BYTES)
+        return fail(CRH_E_INVALID, "text_regex: a table of %d x %d bytes (at most %d)", n_states, n_classes, CRH_REGEX_MAX_TABLE_BYTES);
+    if (!class_of_host || !trans_host) return fail(CRH_E_INVALID, "text_regex: NULL pointer");
+    if (end_class < 0 || end_class >= n_classes) return fail(CRH_E_INVALID, "text_regex: end_class=%d outside 0..%d", end_class, n_classes - 1);
+    if (accept_state < 0 || accept_state >= n_states) return fail(CRH_E_INVALID, "text_regex: accept_state=%d outside 0..%d", accept_state, n_states - 1);
+    for (int b = 0; b < 256; ++b)
+        if (class_of_host[b] >= n_classes) return fail(CRH_E_INVALID, "text_regex: class_of[%d]=%d is no class (%d classes)", b, (int)class_of_host[b], n_classes);
+    for (int i = 0; i < n_states * n_classes; ++i)
+        if (trans_host[i] >= n_states)
+            return fail(CRH_E_INVALID, "text_regex: trans[%d][%d]=%d is no state (%d states)", i / n_classes, i % n_classes, (int)trans_host[i], n_states);
+    for (int c = 0; c < n_classes; ++c)
+        if (trans_host[accept_state * n_classes + c] != accept_state)
+            return fail(CRH_E_INVALID, "text_regex: the accept state %d is not absorbing (class %d leaves it)", accept_state, c);
+    if (t->rows == 0) return CRH_OK;
+    if (!out_words_dev) return fail(CRH_E_INVALID, "text_regex: out_words_dev is NULL");
+    DeviceGuard g(t->device);
+    if (!t->regex_image) {
+        void *img = nullptr;
+        CRH_TRY(text_alloc(&img, kRegexImageMax));
+        t->regex_image = static_cast<uint8_t *>(img);
+    }
+    // the image the kernel copies to LDS: the class map, then the table with the SKIP column (a state's entry: itself) behind
+    // the caller's columns, padded with zeros to whole 16 bytes
+    const int ncols = n_classes + 1;
+    const size_t image_bytes = ((size_t)kRegexClassMap + (size_t)n_states * ncols + 15) / 16 * 16;
+    t->regex_host.assign(image_bytes, 0);
+    std::memcpy(t->regex_host.data(), class_of_host, 256);
+    for (int s = 0; s < n_states; ++s) {
+        uint8_t *row = t->regex_host.data() + kRegexClassMap + (size_t)s * ncols;
+        std::memcpy(row, trans_host + (size_t)s * n_classes, (size_t)n_classes);
+        row[n_classes] = (uint8_t)s;
+    }
+    RegexArgs a{};
+    a.row_off = reinterpret_cast<const int64_t *>(t->row_off);
+    a.bytes = t->bytes;
+    a.rows = t->rows;
+    a.mask = mask_dev;
+    a.out = out_words_dev;
+    a.count = t->count;
+    a.image = reinterpret_cast<const uint32_t *>(t->regex_image);
+    a.image_words = (int)(image_bytes / 4);
+    a.ncols = ncols;
+    a.end_class = end_class;
+    a.accept = accept_state;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (regex_host is pageable: HIP has read it when this call returns, which is what lets the NEXT call on this handle rewrite it
+    // while this one is only enqueued -- without out_count_host nothing else here waits)
+    CRH_HIP(hipMemcpyAsync(t->regex_image, t->regex_host.data(), image_bytes, hipMemcpyHostToDevice, st));
+    CRH_HIP(hipMemsetAsync(t->count, 0, 8, st));
+    const int64_t npairs = ceil_div(ceil_div(t->rows, 32), 2);
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(npairs, kTextWaves), (int64_t)current_device_cus() * 8);
+    hipLaunchKernelGGL(k_text_regex, dim3(blocks), dim3(kTextWaves * 64), image_bytes, st, a);
     CRH_HIP(hipGetLastError());
     if (out_count_host) {
         unsigned long long c = 0ull;

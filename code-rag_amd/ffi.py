@@ -33,6 +33,7 @@ MAX_CLASSES = 8        # CRH_MAX_CLASSES: distinct filters that share one pass o
 ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 LEX_MAX_QUERY_TERMS = 32   # CRH_LEX_MAX_QUERY_TERMS: distinct term ids of one crh_lex_search query
 TEXT_MAX_PATTERNS, TEXT_MAX_PATTERN_BYTES = 8, 64   # CRH_TEXT_MAX_PATTERNS / CRH_TEXT_MAX_PATTERN_BYTES of one crh_text_match
+REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 256, 32768   # CRH_REGEX_MAX_STATES / CRH_REGEX_MAX_TABLE_BYTES of one crh_text_regex
 TEXT_ALL, TEXT_ANY = 0, 1   # CRH_TEXT_ALL / CRH_TEXT_ANY
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
@@ -57,7 +58,7 @@ EXPORTS = (
     "crh_span_select",
     "crh_index_row_mask", "crh_lex_create", "crh_lex_destroy", "crh_lex_clear", "crh_lex_count", "crh_lex_append", "crh_lex_stats",
     "crh_lex_search",
-    "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match",
+    "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match", "crh_text_regex",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -221,6 +222,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_text_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.crh_text_append.argtypes = [vp, i64, vp, vp]
     L.crh_text_match.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, C.POINTER(i64), vp]
+    L.crh_text_regex.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i64), vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -1066,6 +1068,7 @@ class Text:
     """Owning wrapper of one ``crh_text`` handle: the text arena beside one :class:`Index` (same rows, same numbering), matched
     against literal byte patterns on the device."""
     match_calls = 0       # crh_text_match calls issued by all handles (tests count the greps of a job)
+    regex_calls = 0       # crh_text_regex calls issued by all handles
 
     def __init__(self, capacity_rows: int = 0, capacity_bytes: int = 0, device: int = 0):
         self.device = device
@@ -1125,6 +1128,33 @@ class Text:
         Text.match_calls += 1
         check(lib().crh_text_match(self._handle(), n, off.ctypes.data, data.ctypes.data, int(bool(fold_case)), TEXT_ANY if any_of else TEXT_ALL,
                                    _ptr(mask), _ptr(out), C.byref(c) if count else None, stream))
+        return out, (int(c.value) if count else None)
+
+    def regex(self, dfa, mask=None, out=None, count: bool = True, stream: int = 0):
+        """Which rows the byte DFA ``dfa`` matches (``crh_text_regex``): anything with ``n_states``,
+        ``n_classes``, ``class_of`` (256 entries), ``end_class``, ``trans`` (``n_states * n_classes`` entries) and ``accept`` --
+        a ``regex_dfa.RegexDFA``.  It is the library that refuses a table that breaks its limits.  ``mask``, ``out``, ``count``
+        and ``stream`` as in :meth:`match`."""
+        import torch
+        n_states, n_classes = int(dfa.n_states), int(dfa.n_classes)
+        class_of = np.ascontiguousarray(dfa.class_of, dtype=np.uint8).reshape(-1)
+        trans = np.ascontiguousarray(dfa.trans, dtype=np.uint8).reshape(-1)
+        if class_of.size != 256 or n_states < 0 or n_classes < 0 or trans.size != n_states * n_classes:
+            raise NativeError(E_INVALID, f"regex: class_of has {class_of.size} entries (256), trans {trans.size} ({n_states} states x {n_classes} classes)")
+        words = (self.count()[0] + 31) // 32
+        if mask is not None:
+            _typed(mask, "int32", "mask")
+            if not _is_dev(mask) or int(mask.numel()) < words:
+                raise NativeError(E_INVALID, "mask must be a device tensor of one word per 32-row tile")
+        if out is None:
+            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.device}")
+        _typed(out, "int32", "out")
+        if not _is_dev(out) or out.ndim != 1 or int(out.shape[0]) < words:
+            raise NativeError(E_INVALID, f"out must be a device tensor of at least {words} words")
+        c = C.c_int64(0)
+        Text.regex_calls += 1
+        check(lib().crh_text_regex(self._handle(), n_states, n_classes, class_of.ctypes.data, int(dfa.end_class), trans.ctypes.data if trans.size else None,
+                                   int(dfa.accept), _ptr(mask), _ptr(out), C.byref(c) if count else None, stream))
         return out, (int(c.value) if count else None)
 
 

@@ -32,7 +32,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               candidates: int | None = None, max_per_file: int | None = None, extra_queries: list[str] | None = None,
                               fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None,
                               min_score: float | None = None, max_overlap: float | None = None, mode: str | None = None,
-                              contains: str | list[str] | None = None, contains_case: bool | None = None) -> ToolResult:
+                              contains: str | list[str] | None = None, contains_case: bool | None = None,
+                              matches: str | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -45,7 +46,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                 return ToolResult(success=True, data=data, message=f"Found {len(data)} matches like {len(like_ids)} example(s).")
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
                                        ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score), ("max_overlap", max_overlap), ("mode", mode),
-                                       ("contains", contains or None), ("contains_case", contains_case if contains else None)) if v is not None}   # (only when asked for)
+                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches else None),
+                                       ("matches", matches or None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -93,7 +95,11 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             "contains": {"type": "string", "description": "A literal string (or a list of up to 8) every result's code must contain, "
                                                           "punctuation included: 'retry_after=', '.unwrap()', '#include <hip/'",
                          "required": False},
-            "contains_case": {"type": "boolean", "description": "With contains: false ignores the case of ASCII letters (default: true)",
+            "contains_case": {"type": "boolean", "description": "With contains / matches: false ignores the case of ASCII letters (default: true)",
                               "required": False},
+            "matches": {"type": "string", "description": "A regular expression (Python re syntax, ^ and $ at every line; no "
+                                                         "back-references or look-around) that must be found in every result's code: "
+                                                         "'def \\w+_retry\\(', '^\\s*#include\\s*<hip/', '[A-Z][a-z]+Error\\b'",
+                        "required": False},
         },
     }

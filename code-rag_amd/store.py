@@ -16,6 +16,7 @@ from __future__ import annotations
 import asyncio
 import math
 import os
+import re
 import logging
 import threading
 from concurrent.futures import ThreadPoolExecutor
@@ -26,7 +27,7 @@ from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import ffi, lexical
+from . import ffi, lexical, regex_dfa
 from .errors import VectorStoreError
 from .settings import get_settings
 from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet, split_global
@@ -65,7 +66,7 @@ TEXT_KEYS: dict[str, tuple[str, ...]] = {
     CollectionName.CODE_CHUNKS.value: ("content",),
     CollectionName.SUMMARIES.value: ("summary",),
 }
-_TEXT_WORDS = ("contains", "any", "case")
+_TEXT_WORDS = ("contains", "matches", "any", "case")     # "matches": a regular expression
 _ASCII_LOWER = bytes(c + 32 if 65 <= c <= 90 else c for c in range(256))   # the device's folding: ASCII letters only
 _TEXT_CACHE = 8          # match results a collection keeps (a repeated query under the same text filter does not grep again)
 
@@ -105,34 +106,41 @@ def range_bounds(key: str, spec) -> tuple[int, int]:
 
 
 def _is_text(value) -> bool:
-    """A filter value that asks for a substring match: a mapping with the key ``"contains"``."""
-    return isinstance(value, Mapping) and "contains" in value
+    """A filter value that asks for a text match: a mapping with the key ``"contains"`` (substrings) or ``"matches"`` (a
+    regular expression)."""
+    return isinstance(value, Mapping) and ("contains" in value or "matches" in value)
 
 
 def _is_range(value) -> bool:
-    return isinstance(value, Mapping) and "contains" not in value
+    return isinstance(value, Mapping) and not _is_text(value)
 
 
 class TextSpec(NamedTuple):
-    """A ``{"contains": ...}`` filter value, checked: the distinct patterns as sorted UTF-8 bytes, any-of / all-of, and whether
-    case matters (``case=False`` folds ASCII letters only).  Equal specs select the same rows."""
+    """A ``{"contains": ..., "matches": ...}`` filter value, checked: the distinct patterns as sorted UTF-8 bytes (none when only
+    ``matches`` is given), any-of / all-of, whether case matters (``case=False`` folds ASCII letters only, for both), and the
+    regular expression as UTF-8 bytes (None: none).  Equal specs select the same rows."""
     patterns: tuple
     any_of: bool
     case: bool
+    regex: bytes | None = None
 
 
 def text_spec(key: str, spec) -> TextSpec:
-    """``{"contains": str | [str, ...], "any": bool = False, "case": bool = True}`` as a :class:`TextSpec`.  ``ValueError``
-    naming ``key`` for an unknown word, a pattern that is no ``str``, an empty pattern, one over 64 bytes of UTF-8, no pattern
-    at all or more than 8, and flags that are not bools."""
+    """``{"contains": str | [str, ...], "matches": str, "any": bool = False, "case": bool = True}`` -- at least one of
+    ``contains`` and ``matches``; with both, both must hold -- as a :class:`TextSpec`.  ``any`` concerns ``contains`` only,
+    ``case`` both.  ``ValueError`` naming ``key`` for an unknown word, a pattern that is no ``str``, an empty pattern, one over
+    64 bytes of UTF-8, no pattern at all or more than 8, flags that are not bools, and a regular expression that is no ``str``
+    or that ``regex_dfa.compile_regex`` refuses (the construct is named)."""
     unknown = [w for w in spec if w not in _TEXT_WORDS]
     if unknown:
         raise ValueError(f"text filter on {key!r}: unknown word {unknown[0]!r} (use {', '.join(_TEXT_WORDS)})")
-    pats = spec["contains"]
+    if "contains" not in spec and "matches" not in spec:
+        raise ValueError(f"text filter on {key!r}: needs 'contains' (strings), 'matches' (a regular expression) or both")
+    pats = spec.get("contains", [])
     pats = [pats] if isinstance(pats, str) else list(pats) if isinstance(pats, (list, tuple)) else None
     if pats is None or not all(isinstance(p, str) for p in pats):
         raise ValueError(f"text filter on {key!r}: 'contains' takes a str or a list of str, not {spec['contains']!r}")
-    if not 1 <= len(pats) <= ffi.TEXT_MAX_PATTERNS:
+    if not (1 if "contains" in spec else 0) <= len(pats) <= ffi.TEXT_MAX_PATTERNS:
         raise ValueError(f"text filter on {key!r}: {len(pats)} patterns (1..{ffi.TEXT_MAX_PATTERNS} are matched in one pass)")
     raw = [p.encode("utf-8", "surrogatepass") for p in pats]
     for p, b in zip(pats, raw):
@@ -146,11 +154,17 @@ def text_spec(key: str, spec) -> TextSpec:
         flags.append(bool(v))
     if not flags[1]:
         raw = [b.translate(_ASCII_LOWER) for b in raw]     # (what the device compares: folded patterns are equal patterns)
-    return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1])
+    regex = None
+    if "matches" in spec:
+        if not isinstance(spec["matches"], str):
+            raise ValueError(f"text filter on {key!r}: 'matches' takes a str (a regular expression), not {spec['matches']!r}")
+        regex = spec["matches"].encode("utf-8", "surrogatepass")
+        regex_dfa.compile_regex(regex, flags[1], key)              # (refuses with the key named; the DFA stays in its cache)
+    return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1], regex)
 
 
 def has_text_condition(filters, must_not=None) -> bool:
-    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``{"contains": ...}`` value?"""
+    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``{"contains": ...}`` / ``{"matches": ...}`` value?"""
     for f in (filters, must_not):
         for d in (f if isinstance(f, (list, tuple)) else [f]):
             if isinstance(d, Mapping) and any(_is_text(v) for v in d.values()):
@@ -185,6 +199,8 @@ class _Collection:
     (``crh_index_compact``) moves the survivors together on the device and in the tables; the store compacts by itself once
     the dead rows pass a fraction of the collection (the reference deletes and re-inserts every chunk of a file on every
     indexing run, embeddings/indexer.py:61-64)."""
+
+    regex_prefilter = True     # a regex condition first greps for the strings every match holds (tests switch it off to compare)
 
     def __init__(self, name: str, dim: int, dtype: int, capacity: int, device: int, nshards: int = 1, backend: str = "local",
                  group=None, merge_fn=None, compact_dead_fraction: float = 0.25, compact_min_dead: int = 1024):
@@ -378,7 +394,8 @@ class _Collection:
                                  f"(text keys: {', '.join(self.text_keys) or 'none'})")
             return False
         if not _is_text(value):
-            raise ValueError(f"payload key {key!r} holds text: filter it with a mapping {{'contains': str or list of str}}, not {value!r}")
+            raise ValueError(f"payload key {key!r} holds text: filter it with a mapping {{'contains': str or list of str}} or "
+                             f"{{'matches': regular expression}}, not {value!r}")
         texts.append((key, text_spec(key, value), negate))
         return True
 
@@ -413,8 +430,11 @@ class _Collection:
     def _text_condition(self, key: str, spec: TextSpec, negate: bool, others: list) -> "ffi.RowWords":
         """A text condition as the row-bitmap condition of the device filter.  Per owned shard: the words of the OTHER
         conditions (``crh_index_row_mask``; none: the alive words), ``crh_text_match`` under them -- a tile they leave empty
-        costs no read of its text -- and the result as ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  The last few results
-        are kept, keyed by what they were computed from; every result lives in buffers of its own under a tag of its own."""
+        costs no read of its text -- and the result as ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  With a regular
+        expression the literal match runs for ``contains`` if given, otherwise for the strings every match of
+        the expression holds (``regex_prefilter``; none: no literal pass), and ``crh_text_regex`` walks the rows that are left.
+        The last few results are kept, keyed by what they were computed from; every result lives in buffers of its own under
+        a tag of its own."""
         arenas = self._text_ready(key)
         state = (tuple(self.shards.rows), self.shards.count()[1], self.compactions)
         ck = (key, spec, ffi.filter_key(others), state)
@@ -425,7 +445,15 @@ class _Collection:
             for s in self.shards.owned:
                 ix = self.shards.index[s]
                 mask = ix.row_mask(others, stream=stream)
-                w, n = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, stream=stream)
+                if spec.regex is None:
+                    w, n = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, stream=stream)
+                else:
+                    dfa = regex_dfa.compile_regex(spec.regex, spec.case, key)
+                    if spec.patterns:
+                        mask, _ = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, count=False, stream=stream)
+                    elif self.regex_prefilter and dfa.literals:
+                        mask, _ = arenas[s].match(dfa.literals, fold_case=not spec.case, mask=mask, count=False, stream=stream)
+                    w, n = arenas[s].regex(dfa, mask=mask, stream=stream)
                 words[id(ix)] = w
                 total += n
             self.text_match_calls += 1
@@ -454,7 +482,7 @@ class _Collection:
         """client.py:159-169: every point matching the AND of the conditions.  An empty filter matches every point, as
         ``Filter(must=[])`` does."""
         if has_text_condition(filters, must_not):
-            raise ValueError("delete takes no text condition ({'contains': ...}): fetch the matching points (search_text) and delete by id or file")
+            raise ValueError("delete takes no text condition ({'contains': ...} / {'matches': ...}): fetch the matching points (search_text) and delete by id or file")
         dfilt = self.device_filters(filters, must_not)
         if dfilt is None:
             return 0
@@ -1423,7 +1451,7 @@ class HipVectorStore:
         per = _per_query(filters, must_not, nq)
         if per is not None:
             if has_text_condition(filters, must_not):
-                raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...}): a text condition is "
+                raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...} / {'matches': ...}): a text condition is "
                                  "one grep for the whole batch -- pass ONE filter dict")
             if diversity is not None or group is not None:
                 raise ValueError("per-query filters cannot be combined with diversity, group_by or max_overlap (a follow-up: the "
@@ -1701,7 +1729,9 @@ class HipVectorStore:
         literal string(s) -- all of them, or with ``any`` at least one; ``case=False`` folds ASCII letters only; under
         ``must_not`` the points that do not (a point without the text passes).  Exact substring match on the device (Qdrant's
         ``MatchText`` on a field without a full-text index), combinable with everything a filter combines with
-        except per-query filter lists.  1..8 patterns of 1..64 bytes of UTF-8 each."""
+        except per-query filter lists.  1..8 patterns of 1..64 bytes of UTF-8 each.  ``{"matches": regular expression}`` -- alone
+        or beside ``contains``, then both must hold -- keeps the points in whose text Python's ``re`` on bytes (``re.MULTILINE``;
+        ``case=False``: ``re.IGNORECASE``) finds the expression, matched on the device by a DFA."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -1995,7 +2025,7 @@ class HipVectorStore:
             raise VectorStoreError(f"Failed to count in {collection}", cause=e)
 
     # ------------------------------------------------------------------ literal text search
-    def _search_text_sync(self, collection: str, contains, limit: int, filters, must_not, any_of: bool, case: bool) -> dict[str, Any]:
+    def _search_text_sync(self, collection: str, contains, limit: int, filters, must_not, any_of: bool, case: bool, matches=None) -> dict[str, Any]:
         """The text condition joined to the filter, the exact count and the first ``limit`` matching points in insertion order
         (``crh_index_match_rows_cond``), with their ``match_line``; ``limit`` 0 asks for the count alone."""
         col = self._col(collection)
@@ -2005,8 +2035,14 @@ class HipVectorStore:
         if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
             raise ValueError("a text search takes one filter, not per-query filters")
         if key in (filters or {}):
-            raise ValueError(f"the filter already holds a condition on {key!r}: give the strings in `contains`")
-        spec = {"contains": contains, "any": any_of, "case": case}
+            raise ValueError(f"the filter already holds a condition on {key!r}: give the strings in `contains`, the expression in `matches`")
+        if contains is None and matches is None:
+            raise ValueError("a text search needs `contains` (strings), `matches` (a regular expression) or both")
+        spec = {"any": any_of, "case": case}
+        if contains is not None:
+            spec["contains"] = contains
+        if matches is not None:
+            spec["matches"] = matches
         dfilt = col.device_filters({**(filters or {}), key: spec}, must_not)
         if dfilt is None:
             return {"hits": [], "count": 0}
@@ -2016,34 +2052,45 @@ class HipVectorStore:
         sh, lo = col.shards.match_rows(dfilt, int(limit))
         slots = np.sort(col.slots_of(sh, lo))[: int(limit)]
         hits = col.hits(slots, [0.0] * len(slots))
-        pats = text_spec(key, spec).patterns
+        checked = text_spec(key, spec)
+        pats = checked.patterns
+        rx = None if checked.regex is None else re.compile(checked.regex, re.MULTILINE | (0 if case else re.IGNORECASE))
         for hit in hits:
             text, start = hit["payload"].get(key), hit["payload"].get("start_line")
             raw = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else b""
             where = [p for p in ((raw if case else raw.translate(_ASCII_LOWER)).find(pat) for pat in pats) if p >= 0]
+            found = rx.search(raw) if rx is not None else None
+            if found is not None:
+                where.append(found.start())
             first = type(start) is int and where
             hit["match_line"] = start + raw.count(b"\n", 0, min(where)) if first else None
         return {"hits": hits, "count": count}
 
-    async def search_text(self, collection: str, contains, limit: int = 10, filters: dict[str, Any] | None = None,
-                          must_not: dict[str, Any] | None = None, *, any: bool = False, case: bool = True) -> dict[str, Any]:   # noqa: A002
+    async def search_text(self, collection: str, contains=None, limit: int = 10, filters: dict[str, Any] | None = None,
+                          must_not: dict[str, Any] | None = None, *, matches: str | None = None, any: bool = False,   # noqa: A002
+                          case: bool = True) -> dict[str, Any]:
         """Literal text search -- grep over the stored chunks: the points whose text (``content`` of the code chunks, ``summary``
         of the summaries) holds the string ``contains``, or every string of a list (``any``: at least one), under ``filters`` /
         ``must_not`` as in :meth:`search`.  ``case=False`` folds ASCII letters only.  Returns ``{"hits": [...], "count": int}``:
         ``hits`` are the first ``limit`` matching points in insertion order (``{"id", "score": 0.0, "payload", "match_line"}``),
         ``count`` how many points match, exact and not clipped at ``limit``.  ``match_line`` is ``start_line`` plus the number of
         newlines before the first occurrence of any of the strings (None for a point without an int ``start_line``).  Matched
-        on the device; 1..8 strings of 1..64 bytes of UTF-8 each."""
+        on the device; 1..8 strings of 1..64 bytes of UTF-8 each.
+
+        ``matches`` is a regular expression in the syntax of Python's ``re`` ON BYTES, with ``re.MULTILINE``:
+        the points in whose text ``re.search`` finds it; beside ``contains`` both must hold (``any`` concerns the strings
+        only, ``case`` both).  At least one of ``contains`` and ``matches`` is required.  ``match_line`` counts the newlines
+        before the earliest place where one of the strings occurs or the expression's first match starts."""
         try:
-            return await self._run(self._search_text_sync, collection, contains, int(limit), filters, must_not, any, case)
+            return await self._run(self._search_text_sync, collection, contains, int(limit), filters, must_not, any, case, matches)
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
-    async def count_text(self, collection: str, contains, filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                         any: bool = False, case: bool = True) -> int:   # noqa: A002
+    async def count_text(self, collection: str, contains=None, filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
+                         matches: str | None = None, any: bool = False, case: bool = True) -> int:   # noqa: A002
         """How many points :meth:`search_text` matches: exact."""
         try:
-            return (await self._run(self._search_text_sync, collection, contains, 0, filters, must_not, any, case))["count"]
+            return (await self._run(self._search_text_sync, collection, contains, 0, filters, must_not, any, case, matches))["count"]
         except Exception as e:
             raise VectorStoreError(f"Failed to count in {collection}", cause=e)
 

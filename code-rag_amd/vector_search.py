@@ -102,12 +102,18 @@ def _mode_kwargs(mode: str) -> dict:
     return {} if mode == "semantic" else {"mode": mode}
 
 
-def _contains_filter(key: str, contains, contains_case: bool) -> dict:
-    """``contains`` (a str or a list of str: the literal strings a hit's text must ALL hold) as the store's text condition on
-    ``key`` -- ``{}`` without it: the call is then the one issued before, keyword for keyword."""
-    if contains is None:
+def _contains_filter(key: str, contains, contains_case: bool, matches: str | None = None) -> dict:
+    """``contains`` (a str or a list of str: the literal strings a hit's text must ALL hold) and ``matches`` (a regular
+    expression ``re.search`` must find in it) as the store's text condition on ``key`` -- ``{}`` without either: the call is
+    then the one issued before, keyword for keyword."""
+    if contains is None and matches is None:
         return {}
-    return {key: {"contains": contains} if contains_case else {"contains": contains, "case": False}}
+    spec = {} if contains is None else {"contains": contains}
+    if matches is not None:
+        spec["matches"] = matches
+    if not contains_case:
+        spec["case"] = False
+    return {key: spec}
 
 
 def _transform_similar_code_result(hit: dict) -> dict:
@@ -207,7 +213,7 @@ class VectorSearcher:
                           diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                           extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                           max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
-                          contains_case: bool = True) -> list[dict]:
+                          contains_case: bool = True, matches: str | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -230,11 +236,13 @@ class VectorSearcher:
         ``contains`` (not in the reference; Qdrant's ``MatchText``): a literal string, or a list of them, every result's
         ``content`` must hold -- ``retry_after=``, ``.unwrap()`` -- matched exactly on the device (``HipVectorStore.search``,
         DESIGN.md 3.21), in every mode and beside every other argument; ``contains_case=False`` ignores the case of ASCII
-        letters."""
+        letters.  ``matches`` likewise: a regular expression in the syntax of Python's ``re`` on bytes, with ``re.MULTILINE``,
+        that ``re.search`` must find in every result's ``content`` -- ``def \\w+_retry\\(`` -- (DESIGN.md 3.22); beside
+        ``contains`` both must hold, and ``contains_case`` governs both."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
-        filters.update(_contains_filter("content", contains, contains_case))
+        filters.update(_contains_filter("content", contains, contains_case, matches))
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -244,15 +252,16 @@ class VectorSearcher:
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                                extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
-                               mode: str = "semantic", contains: str | list[str] | None = None, contains_case: bool = True) -> list[dict]:
+                               mode: str = "semantic", contains: str | list[str] | None = None, contains_case: bool = True,
+                               matches: str | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
-        ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`; ``contains`` / ``contains_case``
-        likewise, over the ``summary`` text."""
+        ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`; ``contains`` / ``contains_case`` /
+        ``matches`` likewise, over the ``summary`` text."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
-        if contains is not None:
-            filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case))
+        if contains is not None or matches is not None:
+            filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case, matches))
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -263,19 +272,20 @@ class VectorSearcher:
                                 exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,
                                 max_per_file: int | None = None, min_score: float | None = None,
                                 max_overlap: float | None = None, contains: str | list[str] | None = None,
-                                contains_case: bool = True) -> list[dict]:
+                                contains_case: bool = True, matches: str | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
         ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet.  ``max_overlap`` as in
         :meth:`search_code`: no chunk repeats more than that share of a better chunk's lines.  ``contains`` / ``contains_case``
-        as in :meth:`search_code`: only chunks that hold the literal string(s)."""
+        as in :meth:`search_code`: only chunks that hold the literal string(s); ``matches`` likewise: only chunks the regular
+        expression matches."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
         on_device = bool(exact_exclude and exclude_file)
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch,
-                                  _contains_filter("content", contains, contains_case) or _NO_FILTER_KWARG,
+                                  _contains_filter("content", contains, contains_case, matches) or _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
@@ -333,7 +343,7 @@ class VectorSearcher:
                                 max_per_file: int | None = None,
                                 filters_per_query: list[dict | None] | None = None, min_score=None,
                                 max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
-                                contains_case: bool = True) -> list[list[dict]]:
+                                contains_case: bool = True, matches: str | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
         ``candidates`` only).
@@ -343,11 +353,11 @@ class VectorSearcher:
         means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet.  ``min_score``: one number or one per query, as in
         :meth:`search_code`; not together with ``filters_per_query`` either.  ``max_overlap`` as in :meth:`search_code`; not
         together with ``filters_per_query``, ``diversity``, ``max_per_file`` or ``min_score``.  ``contains`` / ``contains_case`` as in
-        :meth:`search_code`, one text condition for the whole batch; not together with ``filters_per_query``."""
+        :meth:`search_code`, one text condition for the whole batch; not together with ``filters_per_query``.  ``matches`` likewise."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
-        if contains is not None and filters_per_query is not None:
-            raise QueryError("contains cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
-        filters.update(_contains_filter("content", contains, contains_case))
+        if (contains is not None or matches is not None) and filters_per_query is not None:
+            raise QueryError("contains / matches cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
+        filters.update(_contains_filter("content", contains, contains_case, matches))
         if filters_per_query is not None:
             if filters:
                 raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")

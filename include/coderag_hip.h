@@ -640,6 +640,25 @@ int crh_text_match(crh_text *t, int n_pat, const int64_t *pat_off_host, const ui
                    const uint32_t *mask_dev /* or NULL */, uint32_t *out_words_dev, int64_t *out_count_host /* or NULL */,
                    void *stream);
 
+/* Which rows a regular expression matches, as a byte DFA the CALLER compiled (the store compiles Python's `re` syntax in
+ * regex_dfa.py; a C host can bring a DFA from any compiler).  The semantics are the table's alone:
+ *   s = 0; for each byte b of the row: s = trans[s * n_classes + class_of[b]]; then s = trans[s * n_classes + end_class];
+ *   the row MATCHES iff s == accept_state.
+ * Only the row's own bytes are walked: a match never sees a neighbouring row.  Checked on the host, CRH_E_INVALID with nothing
+ * launched otherwise: n_states 1..CRH_REGEX_MAX_STATES, n_classes 2..257, n_states * n_classes <= CRH_REGEX_MAX_TABLE_BYTES,
+ * every class_of[b] and end_class < n_classes, every trans entry and accept_state < n_states, and the accept state's row
+ * ABSORBING (every entry is accept_state: the walk of a row stops early once it is reached).  mask_dev, out_words_dev,
+ * out_count_host, `stream`, bits at or past `rows` and the arena without rows behave exactly as in crh_text_match.  The table
+ * travels through a copy the handle owns: the caller may free its arrays on return.  At most ONE crh_text_match or
+ * crh_text_regex per handle may be in flight (they share the handle's counter and table buffer).  A pair of tiles whose two mask
+ * words are 0 costs no read of its text; otherwise a row costs a serial walk of its bytes, and 64 rows advance as fast as the
+ * longest of them.  Deterministic. */
+#define CRH_REGEX_MAX_STATES 256
+#define CRH_REGEX_MAX_TABLE_BYTES 32768 /* n_states * n_classes */
+int crh_text_regex(crh_text *t, int n_states, int n_classes, const uint8_t *class_of_host /* [256] */, int end_class,
+                   const uint8_t *trans_host /* [n_states * n_classes] */, int accept_state, const uint32_t *mask_dev /* or NULL */,
+                   uint32_t *out_words_dev, int64_t *out_count_host /* or NULL */, void *stream);
+
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
  * the HF RobertaModel it wraps).  All pointers are device pointers; activations bf16,
