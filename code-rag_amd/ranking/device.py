@@ -98,7 +98,9 @@ class SideColumns:
             r = r0 + j
             content = p.get("content")
             name = (p.get("entity_name", "") or "").lower().encode("utf-8")
-            h["content_len"][r] = len(content) if content else 0
+            # (a payload may carry anything under "content": what has no length counts as no content -- one odd point must not
+            # take the re-rank of the whole collection down; every row passes here, whether a query ever meets it or not)
+            h["content_len"][r] = len(content) if content and hasattr(content, "__len__") else 0
             h["degree"][r] = -1
             h["file_code"][r] = self._code("file", p.get("file_path", "") or "")
             h["key_code"][r] = self._code("key", merge_key(p))

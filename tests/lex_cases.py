@@ -304,23 +304,17 @@ def store_rows(col):
     return out
 
 
-def store_expected(col, texts, limit, passes=None, k1=1.2, b=0.75, stride=1 << 32):
-    """What ``search_lexical`` must answer: per text ``[(id, score bits), ...]`` and the count -- the restatement run per shard on
-    the texts of the stored payloads, statistics over the ALIVE rows of all shards, lists merged by (score desc, global row asc).
-    ``passes(payload) -> bool``: the filter.  Also returns the per-text GLOBAL-row lists ``(scores, rows)`` for the fusion."""
-    shards = store_rows(col)
-    built = {}
-    for s, (slots, alive) in shards.items():
-        pays = [col.payloads.get(int(t)) if t >= 0 else {} for t in slots]
-        csr = rows_from_texts([point_text(p) for p in pays])
-        ok = alive & np.asarray([passes is None or bool(passes(p)) for p in pays], bool) if len(pays) else alive
-        built[s] = (csr, alive, ok, slots)
+def lists_expected(row_texts, alive, passing, texts, limit, k1=1.2, b=0.75, grow=None):
+    """The expected lexical answer from PLAIN LISTS -- nothing of a store is read: ``row_texts`` the rows' texts (bytes),
+    ``alive`` / ``passing`` a bool per row (``passing``: alive and under the filter), ``grow`` the rows' GLOBAL rows, ascending
+    (None: their positions in the lists).  Statistics over the alive rows, the exact BM25 top-``limit`` over the passing ones,
+    ties to the lower global row.  Returns ``(scores f32 [nq, limit], global rows i64 [nq, limit] (-1: padding), counts i64 [nq],
+    the queries' term ids)``."""
+    off, terms, tf, dl = rows_from_texts(list(row_texts))
+    alive, ok = np.asarray(alive, bool).reshape(-1), np.asarray(passing, bool).reshape(-1)
     term_lists = [query_terms(t) for t in texts]
     ids = np.unique(np.concatenate([np.zeros(0, np.uint32)] + term_lists))
-    df, n_rows, sum_dl = np.zeros(ids.size, np.int64), 0, 0
-    for (off, terms, tf, dl), alive, _, _ in built.values():
-        d, r, t = stats(off, terms, dl, alive, ids)
-        df, n_rows, sum_dl = df + d, n_rows + r, sum_dl + t
+    df, n_rows, sum_dl = stats(off, terms, dl, alive, ids)
     known = dict(zip(ids.tolist(), df.tolist()))
     queries, weights = [], []
     avgdl = f32(1.0)
@@ -331,18 +325,63 @@ def store_expected(col, texts, limit, passes=None, k1=1.2, b=0.75, stride=1 << 3
         w, avgdl = idf([known[v] for v in t.tolist()], n_rows, sum_dl)
         queries.append(t)
         weights.append(w)
-    nq = len(texts)
-    all_s, all_r, counts = [], [], np.zeros(nq, np.int64)
-    for s, ((off, terms, tf, dl), _, ok, _) in built.items():
-        sc, rw, c = bm25_search(off, terms, tf, dl, ok, queries, weights, k1, b, avgdl, limit, s * stride)
-        all_s.append(sc)
-        all_r.append(rw)
-        counts += c
-    sc, rw = np.concatenate(all_s, axis=1), np.concatenate(all_r, axis=1)
-    out_s, out_r, pairs = np.full((nq, limit), -np.inf, f32), np.full((nq, limit), -1, np.int64), []
-    for q in range(nq):
-        real = np.flatnonzero(rw[q] >= 0)
-        order = real[np.lexsort((rw[q, real], -sc[q, real].astype(np.float64)))][:limit]
-        out_s[q, : order.size], out_r[q, : order.size] = sc[q, order], rw[q, order]
-        pairs.append([(col.ids.get(int(built[int(r) // stride][3][int(r) % stride])), int(v.view(np.uint32))) for v, r in zip(sc[q, order], rw[q, order])])
+    sc, ix, counts = bm25_search(off, terms, tf, dl, ok, queries, weights, k1, b, avgdl, limit)
+    if grow is not None:
+        grow = np.asarray(grow, np.int64).reshape(-1)
+        assert (np.diff(grow) > 0).all(), "the lists are in ascending global-row order"
+        ix = np.append(grow, -1)[ix]                             # (-1 picks the padding entry)
+    return sc, ix, counts, queries
+
+
+def hybrid_expected(stored, q_pre, row_texts, alive, passing, texts, limit, c, grow=None):
+    """The expected hybrid answer from plain lists: ``stored`` [n, dim] the preprocessed rows and ``q_pre`` [nq, dim] the
+    preprocessed queries; the other arguments as for :func:`lists_expected`.  The dense top-``c`` by ``oracle.search`` and the
+    lexical top-``c`` by the restatement under the same mask, fused by tests/fuse_cases.py's restatement.  Per query ``[(global
+    row, fused score bits, cosine or None, lexical score or None, matched)]``."""
+    from oracle import search as orc
+    from tests import fuse_cases
+    n = len(row_texts)
+    grow = np.arange(n, dtype=np.int64) if grow is None else np.asarray(grow, np.int64).reshape(-1)
+    ls, lr, _, _ = lists_expected(row_texts, alive, passing, texts, c, grow=grow)
+    if n:
+        es, er = orc.search(np.asarray(stored, f32), np.asarray(q_pre, f32), c, alive=np.asarray(passing, np.uint8))
+    else:
+        es, er = np.full((len(texts), c), -np.inf, f32), np.full((len(texts), c), -1, np.int64)
+    dr = np.append(grow, -1)[er]
+    fused = fuse_cases.fuse_select(np.stack([es, ls], axis=1), np.stack([dr, lr], axis=1), 2, limit, "rrf", 60, None)
+    out = []
+    for q in range(len(texts)):
+        hits = []
+        for j, r in enumerate(fused[0][q].tolist()):
+            if r < 0:
+                continue
+            in_d, in_l = np.flatnonzero(dr[q] == r), np.flatnonzero(lr[q] == r)
+            hits.append((r, int(fused[1][q, j].view(np.uint32)), float(es[q, in_d[0]]) if in_d.size else None,
+                         float(ls[q, in_l[0]]) if in_l.size else None, tuple(n for n, on in (("vector", in_d.size), ("lexical", in_l.size)) if on)))
+        out.append(hits)
+    return out
+
+
+def store_lists(col, passes=None, stride=1 << 32):
+    """A store collection as the plain lists of :func:`lists_expected`, every shard's rows one behind the other: ``(texts, alive,
+    passing, global rows, slots)``."""
+    row_texts, alive, ok, grow, slots = [], [], [], [], []
+    for s, (sl, al) in sorted(store_rows(col).items()):
+        pays = [col.payloads.get(int(t)) if t >= 0 else {} for t in sl]
+        row_texts += [point_text(p) for p in pays]
+        alive += al.tolist()
+        ok += [bool(a) and (passes is None or bool(passes(p))) for a, p in zip(al.tolist(), pays)]
+        grow += (np.arange(len(sl), dtype=np.int64) + s * stride).tolist()
+        slots += np.asarray(sl, np.int64).tolist()
+    return row_texts, alive, ok, grow, slots
+
+
+def store_expected(col, texts, limit, passes=None, k1=1.2, b=0.75, stride=1 << 32):
+    """What ``search_lexical`` must answer: per text ``[(id, score bits), ...]`` and the count -- :func:`lists_expected` on the
+    texts of the stored payloads of every shard (:func:`store_lists`), statistics over the ALIVE rows of all shards.
+    ``passes(payload) -> bool``: the filter.  Also returns the per-text GLOBAL-row lists ``(scores, rows)`` for the fusion."""
+    row_texts, alive, ok, grow, slots = store_lists(col, passes, stride)
+    out_s, out_r, counts, queries = lists_expected(row_texts, alive, ok, texts, limit, k1, b, grow=grow)
+    slot_of = dict(zip(grow, slots))
+    pairs = [[(col.ids.get(slot_of[int(r)]), int(v.view(np.uint32))) for v, r in zip(out_s[q], out_r[q]) if r >= 0] for q in range(len(texts))]
     return pairs, counts.tolist(), (out_s, out_r), queries

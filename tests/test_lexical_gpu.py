@@ -276,34 +276,14 @@ def _pairs(hits):
 
 
 def _hybrid_expected(col, qv, texts, limit, c, passes, ids_of):
-    """The dense top-c by ``oracle.search`` on ``read_rows`` of every shard (global-row order, the alive and filter masks), the
-    lexical top-c by the restatement, fused by tests/fuse_cases.py's restatement: per query the expected hit fields."""
-    from coderag_amd.shards import STRIDE
+    """``lex_cases.hybrid_expected`` on what the store holds: ``read_rows`` of every shard in global-row order, the texts of the
+    stored payloads, the alive and filter masks; per query the expected hit fields."""
     from oracle import search as orc
-    from tests import fuse_cases
-    _, _, (ls, lr), _ = lc.store_expected(col, texts, c, passes)
-    xs, grow, ok, slots = [], [], [], []
-    for sh, (sl, alive) in lc.store_rows(col).items():
-        xs.append(col.shards.index[sh].read_rows(0, len(sl)))
-        grow.append(np.arange(len(sl), dtype=np.int64) + sh * STRIDE)
-        ok.append(alive & np.asarray([passes is None or bool(passes(col.payloads.get(int(t)))) for t in sl], bool))
-        slots.append(sl)
-    x, grow, ok, slots = np.concatenate(xs), np.concatenate(grow), np.concatenate(ok), np.concatenate(slots)
-    es, er = orc.search(x, orc.preprocess(qv, to_bf16=True), c, alive=ok.astype(np.uint8))
-    dr = np.where(er >= 0, grow[np.maximum(er, 0)], -1)
-    fused = fuse_cases.fuse_select(np.stack([es, ls], axis=1), np.stack([dr, lr], axis=1), 2, limit, "rrf", 60, None)
-    slot_of = dict(zip(grow.tolist(), slots.tolist()))
-    out = []
-    for q in range(len(texts)):
-        hits = []
-        for j, r in enumerate(fused[0][q].tolist()):
-            if r < 0:
-                continue
-            in_d, in_l = np.flatnonzero(dr[q] == r), np.flatnonzero(lr[q] == r)
-            hits.append((ids_of(slot_of[r]), int(fused[1][q, j].view(U32)), float(es[q, in_d[0]]) if in_d.size else None,
-                         float(ls[q, in_l[0]]) if in_l.size else None, tuple(n for n, on in (("vector", in_d.size), ("lexical", in_l.size)) if on)))
-        out.append(hits)
-    return out
+    row_texts, alive, ok, grow, slots = lc.store_lists(col, passes)
+    x = np.concatenate([col.shards.index[sh].read_rows(0, len(sl)) for sh, (sl, _) in sorted(lc.store_rows(col).items())])
+    slot_of = dict(zip(grow, slots))
+    want = lc.hybrid_expected(x, orc.preprocess(qv, to_bf16=True), row_texts, alive, ok, texts, limit, c, grow=grow)
+    return [[(ids_of(slot_of[h[0]]),) + h[1:] for h in hits] for hits in want]
 
 
 @pytest.mark.parametrize("shards", [1, 2])
