@@ -14,6 +14,7 @@
 #include "crh_common.h"
 #include "crh_kernels.hpp"
 #include "crh_i8.hpp"
+#include "crh_facet.hpp"
 #include "crh_range.hpp"
 
 namespace crh {
@@ -81,6 +82,10 @@ struct Pending {
     bool range;     // a range batch (crh_search_range): thr the queries' thresholds, counts their in-range totals (device; nullptr: list only)
     RangeThr thr;
     unsigned long long *counts;
+    // a faceting range batch (crh_search_range_facet): the column, and this batch's bins [nq, n_bins] / info [nq, 3] rows (device;
+    // fbins == nullptr: none).  enqueue_batch_range zeroes both before the scan, so a batch that is run again starts from 0.
+    int fcol, n_bins;
+    unsigned long long *fbins, *finfo;
     int path;       // how enqueue_batch nominated the batch's rows: CRH_NOMINATE_INT8 / _BF16 (one launch) / _BF16_3 (three launches, wide scan)
 };
 
@@ -922,6 +927,14 @@ int enqueue_batch_multi(crh_index *h, crh_index::Workspace &w, const float *q_de
                          });
 }
 
+// the bins and info rows of one faceting batch, cleared in stream order
+int facet_zero(unsigned long long *bins, unsigned long long *info, int nq, int n_bins, hipStream_t st)
+{
+    CRH_HIP(hipMemsetAsync(bins, 0, sizeof(unsigned long long) * (size_t)nq * (size_t)n_bins, st));
+    CRH_HIP(hipMemsetAsync(info, 0, sizeof(unsigned long long) * (size_t)nq * 3, st));
+    return CRH_OK;
+}
+
 // One range batch (<= batch_q queries; crh_range.hpp): always the three-launch bf16 form -- over every tile, or over the
 // mask's tile list when it is sparse enough -- with k_range_tau between the thresholds and the main scan, and the count and
 // the cut behind k_select.  List only: the seed scan and k_tau run as in enqueue_three and the threshold can only raise tau.
@@ -932,6 +945,7 @@ int enqueue_batch_range(crh_index *h, crh_index::Workspace &w, const Pending &p,
     const bool sparse = ntiles > 0 && sparse_use(h, mref, p.nq);
     if (ntiles == 0 || (sparse && mref.nlist == 0)) {
         if (p.counts) CRH_HIP(hipMemsetAsync(p.counts, 0, sizeof(unsigned long long) * (size_t)p.nq, st));
+        if (p.fbins) CRH_TRY(facet_zero(p.fbins, p.finfo, p.nq, p.n_bins, st));
         return pad_batch(h, slot, p.nq, p.k, p.out_s, p.out_r, st, sparse);
     }
     const int64_t items = sparse ? mref.nlist : ntiles;   // list positions or tiles
@@ -943,6 +957,7 @@ int enqueue_batch_range(crh_index *h, crh_index::Workspace &w, const Pending &p,
                       : launch_scan<decltype(mode)::value>(h, w, scan_blocks(h, n), st, mref.mask, n, stride, wave_cap, qcap, stt);
     };
     CRH_TRY(launch_prep(h, w, st, p.q_dev, p.nq, width, stt, false));   // (zeroes the slot's SearchStatus)
+    if (p.fbins) CRH_TRY(facet_zero(p.fbins, p.finfo, p.nq, p.n_bins, st));   // (as k_range_tau zeroes counts: a re-run adds to nothing)
     int G = 0;
     if (!p.counts) {
         G = (int)std::min<int64_t>(h->seed_tiles, items);
@@ -956,7 +971,16 @@ int enqueue_batch_range(crh_index *h, crh_index::Workspace &w, const Pending &p,
     CRH_TRY(scan(std::integral_constant<int, 1>{}, (int)items, 1));
     if (h->profiling) CRH_HIP(hipEventRecord(h->ev[2 * slot + 1], st));
     CRH_TRY(launch_select_bf16(h, w, st, p.nq, p.k, margin, p.row_base, p.out_s, p.out_r, stt));
-    if (p.counts) {
+    if (p.counts && p.fbins) {
+        const FacetOut fo{h->codes + (int64_t)p.fcol * h->cap_rows, p.n_bins, p.fbins, p.finfo};
+        if (h->dtype == CRH_DTYPE_F32)
+            hipLaunchKernelGGL((k_range_count<true, true>), dim3(p.nq, kRangeParts), dim3(256), 0, st, w.qlist, stt->qcount, qcap, p.thr, margin, w.qn, h->xt,
+                               h->xf32, h->dim, h->ksteps, p.counts, fo);
+        else
+            hipLaunchKernelGGL((k_range_count<false, true>), dim3(p.nq, kRangeParts), dim3(256), 0, st, w.qlist, stt->qcount, qcap, p.thr, margin, w.qn, h->xt,
+                               h->xf32, h->dim, h->ksteps, p.counts, fo);
+        CRH_HIP(hipGetLastError());
+    } else if (p.counts) {
         if (h->dtype == CRH_DTYPE_F32)
             hipLaunchKernelGGL(k_range_count<true>, dim3(p.nq, kRangeParts), dim3(256), 0, st, w.qlist, stt->qcount, qcap, p.thr, margin, w.qn, h->xt, h->xf32,
                                h->dim, h->ksteps, p.counts);
@@ -1089,6 +1113,19 @@ int finish_pending(crh_index *h, hipStream_t st)
     return CRH_OK;
 }
 
+// the device staging of a call's lists: host outputs are copied from it, crh_search_range_facet leaves its k = 1 lists in it
+int ensure_stage_out(crh_index *h, int64_t elems)
+{
+    if (h->stage_out_elems >= elems) return CRH_OK;
+    dev_free(h->stage_os);
+    dev_free(h->stage_or);
+    h->stage_out_elems = 0;
+    CRH_TRY(dev_alloc(&h->stage_os, elems));
+    CRH_TRY(dev_alloc(&h->stage_or, elems));
+    h->stage_out_elems = elems;
+    return CRH_OK;
+}
+
 // The search driver: every batch of a call enqueued on the stream, and -- unless queries and outputs are the caller's device
 // buffers -- finished and copied back.  What differs between the entry points is passed in: i8_presize (the call may nominate
 // from the int8 copy: its candidate buffers are sized beforehand) and plan(p, q0, left, st), which sets the size of the batch
@@ -1131,15 +1168,7 @@ int search_batches(crh_index *h, int nq, const float *queries, int queries_on_de
     float *os = out_scores;
     int64_t *orow = out_rows;
     if (!out_on_device) {
-        const int64_t elems = (int64_t)nq * k;
-        if (h->stage_out_elems < elems) {
-            dev_free(h->stage_os);
-            dev_free(h->stage_or);
-            h->stage_out_elems = 0;
-            CRH_TRY(dev_alloc(&h->stage_os, elems));
-            CRH_TRY(dev_alloc(&h->stage_or, elems));
-            h->stage_out_elems = elems;
-        }
+        CRH_TRY(ensure_stage_out(h, (int64_t)nq * k));
         os = h->stage_os;
         orow = h->stage_or;
     }
@@ -1205,7 +1234,8 @@ int search_multi_key(crh_index *h, int nq, const float *queries, int queries_on_
 // The range search (crh_range.hpp): the same filter for every query, <= batch_q queries per batch in caller order, each batch
 // with its own thresholds; counts_dev: the totals' device buffer, or nullptr for the list alone
 int search_range_key(crh_index *h, int nq, const float *queries, int queries_on_device, int k, const float *thresholds, const FilterKey &key,
-                     int64_t row_base, float *out_scores, int64_t *out_rows, unsigned long long *counts_dev, int out_on_device, void *stream)
+                     int64_t row_base, float *out_scores, int64_t *out_rows, unsigned long long *counts_dev, int out_on_device, void *stream,
+                     int fcol = -1, int n_bins = 0, unsigned long long *fbins = nullptr, unsigned long long *finfo = nullptr)
 {
     return search_batches(h, nq, queries, queries_on_device, k, key, false, row_base, out_scores, out_rows, out_on_device, stream,
                           [&](Pending &p, int q0, int left, hipStream_t) {
@@ -1213,6 +1243,10 @@ int search_range_key(crh_index *h, int nq, const float *queries, int queries_on_
                               p.range = true;
                               for (int i = 0; i < p.nq; ++i) p.thr.v[i] = thresholds[q0 + i];
                               p.counts = counts_dev ? counts_dev + q0 : nullptr;
+                              p.fcol = fcol;
+                              p.n_bins = n_bins;
+                              p.fbins = fbins ? fbins + (size_t)q0 * (size_t)n_bins : nullptr;
+                              p.finfo = fbins ? finfo + (size_t)q0 * 3 : nullptr;
                               return (int)CRH_OK;
                           });
 }
@@ -2172,6 +2206,72 @@ int crh_index_row_mask(crh_index *h, const crh_condition *conds, int n_conds, ui
     CRH_TRY(build_mask(h, h->ws, key, &m, st));
     CRH_HIP(hipMemcpyAsync(out_mask_dev, m.mask, (size_t)ntiles * 4, hipMemcpyDeviceToDevice, st));
     return CRH_OK;
+}
+
+static int facet_args(crh_index *h, int col, int n_bins, const char *what)
+{
+    if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    if (col < 0 || col >= h->ncols) return fail(CRH_E_INVALID, "%s: column %d outside 0..%d", what, col, h->ncols - 1);
+    if (n_bins < 1) return fail(CRH_E_INVALID, "%s: n_bins=%d must be >= 1", what, n_bins);
+    return CRH_OK;
+}
+
+// The histogram of one code column over the rows a search under these conditions would see (crh_facet.hpp): the mask is the
+// one build_mask hands a search, found in its cache or built; the outputs are cleared and counted into in stream order.
+int crh_index_facet(crh_index *h, int col, const crh_condition *conds, int n_conds, int n_bins, int64_t *out_bins_dev, int64_t *out_info_dev,
+                    void *stream)
+{
+    CRH_TRY(facet_args(h, col, n_bins, "facet"));
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
+    if (!out_bins_dev || !out_info_dev) return fail(CRH_E_INVALID, "facet: NULL output pointer");
+    DeviceGuard g(h->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long *bins = reinterpret_cast<unsigned long long *>(out_bins_dev), *info = reinterpret_cast<unsigned long long *>(out_info_dev);
+    CRH_TRY(facet_zero(bins, info, 1, n_bins, st));
+    if (h->count == 0) return CRH_OK;
+    CRH_TRY(ensure_workspace0(h));
+    MaskRef m;
+    CRH_TRY(build_mask(h, h->ws, key, &m, st));
+    const int32_t *column = h->codes + (int64_t)col * h->cap_rows;
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(h->count, 256), (int64_t)h->cu_count * 8);
+    if (n_bins <= kFacetLdsBins)
+        hipLaunchKernelGGL(k_facet_count<true>, dim3(blocks), dim3(256), 0, st, m.mask, column, h->count, n_bins, bins, info);
+    else
+        hipLaunchKernelGGL(k_facet_count<false>, dim3(blocks), dim3(256), 0, st, m.mask, column, h->count, n_bins, bins, info);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+// The semantic form: a range batch with counts whose k_range_count also adds every counted row to its query's bins.  The
+// lists (k = 1) stay in the index's staging.  The batches are finished before the call returns -- a batch whose candidate
+// lists overflowed has to be run again, and the staging must not outlive the call -- so the outputs are final in stream order.
+int crh_search_range_facet(crh_index *h, int nq, const float *queries, int queries_on_device, const float *thresholds_host,
+                           const crh_condition *conds, int n_conds, int col, int n_bins, int64_t *out_bins_dev, int64_t *out_info_dev, void *stream)
+{
+    CRH_TRY(facet_args(h, col, n_bins, "range facet"));
+    if (nq < 0) return fail(CRH_E_INVALID, "nq < 0");
+    FilterKey key;
+    CRH_TRY(key_from_conditions(h, conds, n_conds, false, key, true));
+    if (nq == 0) return CRH_OK;
+    if (!queries || !out_bins_dev || !out_info_dev) return fail(CRH_E_INVALID, "NULL query or output pointer");
+    if (!thresholds_host) return fail(CRH_E_INVALID, "thresholds_host is NULL");
+    for (int i = 0; i < nq; ++i)
+        if (!std::isfinite(thresholds_host[i])) return fail(CRH_E_INVALID, "thresholds_host[%d]=%g is not a finite number", i, (double)thresholds_host[i]);
+    {
+        DeviceGuard g(h->device);
+        CRH_TRY(ensure_stage_out(h, nq));
+        if (h->stage_cnt_elems < nq) {
+            dev_free(h->stage_cnt);
+            h->stage_cnt_elems = 0;
+            CRH_TRY(dev_alloc(&h->stage_cnt, nq));
+            h->stage_cnt_elems = nq;
+        }
+    }
+    CRH_TRY(search_range_key(h, nq, queries, queries_on_device, 1, thresholds_host, key, 0, h->stage_os, h->stage_or, h->stage_cnt, 1, stream, col,
+                             n_bins, reinterpret_cast<unsigned long long *>(out_bins_dev), reinterpret_cast<unsigned long long *>(out_info_dev)));
+    DeviceGuard g(h->device);
+    return finish_pending(h, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -51,10 +51,14 @@ __global__ __launch_bounds__(64) void k_range_tau(RangeThr thr, float margin, in
 // 16-byte pieces in flight per thread).  The workgroup's total goes into counts[q] with one 64-bit integer atomic: integer
 // additions commute, the result does not depend on the order of arrival.  A list that overflowed (qcount > qcap) gives a
 // partial total here; k_select has flagged the overflow, the batch is run again and k_range_tau zeroes the total first.
-template <bool F32>
+// FACET (crh_search_range_facet; crh_facet.hpp): every row that is counted also adds 1 to its query's bin, `missing` or
+// `out_of_range` by its code in fo.codes, wave-aggregated (facet_add_wave), and the workgroup's total goes into info[q][0] as
+// well.  The host zeroes the batch's bins and info rows on the stream before the scan -- before a re-run too.
+template <bool F32, bool FACET = false>
 __global__ __launch_bounds__(256) void k_range_count(const u32x2 *__restrict__ qlist, const unsigned int *__restrict__ qcount, int qcap, RangeThr thr,
                                                      float margin, const float *__restrict__ qn, const u32x4 *__restrict__ xt,
-                                                     const float *__restrict__ xf32, int dim, int ksteps, unsigned long long *__restrict__ counts)
+                                                     const float *__restrict__ xf32, int dim, int ksteps, unsigned long long *__restrict__ counts,
+                                                     FacetOut fo = FacetOut{})
 {
     constexpr int NT = 256;
     constexpr int ROUNDS = 4;                 // blocks of NT candidates between two re-scoring rounds
@@ -74,14 +78,35 @@ __global__ __launch_bounds__(256) void k_range_count(const u32x2 *__restrict__ q
     const float t = thr.v[q], hi = t + margin, lo = t - margin;
     const u32x2 *ql = qlist + (size_t)q * qcap;
     unsigned int cnt = 0u;
+    unsigned long long *fbins = nullptr, *finfo = nullptr;
+    if constexpr (FACET) {
+        fbins = fo.bins + (size_t)q * fo.n_bins;
+        finfo = fo.info + (size_t)q * 3;
+    }
     // the rows collected so far: every thread reads nband behind a barrier, nobody appends before the next one
     auto rescore = [&]() {
         __syncthreads();
         const unsigned int n = nband;
-        for (unsigned int p = tid; p < n; p += NT) {
-            const uint32_t row = band[p];
-            const float c = F32 ? canonical_dot_f32(xf32, dim, row, qv) : canonical_dot_tiled(xt, ksteps, row, qv);
-            cnt += (c >= t) ? 1u : 0u;
+        if constexpr (FACET) {
+            for (unsigned int p0 = 0; p0 < n; p0 += NT) {   // (workgroup-uniform trip count: the waves aggregate together)
+                const unsigned int p = p0 + tid;
+                bool in = false;
+                int32_t code = -1;
+                if (p < n) {
+                    const uint32_t row = band[p];
+                    const float c = F32 ? canonical_dot_f32(xf32, dim, row, qv) : canonical_dot_tiled(xt, ksteps, row, qv);
+                    in = c >= t;
+                    if (in) code = fo.codes[row];
+                }
+                cnt += in ? 1u : 0u;
+                facet_add_wave(in, code, fo.n_bins, fbins, finfo);
+            }
+        } else {
+            for (unsigned int p = tid; p < n; p += NT) {
+                const uint32_t row = band[p];
+                const float c = F32 ? canonical_dot_f32(xf32, dim, row, qv) : canonical_dot_tiled(xt, ksteps, row, qv);
+                cnt += (c >= t) ? 1u : 0u;
+            }
         }
         __syncthreads();
         if (tid == 0) nband = 0u;
@@ -90,18 +115,21 @@ __global__ __launch_bounds__(256) void k_range_count(const u32x2 *__restrict__ q
     int round = 0;
     for (unsigned int i0 = (unsigned int)blockIdx.y * NT; i0 < M; i0 += gridDim.y * NT) {   // (workgroup-uniform trip count)
         const unsigned int i = i0 + tid;
-        bool inband = false;
+        bool inband = false, above = false;
         uint32_t row = 0u;
         if (i < M) {
             const u32x2 e = ql[i];
             const float a = bits_f32(e.x);
-            if (a >= hi)
+            if (a >= hi) {
                 cnt += 1u;
-            else if (a >= lo) {
+                above = true;
+                row = e.y;
+            } else if (a >= lo) {
                 inband = true;
                 row = e.y;
             }
         }
+        if constexpr (FACET) facet_add_wave(above, above ? fo.codes[row] : -1, fo.n_bins, fbins, finfo);
         const unsigned long long bm = __ballot(inband);   // one LDS atomic per wave, not one per band row
         unsigned int base = 0u;
         if ((tid & 63) == 0 && bm != 0ull) base = atomicAdd(&nband, (unsigned int)__popcll(bm));
@@ -117,7 +145,10 @@ __global__ __launch_bounds__(256) void k_range_count(const u32x2 *__restrict__ q
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
     if ((tid & 63) == 0 && cnt) atomicAdd(&total, cnt);
     __syncthreads();
-    if (tid == 0 && total) atomicAdd(&counts[q], (unsigned long long)total);
+    if (tid == 0 && total) {
+        atomicAdd(&counts[q], (unsigned long long)total);
+        if constexpr (FACET) atomicAdd(&finfo[0], (unsigned long long)total);
+    }
 }
 
 // k_select's list is sorted: its entries below the threshold are a suffix, and become the padding (-inf, -1).

@@ -35,6 +35,8 @@ LEX_MAX_QUERY_TERMS = 32   # CRH_LEX_MAX_QUERY_TERMS: distinct term ids of one c
 TEXT_MAX_PATTERNS, TEXT_MAX_PATTERN_BYTES = 8, 64   # CRH_TEXT_MAX_PATTERNS / CRH_TEXT_MAX_PATTERN_BYTES of one crh_text_match
 REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 256, 32768   # CRH_REGEX_MAX_STATES / CRH_REGEX_MAX_TABLE_BYTES of one crh_text_regex
 TEXT_ALL, TEXT_ANY = 0, 1   # CRH_TEXT_ALL / CRH_TEXT_ANY
+FACET_LDS_BINS = 8192       # CRH_FACET_LDS_BINS: up to this many bins crh_index_facet counts in LDS, above it by runs of equal codes
+FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -59,6 +61,7 @@ EXPORTS = (
     "crh_index_row_mask", "crh_lex_create", "crh_lex_destroy", "crh_lex_clear", "crh_lex_count", "crh_lex_append", "crh_lex_stats",
     "crh_lex_search",
     "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match", "crh_text_regex",
+    "crh_index_facet", "crh_search_range_facet", "crh_facet_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
@@ -223,6 +226,9 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_text_append.argtypes = [vp, i64, vp, vp]
     L.crh_text_match.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, C.POINTER(i64), vp]
     L.crh_text_regex.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i64), vp]
+    L.crh_index_facet.argtypes = [vp, i32, C.POINTER(Condition), i32, i32, vp, vp, vp]
+    L.crh_search_range_facet.argtypes = [vp, i32, vp, i32, vp, C.POINTER(Condition), i32, i32, i32, vp, vp, vp]
+    L.crh_facet_select.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -952,6 +958,61 @@ class Index:
         del keep
         return out
 
+    @staticmethod
+    def _facet_out(out, lead: tuple, n_bins: int):
+        """``out = (bins, info)`` checked: int64 CUDA tensors ``lead + (n_bins,)`` and ``lead + (3,)``."""
+        bins, info = out
+        for x, what, shape in ((bins, "out bins", lead + (n_bins,)), (info, "out info", lead + (3,))):
+            _out(x, "int64", what, shape)
+            if not _is_dev(x):
+                raise NativeError(E_INVALID, f"{what} must be a device tensor")
+        return bins, info
+
+    def facet(self, col: int, n_bins: int, filters=None, out=None, stream: int = 0):
+        """Exact per-code counts of dictionary column ``col`` over the rows a search under ``filters`` sees
+        (``crh_index_facet``; any item form of :func:`_conditions`, :class:`RowWords` included).  Returns / fills ``out =
+        (bins, info)``: int64 CUDA tensors ``[n_bins]`` and ``[3]`` = (counted, missing: code -1, out_of_range: code >=
+        ``n_bins``).  ``n_bins`` up to ``FACET_LDS_BINS`` is counted in LDS, more by runs of equal codes: the bins are the same.
+        Every slot is overwritten.  Enqueues on ``stream``."""
+        import torch
+        n_bins = int(n_bins)
+        if n_bins < 1:
+            raise NativeError(E_INVALID, f"n_bins={n_bins} must be >= 1")
+        if out is None:
+            dev = f"cuda:{self.device}"
+            out = (torch.empty((n_bins,), dtype=torch.int64, device=dev), torch.empty((3,), dtype=torch.int64, device=dev))
+        bins, info = self._facet_out(out, (), n_bins)
+        carr, nc, keep = _conditions(filters, self)
+        check(lib().crh_index_facet(self._handle(), int(col), carr, nc, n_bins, _ptr(bins), _ptr(info), stream))
+        del keep
+        return bins, info
+
+    def search_range_facet(self, queries, thresholds, col: int, n_bins: int, filters=None, out=None, stream: int = 0):
+        """The semantic facet (``crh_search_range_facet``): per query the counts of column ``col`` over the rows IN RANGE as
+        :meth:`search_range` defines it (alive, passes ``filters``, score ``>=`` the query's threshold, inclusive).  Returns /
+        fills ``out = (bins, info)``: int64 CUDA tensors ``[nq, n_bins]`` and ``[nq, 3]`` = (counted -- :meth:`search_range`'s
+        count --, missing, out_of_range).  Overwrites; the batches are finished when the call returns."""
+        import torch
+        queries = _typed(queries, "float32", "queries")
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        nq = int(queries.shape[0])
+        if nq and int(queries.shape[1]) != self.dim:
+            raise NativeError(E_INVALID, f"query dim {queries.shape[1]} != index dim {self.dim}")
+        n_bins = int(n_bins)
+        if n_bins < 1:
+            raise NativeError(E_INVALID, f"n_bins={n_bins} must be >= 1")
+        thr = range_thresholds(thresholds, nq)
+        if out is None:
+            dev = f"cuda:{self.device}"
+            out = (torch.empty((nq, n_bins), dtype=torch.int64, device=dev), torch.empty((nq, 3), dtype=torch.int64, device=dev))
+        bins, info = self._facet_out(out, (nq,), n_bins)
+        carr, nc, keep = _conditions(filters, self)
+        check(lib().crh_search_range_facet(self._handle(), nq, _ptr(queries), _is_dev(queries), thr.ctypes.data, carr, nc, int(col), n_bins,
+                                           _ptr(bins), _ptr(info), stream))
+        del keep
+        return bins, info
+
 
 def lex_queries(queries, idf) -> tuple:
     """Per-query ascending distinct term ids and their idf as the CSR ``crh_lex_search`` takes: (q_off int64, terms uint32, idf
@@ -1232,6 +1293,30 @@ def group_select(scores, rows, codes, k: int, group_size: int, stream: int = 0):
     use_device(dev.index)
     check(lib().crh_group_select(nq, c, k, int(group_size), _ptr(scores), _ptr(rows), _ptr(codes), *(_ptr(x) for x in outs), _ptr(info), stream))
     return outs + (info,)
+
+
+def facet_select(bins, k: int, stream: int = 0):
+    """The facet list (``crh_facet_select``) of histograms left on the device: ``bins`` int64 ``[nq, n_bins]`` (or ``[n_bins]``:
+    one list), counts ``>= 0``.  Returns CUDA tensors ``(codes i32, counts i64)``, each ``[nq, k]`` -- the bins with count > 0 by
+    count descending, ties to the lower code, tail ``(-1, 0)`` -- and ``info`` i64 ``[nq, 2]`` = (bins with count > 0, sum of
+    the bins).  Enqueues only."""
+    import torch
+    if not _is_dev(bins):
+        raise NativeError(E_INVALID, "bins must be a device tensor")
+    _typed(bins, "int64", "bins")
+    if bins.ndim == 1:
+        bins = bins[None, :]
+    if bins.ndim != 2:
+        raise NativeError(E_INVALID, "bins must be [nq, n_bins]")
+    nq, n_bins = (int(v) for v in bins.shape)
+    k = int(k)
+    dev = bins.device
+    codes = torch.empty((nq, max(k, 0)), dtype=torch.int32, device=dev)
+    counts = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+    info = torch.empty((nq, 2), dtype=torch.int64, device=dev)
+    use_device(dev.index)
+    check(lib().crh_facet_select(nq, n_bins, k, _ptr(bins), _ptr(codes), _ptr(counts), _ptr(info), stream))
+    return codes, counts, info
 
 
 def span_select(scores, rows, file_codes, lo, hi, k: int, max_overlap_permille: int, stream: int = 0):

@@ -103,3 +103,48 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                         "required": False},
         },
     }
+
+
+def create_code_facets_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
+    """MCP ``code_facets`` tool (not in the reference): WHERE something lives -- the most frequent files, languages or entity
+    types among the chunks that pass a filter, hold a string or are similar to a description, with exact counts
+    (``VectorSearcher.facet_code``)."""
+    async def code_facets(key: str = "file_path", query: str | None = None, min_score: float | None = None, limit: int = 10,
+                          language: str | None = None, entity_type: str | None = None, contains: str | list[str] | None = None,
+                          contains_case: bool | None = None, matches: str | None = None) -> ToolResult:
+        logger.info(f"[Tool:CodeFacets] Key: '{key}' query: {query!r}")
+        try:
+            searcher = vector_searcher_factory()
+            extra = {k: v for k, v in (("query", query or None), ("min_score", min_score), ("language", language), ("entity_type", entity_type),
+                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches else None),
+                                       ("matches", matches or None)) if v is not None}   # (only when asked for)
+            res = await searcher.facet_code(key=key, limit=limit, **extra)
+            shown, values = len(res["hits"]), res["values"]
+            message = f"{res['total']} chunks carry {values} distinct {key} value(s)" + (f"; the {shown} most frequent are listed." if shown < values else ".")
+            return ToolResult(success=True, data=res, message=message)
+        except Exception as e:  # the catch-all of the reference's tools (tools.py:431-436)
+            logger.error(f"[Tool:CodeFacets] Error: {e}", exc_info=True)
+            return ToolResult(success=False, error=str(e))
+
+    return {
+        "name": "code_facets",
+        "description": ("Count code chunks per file, language or entity type: where a string, a pattern or a concept lives in the "
+                        "code base, with exact counts -- not which chunks."),
+        "function": code_facets,
+        "parameters": {
+            "key": {"type": "string", "description": "What to count by: 'file_path' (the default), 'language', 'entity_type', "
+                                                     "'entity_name' or 'project_name'", "required": False},
+            "query": {"type": "string", "description": "With min_score: count only chunks at least that similar to this natural "
+                                                       "language description", "required": False},
+            "min_score": {"type": "number", "description": "With query: the similarity score a chunk must reach to be counted", "required": False},
+            "limit": {"type": "integer", "description": "How many values to list, most frequent first (default: 10, at most 1024)", "required": False},
+            "language": {"type": "string", "description": "Count only chunks in this language", "required": False},
+            "entity_type": {"type": "string", "description": "Count only chunks of this type: function, class, method", "required": False},
+            "contains": {"type": "string", "description": "Count only chunks whose code contains this literal string (or every string "
+                                                          "of a list of up to 8): 'TODO(', '.unwrap()'", "required": False},
+            "contains_case": {"type": "boolean", "description": "With contains / matches: false ignores the case of ASCII letters (default: true)",
+                              "required": False},
+            "matches": {"type": "string", "description": "Count only chunks in whose code this regular expression (Python re syntax) is found",
+                        "required": False},
+        },
+    }

@@ -518,6 +518,41 @@ class ShardSet:
             self._mask_lists(cs, cr, ~np.asarray(live, bool).reshape(nq * m))
         return tuple(_host(a) for a in ffi.fuse_select(cs, cr, m, k, method, rrf_k, weights, stream=self._stream()))
 
+    # ------------------------------------------------------------------ facets
+    def facet(self, dfilt, col: int, n_bins: int, k: int, queries=None, thr=None):
+        """Exact per-code counts of column ``col`` over all shards and their top-``k`` list, as host arrays: ``(codes i32 [nq,
+        k], counts i64 [nq, k], sel i64 [nq, 2] = (codes counted, rows counted under a code), info i64 [nq, 3] = (counted,
+        missing, out of range))``; the tail of a list is (-1, 0).  Without ``queries`` (``nq`` = 1) the rows ``dfilt`` keeps
+        count (``crh_index_facet``); with ``queries`` [nq, dim] and ``thr`` [nq] those of them whose score reaches the query's
+        threshold (``crh_search_range_facet``).  Every owned shard fills a slab of its own -- dictionary codes are the
+        collection's, the same on every shard --, the slabs are summed, ONE :meth:`reduce` (SUM) completes bins and info in
+        one buffer, and ONE ``crh_facet_select`` runs on the sum."""
+        nq = 1 if queries is None else int(len(queries))
+        n_bins, k = int(n_bins), int(k)
+        if queries is not None and nq * n_bins > ffi.FACET_MAX_ENTRIES:
+            raise ValueError(f"a semantic facet of {nq} queries x {n_bins} values asks for {nq * n_bins} bin entries per shard, "
+                             f"more than {ffi.FACET_MAX_ENTRIES}: send fewer queries per call")
+        stream = self._stream()
+        slab = self._full((nq * (n_bins + 3),), 0, "int64")                # [bins | info]: one buffer, one all-reduce
+        bins, info = slab[: nq * n_bins].reshape(nq, n_bins), slab[nq * n_bins:].reshape(nq, 3)
+        if queries is not None and self._native() and not hasattr(queries, "data_ptr"):
+            queries = self._local(np.ascontiguousarray(queries, dtype=np.float32))
+        for i, s in enumerate(self.owned):
+            ix = self.index[s]
+            kw = {"stream": stream} if self._native() else {}
+            if i == 0 and self._native():
+                kw["out"] = (bins if queries is not None else bins[0], info if queries is not None else info[0])
+            if queries is None:
+                b, f = ix.facet(col, n_bins, filters=dfilt, **kw)
+            else:
+                b, f = ix.search_range_facet(queries, thr, col, n_bins, filters=dfilt, **kw)
+            if "out" not in kw:
+                bins += b.reshape(nq, n_bins)
+                info += f.reshape(nq, 3)
+        self.reduce(slab, "SUM")
+        codes, counts, sel = ffi.facet_select(bins, k, stream=stream)
+        return _host(codes), _host(counts), _host(sel), _host(info)
+
     # ------------------------------------------------------------------ keyword search (BM25; DESIGN.md 3.20)
     # ``lex`` = {shard: ffi.Lex}: the forward indexes beside the owned shards, rows numbered like the shards' (the collection
     # builds and keeps them).  Tombstones and filters reach them as the validity words of ``Index.row_mask`` only.

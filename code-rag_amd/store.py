@@ -662,6 +662,27 @@ class _Collection:
         scores, shard, local, totals = self.shards.search_range(queries, limit, thresholds, dfilt, counts)
         return scores, self.slots_of(shard, local), totals
 
+    def facet_column(self, key: str) -> int:
+        """The device column of a key whose values can be counted: one of the dictionary keys.  ``ValueError`` naming them for a
+        numeric key (its column holds the values themselves, not codes: no histogram of lines in this version) and for any other."""
+        if key in self.numeric_keys:
+            raise ValueError(f"payload key {key!r} holds numbers: a facet counts the values of a dictionary key "
+                             f"(filterable: {', '.join(self.keys)})")
+        return self._column(key)
+
+    def facet(self, key: str, limit: int, dfilt, queries: np.ndarray | None = None, thresholds=None) -> list[dict[str, Any]]:
+        """Per query -- one without ``queries`` -- the values of ``key`` among the rows that count (``ShardSet.facet``; DESIGN.md
+        3.23): ``{"hits": [{"value", "count"}], "values", "total", "missing"}``.  The device keeps ONE code (0) for "the key is
+        absent" and "its value is None", as the filters do: those rows are counted under the value None -- the rows a filter
+        ``{key: None}`` selects.  ``missing`` counts rows whose column holds -1, which no upsert of this store writes."""
+        book = self.payloads.cols[key]
+        n_bins = len(book.values) + 1                                       # code = position in `values` + 1; 0: no value
+        codes, counts, sel, info = self.shards.facet(dfilt, self.facet_column(key), n_bins, limit, queries, thresholds)
+        if info[:, 2].any():
+            raise RuntimeError(f"facet of {key!r}: {int(info[:, 2].sum())} rows carry a code beyond the dictionary's {n_bins} entries")
+        return [{"hits": [{"value": None if c == 0 else book.values[c - 1], "count": int(n)} for c, n in zip(codes[q].tolist(), counts[q].tolist()) if c >= 0],
+                 "values": int(sel[q, 0]), "total": int(sel[q, 1]), "missing": int(info[q, 1])} for q in range(codes.shape[0])]
+
     def search_multi(self, queries: np.ndarray, limit: int, class_dfilts, query_class) -> tuple[np.ndarray, np.ndarray]:
         """The same for a batch whose queries carry different filters: query ``i`` under ``class_dfilts[query_class[i]]``."""
         scores, shard, local = self.shards.search_multi(queries, limit, class_dfilts, query_class)
@@ -1216,6 +1237,23 @@ class _RawClient:
         n = await self._store._run(work)
         return type("CountResult", (), {"count": n})()
 
+    async def facet(self, collection_name: str, key: str, facet_filter=None, limit: int = 10, exact: bool = True):
+        """Qdrant's ``client.facet``: an object with ``.hits[i].value`` / ``.hits[i].count`` (``FacetResponse``), the ``limit``
+        most frequent values of ``key`` among the points ``facet_filter`` keeps -- always exact, whatever ``exact`` says; ties
+        go to the value stored first (Qdrant: to the value itself).  The filter's keys must be coded on the device."""
+        def work():
+            col = self._store._col(collection_name)
+            col.facet_column(key)
+            if not 1 <= int(limit) <= ffi.MAX_K:
+                raise ValueError(f"facet: limit {limit} outside 1..{ffi.MAX_K}")
+            dfilt = self._device_filter(col, self._conditions(facet_filter))
+            if dfilt is None:
+                raise ValueError(f"facet_filter holds a condition the device cannot evaluate (filterable: {', '.join(col.keys + col.numeric_keys)})")
+            return col.facet(key, int(limit), dfilt)[0]
+        res = await self._store._run(work)
+        hits = [type("FacetValueHit", (), {"value": h["value"], "count": h["count"]})() for h in res["hits"]]
+        return type("FacetResponse", (), {"hits": hits})()
+
     async def delete(self, collection_name: str, points_selector=None):
         flt = getattr(points_selector, "filter", points_selector)
 
@@ -1605,6 +1643,74 @@ class HipVectorStore:
             return (await self._range_call(collection, [query_vector], score_threshold, 0, filters, must_not, True))[1][0]
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    # ------------------------------------------------------------------ facets
+    def _facet_sync(self, collection: str, key: str, limit: int, filters, must_not, queries, thresholds) -> list[dict[str, Any]]:
+        """One facet job on the worker: the filter's conditions (text conditions grep here, through the collection's cache), the
+        histogram, its list, and the codes mapped back to values -- all under the store's lock, so the dictionaries are the ones
+        the codes were counted with."""
+        col = self._col(collection)
+        nq = 1 if queries is None else queries.shape[0]
+        dfilt = col.device_filters(filters, must_not)
+        if dfilt is None or nq == 0:                                        # (a value the collection never stored: nothing counts)
+            return [{"hits": [], "values": 0, "total": 0, "missing": 0} for _ in range(nq)]
+        return col.facet(key, limit, dfilt, queries, thresholds)
+
+    async def _facet_call(self, collection: str, key: str, limit, filters, must_not, query_vectors, score_threshold) -> list[dict[str, Any]]:
+        """Argument checks for the caller alone, then one job."""
+        col = self._col(collection)
+        col.facet_column(key)
+        limit = int(limit)
+        if not 1 <= limit <= ffi.MAX_K:
+            raise ValueError(f"facet: limit {limit} outside 1..{ffi.MAX_K}")
+        if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+            raise ValueError("a facet takes one filter, not per-query filters")
+        q = thr = None
+        if (query_vectors is None) != (score_threshold is None):
+            raise ValueError("facet: query_vector and score_threshold come together (the rows at least that similar count) or not at all")
+        if query_vectors is not None:
+            q = np.asarray(query_vectors, dtype=np.float32)
+            if q.ndim != 2 or (q.shape[0] and q.shape[1] != col.shards.dim):
+                raise ValueError(f"query dim {q.shape[-1] if q.ndim else 0} != index dim {col.shards.dim}")
+            thr = self._range_args(score_threshold, q.shape[0])
+            self.search_passes += (q.shape[0] + 63) // 64
+        return await self._run(self._facet_sync, collection, key, limit, filters, must_not, q, thr)
+
+    async def facet(self, collection: str, key: str, limit: int = 10, filters: dict[str, Any] | None = None,
+                    must_not: dict[str, Any] | None = None, *, query_vector: list[float] | None = None,
+                    score_threshold: float | None = None) -> dict[str, Any]:
+        """Qdrant's ``client.facet(collection_name, key, facet_filter, limit, exact=True)``: the values of payload key ``key``
+        among the points that COUNT, with how many points carry each -- "how many chunks per file hold ``TODO(``", "which
+        languages make up this project".  A point counts iff it is alive and passes ``filters`` / ``must_not`` (everything
+        :meth:`search` takes, ``{"content": {"contains": ...}}`` / ``{"matches": ...}`` included); with ``query_vector`` and
+        ``score_threshold`` -- both or neither -- its score must also be ``>= score_threshold``, exactly :meth:`count_similar`'s
+        rule: "in which files does this concept live".  Returns ``{"hits": [{"value", "count"}, ...], "values", "total",
+        "missing"}``: ``hits`` are the ``limit`` (1..1024) most frequent values, count descending, ties to the value STORED
+        FIRST (Qdrant breaks ties by the value itself); ``values`` how many distinct values were counted and ``total`` how many
+        points carry one, neither clipped at ``limit``; ``total + missing`` is what :meth:`count` / :meth:`count_similar` return
+        for the same arguments.  ``key`` is one of the collection's dictionary-coded keys.  A point without the key is counted
+        under the value None, as a filter ``{key: None}`` selects it.  Counted, selected and sorted on the device, exact
+        (DESIGN.md 3.23)."""
+        try:
+            return (await self._facet_call(collection, key, limit, filters, must_not, None if query_vector is None else [query_vector],
+                                           score_threshold))[0]
+        except VectorStoreError:
+            raise
+        except Exception as e:
+            raise VectorStoreError(f"Failed to facet {collection}", cause=e)
+
+    async def facet_batch(self, collection: str, key: str, query_vectors, score_threshold, limit: int = 10,
+                          filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+        """:meth:`facet` for several queries in one pass per 64: ``score_threshold`` is one number or one per query; one result
+        per query."""
+        try:
+            if query_vectors is None or score_threshold is None:
+                raise ValueError("facet_batch needs query vectors and a score threshold")
+            return await self._facet_call(collection, key, limit, filters, must_not, query_vectors, score_threshold)
+        except VectorStoreError:
+            raise
+        except Exception as e:
+            raise VectorStoreError(f"Failed to facet {collection}", cause=e)
 
     @staticmethod
     def _mmr_args(limit: int, diversity: float | None, candidates: int | None) -> tuple[float | None, int | None]:

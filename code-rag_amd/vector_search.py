@@ -336,6 +336,34 @@ class VectorSearcher:
             raise QueryError("Failed to fetch the chunks at a line", cause=e)
         return [_project({"score": 0.0, "payload": p}, _CODE_KEYS) for p in payloads]
 
+    async def facet_code(self, key: str = "file_path", query: str | None = None, min_score: float | None = None,
+                         limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None, entity_type: str | None = None,
+                         project_name: str | list[str] | None = None, contains: str | list[str] | None = None,
+                         contains_case: bool = True, matches: str | None = None) -> dict:
+        """WHERE something lives, not which chunks (not in the reference, whose callers fetch hits and count them in Python):
+        the ``limit`` most frequent values of ``key`` -- a file path, a language, an entity type -- among the code chunks that
+        pass the filters, with their counts (``HipVectorStore.facet``): ``{"hits": [{"value", "count"}], "values", "total",
+        "missing"}``.  ``contains`` / ``contains_case`` / ``matches`` as in :meth:`search_code`: how many chunks per file hold
+        ``TODO(``.  With ``query`` and ``min_score`` -- both or neither -- ``query`` is embedded and only chunks at least that
+        similar to it count: in which files does this concept live.  Counts are exact; ties go to the value indexed first."""
+        if (query is None) != (min_score is None):
+            raise QueryError("facet_code: query and min_score come together or not at all")
+        if query is not None and not query.strip():
+            raise QueryError("Search query cannot be empty")
+        filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
+        filters.update(_contains_filter("content", contains, contains_case, matches))
+        try:
+            kwargs = {}
+            if query is not None:
+                kwargs = {"query_vector": await self.embedder.embed(query), "score_threshold": min_score}
+            return await self.qdrant.facet(collection=CollectionName.CODE_CHUNKS.value, key=key, limit=limit, filters=filters or None, **kwargs)
+        except EmbeddingError as e:
+            logger.error(f"Embedding error: {e}")
+            raise QueryError("Failed to embed search query", cause=e)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to count code by value", cause=e)
+
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,

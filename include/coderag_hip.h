@@ -551,6 +551,53 @@ int crh_index_match_rows(crh_index *h, const crh_filter *filters, int n_filters,
 int crh_index_match_rows_cond(crh_index *h, const crh_condition *conds, int n_conds, int64_t limit,
                               int64_t *rows_out_host, int64_t *n_out);
 
+/* ---- facets: exact per-value counts of one dictionary column, under any filter or score threshold.  Qdrant's counterpart is
+ * client.facet(collection_name, key, facet_filter, limit, exact); the reference's callers fetch hits and count them in Python.
+ * The definitions are this repository's own and exact.  A row COUNTS iff it is alive and passes the conditions
+ * -- and, in the semantic form, is IN RANGE as crh_search_range defines it (canonical f32 score >= thr, inclusive).  With c the
+ * code of a counting row in column `col`: bins[c] += 1 for 0 <= c < n_bins, missing += 1 for c < 0 (-1: the key is absent),
+ * out_of_range += 1 for c >= n_bins (written nowhere).  info = (counted, missing, out_of_range), counted = sum(bins) + missing +
+ * out_of_range = what crh_index_match_rows_cond / crh_search_range count for the same arguments.  All sums are integer atomics:
+ * integer additions commute, so the result is deterministic -- the same on every call and on a batch that is run again. */
+#define CRH_FACET_LDS_BINS 8192 /* up to this many bins a workgroup counts in LDS; above, waves aggregate runs of equal codes */
+
+/* Replaces client.facet(key, facet_filter, exact=True) before its ordering.  The mask is built (or found) by the same routine
+ * and mask cache crh_index_row_mask and a search use; every condition mode of crh_index_match_rows_cond is taken, row bitmaps
+ * (CRH_COND_WORDS / _NOT_WORDS) included.  A tile whose mask word is 0 does not have its codes read.  n_bins chooses the
+ * kernel's route and nothing else: both give the same bins.  out_bins_dev int64 [n_bins], out_info_dev int64
+ * [3], device memory; every slot is overwritten (an empty index writes zeros).  col outside 0..n_code_cols-1 and n_bins < 1 are
+ * CRH_E_INVALID with nothing launched; the index does not know which of its columns hold dictionary codes and which values
+ * (CRH_COND_BETWEEN): a histogram of a numeric column is refused by the store.  Enqueues on `stream`. */
+int crh_index_facet(crh_index *h, int col, const crh_condition *conds, int n_conds, int n_bins,
+                    int64_t *out_bins_dev /* [n_bins] */, int64_t *out_info_dev /* [3]: counted, missing, out_of_range */,
+                    void *stream);
+
+/* The semantic form -- client.facet under a filter Qdrant cannot express: "at cosine >= thr to this query".  A range batch with
+ * counts (crh_search_range: thresholds, batches of 64 / 32 queries, the three-launch bf16 scan, CRH_E_CAPACITY for a threshold
+ * so low that a query's candidates exceed the workspace budget) whose counting kernel adds every in-range row to its query's
+ * bins, lanes with equal codes aggregated per wave.  out_bins_dev int64 [nq, n_bins], out_info_dev int64 [nq, 3], device
+ * memory, overwritten: there is no accumulate mode -- the shards of one process each get a slab of their own and the caller
+ * sums them.  A batch's bins and info rows are cleared on the stream before its scan, so a batch that is run again because its
+ * candidate lists overflowed gives what a first run gives.  The batches are finished before the call returns (no
+ * crh_search_finish is needed); info[i][0] is crh_search_range's out_counts[i].  A NaN or infinite threshold, a bad column and
+ * n_bins < 1 are CRH_E_INVALID with nothing launched. */
+int crh_search_range_facet(crh_index *h, int nq, const float *queries, int queries_on_device,
+                           const float *thresholds_host /* [nq], copied by the call */,
+                           const crh_condition *conds, int n_conds, int col, int n_bins,
+                           int64_t *out_bins_dev /* [nq, n_bins] */, int64_t *out_info_dev /* [nq, 3] */, void *stream);
+
+/* The FACET LIST of nq histograms (int64 [nq, n_bins], counts >= 0 -- the bins above, summed over shards and ranks by the
+ * caller): the bins with count > 0 ordered by count descending, ties to the LOWER CODE -- the value stored first; Qdrant's
+ * client.facet breaks ties by the value itself -- cut at k.  out_codes_dev int32 / out_counts_dev int64, each [nq, k], the tail
+ * (-1, 0): a zero count is never returned.  out_info_dev int64 [nq, 2] = (bins with count > 0, sum of the bins).  The first j
+ * entries of a k-entry list are the j-entry list.  Exact for any non-negative int64 counts (radix select of the k-th largest,
+ * ordered compaction, sort of the survivors).  1 <= k <= CRH_MAX_K, n_bins >= 1, nq >= 0, anything else CRH_E_INVALID with
+ * nothing launched.  Needs no index handle (launches on the current device, like crh_group_select).  Deterministic; enqueues
+ * only; writes every output slot. */
+int crh_facet_select(int nq, int n_bins, int k, const int64_t *bins_dev /* [nq, n_bins] */,
+                     int32_t *out_codes_dev /* [nq, k] */, int64_t *out_counts_dev /* [nq, k] */,
+                     int64_t *out_info_dev /* [nq, 2] */, void *stream);
+
 /* ---- exact BM25 keyword search on the device.  Qdrant's counterpart is a sparse (BM25) vector searched beside the dense one,
  * query_points(prefetch=[dense, sparse], query=FusionQuery(RRF)); the fusion half is crh_fuse_select.  The definitions are this
  * repository's own and exact.
