@@ -1,5 +1,6 @@
-// crh_text.hip -- literal substring match (k_text_match) and regular-expression match by byte DFA (k_text_regex, described where it
-// stands) over the chunks' text in HBM (gfx950 / CDNA4 only).
+// crh_text.hip -- literal substring match (k_text_match), regular-expression match by byte DFA (k_text_regex) and approximate
+// substring match within a bounded edit distance (k_text_fuzzy; both described where they stand) over the chunks' text in HBM
+// (gfx950 / CDNA4 only).
 //
 // Replaces what Qdrant answers for FieldCondition(key, match=MatchText(text)) on a field WITHOUT a full-text index: an exact
 // substring match ("chunks that contain `retry_after=`").  The definition is THIS repository's (tests/text_cases.py
@@ -307,6 +308,142 @@ __global__ __launch_bounds__(kTextWaves * 64) void k_text_regex(const RegexArgs 
     if (lane == 0 && found) atomicAdd(a.count, (unsigned long long)found);
 }
 
+// ---- k_text_fuzzy: approximate substring match, at most CRH_FUZZY_MAX_EDITS byte edits
+//
+// A row's DISTANCE is min over its substrings S of Levenshtein(P, S) = min_j D[m][j] of Sellers' table (D[0][j] = 0, D[i][0] = i);
+// level d of the output holds the rows whose distance is <= d.  The lane and tile shape is k_text_regex's: one wave per pair of
+// tiles, one lane per row, the same 16-byte aligned loads (so the same bound: at most 15 bytes behind a row's end, inside
+// kTextSlack), a pair whose mask words are 0 stores zeros in every level and reads no byte.  A lane keeps one column of the table
+// as Myers' two difference vectors (Pv: D[i][j] - D[i-1][j] = +1, Mv: = -1; bit i - 1 is row i) in a W = 32- or 64-bit word and
+// D[m][j] as a running score; the best score is the row's distance, exact for every level at once.  Bits at and above m hold
+// garbage that never comes down: the column step carries and shifts upwards only.  The equality table Peq[byte] (bit i: P[i]
+// equals the byte; with fold_case the ASCII letters of both sides folded, so the text itself is never folded) is made in LDS
+// once per workgroup, thread b making entry b from the pattern in the kernel's arguments; its lookup depends on the text byte
+// alone and the 16 of a chunk are issued before the chunk's first column step.  A byte outside the lane's [begin, end) is walked
+// like any other and its step discarded by selects, so the walk has no divergent branch.  A lane whose best score is 0 is
+// settled; the wave loops while any lane has bytes left and is not.  Each level is one ballot ANDed with the mask words and stored
+// by lane 0; each level's count is one integer atomic per wave.
+struct FuzzyArgs {
+    const int64_t *row_off;
+    const uint8_t *bytes;
+    int64_t rows;
+    const uint32_t *mask;        // one word per tile, or nullptr: every row
+    uint32_t *out;               // [k + 1][ntiles]
+    unsigned long long *count;   // [k + 1], += set bits
+    int m, k, fold;
+    uint32_t pat[CRH_TEXT_MAX_PATTERN_BYTES / 4];   // the pattern's bytes (folded when the match folds), zeros behind
+};
+
+template <typename W, int J>
+__device__ __forceinline__ void fuzzy_eqs(const text_u32x4 &w, const W *peq, W (&eq)[kTextLane])
+{
+    const uint32_t d = J / 4 == 0 ? w.x : J / 4 == 1 ? w.y : J / 4 == 2 ? w.z : w.w;
+    eq[J] = peq[(d >> (8 * (J % 4))) & 0xffu];
+    if constexpr (J + 1 < kTextLane) fuzzy_eqs<W, J + 1>(w, peq, eq);
+}
+
+template <typename W>
+__global__ __launch_bounds__(kTextWaves * 64) void k_text_fuzzy(const FuzzyArgs a)
+{
+    static_assert(kTextWaves * 64 == 256, "one thread per entry of the equality table");
+    __shared__ W peq[256];
+    {
+        uint32_t b = threadIdx.x;                                         // (kTextWaves * 64 == 256: one entry per thread)
+        if (a.fold && b >= 'A' && b <= 'Z') b |= 0x20u;
+        W e = 0;
+#pragma unroll
+        for (int i = 0; i < (int)sizeof(W) * 8; ++i)
+            if (i < a.m && ((a.pat[i / 4] >> (8 * (i % 4))) & 0xffu) == b) e |= (W)1 << i;
+        peq[threadIdx.x] = e;
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ntiles = (a.rows + 31) / 32, npairs = (ntiles + 1) / 2;
+    const int m = a.m, k = a.k;
+    const W top = (W)1 << (m - 1);
+    unsigned int found[CRH_FUZZY_MAX_EDITS + 1] = {0u, 0u, 0u, 0u};      // per level: set bits this wave has written (wave-uniform)
+
+    for (int64_t pr = (int64_t)blockIdx.x * kTextWaves + wave; pr < npairs; pr += (int64_t)gridDim.x * kTextWaves) {
+        const int64_t t0 = pr * 2, r0 = pr * 64;
+        const bool second = t0 + 1 < ntiles;                              // (wave-uniform) does the pair's second tile exist?
+        uint32_t m0 = a.mask ? a.mask[t0] : 0xffffffffu;
+        uint32_t m1 = second ? (a.mask ? a.mask[t0 + 1] : 0xffffffffu) : 0u;
+        const int64_t left = a.rows - r0;                                 // >= 1
+        if (left < 32) m0 &= (1u << (int)left) - 1u;
+        if (left < 64) m1 &= left <= 32 ? 0u : (1u << (int)(left - 32)) - 1u;
+        m0 = __builtin_amdgcn_readfirstlane(m0);
+        m1 = __builtin_amdgcn_readfirstlane(m1);
+        if ((m0 | m1) == 0u) {                                            // (wave-uniform) nothing of the pair is read
+            if (lane == 0) {
+#pragma unroll
+                for (int d = 0; d <= CRH_FUZZY_MAX_EDITS; ++d) {
+                    if (d > k) break;
+                    a.out[d * ntiles + t0] = 0u;
+                    if (second) a.out[d * ntiles + t0 + 1] = 0u;
+                }
+            }
+            continue;
+        }
+        const bool active = (((lane < 32 ? m0 : m1) >> (lane & 31)) & 1u) != 0u;   // (a set bit is a row below `rows`)
+        int64_t begin = 0, end = 0;
+        if (active) {
+            begin = a.row_off[r0 + lane];
+            end = a.row_off[r0 + lane + 1];
+        }
+        int64_t p = begin < end ? begin & ~(int64_t)(kTextLane - 1) : end;
+        W pv = ~(W)0, mv = 0;
+        int score = m, best = m;                                          // (D[m][0] = m: the empty row's distance)
+        text_u32x4 cur = p < end ? *reinterpret_cast<const text_u32x4 *>(a.bytes + p) : text_u32x4{0u, 0u, 0u, 0u};
+        while (__ballot(p < end && best != 0) != 0ull) {
+            const int64_t pn = p + kTextLane;
+            // (unconditional, so that nothing waits for it before the walk: a lane without a next chunk reloads the arena's first)
+            const text_u32x4 nxt = *reinterpret_cast<const text_u32x4 *>(a.bytes + (pn < end ? pn : 0));
+            // the lane's bytes of this chunk that lie inside its row: [lo, hi) of 0..16 (none once p >= end)
+            const int64_t dlo = begin - p, dhi = end - p;
+            const int lo = dlo > 0 ? (int)dlo : 0;
+            const int hi = dhi >= kTextLane ? kTextLane : dhi > 0 ? (int)dhi : 0;
+            W eq[kTextLane];
+            fuzzy_eqs<W, 0>(cur, peq, eq);                                // (independent of the state: off the chain)
+#pragma unroll
+            for (int j = 0; j < kTextLane; ++j) {
+                const bool in = j >= lo && j < hi;
+                const W e = eq[j];
+                const W xv = e | mv;
+                const W xh = (((e & pv) + pv) ^ pv) | e;
+                W ph = mv | ~(xh | pv);
+                W mh = pv & xh;
+                const int ns = score + ((ph & top) != 0 ? 1 : 0) - ((mh & top) != 0 ? 1 : 0);
+                ph <<= 1;                                                 // (no carry in: D[0][j] - D[0][j-1] = 0, a match may start anywhere)
+                mh <<= 1;
+                const W npv = mh | ~(xv | ph), nmv = ph & xv;
+                pv = in ? npv : pv;
+                mv = in ? nmv : mv;
+                score = in ? ns : score;
+                best = min(best, score);
+            }
+            p = pn;
+            cur = nxt;
+        }
+#pragma unroll
+        for (int d = 0; d <= CRH_FUZZY_MAX_EDITS; ++d) {
+            if (d > k) break;
+            const unsigned long long hit = __ballot(active && best <= d);
+            const uint32_t w0 = (uint32_t)hit & m0, w1 = (uint32_t)(hit >> 32) & m1;
+            if (lane == 0) {
+                a.out[d * ntiles + t0] = w0;
+                if (second) a.out[d * ntiles + t0 + 1] = w1;
+            }
+            found[d] += (unsigned int)(__popc(w0) + __popc(w1));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int d = 0; d <= CRH_FUZZY_MAX_EDITS; ++d)
+            if (d <= k && found[d]) atomicAdd(a.count + d, (unsigned long long)found[d]);
+    }
+}
+
 int text_alloc(void **p, int64_t bytes)
 {
     hipError_t e = hipMalloc(p, (size_t)std::max<int64_t>(bytes, 1));
@@ -347,7 +484,7 @@ struct crh_text {
     int64_t cap_off = 0, cap_bytes = 0;   // in bytes: of row_off (8 per entry), of bytes (without the slack)
     uint8_t *row_off = nullptr;           // int64 [rows + 1]
     uint8_t *bytes = nullptr;             // nbytes, then kTextSlack zeros
-    unsigned long long *count = nullptr;  // the match's / the regex's counter
+    unsigned long long *count = nullptr;  // CRH_FUZZY_MAX_EDITS + 1 counters: the match's / the regex's is the first, the fuzzy match's one per level
     uint8_t *regex_image = nullptr;       // kRegexImageMax bytes, allocated by the first crh_text_regex
     std::vector<uint8_t> regex_host;      // the image the last crh_text_regex uploaded (the copy's source outlives the call)
 };
@@ -371,7 +508,7 @@ int crh_text_create(int device, int64_t capacity_rows, int64_t capacity_bytes, c
     void *cnt = nullptr;
     int rc = text_grow(&t->row_off, &t->cap_off, 0, (capacity_rows + 1) * 8, 0);   // (zeroed: row_off[0] = 0)
     if (rc == CRH_OK) rc = text_grow(&t->bytes, &t->cap_bytes, 0, capacity_bytes, kTextSlack);
-    if (rc == CRH_OK) rc = text_alloc(&cnt, 8);
+    if (rc == CRH_OK) rc = text_alloc(&cnt, 8 * (CRH_FUZZY_MAX_EDITS + 1));
     t->count = static_cast<unsigned long long *>(cnt);
     if (rc != CRH_OK) {
         crh_text_destroy(t);
@@ -566,6 +703,51 @@ int crh_text_regex(crh_text *t, int n_states, int n_classes, const uint8_t *clas
         CRH_HIP(hipMemcpyAsync(&c, t->count, 8, hipMemcpyDeviceToHost, st));
         CRH_HIP(hipStreamSynchronize(st));
         *out_count_host = (int64_t)c;
+    }
+    return CRH_OK;
+}
+
+int crh_text_fuzzy(crh_text *t, const uint8_t *pat_host, int len, int max_edits, int fold_case, const uint32_t *mask_dev,
+                   uint32_t *out_words_dev, int64_t *out_counts_host, void *stream)
+{
+    // (the arguments first, the handle after them: a caller's mistake is named whatever it passes as the handle)
+    if (len < 1 || len > CRH_TEXT_MAX_PATTERN_BYTES) return fail(CRH_E_INVALID, "text_fuzzy: len=%d outside 1..%d", len, CRH_TEXT_MAX_PATTERN_BYTES);
+    if (max_edits < 0 || max_edits > CRH_FUZZY_MAX_EDITS) return fail(CRH_E_INVALID, "text_fuzzy: max_edits=%d outside 0..%d", max_edits, CRH_FUZZY_MAX_EDITS);
+    if (len <= max_edits) return fail(CRH_E_INVALID, "text_fuzzy: len=%d is not above max_edits=%d (every row would match)", len, max_edits);
+    if (!pat_host) return fail(CRH_E_INVALID, "text_fuzzy: pat_host is NULL");
+    if (!t) return fail(CRH_E_INVALID, "text_fuzzy: the text handle is NULL");
+    if (out_counts_host) std::fill(out_counts_host, out_counts_host + max_edits + 1, (int64_t)0);
+    if (t->rows == 0) return CRH_OK;   // (before the output is looked at, as in crh_text_match / crh_text_regex: a buffer of 0 words may be NULL)
+    if (!out_words_dev) return fail(CRH_E_INVALID, "text_fuzzy: out_words_dev is NULL");
+    FuzzyArgs a{};
+    a.row_off = reinterpret_cast<const int64_t *>(t->row_off);
+    a.bytes = t->bytes;
+    a.rows = t->rows;
+    a.mask = mask_dev;
+    a.out = out_words_dev;
+    a.count = t->count;
+    a.m = len;
+    a.k = max_edits;
+    a.fold = fold_case != 0;
+    uint8_t *pb = reinterpret_cast<uint8_t *>(a.pat);
+    for (int i = 0; i < len; ++i) {
+        uint8_t c = pat_host[i];
+        if (fold_case && c >= 'A' && c <= 'Z') c = (uint8_t)(c | 0x20);
+        pb[i] = c;
+    }
+    DeviceGuard g(t->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CRH_HIP(hipMemsetAsync(t->count, 0, 8 * (size_t)(max_edits + 1), st));
+    const int64_t npairs = ceil_div(ceil_div(t->rows, 32), 2);
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(npairs, kTextWaves), (int64_t)current_device_cus() * 8);
+    if (len <= 32) hipLaunchKernelGGL(k_text_fuzzy<uint32_t>, dim3(blocks), dim3(kTextWaves * 64), 0, st, a);
+    else hipLaunchKernelGGL(k_text_fuzzy<unsigned long long>, dim3(blocks), dim3(kTextWaves * 64), 0, st, a);
+    CRH_HIP(hipGetLastError());
+    if (out_counts_host) {
+        unsigned long long c[CRH_FUZZY_MAX_EDITS + 1] = {0ull, 0ull, 0ull, 0ull};
+        CRH_HIP(hipMemcpyAsync(c, t->count, 8 * (size_t)(max_edits + 1), hipMemcpyDeviceToHost, st));
+        CRH_HIP(hipStreamSynchronize(st));
+        for (int d = 0; d <= max_edits; ++d) out_counts_host[d] = (int64_t)c[d];
     }
     return CRH_OK;
 }

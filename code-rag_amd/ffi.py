@@ -34,6 +34,7 @@ ABI_VERSION = 4        # CRH_ABI_VERSION of include/coderag_hip.h
 LEX_MAX_QUERY_TERMS = 32   # CRH_LEX_MAX_QUERY_TERMS: distinct term ids of one crh_lex_search query
 TEXT_MAX_PATTERNS, TEXT_MAX_PATTERN_BYTES = 8, 64   # CRH_TEXT_MAX_PATTERNS / CRH_TEXT_MAX_PATTERN_BYTES of one crh_text_match
 REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 256, 32768   # CRH_REGEX_MAX_STATES / CRH_REGEX_MAX_TABLE_BYTES of one crh_text_regex
+FUZZY_MAX_EDITS = 3    # CRH_FUZZY_MAX_EDITS: byte edits one crh_text_fuzzy allows at most
 TEXT_ALL, TEXT_ANY = 0, 1   # CRH_TEXT_ALL / CRH_TEXT_ANY
 FACET_LDS_BINS = 8192       # CRH_FACET_LDS_BINS: up to this many bins crh_index_facet counts in LDS, above it by runs of equal codes
 FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
@@ -61,6 +62,7 @@ EXPORTS = (
     "crh_index_row_mask", "crh_lex_create", "crh_lex_destroy", "crh_lex_clear", "crh_lex_count", "crh_lex_append", "crh_lex_stats",
     "crh_lex_search",
     "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match", "crh_text_regex",
+    "crh_text_fuzzy",
     "crh_index_facet", "crh_search_range_facet", "crh_facet_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
@@ -226,6 +228,7 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_text_append.argtypes = [vp, i64, vp, vp]
     L.crh_text_match.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, C.POINTER(i64), vp]
     L.crh_text_regex.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(i64), vp]
+    L.crh_text_fuzzy.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.crh_index_facet.argtypes = [vp, i32, C.POINTER(Condition), i32, i32, vp, vp, vp]
     L.crh_search_range_facet.argtypes = [vp, i32, vp, i32, vp, C.POINTER(Condition), i32, i32, i32, vp, vp, vp]
     L.crh_facet_select.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
@@ -1130,6 +1133,7 @@ class Text:
     against literal byte patterns on the device."""
     match_calls = 0       # crh_text_match calls issued by all handles (tests count the greps of a job)
     regex_calls = 0       # crh_text_regex calls issued by all handles
+    fuzzy_calls = 0       # crh_text_fuzzy calls issued by all handles
 
     def __init__(self, capacity_rows: int = 0, capacity_bytes: int = 0, device: int = 0):
         self.device = device
@@ -1217,6 +1221,34 @@ class Text:
         check(lib().crh_text_regex(self._handle(), n_states, n_classes, class_of.ctypes.data, int(dfa.end_class), trans.ctypes.data if trans.size else None,
                                    int(dfa.accept), _ptr(mask), _ptr(out), C.byref(c) if count else None, stream))
         return out, (int(c.value) if count else None)
+
+    def fuzzy(self, pattern, edits: int, fold_case: bool = False, mask=None, out=None, count: bool = True, stream: int = 0):
+        """Which rows hold the byte ``pattern`` within ``edits`` edits (``crh_text_fuzzy``): a row's distance is
+        the least Levenshtein distance between the pattern and any substring of the row, counted in BYTES (insertion, deletion
+        and substitution of one byte cost 1 each), and level ``d`` of the result holds the rows whose distance is at most
+        ``d``.  ``fold_case`` folds ASCII letters only.  ``mask`` and ``stream`` as in :meth:`match`.  Returns ``(levels int32
+        device tensor [edits + 1, ceil(rows / 32)], per-level counts as a list or None)``: the levels are nested, the last one
+        is the filter's bitmap; with ``count`` the call waits on ``stream``.  It is the library that refuses a length outside
+        1..64, ``edits`` outside 0..3 and a pattern not longer than ``edits``."""
+        import torch
+        data = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        edits = int(edits)
+        words = (self.count()[0] + 31) // 32
+        levels = edits + 1 if 0 <= edits <= FUZZY_MAX_EDITS else 1           # (an edits the library refuses allocates one level)
+        if mask is not None:
+            _typed(mask, "int32", "mask")
+            if not _is_dev(mask) or int(mask.numel()) < words:
+                raise NativeError(E_INVALID, "mask must be a device tensor of one word per 32-row tile")
+        if out is None:
+            out = torch.empty((levels, words), dtype=torch.int32, device=f"cuda:{self.device}")
+        _typed(out, "int32", "out")
+        if not _is_dev(out) or tuple(out.shape) != (levels, words) or not out.is_contiguous():
+            raise NativeError(E_INVALID, f"out must be a contiguous device tensor of {levels} levels x {words} words")
+        c = (C.c_int64 * (FUZZY_MAX_EDITS + 1))()
+        Text.fuzzy_calls += 1
+        check(lib().crh_text_fuzzy(self._handle(), data.ctypes.data if data.size else None, int(data.size), edits, int(bool(fold_case)),
+                                   _ptr(mask), _ptr(out), c if count else None, stream))
+        return out, ([int(v) for v in c[:levels]] if count else None)
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

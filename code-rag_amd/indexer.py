@@ -381,7 +381,8 @@ class VectorSearcher:
                           project_name: str | list[str] | None = None, *, diversity: float | None = None,
                           candidates: int | None = None, max_per_file: int | None = None,
                           min_score: float | None = None, max_overlap: float | None = None, mode: str = "semantic",
-                          contains: str | list[str] | None = None, matches: str | None = None) -> list[CodeSearchResult]:
+                          contains: str | list[str] | None = None, matches: str | None = None,
+                          fuzzy: str | None = None, edits: int | None = None) -> list[CodeSearchResult]:
         """``mode`` (not in the reference): "semantic" (the default: everything below), "lexical" (the store's exact keyword
         search of ``query``, nothing embedded) or "hybrid" (both, fused by reciprocal rank); the keyword modes take the
         filters and ``candidates`` only.
@@ -392,10 +393,11 @@ class VectorSearcher:
         than ``limit``; ``max_overlap`` likewise: no result repeats more than that share of a better result's lines (the store's
         ``max_overlap``); ``contains`` likewise: a literal string, or a list of them, every result's ``content`` must hold (the
         store's text condition, matched exactly on the device); ``matches`` likewise: a regular expression (Python's ``re`` on
-        bytes, ``re.MULTILINE``) that must be found in every result's ``content``; beside ``contains`` both must hold."""
+        bytes, ``re.MULTILINE``) that must be found in every result's ``content``; beside ``contains`` both must hold;
+        ``fuzzy`` / ``edits`` likewise: a string every result's ``content`` must hold within so many byte edits (0..3)."""
         filters = _only_set(language=language, entity_type=entity_type, project_name=project_name)
-        if contains is not None or matches is not None:
-            text = {k: v for k, v in (("contains", contains), ("matches", matches)) if v is not None}
+        if contains is not None or matches is not None or fuzzy is not None or edits is not None:
+            text = {k: v for k, v in (("contains", contains), ("matches", matches), ("fuzzy", fuzzy), ("edits", edits)) if v is not None}
             filters = dict(filters or {}, content=text)
         hits = await self._run(CollectionName.CODE_CHUNKS.value, query, limit, filters,
                                "code_search", "Code", diversity, candidates, max_per_file, min_score, max_overlap, **_mode_given(mode))

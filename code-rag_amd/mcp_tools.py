@@ -33,7 +33,7 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None,
                               min_score: float | None = None, max_overlap: float | None = None, mode: str | None = None,
                               contains: str | list[str] | None = None, contains_case: bool | None = None,
-                              matches: str | None = None) -> ToolResult:
+                              matches: str | None = None, fuzzy: str | None = None, edits: int | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -46,8 +46,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                 return ToolResult(success=True, data=data, message=f"Found {len(data)} matches like {len(like_ids)} example(s).")
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
                                        ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score), ("max_overlap", max_overlap), ("mode", mode),
-                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches else None),
-                                       ("matches", matches or None)) if v is not None}   # (only when asked for)
+                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches or fuzzy else None),
+                                       ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -95,12 +95,19 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             "contains": {"type": "string", "description": "A literal string (or a list of up to 8) every result's code must contain, "
                                                           "punctuation included: 'retry_after=', '.unwrap()', '#include <hip/'",
                          "required": False},
-            "contains_case": {"type": "boolean", "description": "With contains / matches: false ignores the case of ASCII letters (default: true)",
+            "contains_case": {"type": "boolean", "description": "With contains / matches / fuzzy: false ignores the case of ASCII letters (default: true)",
                               "required": False},
             "matches": {"type": "string", "description": "A regular expression (Python re syntax, ^ and $ at every line; no "
                                                          "back-references or look-around) that must be found in every result's code: "
                                                          "'def \\w+_retry\\(', '^\\s*#include\\s*<hip/', '[A-Z][a-z]+Error\\b'",
                         "required": False},
+            "fuzzy": {"type": "string", "description": "An identifier or string (up to 64 bytes) every result's code must contain up "
+                                                       "to a few typos: 'parse_retry_aftr' finds parse_retry_after, 'HTTPServerEror' "
+                                                       "finds HTTPServerError; use it when the exact spelling is not known",
+                      "required": False},
+            "edits": {"type": "integer", "description": "With fuzzy: how many single-character insertions, deletions or substitutions "
+                                                        "are allowed, 0..3 (default: 1 for up to 5 characters, 2 above; a swapped pair "
+                                                        "of characters counts as 2)", "required": False},
         },
     }
 
@@ -111,13 +118,14 @@ def create_code_facets_tool(vector_searcher_factory: Callable[[], Any]) -> dict[
     (``VectorSearcher.facet_code``)."""
     async def code_facets(key: str = "file_path", query: str | None = None, min_score: float | None = None, limit: int = 10,
                           language: str | None = None, entity_type: str | None = None, contains: str | list[str] | None = None,
-                          contains_case: bool | None = None, matches: str | None = None) -> ToolResult:
+                          contains_case: bool | None = None, matches: str | None = None, fuzzy: str | None = None,
+                          edits: int | None = None) -> ToolResult:
         logger.info(f"[Tool:CodeFacets] Key: '{key}' query: {query!r}")
         try:
             searcher = vector_searcher_factory()
             extra = {k: v for k, v in (("query", query or None), ("min_score", min_score), ("language", language), ("entity_type", entity_type),
-                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches else None),
-                                       ("matches", matches or None)) if v is not None}   # (only when asked for)
+                                       ("contains", contains or None), ("contains_case", contains_case if contains or matches or fuzzy else None),
+                                       ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None)) if v is not None}   # (only when asked for)
             res = await searcher.facet_code(key=key, limit=limit, **extra)
             shown, values = len(res["hits"]), res["values"]
             message = f"{res['total']} chunks carry {values} distinct {key} value(s)" + (f"; the {shown} most frequent are listed." if shown < values else ".")
@@ -142,9 +150,13 @@ def create_code_facets_tool(vector_searcher_factory: Callable[[], Any]) -> dict[
             "entity_type": {"type": "string", "description": "Count only chunks of this type: function, class, method", "required": False},
             "contains": {"type": "string", "description": "Count only chunks whose code contains this literal string (or every string "
                                                           "of a list of up to 8): 'TODO(', '.unwrap()'", "required": False},
-            "contains_case": {"type": "boolean", "description": "With contains / matches: false ignores the case of ASCII letters (default: true)",
+            "contains_case": {"type": "boolean", "description": "With contains / matches / fuzzy: false ignores the case of ASCII letters (default: true)",
                               "required": False},
             "matches": {"type": "string", "description": "Count only chunks in whose code this regular expression (Python re syntax) is found",
                         "required": False},
+            "fuzzy": {"type": "string", "description": "Count only chunks whose code contains this string up to a few typos "
+                                                       "('parse_retry_aftr' finds parse_retry_after)", "required": False},
+            "edits": {"type": "integer", "description": "With fuzzy: the insertions, deletions or substitutions allowed, 0..3 "
+                                                        "(default: 1 for up to 5 characters, 2 above)", "required": False},
         },
     }

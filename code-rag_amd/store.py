@@ -66,8 +66,11 @@ TEXT_KEYS: dict[str, tuple[str, ...]] = {
     CollectionName.CODE_CHUNKS.value: ("content",),
     CollectionName.SUMMARIES.value: ("summary",),
 }
-_TEXT_WORDS = ("contains", "matches", "any", "case")     # "matches": a regular expression
+# "matches": a regular expression; "fuzzy" / "edits": a string within so many byte edits
+_TEXT_WORDS = ("contains", "matches", "fuzzy", "edits", "any", "case")
+_TEXT_KINDS = ("contains", "matches", "fuzzy")            # a text filter carries at least one of these
 _ASCII_LOWER = bytes(c + 32 if 65 <= c <= 90 else c for c in range(256))   # the device's folding: ASCII letters only
+_FUZZY_MIN_PIECE = 3     # the pigeonhole prefilter of an approximate match runs when its shortest piece has at least so many bytes
 _TEXT_CACHE = 8          # match results a collection keeps (a repeated query under the same text filter does not grep again)
 
 
@@ -106,9 +109,9 @@ def range_bounds(key: str, spec) -> tuple[int, int]:
 
 
 def _is_text(value) -> bool:
-    """A filter value that asks for a text match: a mapping with the key ``"contains"`` (substrings) or ``"matches"`` (a
-    regular expression)."""
-    return isinstance(value, Mapping) and ("contains" in value or "matches" in value)
+    """A filter value that asks for a text match: a mapping with the key ``"contains"`` (substrings), ``"matches"`` (a
+    regular expression) or ``"fuzzy"`` (a string within a bounded number of edits)."""
+    return isinstance(value, Mapping) and any(w in value for w in _TEXT_KINDS)
 
 
 def _is_range(value) -> bool:
@@ -118,24 +121,37 @@ def _is_range(value) -> bool:
 class TextSpec(NamedTuple):
     """A ``{"contains": ..., "matches": ...}`` filter value, checked: the distinct patterns as sorted UTF-8 bytes (none when only
     ``matches`` is given), any-of / all-of, whether case matters (``case=False`` folds ASCII letters only, for both), and the
-    regular expression as UTF-8 bytes (None: none).  Equal specs select the same rows."""
+    regular expression as UTF-8 bytes (None: none); the approximate pattern as UTF-8 bytes (None: none; folded like the
+    patterns) and the byte edits it allows.  Equal specs select the same rows."""
     patterns: tuple
     any_of: bool
     case: bool
     regex: bytes | None = None
+    fuzzy: bytes | None = None
+    edits: int = 0
+
+
+def default_edits(nbytes: int) -> int:
+    """The edits a ``fuzzy`` pattern of ``nbytes`` bytes allows when none are given: 1 up to 5 bytes, 2 above -- and 0 for a
+    single byte, since a pattern must be longer than its edits (one that is not matches every row)."""
+    return min(1 if nbytes <= 5 else 2, max(nbytes - 1, 0))
 
 
 def text_spec(key: str, spec) -> TextSpec:
-    """``{"contains": str | [str, ...], "matches": str, "any": bool = False, "case": bool = True}`` -- at least one of
-    ``contains`` and ``matches``; with both, both must hold -- as a :class:`TextSpec`.  ``any`` concerns ``contains`` only,
-    ``case`` both.  ``ValueError`` naming ``key`` for an unknown word, a pattern that is no ``str``, an empty pattern, one over
-    64 bytes of UTF-8, no pattern at all or more than 8, flags that are not bools, and a regular expression that is no ``str``
-    or that ``regex_dfa.compile_regex`` refuses (the construct is named)."""
+    """``{"contains": str | [str, ...], "matches": str, "fuzzy": str, "edits": int, "any": bool = False, "case": bool = True}``
+    -- at least one of ``contains``, ``matches`` and ``fuzzy``; all that are given must hold -- as a :class:`TextSpec`.  ``any``
+    concerns ``contains`` only, ``case`` all of them.  ``fuzzy`` keeps the rows in which some substring is
+    within ``edits`` insertions, deletions or substitutions of one BYTE of the string (0..3; :func:`default_edits` when left
+    out); the string has 1..64 bytes of UTF-8 and more bytes than ``edits``.  ``ValueError`` naming ``key`` for an unknown
+    word, a pattern that is no ``str``, an empty pattern, one over 64 bytes of UTF-8, no pattern at all or more than 8, flags
+    that are not bools, a regular expression that is no ``str`` or that ``regex_dfa.compile_regex`` refuses (the construct is
+    named), ``edits`` without ``fuzzy``, ``edits`` that is no int or outside 0..3, and a ``fuzzy`` not longer than its edits."""
     unknown = [w for w in spec if w not in _TEXT_WORDS]
     if unknown:
         raise ValueError(f"text filter on {key!r}: unknown word {unknown[0]!r} (use {', '.join(_TEXT_WORDS)})")
-    if "contains" not in spec and "matches" not in spec:
-        raise ValueError(f"text filter on {key!r}: needs 'contains' (strings), 'matches' (a regular expression) or both")
+    if not any(w in spec for w in _TEXT_KINDS):
+        raise ValueError(f"text filter on {key!r}: needs 'contains' (strings), 'matches' (a regular expression), 'fuzzy' (a string "
+                         f"within 'edits' edits) or several of them")
     pats = spec.get("contains", [])
     pats = [pats] if isinstance(pats, str) else list(pats) if isinstance(pats, (list, tuple)) else None
     if pats is None or not all(isinstance(p, str) for p in pats):
@@ -160,11 +176,67 @@ def text_spec(key: str, spec) -> TextSpec:
             raise ValueError(f"text filter on {key!r}: 'matches' takes a str (a regular expression), not {spec['matches']!r}")
         regex = spec["matches"].encode("utf-8", "surrogatepass")
         regex_dfa.compile_regex(regex, flags[1], key)              # (refuses with the key named; the DFA stays in its cache)
-    return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1], regex)
+    if "fuzzy" not in spec:
+        if "edits" in spec:
+            raise ValueError(f"text filter on {key!r}: 'edits' stands beside 'fuzzy' only")
+        return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1], regex)
+    if not isinstance(spec["fuzzy"], str):
+        raise ValueError(f"text filter on {key!r}: 'fuzzy' takes a str, not {spec['fuzzy']!r}")
+    fuzzy = spec["fuzzy"].encode("utf-8", "surrogatepass")
+    if not 1 <= len(fuzzy) <= ffi.TEXT_MAX_PATTERN_BYTES:
+        raise ValueError(f"text filter on {key!r}: the 'fuzzy' pattern {spec['fuzzy'][:80]!r} has {len(fuzzy)} bytes of UTF-8 (1..{ffi.TEXT_MAX_PATTERN_BYTES})")
+    edits = spec.get("edits")
+    if edits is None:
+        edits = default_edits(len(fuzzy))
+    if isinstance(edits, (bool, np.bool_)) or not isinstance(edits, (int, np.integer)) or not 0 <= edits <= ffi.FUZZY_MAX_EDITS:
+        raise ValueError(f"text filter on {key!r}: edits={edits!r} is not an int in 0..{ffi.FUZZY_MAX_EDITS}")
+    if len(fuzzy) <= edits:
+        raise ValueError(f"text filter on {key!r}: the 'fuzzy' pattern {spec['fuzzy']!r} has {len(fuzzy)} bytes, not more than "
+                         f"edits={int(edits)} (every text would match)")
+    return TextSpec(tuple(sorted(set(raw))), flags[0], flags[1], regex, fuzzy if flags[1] else fuzzy.translate(_ASCII_LOWER), int(edits))
+
+
+def fuzzy_distance(pattern: bytes, text: bytes) -> tuple[int, int]:
+    """``(distance, last)`` of an approximate match by its definition, on the host: the least Levenshtein
+    distance between ``pattern`` and any substring of ``text`` -- Sellers' table, ``D[0][j] = 0``, ``D[i][0] = i``, the minimum of
+    its last row -- and the index of the last byte of the first substring that reaches it (-1: the empty substring at the text's
+    start does, which takes ``len(pattern)`` edits).  Neither side is folded here.  For the hits a text search returns, not
+    for filtering: that is the device's work."""
+    m = len(pattern)
+    pat = np.frombuffer(pattern, np.uint8)
+    col = np.arange(m + 1, dtype=np.int64)
+    best, last = m, -1
+    steps = np.arange(m + 1, dtype=np.int64)
+    for j, c in enumerate(text):
+        diag = col[:-1] + (pat != c)
+        new = np.empty_like(col)
+        new[0] = 0
+        new[1:] = np.minimum(diag, col[1:] + 1)
+        new = np.minimum.accumulate(new - steps) + steps                 # (the deletions down the column: new[i] = min(new[i], new[i-1] + 1))
+        col = new
+        if col[m] < best:
+            best, last = int(col[m]), j
+            if best == 0:
+                break
+    return best, last
+
+
+def fuzzy_pieces(pattern: bytes, edits: int) -> tuple:
+    """The exact prefilter of an approximate match (pigeonhole): ``pattern`` cut into ``edits + 1`` contiguous
+    pieces of nearly equal length.  ``edits`` edits touch at most ``edits`` of them, so every occurrence within ``edits`` edits
+    holds one piece verbatim, and only the rows that hold ANY piece need the walk.  ``()`` when the cut cannot help: no edits
+    (the walk is then the grep), or a shortest piece under ``_FUZZY_MIN_PIECE`` bytes -- a piece of one or two bytes occurs in
+    almost every chunk of code, so its grep costs a pass and removes next to nothing."""
+    n = edits + 1
+    if edits == 0 or len(pattern) // n < _FUZZY_MIN_PIECE:
+        return ()
+    cuts = [len(pattern) * i // n for i in range(n + 1)]
+    return tuple(sorted({pattern[a:b] for a, b in zip(cuts, cuts[1:])}))
 
 
 def has_text_condition(filters, must_not=None) -> bool:
-    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``{"contains": ...}`` / ``{"matches": ...}`` value?"""
+    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``{"contains": ...}`` / ``{"matches": ...}`` /
+    ``{"fuzzy": ...}`` value?"""
     for f in (filters, must_not):
         for d in (f if isinstance(f, (list, tuple)) else [f]):
             if isinstance(d, Mapping) and any(_is_text(v) for v in d.values()):
@@ -201,6 +273,7 @@ class _Collection:
     indexing run, embeddings/indexer.py:61-64)."""
 
     regex_prefilter = True     # a regex condition first greps for the strings every match holds (tests switch it off to compare)
+    fuzzy_prefilter = True     # an approximate condition first greps for the pieces one of which every match holds (likewise)
 
     def __init__(self, name: str, dim: int, dtype: int, capacity: int, device: int, nshards: int = 1, backend: str = "local",
                  group=None, merge_fn=None, compact_dead_fraction: float = 0.25, compact_min_dead: int = 1024):
@@ -229,7 +302,7 @@ class _Collection:
         # substring side, DERIVED the same way: text key -> shard -> ffi.Text of its rows, built from the payload
         # tables on the first text filter, extended lazily, dropped by compact() and load(); never part of a snapshot
         self._text: dict[str, dict[int, Any]] = {}
-        self._text_cache: dict[tuple, tuple] = {}    # (key, spec, other conditions, collection state) -> (tag, words per index, count)
+        self._text_cache: dict[tuple, tuple] = {}    # (key, spec, other conditions, collection state) -> (tag, words per index, count, the levels of an approximate match or None)
         self.text_match_calls = 0            # text conditions resolved by a grep so far (repeated filters reuse the words)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
@@ -394,8 +467,8 @@ class _Collection:
                                  f"(text keys: {', '.join(self.text_keys) or 'none'})")
             return False
         if not _is_text(value):
-            raise ValueError(f"payload key {key!r} holds text: filter it with a mapping {{'contains': str or list of str}} or "
-                             f"{{'matches': regular expression}}, not {value!r}")
+            raise ValueError(f"payload key {key!r} holds text: filter it with a mapping {{'contains': str or list of str}}, "
+                             f"{{'matches': regular expression}} or {{'fuzzy': str, 'edits': 0..{ffi.FUZZY_MAX_EDITS}}}, not {value!r}")
         texts.append((key, text_spec(key, value), negate))
         return True
 
@@ -433,19 +506,49 @@ class _Collection:
         costs no read of its text -- and the result as ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  With a regular
         expression the literal match runs for ``contains`` if given, otherwise for the strings every match of
         the expression holds (``regex_prefilter``; none: no literal pass), and ``crh_text_regex`` walks the rows that are left.
-        The last few results are kept, keyed by what they were computed from; every result lives in buffers of its own under
-        a tag of its own."""
+        With an approximate pattern ``crh_text_fuzzy`` goes last, under the words of the passes before it and
+        -- ``fuzzy_prefilter``, when :func:`fuzzy_pieces` cuts any -- under a grep for the pieces one of which every match
+        holds; its last level is the condition, and all its levels stay with the result (:meth:`_text_levels`).  The last few
+        results are kept, keyed by what they were computed from; every result lives in buffers of its own under a tag of its
+        own."""
+        hit = self._text_result(key, spec, others)
+        return ffi.RowWords(hit[0], hit[1], negate)
+
+    def _text_levels(self, key: str, spec: TextSpec, others: list) -> tuple[list, list]:
+        """The levels of an approximate condition as ``([RowWords of level 0 .. edits], [rows at distance 0 .. edits])``: level
+        ``d`` holds the rows (under ``others`` and the spec's other words) whose distance is at most ``d``; from the result
+        :meth:`_text_condition` computed or kept, so it costs no second walk."""
+        hit = self._text_result(key, spec, others)
+        tags, levels, counts = hit[3]
+        return ([ffi.RowWords(tags[d], {i: lv[d] for i, lv in levels.items()}) for d in range(spec.edits + 1)],
+                [counts[0]] + [counts[d] - counts[d - 1] for d in range(1, spec.edits + 1)])
+
+    def _text_result(self, key: str, spec: TextSpec, others: list) -> tuple:
+        """``(tag, {id(index): words}, rows, fuzzy)`` of a text condition, computed or taken from the cache; ``fuzzy`` is None
+        or ``(tags, {id(index): levels [edits + 1, words]}, cumulative counts)``, the last level being ``words`` under ``tag``."""
         arenas = self._text_ready(key)
         state = (tuple(self.shards.rows), self.shards.count()[1], self.compactions)
         ck = (key, spec, ffi.filter_key(others), state)
         hit = self._text_cache.pop(ck, None)
         if hit is None:
-            words, total = {}, 0
+            words, total, levels, counts = {}, 0, {}, [0] * (spec.edits + 1)
             stream = self.shards._stream()
             for s in self.shards.owned:
                 ix = self.shards.index[s]
                 mask = ix.row_mask(others, stream=stream)
-                if spec.regex is None:
+                if spec.fuzzy is not None:
+                    if spec.patterns:
+                        mask, _ = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, count=False, stream=stream)
+                    if spec.regex is not None:
+                        mask, _ = arenas[s].regex(regex_dfa.compile_regex(spec.regex, spec.case, key), mask=mask, count=False, stream=stream)
+                    pieces = fuzzy_pieces(spec.fuzzy, spec.edits) if self.fuzzy_prefilter else ()
+                    if pieces:
+                        mask, _ = arenas[s].match(pieces, fold_case=not spec.case, any_of=True, mask=mask, count=False, stream=stream)
+                    lv, cs = arenas[s].fuzzy(spec.fuzzy, spec.edits, fold_case=not spec.case, mask=mask, stream=stream)
+                    levels[id(ix)] = lv
+                    counts = [a + b for a, b in zip(counts, cs)]
+                    w, n = lv[spec.edits], cs[spec.edits]
+                elif spec.regex is None:
                     w, n = arenas[s].match(spec.patterns, fold_case=not spec.case, any_of=spec.any_of, mask=mask, stream=stream)
                 else:
                     dfa = regex_dfa.compile_regex(spec.regex, spec.case, key)
@@ -457,11 +560,15 @@ class _Collection:
                 words[id(ix)] = w
                 total += n
             self.text_match_calls += 1
-            hit = (ffi.next_words_tag(), words, total)
+            fuzzy = None
+            if spec.fuzzy is not None:                                    # (the last level IS the condition: one tag for both)
+                tags = [ffi.next_words_tag() for _ in range(spec.edits + 1)]
+                fuzzy = (tags, levels, counts)
+            hit = (fuzzy[0][-1] if fuzzy else ffi.next_words_tag(), words, total, fuzzy)
             while len(self._text_cache) >= _TEXT_CACHE:
                 self._text_cache.pop(next(iter(self._text_cache)))       # (the least recently used: hits are re-inserted below)
         self._text_cache[ck] = hit
-        return ffi.RowWords(hit[0], hit[1], negate)
+        return hit
 
     def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None, must_not: dict[str, Any] | None = None) -> np.ndarray:
         """Alive slots matching every condition, in insertion order -- resolved on the device from the code columns."""
@@ -482,7 +589,7 @@ class _Collection:
         """client.py:159-169: every point matching the AND of the conditions.  An empty filter matches every point, as
         ``Filter(must=[])`` does."""
         if has_text_condition(filters, must_not):
-            raise ValueError("delete takes no text condition ({'contains': ...} / {'matches': ...}): fetch the matching points (search_text) and delete by id or file")
+            raise ValueError("delete takes no text condition ({'contains': ...} / {'matches': ...} / {'fuzzy': ...}): fetch the matching points (search_text) and delete by id or file")
         dfilt = self.device_filters(filters, must_not)
         if dfilt is None:
             return 0
@@ -1489,7 +1596,7 @@ class HipVectorStore:
         per = _per_query(filters, must_not, nq)
         if per is not None:
             if has_text_condition(filters, must_not):
-                raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...} / {'matches': ...}): a text condition is "
+                raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...} / {'matches': ...} / {'fuzzy': ...}): a text condition is "
                                  "one grep for the whole batch -- pass ONE filter dict")
             if diversity is not None or group is not None:
                 raise ValueError("per-query filters cannot be combined with diversity, group_by or max_overlap (a follow-up: the "
@@ -1682,7 +1789,7 @@ class HipVectorStore:
         """Qdrant's ``client.facet(collection_name, key, facet_filter, limit, exact=True)``: the values of payload key ``key``
         among the points that COUNT, with how many points carry each -- "how many chunks per file hold ``TODO(``", "which
         languages make up this project".  A point counts iff it is alive and passes ``filters`` / ``must_not`` (everything
-        :meth:`search` takes, ``{"content": {"contains": ...}}`` / ``{"matches": ...}`` included); with ``query_vector`` and
+        :meth:`search` takes, ``{"content": {"contains": ...}}`` / ``{"matches": ...}`` / ``{"fuzzy": ...}`` included); with ``query_vector`` and
         ``score_threshold`` -- both or neither -- its score must also be ``>= score_threshold``, exactly :meth:`count_similar`'s
         rule: "in which files does this concept live".  Returns ``{"hits": [{"value", "count"}, ...], "values", "total",
         "missing"}``: ``hits`` are the ``limit`` (1..1024) most frequent values, count descending, ties to the value STORED
@@ -1837,7 +1944,10 @@ class HipVectorStore:
         ``MatchText`` on a field without a full-text index), combinable with everything a filter combines with
         except per-query filter lists.  1..8 patterns of 1..64 bytes of UTF-8 each.  ``{"matches": regular expression}`` -- alone
         or beside ``contains``, then both must hold -- keeps the points in whose text Python's ``re`` on bytes (``re.MULTILINE``;
-        ``case=False``: ``re.IGNORECASE``) finds the expression, matched on the device by a DFA."""
+        ``case=False``: ``re.IGNORECASE``) finds the expression, matched on the device by a DFA.
+        ``{"fuzzy": string, "edits": 0..3}`` -- alone or beside the other two, then all must hold -- keeps the points whose text
+        holds the string within that many insertions, deletions or substitutions of one BYTE (``edits`` left out: 1 up to 5
+        bytes, 2 above), matched on the device by a bit-parallel edit-distance walk."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -2131,9 +2241,11 @@ class HipVectorStore:
             raise VectorStoreError(f"Failed to count in {collection}", cause=e)
 
     # ------------------------------------------------------------------ literal text search
-    def _search_text_sync(self, collection: str, contains, limit: int, filters, must_not, any_of: bool, case: bool, matches=None) -> dict[str, Any]:
+    def _search_text_sync(self, collection: str, contains, limit: int, filters, must_not, any_of: bool, case: bool, matches=None,
+                          fuzzy=None, edits=None) -> dict[str, Any]:
         """The text condition joined to the filter, the exact count and the first ``limit`` matching points in insertion order
-        (``crh_index_match_rows_cond``), with their ``match_line``; ``limit`` 0 asks for the count alone."""
+        (``crh_index_match_rows_cond``), with their ``match_line``; ``limit`` 0 asks for the count alone.  With ``fuzzy`` the
+        points come by ``(distance, insertion order)``: level by level, the rows of level ``d`` that are not of level ``d - 1``."""
         col = self._col(collection)
         if not col.text_keys:
             raise ValueError(f"collection {col.name!r} has no text key to search")
@@ -2141,14 +2253,21 @@ class HipVectorStore:
         if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
             raise ValueError("a text search takes one filter, not per-query filters")
         if key in (filters or {}):
-            raise ValueError(f"the filter already holds a condition on {key!r}: give the strings in `contains`, the expression in `matches`")
-        if contains is None and matches is None:
-            raise ValueError("a text search needs `contains` (strings), `matches` (a regular expression) or both")
+            raise ValueError(f"the filter already holds a condition on {key!r}: give the strings in `contains`, the expression in `matches`, "
+                             f"the approximate string in `fuzzy`")
+        if contains is None and matches is None and fuzzy is None:
+            raise ValueError("a text search needs `contains` (strings), `matches` (a regular expression), `fuzzy` (a string within `edits` edits) or several of them")
         spec = {"any": any_of, "case": case}
         if contains is not None:
             spec["contains"] = contains
         if matches is not None:
             spec["matches"] = matches
+        if fuzzy is not None:
+            spec["fuzzy"] = fuzzy
+        if edits is not None:
+            spec["edits"] = edits
+        if fuzzy is not None:
+            return self._search_fuzzy_sync(col, key, spec, limit, filters, must_not)
         dfilt = col.device_filters({**(filters or {}), key: spec}, must_not)
         if dfilt is None:
             return {"hits": [], "count": 0}
@@ -2172,9 +2291,49 @@ class HipVectorStore:
             hit["match_line"] = start + raw.count(b"\n", 0, min(where)) if first else None
         return {"hits": hits, "count": count}
 
+    def _search_fuzzy_sync(self, col: "_Collection", key: str, spec: dict, limit: int, filters, must_not) -> dict[str, Any]:
+        """:meth:`_search_text_sync` with an approximate pattern: one resolution of the filter (which walks the text once, every
+        level at a time), then per level ``d`` the first rows of level ``d`` (``CRH_COND_WORDS``) that are not of level ``d - 1``
+        (``CRH_COND_NOT_WORDS``), until ``limit`` points are fetched.  The levels hold every condition that is no text condition
+        already (the walk ran under their words), so the two row bitmaps are the whole filter of a fetch -- unless ``must_not``
+        carries a text condition of its own: text conditions are resolved beside each other, never under each other, so its row
+        bitmap joins every fetch, and the rows at each distance are then counted under it (``count_matching``) instead of taken
+        from the walk.  ``distance`` and ``match_line`` of the returned points are computed on the host, by the definition."""
+        checked = text_spec(key, spec)
+        none = {"hits": [], "count": 0, "counts_by_distance": [0] * (checked.edits + 1)}
+        dfilt = col.device_filters({**(filters or {}), key: spec}, must_not)
+        if dfilt is None:
+            return none
+        levels, by_distance = col._text_levels(key, checked, [c for c in dfilt if not isinstance(c, ffi.RowWords)])
+        # the other text conditions (must_not's): every row bitmap of the filter but the fuzzy condition's own, which is the last level
+        beside = [c for c in dfilt if isinstance(c, ffi.RowWords) and (c.negate or c.tag != levels[-1].tag)]
+
+        def exactly(d: int) -> list:
+            return [levels[d]] + ([ffi.RowWords(levels[d - 1].tag, levels[d - 1].words, True)] if d else []) + beside
+
+        if beside:
+            by_distance = [int(col.shards.count_matching(exactly(d))) for d in range(len(levels))]
+        out = {"hits": [], "count": int(sum(by_distance)), "counts_by_distance": [int(c) for c in by_distance]}
+        for d in range(len(levels)):
+            want = int(limit) - len(out["hits"])
+            if want <= 0:
+                break
+            if by_distance[d] == 0:
+                continue
+            sh, lo = col.shards.match_rows(exactly(d), want)
+            slots = np.sort(col.slots_of(sh, lo))[:want]
+            for hit in col.hits(slots, [0.0] * len(slots)):
+                text, start = hit["payload"].get(key), hit["payload"].get("start_line")
+                raw = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else b""
+                dist, last = fuzzy_distance(checked.fuzzy, raw if checked.case else raw.translate(_ASCII_LOWER))
+                hit["distance"] = dist
+                hit["match_line"] = start + raw.count(b"\n", 0, max(last, 0)) if type(start) is int else None
+                out["hits"].append(hit)
+        return out
+
     async def search_text(self, collection: str, contains=None, limit: int = 10, filters: dict[str, Any] | None = None,
                           must_not: dict[str, Any] | None = None, *, matches: str | None = None, any: bool = False,   # noqa: A002
-                          case: bool = True) -> dict[str, Any]:
+                          case: bool = True, fuzzy: str | None = None, edits: int | None = None) -> dict[str, Any]:
         """Literal text search -- grep over the stored chunks: the points whose text (``content`` of the code chunks, ``summary``
         of the summaries) holds the string ``contains``, or every string of a list (``any``: at least one), under ``filters`` /
         ``must_not`` as in :meth:`search`.  ``case=False`` folds ASCII letters only.  Returns ``{"hits": [...], "count": int}``:
@@ -2186,17 +2345,27 @@ class HipVectorStore:
         ``matches`` is a regular expression in the syntax of Python's ``re`` ON BYTES, with ``re.MULTILINE``:
         the points in whose text ``re.search`` finds it; beside ``contains`` both must hold (``any`` concerns the strings
         only, ``case`` both).  At least one of ``contains`` and ``matches`` is required.  ``match_line`` counts the newlines
-        before the earliest place where one of the strings occurs or the expression's first match starts."""
+        before the earliest place where one of the strings occurs or the expression's first match starts.
+
+        ``fuzzy`` is a string the text must hold within ``edits`` edits: some substring of the text is at most
+        ``edits`` insertions, deletions or substitutions of one BYTE away from it (a transposition is two; a multi-byte
+        character counts per byte; ``case=False`` folds ASCII letters on both sides).  ``edits`` is 0..3 and less than the
+        string's bytes; left out it is 1 for up to 5 bytes and 2 above.  Beside ``contains`` / ``matches`` all must hold.  The
+        hits then come ordered by ``(distance, insertion order)`` and carry ``distance`` -- the least edit distance between the
+        string and any substring of the text -- and ``match_line``: ``start_line`` plus the newlines before the LAST byte of the
+        first substring that reaches that distance.  The result also carries ``counts_by_distance``, the exact number of
+        matching points at each distance ``0 .. edits`` (``count`` is their sum)."""
         try:
-            return await self._run(self._search_text_sync, collection, contains, int(limit), filters, must_not, any, case, matches)
+            return await self._run(self._search_text_sync, collection, contains, int(limit), filters, must_not, any, case, matches, fuzzy, edits)
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 
     async def count_text(self, collection: str, contains=None, filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, *,
-                         matches: str | None = None, any: bool = False, case: bool = True) -> int:   # noqa: A002
+                         matches: str | None = None, any: bool = False, case: bool = True, fuzzy: str | None = None,   # noqa: A002
+                         edits: int | None = None) -> int:
         """How many points :meth:`search_text` matches: exact."""
         try:
-            return (await self._run(self._search_text_sync, collection, contains, 0, filters, must_not, any, case, matches))["count"]
+            return (await self._run(self._search_text_sync, collection, contains, 0, filters, must_not, any, case, matches, fuzzy, edits))["count"]
         except Exception as e:
             raise VectorStoreError(f"Failed to count in {collection}", cause=e)
 

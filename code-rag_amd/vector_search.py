@@ -102,15 +102,20 @@ def _mode_kwargs(mode: str) -> dict:
     return {} if mode == "semantic" else {"mode": mode}
 
 
-def _contains_filter(key: str, contains, contains_case: bool, matches: str | None = None) -> dict:
+def _contains_filter(key: str, contains, contains_case: bool, matches: str | None = None, fuzzy: str | None = None,
+                     edits: int | None = None) -> dict:
     """``contains`` (a str or a list of str: the literal strings a hit's text must ALL hold) and ``matches`` (a regular
     expression ``re.search`` must find in it) as the store's text condition on ``key`` -- ``{}`` without either: the call is
     then the one issued before, keyword for keyword."""
-    if contains is None and matches is None:
+    if contains is None and matches is None and fuzzy is None and edits is None:
         return {}
     spec = {} if contains is None else {"contains": contains}
     if matches is not None:
         spec["matches"] = matches
+    if fuzzy is not None:
+        spec["fuzzy"] = fuzzy
+    if edits is not None:
+        spec["edits"] = edits                                          # (alone: the store refuses it by name)
     if not contains_case:
         spec["case"] = False
     return {key: spec}
@@ -213,7 +218,8 @@ class VectorSearcher:
                           diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                           extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                           max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
-                          contains_case: bool = True, matches: str | None = None) -> list[dict]:
+                          contains_case: bool = True, matches: str | None = None,
+                          fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -238,11 +244,15 @@ class VectorSearcher:
         DESIGN.md 3.21), in every mode and beside every other argument; ``contains_case=False`` ignores the case of ASCII
         letters.  ``matches`` likewise: a regular expression in the syntax of Python's ``re`` on bytes, with ``re.MULTILINE``,
         that ``re.search`` must find in every result's ``content`` -- ``def \\w+_retry\\(`` -- (DESIGN.md 3.22); beside
-        ``contains`` both must hold, and ``contains_case`` governs both."""
+        ``contains`` both must hold, and ``contains_case`` governs both.  ``fuzzy`` likewise: a string every result's ``content``
+        must hold within ``edits`` BYTE insertions, deletions or substitutions (0..3; default 1 for up to 5 bytes, 2 above) --
+        ``parse_retry_aftr`` finds ``parse_retry_after`` -- matched exactly on the device; beside the other two
+        all must hold, and ``contains_case`` governs it too.  :meth:`search_summaries`, :meth:`find_similar_code`,
+        :meth:`facet_code` and :meth:`search_code_batch` take ``fuzzy`` / ``edits`` the same way."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
-        filters.update(_contains_filter("content", contains, contains_case, matches))
+        filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -253,15 +263,15 @@ class VectorSearcher:
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                                extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                                mode: str = "semantic", contains: str | list[str] | None = None, contains_case: bool = True,
-                               matches: str | None = None) -> list[dict]:
+                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
         ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`; ``contains`` / ``contains_case`` /
         ``matches`` likewise, over the ``summary`` text."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {"project_name": project_name} if project_name else None
-        if contains is not None or matches is not None:
-            filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case, matches))
+        if contains is not None or matches is not None or fuzzy is not None or edits is not None:
+            filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case, matches, fuzzy, edits))
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -272,7 +282,8 @@ class VectorSearcher:
                                 exact_exclude: bool = False, *, diversity: float | None = None, candidates: int | None = None,
                                 max_per_file: int | None = None, min_score: float | None = None,
                                 max_overlap: float | None = None, contains: str | list[str] | None = None,
-                                contains_case: bool = True, matches: str | None = None) -> list[dict]:
+                                contains_case: bool = True, matches: str | None = None,
+                                fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
@@ -285,7 +296,7 @@ class VectorSearcher:
         on_device = bool(exact_exclude and exclude_file)
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch,
-                                  _contains_filter("content", contains, contains_case, matches) or _NO_FILTER_KWARG,
+                                  _contains_filter("content", contains, contains_case, matches, fuzzy, edits) or _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
@@ -339,19 +350,20 @@ class VectorSearcher:
     async def facet_code(self, key: str = "file_path", query: str | None = None, min_score: float | None = None,
                          limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None, entity_type: str | None = None,
                          project_name: str | list[str] | None = None, contains: str | list[str] | None = None,
-                         contains_case: bool = True, matches: str | None = None) -> dict:
+                         contains_case: bool = True, matches: str | None = None, fuzzy: str | None = None,
+                         edits: int | None = None) -> dict:
         """WHERE something lives, not which chunks (not in the reference, whose callers fetch hits and count them in Python):
         the ``limit`` most frequent values of ``key`` -- a file path, a language, an entity type -- among the code chunks that
         pass the filters, with their counts (``HipVectorStore.facet``): ``{"hits": [{"value", "count"}], "values", "total",
-        "missing"}``.  ``contains`` / ``contains_case`` / ``matches`` as in :meth:`search_code`: how many chunks per file hold
-        ``TODO(``.  With ``query`` and ``min_score`` -- both or neither -- ``query`` is embedded and only chunks at least that
+        "missing"}``.  ``contains`` / ``contains_case`` / ``matches`` / ``fuzzy`` / ``edits`` as in :meth:`search_code`: how many
+        chunks per file hold ``TODO(``.  With ``query`` and ``min_score`` -- both or neither -- ``query`` is embedded and only chunks at least that
         similar to it count: in which files does this concept live.  Counts are exact; ties go to the value indexed first."""
         if (query is None) != (min_score is None):
             raise QueryError("facet_code: query and min_score come together or not at all")
         if query is not None and not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
-        filters.update(_contains_filter("content", contains, contains_case, matches))
+        filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
         try:
             kwargs = {}
             if query is not None:
@@ -371,7 +383,8 @@ class VectorSearcher:
                                 max_per_file: int | None = None,
                                 filters_per_query: list[dict | None] | None = None, min_score=None,
                                 max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
-                                contains_case: bool = True, matches: str | None = None) -> list[list[dict]]:
+                                contains_case: bool = True, matches: str | None = None,
+                                fuzzy: str | None = None, edits: int | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
         ``candidates`` only).
@@ -383,9 +396,9 @@ class VectorSearcher:
         together with ``filters_per_query``, ``diversity``, ``max_per_file`` or ``min_score``.  ``contains`` / ``contains_case`` as in
         :meth:`search_code`, one text condition for the whole batch; not together with ``filters_per_query``.  ``matches`` likewise."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
-        if (contains is not None or matches is not None) and filters_per_query is not None:
-            raise QueryError("contains / matches cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
-        filters.update(_contains_filter("content", contains, contains_case, matches))
+        if (contains is not None or matches is not None or fuzzy is not None or edits is not None) and filters_per_query is not None:
+            raise QueryError("contains / matches / fuzzy cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
+        filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
         if filters_per_query is not None:
             if filters:
                 raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")

@@ -706,6 +706,24 @@ int crh_text_regex(crh_text *t, int n_states, int n_classes, const uint8_t *clas
                    const uint8_t *trans_host /* [n_states * n_classes] */, int accept_state, const uint32_t *mask_dev /* or NULL */,
                    uint32_t *out_words_dev, int64_t *out_count_host /* or NULL */, void *stream);
 
+/* Which rows hold the pattern within a bounded number of byte edits: approximate substring match.  A row's
+ * DISTANCE is the minimum over all substrings S of the row of Levenshtein(pattern, S), where the insertion, the deletion and
+ * the substitution of one BYTE cost 1 each (a transposition therefore 2): min over j of D[len][j] of Sellers' table, D[0][j] = 0,
+ * D[i][0] = i.  The empty row's distance is len.  The work is on bytes, like crh_text_regex: a multi-byte UTF-8 character is as
+ * many edits as bytes of it differ.  fold_case folds the ASCII letters of both sides, exactly as crh_text_match does.
+ * out_words_dev receives max_edits + 1 LEVELS of ceil(rows / 32) words each, level d behind level d - 1: bit r of level d is set
+ * iff row r's distance is <= d and its bit of mask_dev is set -- the levels are nested, level max_edits is the filter's bitmap,
+ * level 0 equals crh_text_match of the same pattern.  out_counts_host, when given, receives the max_edits + 1 levels' set bits
+ * and makes the call wait on `stream`; without it the call only enqueues.  CRH_E_INVALID with nothing launched: len outside
+ * 1..CRH_TEXT_MAX_PATTERN_BYTES, max_edits outside 0..CRH_FUZZY_MAX_EDITS, len <= max_edits (every row would match), NULL
+ * pointers.  mask_dev, bits at or past `rows`, the arena without rows (CRH_OK, nothing launched, counts 0) and the one call in
+ * flight per handle are as in crh_text_match.  A pair of tiles whose two mask words are 0 costs no read of its text; otherwise a
+ * row costs a serial walk of its bytes, and 64 rows advance as fast as the longest of them.  Deterministic. */
+#define CRH_FUZZY_MAX_EDITS 3
+int crh_text_fuzzy(crh_text *t, const uint8_t *pat_host, int len, int max_edits, int fold_case,
+                   const uint32_t *mask_dev /* or NULL */, uint32_t *out_words_dev /* [max_edits + 1][ceil(rows / 32)] */,
+                   int64_t *out_counts_host /* [max_edits + 1] or NULL */, void *stream);
+
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
  * the HF RobertaModel it wraps).  All pointers are device pointers; activations bf16,
