@@ -22,6 +22,13 @@
 // are simply nominated more often; when the candidate buffers overflow the host re-runs the batch on the bf16 scan
 // (finish_pending) and, after three overflows in a row, rests the int8 copy of that index for 4096 batches.
 //
+// NON-FINITE VECTORS (a NaN score is no score).  A stored row that holds a NaN (a raw NaN or infinity leaves one:
+// k_append) has no score to bound.  It is quantised to zeros under the scale kI8NoBound = 1e30: with s_q <= 1 / 16256 * (1 + 2^-22)
+// and B_q < 1.3e7 at D <= 1536 (dn, gn < 20, |Q|_2 < 6.4e5) its half-width is below 1e33, finite in every expression that takes
+// it, and its lower end (~ -1e33) never enters a threshold: a threshold is a lower bound of the k-th score and the row has none.
+// It is nominated (its upper end reaches every threshold), costs one fast score (-inf: sum8) and is dropped by k_select_final.
+// A canonical query that holds a NaN is flagged by prep_query_i8 (qpar[.][3]); the threshold step gives it tau = +inf: no candidate.
+//
 // ROW-MAJOR ROWS (round 4).  The selection behind this scan fetches SINGLE rows: ~800 survivors per query and 10M rows.  In the
 // tiled image a row is 48 runs of 32 bytes, 1 KiB apart -- 48 HBM lines of 128 bytes for 1536 useful bytes, and the fetch rate of
 // one CU (~24 GB/s of lines) is what bounded k_select (stamps: 50 us for 208 rows per workgroup, whatever the arithmetic).  An index
@@ -43,6 +50,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int kI8SampleTiles = 8192;   // most sample tiles behind the thresholds of k_scan_i8 (a workgroup keeps one query's maxima in LDS)
 constexpr float kI8QueryLevels = 16256.0f;   // 127 * 128: Q = 128 H + L with H in [-127, 127], L in [-64, 63]
+constexpr float kI8NoBound = 1e30f;          // the row scale of a stored row that holds a NaN or an infinity (k_requant_i8)
 
 #ifdef CRH_ENABLE_DEBUG
 // libcoderag_hip_debug.so only (crh_debug_i8_intervals, tests/test_i8_intervals_gpu.py): while `lo` is set, the sample launch of
@@ -100,16 +108,25 @@ __global__ __launch_bounds__(64) void k_requant_i8(const u32x4 *__restrict__ xt,
             }
         }
     };
-    float m = 0.f;
+    float m = 0.f, chk = 0.f;
     for (int p = 0; p < ks8; ++p) {
         float v[16];
         fetch16(p, v, true);
 #pragma unroll
-        for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[j]));
+        for (int j = 0; j < 16; ++j) {
+            m = fmaxf(m, fabsf(v[j]));                  // (fmaxf passes a NaN by ...
+            chk = fmaf(v[j], 0.f, chk);                 // ... this does not: NaN as soon as one element is NaN or infinite)
+        }
     }
     m = fmaxf(m, __shfl_xor(m, 32));
-    if (!(m < INFINITY)) m = 0.f;                       // (a row holding inf / nan: quantised to zeros, scale 0)
-    const float s_r = m / 127.0f;
+    chk += __shfl_xor(chk, 32);
+    const bool unbounded = chk != chk;                  // every score of this row is NaN: no score
+    if (unbounded) m = 0.f;                             // quantised to zeros ...
+    // ... under the scale kI8NoBound: its interval is +-kI8NoBound * s_q * B_q -- finite (s_q B_q < 1e4: header), wider than any
+    // score, so the row's LOWER end never raises a threshold (it is no lower bound of a score that does not exist), the row is
+    // nominated wherever a query has a scale, and k_select_final drops it when it comes to the canonical chain.  A row of zeros
+    // keeps scale 0: its score IS 0, and [-c, +c] bounds it.
+    const float s_r = unbounded ? kI8NoBound : m / 127.0f;
     const float inv = m > 0.f ? 127.0f / m : 0.f;
     float dsq = 0.f;
     for (int p = 0; p < ks8; ++p) {
@@ -147,7 +164,7 @@ __global__ __launch_bounds__(64) void k_requant_i8(const u32x4 *__restrict__ xt,
 // ------------------------------------------------------------------ canonical queries -> 15-bit integer images
 // One wave per query slot (64 of them; slots >= nq hold zero queries).  src: the canonical query k_prep_queries has just worked out.
 // qfrag8: [QB][2 (H, L)][KS8][64] u32x4 MFMA operand pieces (lane l: query 32 b + (l & 31), elements 32p + 16 (l >> 5) .. + 15).
-// qpar:   [64][4] = s_q, |Q|_2, gn (bound of |g|_2), 0.
+// qpar:   [64][4] = s_q, |Q|_2, gn (bound of |g|_2), 1 if the canonical query holds a NaN (a raw NaN or infinity: no score) else 0.
 // Called by k_prep_queries<.., true> (crh_kernels.hpp) with the canonical query still in LDS: one launch prepares both images
 // (round 3 launched a second kernel that read the canonical queries back from global memory).
 __device__ __forceinline__ void prep_query_i8(const float *src /* the canonical query, LDS */, int dim, int qi, u32x4 *__restrict__ qfrag8,
@@ -163,12 +180,14 @@ __device__ __forceinline__ void prep_query_i8(const float *src /* the canonical 
     const float s_q = m / kI8QueryLevels;
     const float inv = m > 0.f ? kI8QueryLevels / m : 0.f;
     float qsq = 0.f, gsq = 0.f;
+    bool nan_seen = false;                                // the canonical query holds a NaN: every score of this query is NaN
     uint32_t *out32 = reinterpret_cast<uint32_t *>(qfrag8);
     for (int c8 = lane; c8 < (dim >> 3); c8 += 64) {      // 8 consecutive elements
         uint32_t hb[2] = {0u, 0u}, lb[2] = {0u, 0u};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float y = src[c8 * 8 + j] * inv;
+            nan_seen |= src[c8 * 8 + j] != src[c8 * 8 + j];
             y = (y == y) ? y : 0.f;
             float Qf = rintf(y);
             Qf = fminf(fmaxf(Qf, -kI8QueryLevels), kI8QueryLevels);
@@ -194,13 +213,14 @@ __device__ __forceinline__ void prep_query_i8(const float *src /* the canonical 
         qsq += __shfl_xor(qsq, d);
         gsq += __shfl_xor(gsq, d);
     }
+    const bool any_nan = __ballot(nan_seen) != 0ull;
     if (lane == 0) {
         // gn: |g| as evaluated + the f32 evaluation's share (y off by <= 16256 * 2^-23, s_q * inv off 1 by 2^-22 -> each g_i moves
         // by < 6e-3; over 1536 elements < 0.24)
         qpar[qi * 4 + 0] = s_q;
         qpar[qi * 4 + 1] = sqrtf(qsq) * 1.0001f;
         qpar[qi * 4 + 2] = m > 0.f ? sqrtf(gsq) * 1.001f + 0.25f : 0.f;
-        qpar[qi * 4 + 3] = 0.f;
+        qpar[qi * 4 + 3] = any_nan ? 1.f : 0.f;           // 1: the threshold step nominates nothing for this query
     }
 }
 
@@ -477,7 +497,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_scan_i8(
     if constexpr (PART == 2)
     for (int q = blockIdx.x; q < NQS; q += gridDim.x) {
         float t = -INFINITY;
-        if (q >= nq) {
+        if (q >= nq || qpar[q * 4 + 3] != 0.f) {          // a padding slot, or a query whose every score is NaN: similar to nothing
             t = INFINITY;
         } else if (G >= k) {
             constexpr int DIM = KS8 * 32;

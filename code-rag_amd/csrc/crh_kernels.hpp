@@ -65,7 +65,8 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float x)
 }
 __device__ __forceinline__ float bf16_bits_f32(uint32_t b) { return bits_f32(b << 16); }
 
-// order-preserving map f32 -> u32 (larger float <=> larger uint); no NaNs reach it.
+// order-preserving map f32 -> u32 (larger float <=> larger uint); no NaNs reach it: the scans' maxima come out of fmaxf, the
+// fast scores out of sum8, the interval ends of the int8 scan are finite, and a canonical score is keyed by score_key below.
 __device__ __forceinline__ uint32_t ord_f32(float f)
 {
     uint32_t u = f32_bits(f);
@@ -75,6 +76,14 @@ __device__ __forceinline__ float unord_f32(uint32_t o)
 {
     uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
     return bits_f32(u);
+}
+// The ranking key of a survivor's canonical score: (ord(score) << 32) | ~row -- descending score, then ascending row.  A NaN
+// score is no score (the row or the query holds a NaN or an infinity): its key is kNoKey = 0, below every real
+// key (ord(-inf) = 0x007fffff), and select_tail writes it as padding.
+constexpr unsigned long long kNoKey = 0ull;
+__device__ __forceinline__ unsigned long long score_key(float score, uint32_t row)
+{
+    return score == score ? ((unsigned long long)ord_f32(score) << 32) | (unsigned long long)(~row) : kNoKey;
 }
 
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
@@ -1565,7 +1574,8 @@ __device__ __forceinline__ float sum8(float acc)
 }
 
 // Step 4 of k_select: exact top-k of Ms unique keys (descending score, ascending row), written with row_base added.  The keys
-// sit in LDS (`lkeys`, when in_lds) or in global memory (`sk`).
+// sit in LDS (`lkeys`, when in_lds) or in global memory (`sk`).  kNoKey entries (survivors whose score is NaN: score_key) are the
+// only equal keys; they rank behind every real key, in list order among themselves, and come out as padding.
 template <int NT>
 __device__ void select_tail(const unsigned long long *sk, unsigned int Ms, bool in_lds, unsigned long long *lkeys, unsigned long long *sortbuf,
                             unsigned int *hist, unsigned int *bcast, unsigned int *scount_p, int k, int64_t row_base, float *os, int64_t *orow)
@@ -1581,9 +1591,11 @@ __device__ void select_tail(const unsigned long long *sk, unsigned int Ms, bool 
             const unsigned long long key = lkeys[p];
             unsigned int rank = 0u;
             for (unsigned int j = 0; j < Ms; ++j) rank += (lkeys[j] > key) ? 1u : 0u;
+            if (key == kNoKey)                           // (rare: the real keys pay nothing for it)
+                for (unsigned int j = 0; j < p; ++j) rank += (lkeys[j] == kNoKey) ? 1u : 0u;
             if (rank < k2) {
-                os[rank] = unord_f32((uint32_t)(key >> 32));
-                orow[rank] = row_base + (int64_t)(uint32_t)(~(uint32_t)key);
+                os[rank] = key != kNoKey ? unord_f32((uint32_t)(key >> 32)) : -INFINITY;
+                orow[rank] = key != kNoKey ? row_base + (int64_t)(uint32_t)(~(uint32_t)key) : -1;
             }
         }
         for (unsigned int i = k2 + tid; i < (unsigned int)k; i += NT) {
@@ -1603,15 +1615,15 @@ __device__ void select_tail(const unsigned long long *sk, unsigned int Ms, bool 
     __syncthreads();
     for (unsigned int p = tid; p < Ms; p += NT) {
         const unsigned long long key = sk[p];
-        if (key >= kkey) {
+        if (key >= kkey && key != kNoKey) {             // (sortbuf starts out as kNoKey everywhere: those need no slot)
             const unsigned int o = atomicAdd(&scount, 1u);
             if (o < (unsigned int)CRH_MAX_K) sortbuf[o] = key;
         }
     }
     wg_bitonic_desc<NT>(sortbuf, P);
     for (int i = tid; i < k; i += NT) {
-        if (i < (int)k2) {
-            const unsigned long long key = sortbuf[i];
+        const unsigned long long key = i < (int)k2 ? sortbuf[i] : kNoKey;
+        if (key != kNoKey) {
             os[i] = unord_f32((uint32_t)(key >> 32));
             orow[i] = row_base + (int64_t)(uint32_t)(~(uint32_t)key);
         } else {
@@ -1781,7 +1793,7 @@ __global__ __launch_bounds__(1024) void k_select(const u32x2 *__restrict__ qlist
     for (unsigned int p = tid; p < Ms; p += NT) {
         const uint32_t row = (uint32_t)(in_lds ? lkeys[p] : sk[p]);
         const float c = F32 ? canonical_dot_f32(xf32, dim, row, qv) : canonical_dot_tiled(xt, ksteps, row, qv);
-        const unsigned long long key = ((unsigned long long)ord_f32(c) << 32) | (unsigned long long)(~row);
+        const unsigned long long key = score_key(c, row);   // (behind a bf16 scan no NaN score is nominated: kNoKey is never taken here)
         if (in_lds)
             lkeys[p] = key;
         else
@@ -1802,8 +1814,8 @@ __global__ __launch_bounds__(1024) void k_select(const u32x2 *__restrict__ qlist
 //   2. the canonical score of its rows: the rows are STAGED in LDS first (all threads fetch, one round trip for the lot), then
 //      one thread per row walks the ordered chain out of LDS -- the chain used to sit behind a dozen dependent memory round
 //      trips per row (32 us for ~100 rows per query, stamps of round 4);
-//   3. keys (ord(score) << 32) | ~row published in `ckeys`; the workgroup that arrives last ranks them: exact top-k,
-//      descending score, ascending row, row_base added.
+//   3. keys score_key(score, row) published in `ckeys` (a NaN score: kNoKey); the workgroup that arrives last ranks them: exact
+//      top-k, descending score, ascending row, row_base added.
 template <bool F32>
 __global__ __launch_bounds__(256) void k_select_final(const unsigned long long *__restrict__ fkeys, unsigned long long *__restrict__ ckeys, int qcap,
                                                       const float *__restrict__ qn, const u32x4 *__restrict__ xt, const float *__restrict__ xf32,
@@ -1927,7 +1939,9 @@ __global__ __launch_bounds__(256) void k_select_final(const unsigned long long *
                     }
                 }
                 const uint32_t row = mine[r0 + (unsigned int)tid];
-                cq[gbase + r0 + (unsigned int)tid] = ((unsigned long long)ord_f32(acc) << 32) | (unsigned long long)(~row);
+                // (the int8 intervals of a row that holds a NaN or an infinity bound nothing: such a row is nominated, reaches this
+                // chain whenever fewer than k rows beat its fast score of -inf, and is dropped HERE: score_key -> kNoKey)
+                cq[gbase + r0 + (unsigned int)tid] = score_key(acc, row);
             }
             __syncthreads();
         }

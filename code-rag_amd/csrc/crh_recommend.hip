@@ -236,7 +236,9 @@ __global__ __launch_bounds__(kRecMaxThreads) void k_recommend_select(int P, int 
         p_ord = 0u;
 #pragma unroll
         for (int j = 0; j < kRecMaxEx; ++j) {
-            const uint32_t o = rec_ord(acc[j]);
+            // (a NaN score is no score, DESIGN.md 3.25 -- the example holds a NaN or an infinity; the candidates come out of a
+            // search and hold none: that example counts as -inf, it neither wins a row nor vetoes one)
+            const uint32_t o = rec_ord(acc[j] == acc[j] ? acc[j] : -INFINITY);
             if (j < np) {
                 if (o > p_ord) {
                     p_ord = o;

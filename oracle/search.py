@@ -81,7 +81,8 @@ def dot(a: np.ndarray, b: np.ndarray) -> float:
 
 
 def scores(corpus_pre: np.ndarray, queries_pre: np.ndarray) -> np.ndarray:
-    """The canonical f32 score of every (query, row) pair of preprocessed inputs -- what :func:`search` ranks by: [nq, n] f32."""
+    """The canonical f32 score of every (query, row) pair of preprocessed inputs -- what :func:`search` ranks by: [nq, n] f32.
+    NaN where :func:`search` leaves the pair out; rank or count on it with ``>=``, which does the same."""
     x = np.ascontiguousarray(corpus_pre, dtype=np.float32)
     q = np.ascontiguousarray(queries_pre, dtype=np.float32)
     if q.ndim == 1:
@@ -94,7 +95,8 @@ def scores(corpus_pre: np.ndarray, queries_pre: np.ndarray) -> np.ndarray:
 def search(corpus_pre: np.ndarray, queries_pre: np.ndarray, k: int, alive: np.ndarray | None = None,
            codes: np.ndarray | None = None, filters: list[tuple[int, int]] | None = None,
            threads: int | None = None):
-    """Exact top-k on already preprocessed corpus/queries.  Returns (scores[nq,k] f32, rows[nq,k] i64)."""
+    """Exact top-k on already preprocessed corpus/queries.  Returns (scores[nq,k] f32, rows[nq,k] i64).  A (query, row) pair
+    whose score is NaN -- either side holds a NaN, as a raw NaN or infinity leaves one -- is in no list (search_oracle.c's header)."""
     x = np.ascontiguousarray(corpus_pre, dtype=np.float32)
     q = np.ascontiguousarray(queries_pre, dtype=np.float32)
     if q.ndim == 1:
@@ -141,6 +143,7 @@ def search_fp64(corpus_pre: np.ndarray, queries_pre: np.ndarray, k: int, alive: 
     x = np.asarray(corpus_pre, dtype=np.float64)
     q = np.atleast_2d(np.asarray(queries_pre, dtype=np.float64))
     s = q @ x.T
+    s[np.isnan(s)] = -np.inf                     # a NaN score is no score (search_oracle.c's header)
     if alive is not None:
         s[:, ~np.asarray(alive, dtype=bool)] = -np.inf
     order = np.lexsort((np.broadcast_to(np.arange(x.shape[0]), s.shape), -s), axis=1)[:, :k]
@@ -156,7 +159,7 @@ def search_fp64(corpus_pre: np.ndarray, queries_pre: np.ndarray, k: int, alive: 
 def search_blas(corpus_pre: np.ndarray, queries_pre: np.ndarray, k: int):
     """Fast CPU exact scan (BLAS sgemm + argpartition): bench.py's cpu_baseline leg, all host cores.
 
-    Same results as :func:`search` up to fp32 summation order; it stands in for "Qdrant exact scan"
+    Same results as :func:`search` up to fp32 summation order on finite inputs; it stands in for "Qdrant exact scan"
     when timing the CPU side.
     """
     s = np.asarray(queries_pre, dtype=np.float32) @ np.asarray(corpus_pre, dtype=np.float32).T

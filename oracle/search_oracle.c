@@ -25,6 +25,16 @@
  *       vectors; results in descending score.
  * Tie order is unspecified upstream; this repo defines it: lower row first.
  *
+ * A NaN score is no score.  A stored row or a query that holds a NaN or an
+ * infinity preprocesses to a vector with NaN elements (NaN -> every element
+ * NaN; +-inf -> zeros with a NaN where the infinity stood), and every score it
+ * takes part in is NaN.  Upstream leaves such a pair undefined; this repo
+ * defines it: the pair is in no result list, exactly as `score >= t` is false
+ * for it.  orc_search skips it, so its lists are sorted and free of NaN;
+ * orc_merge_topk is only ever given such lists (and padding) and therefore
+ * never compares a NaN; orc_scores reports the NaN as it is -- whoever ranks
+ * or counts on that matrix leaves the NaN entries out.
+ *
  * PARITY UNPINNED at the Qdrant boundary: the reference holds no golden
  * vector for any score or order (tests/test_database.py:88-124 needs a live
  * server and only asserts ">= 1 hit").  The fixtures under tests/golden/ pin
@@ -93,7 +103,8 @@ float orc_dot(const float *a, const float *b, int d)
 }
 
 /* The canonical score of EVERY (query, row) pair: out[q * n + r] = orc_dot(query q, row r) -- what orc_search ranks by,
- * without the ranking (tests/test_i8_intervals_gpu.py checks per-row score intervals against it). */
+ * without the ranking (tests/test_i8_intervals_gpu.py checks per-row score intervals against it).  A pair that involves a
+ * non-finite vector reads NaN here; orc_search leaves it out. */
 void orc_scores(const float *corpus, int64_t n, int d, const float *queries, int nq, float *out)
 {
 #pragma omp parallel for schedule(static)
@@ -110,7 +121,9 @@ static int row_passes(int64_t r, const uint8_t *alive, const int32_t *codes, int
     return 1;
 }
 
-/* better(a,b): a ranks strictly before b -- higher score, then lower row. */
+/* better(a,b): a ranks strictly before b -- higher score, then lower row.
+ * Neither score is NaN: orc_search never lets one in, orc_merge_topk takes
+ * orc_search's lists. */
 static int better(float sa, int64_t ra, float sb, int64_t rb)
 {
     if (sa > sb) return 1;
@@ -123,8 +136,8 @@ static int better(float sa, int64_t ra, float sb, int64_t rb)
  * corpus: n x d f32 (already cosine_preprocess'ed; bf16-rounded when the
  * store keeps bf16).  alive: n bytes or NULL.  codes: n x ncols int32
  * dictionary codes or NULL; (fcols[f], fvals[f]) are AND-ed equalities
- * (client.py:171-176).  Output rows beyond the number of passing rows are
- * (-inf, -1).  Eight rows are scored together so the add chains pipeline;
+ * (client.py:171-176).  A row whose score is NaN is skipped (header).  Output
+ * rows beyond the number of rows that pass and score are (-inf, -1).  Eight rows are scored together so the add chains pipeline;
  * each dot product keeps its own strictly sequential order.
  */
 int orc_search(const float *corpus, int64_t n, int d, const uint8_t *alive,
@@ -162,6 +175,7 @@ int orc_search(const float *corpus, int64_t n, int d, const uint8_t *alive,
                 int64_t r = r0 + j;
                 if (!row_passes(r, alive, codes, ncols, fcols, fvals, nfilt)) continue;
                 float s = acc[j];
+                if (s != s) continue; /* a NaN score is no score (header) */
                 if (cnt == k && !better(s, r, bs[k - 1], br[k - 1])) continue;
                 int pos = cnt < k ? cnt : k - 1;
                 while (pos > 0 && better(s, r, bs[pos - 1], br[pos - 1])) {
@@ -180,7 +194,8 @@ int orc_search(const float *corpus, int64_t n, int d, const uint8_t *alive,
 
 /*
  * Merge `nlists` per-shard top-k lists (each nq x k, sorted, padded with
- * (-inf,-1)) into one nq x k list: same total order as orc_search.  This is the
+ * (-inf,-1), free of NaN as orc_search leaves them) into one nq x k list: same
+ * total order as orc_search.  This is the
  * step an 8-GPU row-sharded search performs after its all-gather.
  */
 int orc_merge_topk(int nlists, int nq, int k, const float *scores, const int64_t *rows,

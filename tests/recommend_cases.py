@@ -10,6 +10,7 @@ it); its slots are ``[P positives | N negatives]`` of which the first ``n_pos`` 
   is the plain exact top-``limit`` for ``q`` with the example rows removed.
 * ``best``: ``s(e, x)`` = the score a search gives row ``x`` for the raw query ``e`` (``orc.preprocess`` then ``orc_dot``);
   ``p(x) = max_j s(pos_j, x)`` (``best`` = the lowest ``j`` attaining it), ``n(x) = max_j s(neg_j, x)`` (-inf without negatives);
+  a NaN ``s(e, x)`` -- the example holds a NaN or an infinity -- is no score and stands as -inf in both maxima;
   KEPT iff no example row and ``ord(p) > ord(n)``; the answer is the first ``limit`` kept rows by descending ``p``, ties to the
   lower row.
 * the selection from lists: list ``j`` is the exact top-``c`` of positive ``j``; the first flat entry of a row stands for it;
@@ -84,6 +85,7 @@ def recommend_select(scores, rows, cand_vecs, examples, example_rows, P, N, k, s
         if best and d:
             live = list(range(n_pos[q])) + list(range(P, P + n_neg[q]))
             s = example_scores(np.asarray(examples, F32)[q, live], np.asarray(cand_vecs, F32)[q, first], bf16)
+            s = np.where(np.isnan(s), F32(-np.inf), s)                  # a NaN score is no score: that example neither wins nor vetoes
             so = ord_f32(s).astype(np.int64)
             p_ord, which = so[:n_pos[q]].max(0), so[:n_pos[q]].argmax(0).astype(np.int32)       # (argmax: the first maximum)
             n_ord = so[n_pos[q]:].max(0) if n_neg[q] else np.full((d,), NEG_INF_ORD, np.int64)
