@@ -412,15 +412,37 @@ int upload_sets(MaskCache &c, hipStream_t st)
     return CRH_OK;
 }
 
+// the two launches of a tile list: one workgroup per 256 mask words in both (blockcnt: one word per workgroup)
+void launch_tile_list(const uint32_t *words, int64_t ntiles, uint32_t *blockcnt, uint32_t *list, uint32_t *len, hipStream_t st)
+{
+    const unsigned nb = (unsigned)ceil_div(ntiles, 256);
+    hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt);
+    hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt, list, len);
+}
+
+#ifdef CRH_ENABLE_DEBUG   // helpers of the crh_debug_* selection entry points below
+template <typename T>
+struct DebugBuf {   // a device array of a debug entry point, released when the call returns
+    T *p = nullptr;
+    ~DebugBuf() { dev_free(p); }
+};
+
+template <int NT, int NB, typename KeyT>
+void launch_debug_kth(const void *keys, unsigned nsets, unsigned n, const unsigned *ks, unsigned floor_key, unsigned nblocks,
+                      unsigned long long *kmin, unsigned long long *kmax)
+{
+    hipLaunchKernelGGL((k_debug_kth<NT, NB, KeyT>), dim3(nblocks), dim3(NT), 0, nullptr, static_cast<const KeyT *>(keys), nsets, n, ks,
+                       (uint32_t)floor_key, kmin, kmax);
+}
+#endif
+
 // the populated tiles of a row mask, in order, into list_buf (laid out like Workspace::tilelist); their number decides the
 // route, so the host waits for it -- once per mask, not per batch
 int make_tile_list(crh_index *h, const uint32_t *words, uint32_t *list_buf, hipStream_t st, int64_t *nlist)
 {
     const int64_t ntiles = ceil_div(h->count, kTileRows);
-    const unsigned nb = (unsigned)ceil_div(ntiles, 256);
     uint32_t *blockcnt = list_buf + h->cap_tiles, *len = blockcnt + ceil_div(h->cap_tiles, 256);
-    hipLaunchKernelGGL(k_tilelist_count, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt);
-    hipLaunchKernelGGL(k_tilelist_fill, dim3(nb), dim3(256), 0, st, words, ntiles, blockcnt, list_buf, len);
+    launch_tile_list(words, ntiles, blockcnt, list_buf, len, st);
     CRH_HIP(hipGetLastError());
     uint32_t n = 0;
     CRH_HIP(hipMemcpyAsync(&n, len, 4, hipMemcpyDeviceToHost, st));
@@ -1934,6 +1956,102 @@ int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, co
     CRH_HIP(hipMemcpy(srow_out, h->srow, (size_t)count * 4, hipMemcpyDeviceToHost));
     CRH_HIP(hipMemcpy(dn_out, h->i8stat, 4, hipMemcpyDeviceToHost));
     *c_abs_out = c_abs;
+    return CRH_OK;
+}
+
+// The product's instantiations of wg_kth_largest_fast / wg_kth_largest on the caller's key sets (k_debug_kth, crh_kernels.hpp).
+int crh_debug_kth_largest(int variant, const void *keys, unsigned nsets, unsigned n, const unsigned *k, unsigned floor_key, unsigned nblocks,
+                          unsigned long long *key_out)
+{
+    const bool u64 = (variant & CRH_DEBUG_SEL_U64) != 0;
+    const int shape = variant & ~CRH_DEBUG_SEL_U64;
+    if (variant < 0 || shape > CRH_DEBUG_SEL_RADIX_256) return fail(CRH_E_INVALID, "debug_kth_largest: unknown variant %d", variant);
+    if (u64 && shape <= CRH_DEBUG_SEL_FAST_256) return fail(CRH_E_INVALID, "debug_kth_largest: wg_kth_largest_fast takes u32 keys (variant %d)", variant);
+    if (u64 && shape == CRH_DEBUG_SEL_RADIX_512) return fail(CRH_E_INVALID, "debug_kth_largest: the product has no u64 radix select of 512 threads");
+    if (!keys || !k || !key_out) return fail(CRH_E_INVALID, "debug_kth_largest: NULL pointer");
+    if (nsets < 1 || nsets > 65535u || n < 1 || (uint64_t)nsets * n > (1ull << 28)) return fail(CRH_E_INVALID, "debug_kth_largest: nsets=%u, n=%u out of range", nsets, n);
+    if (nblocks < 1 || nblocks > 65535u) return fail(CRH_E_INVALID, "debug_kth_largest: nblocks=%u outside 1..65535", nblocks);
+    for (unsigned s = 0; s < nsets; ++s)
+        if (k[s] < 1 || k[s] > n) return fail(CRH_E_INVALID, "debug_kth_largest: k[%u]=%u outside 1..n=%u", s, k[s], n);
+    const size_t kbytes = (size_t)nsets * n * (u64 ? 8 : 4);
+    DebugBuf<unsigned char> kd;
+    DebugBuf<unsigned> ksd;
+    DebugBuf<unsigned long long> mm;   // [2][nsets]: the smallest and the largest key any thread of a set's workgroup returned
+    CRH_TRY(dev_alloc(&kd.p, (int64_t)kbytes));
+    CRH_TRY(dev_alloc(&ksd.p, nsets));
+    CRH_TRY(dev_alloc(&mm.p, 2 * (int64_t)nsets));
+    CRH_HIP(hipMemcpy(kd.p, keys, kbytes, hipMemcpyHostToDevice));
+    CRH_HIP(hipMemcpy(ksd.p, k, (size_t)nsets * 4, hipMemcpyHostToDevice));
+    CRH_HIP(hipMemset(mm.p, 0xff, (size_t)nsets * 8));
+    CRH_HIP(hipMemset(mm.p + nsets, 0, (size_t)nsets * 8));
+    unsigned long long *kmin = mm.p, *kmax = mm.p + nsets;
+    switch (variant) {
+    case CRH_DEBUG_SEL_FAST_1024: launch_debug_kth<1024, 1024, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_FAST_512: launch_debug_kth<512, 512, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_FAST_256: launch_debug_kth<256, 256, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_RADIX_1024: launch_debug_kth<1024, 0, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_RADIX_512: launch_debug_kth<512, 0, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_RADIX_256: launch_debug_kth<256, 0, uint32_t>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    case CRH_DEBUG_SEL_RADIX_1024 | CRH_DEBUG_SEL_U64: launch_debug_kth<1024, 0, unsigned long long>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    default: launch_debug_kth<256, 0, unsigned long long>(kd.p, nsets, n, ksd.p, floor_key, nblocks, kmin, kmax); break;
+    }
+    CRH_HIP(hipGetLastError());
+    CRH_HIP(hipDeviceSynchronize());
+    std::vector<unsigned long long> got(2 * (size_t)nsets);
+    CRH_HIP(hipMemcpy(got.data(), mm.p, got.size() * 8, hipMemcpyDeviceToHost));
+    for (unsigned s = 0; s < nsets; ++s) {
+        if (got[s] != got[nsets + s])
+            return fail(CRH_E_INTERNAL, "debug_kth_largest: the threads of set %u returned different keys (%llx .. %llx)", s, got[s], got[nsets + s]);
+        key_out[s] = got[s];
+    }
+    return CRH_OK;
+}
+
+// select_tail<1024> (k_select's) or select_tail<256> (k_select_final's) on the caller's keys (k_debug_select_tail).
+int crh_debug_select_tail(int variant, const unsigned long long *keys, unsigned Ms, int k, int64_t row_base, float *scores_out, int64_t *rows_out)
+{
+    if (variant != CRH_DEBUG_TAIL_1024 && variant != CRH_DEBUG_TAIL_256) return fail(CRH_E_INVALID, "debug_select_tail: unknown variant %d", variant);
+    if (!keys || !scores_out || !rows_out) return fail(CRH_E_INVALID, "debug_select_tail: NULL pointer");
+    if (Ms < 1 || Ms > (1u << 24)) return fail(CRH_E_INVALID, "debug_select_tail: Ms=%u outside 1..2^24", Ms);
+    if (k < 1 || k > CRH_MAX_K) return fail(CRH_E_INVALID, "debug_select_tail: k=%d outside 1..%d", k, CRH_MAX_K);
+    DebugBuf<unsigned long long> kd;
+    DebugBuf<float> os;
+    DebugBuf<int64_t> orow;
+    CRH_TRY(dev_alloc(&kd.p, Ms));
+    CRH_TRY(dev_alloc(&os.p, k));
+    CRH_TRY(dev_alloc(&orow.p, k));
+    CRH_HIP(hipMemcpy(kd.p, keys, (size_t)Ms * 8, hipMemcpyHostToDevice));
+    CRH_HIP(hipMemset(os.p, 0x55, (size_t)k * 4));      // (an entry the helper leaves unwritten comes back as neither a score nor padding)
+    CRH_HIP(hipMemset(orow.p, 0x55, (size_t)k * 8));
+    if (variant == CRH_DEBUG_TAIL_1024)
+        hipLaunchKernelGGL(k_debug_select_tail<1024>, dim3(1), dim3(1024), 0, nullptr, kd.p, Ms, k, row_base, os.p, orow.p);
+    else
+        hipLaunchKernelGGL(k_debug_select_tail<256>, dim3(1), dim3(256), 0, nullptr, kd.p, Ms, k, row_base, os.p, orow.p);
+    CRH_HIP(hipGetLastError());
+    CRH_HIP(hipDeviceSynchronize());
+    CRH_HIP(hipMemcpy(scores_out, os.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+    CRH_HIP(hipMemcpy(rows_out, orow.p, (size_t)k * 8, hipMemcpyDeviceToHost));
+    return CRH_OK;
+}
+
+// make_tile_list's two launches (launch_tile_list) on the caller's mask words.  list_out [ntiles] goes IN as well: what the
+// caller put there is what the list buffer holds before the launches, so the entries past *len_out show what was left alone.
+int crh_debug_tile_list(const uint32_t *mask_words, int64_t ntiles, uint32_t *list_out, uint32_t *len_out)
+{
+    if (!mask_words || !list_out || !len_out) return fail(CRH_E_INVALID, "debug_tile_list: NULL pointer");
+    if (ntiles < 1 || ntiles > (1LL << 26)) return fail(CRH_E_INVALID, "debug_tile_list: ntiles=%lld outside 1..2^26", (long long)ntiles);
+    DebugBuf<uint32_t> words, list;   // list: [ntiles] the list, then one count per workgroup, then the length (Workspace::tilelist)
+    const int64_t nb = ceil_div(ntiles, 256);
+    CRH_TRY(dev_alloc(&words.p, ntiles));
+    CRH_TRY(dev_alloc(&list.p, ntiles + nb + 1));
+    CRH_HIP(hipMemcpy(words.p, mask_words, (size_t)ntiles * 4, hipMemcpyHostToDevice));
+    CRH_HIP(hipMemcpy(list.p, list_out, (size_t)ntiles * 4, hipMemcpyHostToDevice));
+    CRH_HIP(hipMemset(list.p + ntiles, 0xff, (size_t)(nb + 1) * 4));
+    launch_tile_list(words.p, ntiles, list.p + ntiles, list.p, list.p + ntiles + nb, nullptr);
+    CRH_HIP(hipGetLastError());
+    CRH_HIP(hipDeviceSynchronize());
+    CRH_HIP(hipMemcpy(list_out, list.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
+    CRH_HIP(hipMemcpy(len_out, list.p + ntiles + nb, 4, hipMemcpyDeviceToHost));
     return CRH_OK;
 }
 #endif  // CRH_ENABLE_DEBUG

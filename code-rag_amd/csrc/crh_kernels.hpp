@@ -1576,6 +1576,8 @@ __device__ __forceinline__ float sum8(float acc)
 // Step 4 of k_select: exact top-k of Ms unique keys (descending score, ascending row), written with row_base added.  The keys
 // sit in LDS (`lkeys`, when in_lds) or in global memory (`sk`).  kNoKey entries (survivors whose score is NaN: score_key) are the
 // only equal keys; they rank behind every real key, in list order among themselves, and come out as padding.
+// kSelectLdsKeys: how many keys `lkeys` holds -- in_lds is Ms <= kSelectLdsKeys for every caller.
+constexpr unsigned int kSelectLdsKeys = 2048;
 template <int NT>
 __device__ void select_tail(const unsigned long long *sk, unsigned int Ms, bool in_lds, unsigned long long *lkeys, unsigned long long *sortbuf,
                             unsigned int *hist, unsigned int *bcast, unsigned int *scount_p, int k, int64_t row_base, float *os, int64_t *orow)
@@ -1633,6 +1635,55 @@ __device__ void select_tail(const unsigned long long *sk, unsigned int Ms, bool 
     }
 }
 
+#ifdef CRH_ENABLE_DEBUG
+// libcoderag_hip_debug.so only (crh_debug_kth_largest / crh_debug_select_tail, tests/test_select_gpu.py): thin harnesses that CALL
+// the helpers above with the product's template arguments on key sets given by the caller -- nothing here restates them.
+//
+// NB > 0: wg_kth_largest_fast<NT, NB, 256>;  NB == 0: wg_kth_largest<KeyT, NT>.  Workgroup b walks sets b, b + gridDim.x, ...
+// with the helper's scratch reused from set to set behind ONE barrier, as the threshold loop of k_scan_fused does; the keys
+// are read from global memory through `get`, as k_select's unstaged path reads them.  EVERY thread folds the key it was handed
+// into kmin / kmax (global atomics: no barrier is added), so the host sees whether the workgroup agreed on it.
+template <int NT, int NB, typename KeyT>
+__global__ __launch_bounds__(NT) void k_debug_kth(const KeyT *__restrict__ keys, unsigned int nsets, unsigned int n, const unsigned int *__restrict__ ks,
+                                                  uint32_t floor_key, unsigned long long *__restrict__ kmin, unsigned long long *__restrict__ kmax)
+{
+    __shared__ unsigned int hist[(NT / 64) * 256];
+    __shared__ unsigned int bcast[2];
+    __shared__ unsigned int fast[NB + 256 + 2 * (NT / 64) + 8];
+    for (unsigned int s = blockIdx.x; s < nsets; s += gridDim.x) {
+        const KeyT *col = keys + (size_t)s * n;
+        auto get = [&](unsigned int i) { return col[i]; };
+        KeyT key;
+        if constexpr (NB > 0)
+            key = wg_kth_largest_fast<NT, NB, 256>(get, n, ks[s], floor_key, fast, hist, bcast);
+        else
+            key = wg_kth_largest<KeyT, NT>(get, n, ks[s], hist, bcast);
+        atomicMin(&kmin[s], (unsigned long long)key);
+        atomicMax(&kmax[s], (unsigned long long)key);
+        __syncthreads();
+    }
+}
+
+// select_tail<NT> on Ms keys of global memory; in_lds by the rule of k_select / k_select_final, the keys copied into LDS as
+// k_select_final copies them.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_debug_select_tail(const unsigned long long *__restrict__ sk, unsigned int Ms, int k, int64_t row_base,
+                                                          float *__restrict__ os, int64_t *__restrict__ orow)
+{
+    __shared__ unsigned long long lkeys[kSelectLdsKeys];
+    __shared__ unsigned long long sortbuf[CRH_MAX_K];
+    __shared__ unsigned int hist[(NT / 64) * 256];
+    __shared__ unsigned int bcast[2];
+    __shared__ unsigned int scount;
+    const bool in_lds = Ms <= kSelectLdsKeys;
+    if (in_lds) {
+        for (unsigned int p = threadIdx.x; p < Ms; p += NT) lkeys[p] = sk[p];
+        __syncthreads();
+    }
+    select_tail<NT>(sk, Ms, in_lds, lkeys, sortbuf, hist, bcast, &scount, k, row_base, os, orow);
+}
+#endif  // CRH_ENABLE_DEBUG
+
 // ------------------------------------------------------------------ final selection
 
 // One workgroup per query.  From the query's candidate list (approximate MFMA scores):
@@ -1658,7 +1709,7 @@ __global__ __launch_bounds__(1024) void k_select(const u32x2 *__restrict__ qlist
                                                   const u32x4 *__restrict__ xrow = nullptr)
 {
     constexpr int NT = 1024;
-    constexpr unsigned int LCAP = 2048;   // survivors kept in LDS (the normal case: ~k + a few)
+    constexpr unsigned int LCAP = kSelectLdsKeys;   // survivors kept in LDS (the normal case: ~k + a few)
     constexpr unsigned int SCAP = 16384;  // candidate scores kept in LDS for the selection passes (64 KB)
     __shared__ uint32_t lscore[SCAP];
     __shared__ float qv[2048];
@@ -1823,7 +1874,7 @@ __global__ __launch_bounds__(256) void k_select_final(const unsigned long long *
                                                       float *__restrict__ out_scores, int64_t *__restrict__ out_rows, SearchStatus *__restrict__ status)
 {
     constexpr int NT = 256;
-    constexpr unsigned int LCAP = 2048;             // keys ranked out of LDS
+    constexpr unsigned int LCAP = kSelectLdsKeys;   // keys ranked out of LDS
     constexpr unsigned int MINE = 512;              // rows of one workgroup per round of canonical chains
     constexpr int STAGE_U4 = 4096;                  // 64 KB of staged rows
     __shared__ u32x4 stage[STAGE_U4];

@@ -66,7 +66,8 @@ EXPORTS = (
     "crh_index_facet", "crh_search_range_facet", "crh_facet_select",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
-DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals")
+DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
+                 "crh_debug_kth_largest", "crh_debug_select_tail", "crh_debug_tile_list")
 DEBUG_LIB_PATH = Path(os.environ.get("CODERAG_HIP_DEBUG_LIB", PKG_DIR / "lib" / "libcoderag_hip_debug.so"))
 
 RR_NAME_BYTES, RR_MAX_ENTITIES, RR_ENTITY_BYTES = 64, 8, 48
@@ -238,6 +239,9 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
         L.crh_debug_read_ceiling.argtypes = [vp, vp]
         L.crh_debug_i8_move.argtypes = [vp]
         L.crh_debug_i8_intervals.argtypes = [vp, i32, vp, i32, C.POINTER(Filter), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.crh_debug_kth_largest.argtypes = [i32, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, vp]
+        L.crh_debug_select_tail.argtypes = [i32, vp, C.c_uint, i32, i64, vp, vp]
+        L.crh_debug_tile_list.argtypes = [vp, i64, vp, vp]
     for name in EXPORTS + (DEBUG_EXPORTS if debug else ()):
         if name != "crh_last_error":
             getattr(L, name).restype = i32
@@ -438,6 +442,51 @@ def debug_i8_intervals(handle, rows: int, dim: int, queries, k: int, filters=Non
                                    ("hi_rec", "hi", "lo", "srow", "qpar", "dn", "c_abs", "tau"))), L)
     out["dn"], out["c_abs"] = np.float32(out["dn"][0]), np.float32(out["c_abs"][0])
     return out
+
+
+# ``variant`` of crh_debug_kth_largest (coderag_hip.h): the product's instantiations of the selection helpers
+DEBUG_SEL_FAST = {1024: 0, 512: 1, 256: 2}      # wg_kth_largest_fast<NT, NT, 256>
+DEBUG_SEL_RADIX = {1024: 3, 512: 4, 256: 5}     # wg_kth_largest<u32, NT>; | DEBUG_SEL_U64: wg_kth_largest<u64, NT> (1024, 256)
+DEBUG_SEL_U64 = 8
+DEBUG_TAIL = {1024: 0, 256: 1}                  # select_tail<NT>
+
+
+def debug_kth_largest(variant: int, keys, k, floor_key: int = 0, nblocks: int | None = None) -> np.ndarray:
+    """``crh_debug_kth_largest`` (debug library only): the ``k[s]``-th largest key of each row of ``keys`` [nsets, n] (uint32, or
+    uint64 for the ``DEBUG_SEL_U64`` variants) as the product's selection helper of that ``variant`` returns it, uint64 [nsets].
+    ``nblocks`` workgroups share the sets (default: one each)."""
+    keys = np.asarray(keys)
+    if keys.dtype not in (np.uint32, np.uint64) or keys.ndim != 2:
+        raise NativeError(E_INVALID, "keys must be a uint32 or uint64 array [nsets, n]")
+    keys = np.ascontiguousarray(keys)
+    nsets, n = keys.shape
+    ks = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint32), (nsets,)))
+    out = np.zeros((nsets,), np.uint64)
+    L = debug_lib()
+    wide = variant | DEBUG_SEL_U64 if keys.dtype == np.uint64 else variant
+    check(L.crh_debug_kth_largest(int(wide), keys.ctypes.data, nsets, n, ks.ctypes.data, int(floor_key),
+                                  nsets if nblocks is None else int(nblocks), out.ctypes.data), L)
+    return out
+
+
+def debug_select_tail(variant: int, keys, k: int, row_base: int = 0):
+    """``crh_debug_select_tail`` (debug library only): (scores float32 [k], rows int64 [k]) that ``select_tail`` of that ``variant``
+    writes for the uint64 ``keys``."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    scores, rows = np.empty((max(int(k), 0),), np.float32), np.empty((max(int(k), 0),), np.int64)
+    L = debug_lib()
+    check(L.crh_debug_select_tail(int(variant), keys.ctypes.data, keys.size, int(k), int(row_base), scores.ctypes.data, rows.ctypes.data), L)
+    return scores, rows
+
+
+def debug_tile_list(mask_words, sentinel: int = 0xffffffff):
+    """``crh_debug_tile_list`` (debug library only): (list uint32 [ntiles], len) of the two tile-list launches for the uint32
+    ``mask_words``; the list buffer holds ``sentinel`` everywhere before them."""
+    words = np.ascontiguousarray(mask_words, dtype=np.uint32).reshape(-1)
+    lst, ln = np.full((words.size,), sentinel, np.uint32), np.zeros((1,), np.uint32)
+    L = debug_lib()
+    check(L.crh_debug_tile_list(words.ctypes.data, words.size, lst.ctypes.data, ln.ctypes.data), L)
+    return lst, int(ln[0])
 
 
 def range_thresholds(thresholds, nq: int) -> np.ndarray:

@@ -835,6 +835,39 @@ int crh_debug_i8_intervals(crh_index *h, int nq, const float *queries, int k, co
                            float *hi_rec_out, float *hi_out, float *lo_out, float *srow_out, float *qpar_out, float *dn_out,
                            float *c_abs_out, float *tau_out);
 
+/* Test support: the workgroup-wide selection helpers every returned id and score passes through (crh_kernels.hpp), called by
+ * thin harness kernels with the product's own template arguments on key sets the caller supplies.  All pointers are host
+ * pointers; bad arguments are CRH_E_INVALID and launch nothing.  tests/select_cases.py, tests/test_select_gpu.py.
+ *
+ * crh_debug_kth_largest: key_out[s] = the k[s]-th largest (1-based, 1 <= k[s] <= n) of keys[s][0..n), s < nsets.  `variant` is
+ * one of the product's instantiations: CRH_DEBUG_SEL_FAST_* = wg_kth_largest_fast<NT, NB, 256> with NT = NB = 1024 / 512 / 256
+ * (u32 keys; keys <= floor_key stay out of the bucket range), CRH_DEBUG_SEL_RADIX_* = wg_kth_largest<u32, NT> (floor_key
+ * unused), and CRH_DEBUG_SEL_RADIX_1024 / _256 | CRH_DEBUG_SEL_U64 = wg_kth_largest<u64, NT> on u64 keys.  Workgroup b of
+ * nblocks takes sets b, b + nblocks, ... one after the other on the same scratch.  CRH_E_INTERNAL when the threads of a
+ * workgroup came back with different keys. */
+#define CRH_DEBUG_SEL_FAST_1024 0
+#define CRH_DEBUG_SEL_FAST_512 1
+#define CRH_DEBUG_SEL_FAST_256 2
+#define CRH_DEBUG_SEL_RADIX_1024 3
+#define CRH_DEBUG_SEL_RADIX_512 4
+#define CRH_DEBUG_SEL_RADIX_256 5
+#define CRH_DEBUG_SEL_U64 8 /* or-ed in: the keys are 64 bits wide */
+int crh_debug_kth_largest(int variant, const void *keys, unsigned nsets, unsigned n, const unsigned *k, unsigned floor_key,
+                          unsigned nblocks, unsigned long long *key_out);
+
+/* select_tail<1024> (CRH_DEBUG_TAIL_1024: k_select's) or select_tail<256> (CRH_DEBUG_TAIL_256: k_select_final's) on Ms keys
+ * (ord(score) << 32) | ~row, unique apart from 0 = "no key": the top k (1..CRH_MAX_K) as scores_out [k] / rows_out [k] with
+ * row_base added, padding (-inf, -1).  The keys are ranked out of LDS or by the general path by the kernels' own rule. */
+#define CRH_DEBUG_TAIL_1024 0
+#define CRH_DEBUG_TAIL_256 1
+int crh_debug_select_tail(int variant, const unsigned long long *keys, unsigned Ms, int k, int64_t row_base, float *scores_out,
+                          int64_t *rows_out);
+
+/* The tile list of a row mask (the two launches a filtered search makes): the ascending numbers of the non-zero words of
+ * mask_words [ntiles] into list_out, their count into *len_out.  list_out [ntiles] is read first -- it is what the list buffer
+ * holds before the launches -- and copied back whole, so the caller sees what lies past the count. */
+int crh_debug_tile_list(const uint32_t *mask_words, int64_t ntiles, uint32_t *list_out, uint32_t *len_out);
+
 /* Timing ablations of the GEMM main loop (variant 0 = the real kernel; others skip a pipeline stage and return
  * garbage).  Development aid used by tools/gemm_ablate.py; not part of the product path. */
 int crh_debug_gemm_variant(const void *x, const void *w, const float *bias, void *y, int T, int N, int K,
