@@ -14,7 +14,9 @@ bf16: the expected output is bf16_rne(float64 result), compared on BITS.  The bi
 256, where an integer needs rounding (ROUNDED_SHARE / TIE_SHARE, proved per case by tests/test_gemm_cases_host.py): a rounding
 point moved before the bias or the residual changes bits.
 
-Tolerance cases state their bound where it is computed: gelu_bound, layernorm64, ln_apply64, STATS_*.
+Tolerance cases state their bound where it is computed: gelu_bound, layernorm64, ln_apply64, STATS_*; for the hard LayerNorm rows
+(tiny variance, large offset, outliers: tests/ln_cases.py, run by the same children through identity weights) stats_bound and
+dev_stats_tolerance of that file.  No bound here or there was chosen by looking at what a GPU returned.
 """
 import functools
 import hashlib
@@ -93,6 +95,16 @@ VARIANTS = {
     "res_ln": ("crh_gemm_bf16_bias_res_ln", 2, "tol"),           # K > 1024 out of place; K <= 1024 with y == residual
     "bias_lnres": ("crh_gemm_bf16_bias_res_ln", 0, "tol"),       # K <= 1024, y != residual: k_layernorm768_res adds the residual
     "bias_res32_ln": ("crh_gemm_bf16_bias_res32_ln", 0, "tol"),  # k_layernorm768_res32
+    # the hard LayerNorm rows of tests/ln_cases.py behind identity weights (..._e12: eps = 1e-12, the first three families)
+    "hard_res_ln": ("crh_gemm_bf16_bias_res_ln", 2, "tol"),
+    "hard_bias_lnres": ("crh_gemm_bf16_bias_res_ln", 0, "tol"),
+    "hard_bias_res32_ln": ("crh_gemm_bf16_bias_res32_ln", 0, "tol"),
+    "hard_res_raw": ("crh_gemm_bf16_res_lnstats", 5, "exact"),   # the stored row on bits; stats_out within ln_cases.stats_bound
+    "hard_lnin": ("crh_gemm_bf16_lnin", 3, "tol"),               # W' = diag(gamma): the consumer GEMM is the LayerNorm itself
+    "hard_res_ln_e12": ("crh_gemm_bf16_bias_res_ln", 2, "tol"),
+    "hard_bias_lnres_e12": ("crh_gemm_bf16_bias_res_ln", 0, "tol"),
+    "hard_bias_res32_ln_e12": ("crh_gemm_bf16_bias_res32_ln", 0, "tol"),
+    "hard_res_raw_e12": ("crh_gemm_bf16_res_lnstats", 5, "exact"),
 }
 AGREE_VARIANTS = ("bias", "lnin", "res_raw", "res_norm", "res_ln", "bias_lnres", "bias_res32_ln")     # epilogues 0, 2, 3, 5
 
@@ -119,7 +131,8 @@ def cases(kernel: str):
     out = [Case(f"{kernel}-{v}-{T}x{N}x{K}", kernel, v, T, N, K) for (T, N, K) in SHAPES[kernel] for v in variants_for(T, N, K)]
     if kernel == KERNELS[0]:        # the LayerNorm-only entry involves no tiled kernel: it runs once, in the first child
         out += [Case(f"{kernel}-ln_apply-{T}x768x0", kernel, "ln_apply", T, 768, 0) for T in LN_APPLY_T]
-    return out
+    from tests import ln_cases      # (imports this module: not at the top)
+    return out + ln_cases.cases(kernel)
 
 
 def is_ragged(kernel: str, T: int) -> bool:
@@ -302,7 +315,13 @@ def layernorm64(pre: np.ndarray, gamma: np.ndarray, beta: np.ndarray, eps: float
       y     ((v - mu) rstd) g + b: |g| rstd (d mu + u |d|) from the difference, (16 + 2) u |g z| from rstd and the two products,
             u |y| from the last addition: <= u (|g| (20 Vmax / sigma + 19 |z|) + |y|), z = (v - mu) / sigma.
     E = u (24 |g| (Vmax / sigma + |z|) + |y|): the constants rounded up to one.  The bf16 result is within
-    2^-8 |ref| + (1 + 2^-8) E of the reference (the rounding acts on a value within E of it); the f32 copy of ..._res32_ln within E."""
+    2^-8 |ref| + (1 + 2^-8) E of the reference (the rounding acts on a value within E of it); the f32 copy of ..._res32_ln within E.
+    k_embed_ln forms v by two f32 additions (mirrored by its reference, so v is exact here too) and DIVIDES the two sums by 768 where
+    the others multiply by the rounded 1/768: one rounding (u) where the derivation counts two, so E covers it unchanged.
+    Rows whose mean dwarfs their spread, or whose variance is below eps (tests/ln_cases.py; sigma includes eps), need what "nothing"
+    above assumed of Vmax / sigma: the squared error of mu enters var + eps as (20 u Vmax / sigma)^2 and y as half of that times
+    |g z|, 200 u^2 (Vmax / sigma)^2 |g z|.  It stays below the 4 u |g| Vmax / sigma that rounding 20 up to 24 left over as long as
+    (Vmax / sigma) |z| <= 4 / (200 u) = 3.3e5, which tests/test_ln_cases_host.py checks for every row used (a constant row has z = 0)."""
     g, b = gamma.astype(np.float64), beta.astype(np.float64)
     mu = pre.mean(-1, keepdims=True)
     sigma = np.sqrt(((pre - mu) ** 2).mean(-1, keepdims=True) + eps)
@@ -325,7 +344,9 @@ def row_stats64(rows: np.ndarray, eps: float = LN_EPS):
 
 
 # epilogue 5's stats_out: the criterion of test_folded_producer_gemm_residual_and_statistics, against float64 statistics of the
-# rows AS STORED
+# rows AS STORED.  (Rows of order one; what the LnAcc / ln_join / k_ln_finalize arithmetic may lose on ANY row is derived in
+# tests/ln_cases.py, stats_bound: |d var| <= u (349 s^2 + 122 V s) + (50 u V)^2, |d mu| <= 34 u V -- on a unit row 2.3e-5 of rstd, these
+# constants; the hard rows are held to the larger of the two.)
 STATS_RTOL, STATS_NMR_ATOL = 2e-5, 2e-6
 
 
@@ -363,12 +384,13 @@ def ln_apply64(i: LnApplyInputs):
 
 # ---------------------------------------------------------------- coverage (DESIGN.md's table is checked against this)
 
-def coverage(records) -> dict:
-    """(kernel, epilogue, entry) -> [cases, ragged ones, multi-tile ones] over records / Cases."""
+def coverage(records, hard: bool = False) -> dict:
+    """(kernel, epilogue, entry) -> [cases, ragged ones, multi-tile ones] over records / Cases: of the matrix proper, or (hard) of the
+    hard LayerNorm rows that tests/ln_cases.py sends through the same kernels -- two tables in DESIGN.md."""
     out = {}
     for r in records:
         r = r._asdict() if isinstance(r, Case) else r
-        if r["variant"] == "ln_apply":
+        if r["variant"] not in VARIANTS or r["variant"].startswith("hard_") != hard:      # (not in VARIANTS: no tiled kernel involved)
             continue
         entry, epi, _ = VARIANTS[r["variant"]]
         c = out.setdefault((r["kernel"], epi, entry), [0, 0, 0])
@@ -381,9 +403,9 @@ def coverage(records) -> dict:
 KERNEL_NAME = {"mid": "k_gemm_mid", "nt": "k_gemm_nt", "pp": "g256::k_gemm_pp"}
 
 
-def coverage_table(records) -> str:
+def coverage_table(records, hard: bool = False) -> str:
     """The markdown table of DESIGN.md: one line per (kernel, epilogue, entry): cases / ragged T / more than one tile."""
-    cov = coverage(records)
+    cov = coverage(records, hard)
     lines = ["| kernel | epilogue | entry point | cases | ragged T | multi-tile |", "|---|---|---|---|---|---|"]
     for k in KERNELS:
         for (kk, epi, entry), (n, rag, multi) in sorted(cov.items(), key=lambda kv: (kv[0][1], kv[0][2])):
@@ -526,6 +548,9 @@ def _main(argv) -> int:
         if kernel == KERNELS[0]:
             for T in LN_APPLY_T:
                 run_ln_apply(T)
+        from tests import ln_cases
+        from types import SimpleNamespace
+        ln_cases.run_child(kernel, L, SimpleNamespace(dev=dev, guarded=guarded, guards_ok=guards_ok, sha=sha, up=up, call=call), records)
     except ffi.NativeError as e:        # an error return from the library: the one way to a non-zero exit that is not a crash
         error, rc = str(e), 3
     with open(args.out, "w") as f:

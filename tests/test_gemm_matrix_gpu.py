@@ -13,6 +13,7 @@ import time
 import pytest
 
 from tests import gemm_cases as gc
+from tests import ln_cases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,20 +66,28 @@ def test_case(runs, case):
     term of the float64 LayerNorm of the exactly known rows (gemm_cases.layernorm64 / ln_apply64); the f32 residual that
     ..._res32_ln writes back within the f32 term alone.  Epilogue 5's statistics: rtol 2e-5 (nmr: + 2e-6) of the float64 statistics of
     the rows as stored.  crh_layernorm_apply in place gives the bits it gives out of place.  Guard rows around every written
-    buffer keep their sentinel."""
+    buffer keep their sentinel.
+    The hard LayerNorm rows of tests/ln_cases.py (hard_*: tiny variance, large offsets, outliers, eps = 1e-12) reach every site
+    through identity weights and are read the same way: the standalone kernels and k_embed_ln against layernorm64's bound, epilogue
+    5's stored rows on bits and its stats_out against ln_cases.stats_bound, crh_layernorm_apply and epilogue 3 fed with the
+    device's own stats_out against ln_cases.dev_stats_tolerance; the embedding records count wrong mask words in diff_words."""
     r = _record(runs, case.kernel, case.id)
     assert r["guards_ok"], r
     if case.variant == "ln_apply":
         assert r["excess"] <= 0 and r["diff_words"] == 0, r
+        return
+    if case.variant in ln_cases.NO_GEMM_VARIANTS:
+        assert (r["T"], r["variant"]) == (case.T, case.variant) and r["excess"] is not None and r["excess"] <= 0, r
+        assert r["diff_words"] == 0 if "embed" in case.variant else r["diff_words"] is None, r
         return
     assert (r["kernel"], r["T"], r["N"], r["K"], r["variant"]) == (case.kernel, case.T, case.N, case.K, case.variant)
     if gc.VARIANTS[case.variant][2] == "exact":
         assert r["diff_words"] == 0, r
     else:
         assert r["excess"] is not None and r["excess"] <= 0, r
-    if case.variant in ("res_raw", "res_norm"):
+    if case.variant in ("res_raw", "res_norm") + ln_cases.STATS_VARIANTS:
         assert r["stats_excess"] is not None and r["stats_excess"] <= 0, r
-    if case.variant == "bias_res32_ln":
+    if case.variant in ("bias_res32_ln", "hard_bias_res32_ln", "hard_bias_res32_ln_e12"):
         assert r["aux_excess"] is not None and r["aux_excess"] <= 0, r
 
 
@@ -100,6 +109,37 @@ def test_the_three_kernels_agree_to_the_bit(runs):
         assert len({r["sha_out"] for r in recs}) == 1, (key, [(r["kernel"], r["sha_out"][:12]) for r in recs])
         if key[0] in ("res_raw", "res_norm"):
             assert recs[0]["sha_stats"] and len({r["sha_stats"] for r in recs}) == 1, (key, [(r["kernel"], r["sha_stats"][:12]) for r in recs])
+
+
+def test_the_three_kernels_agree_to_the_bit_on_the_hard_layernorm_rows(runs):
+    """What the comment above struct LnAcc promises, where it is hardest to keep: on rows of tiny variance, large offset and single
+    outliers every kernel stores the same bytes and builds the same stats_out -- and so does everything computed from them (the
+    LayerNorm kernels after the GEMM, epilogue 3 fed with those statistics)."""
+    seen = {}
+    for k in gc.KERNELS:
+        for c in ln_cases.cases(k):
+            if c.variant in ln_cases.AGREE:
+                seen.setdefault((c.variant, c.T, c.K), []).append(c)
+    assert {v for (v, _, _) in seen} == set(ln_cases.AGREE) and all(len(cs) == len(gc.KERNELS) for cs in seen.values())
+    for key, cs in sorted(seen.items()):
+        recs = [_record(runs, c.kernel, c.id) for c in cs]
+        assert len({r["sha_out"] for r in recs}) == 1, (key, [(r["kernel"], r["sha_out"][:12]) for r in recs])
+        if key[0] in ln_cases.STATS_VARIANTS:
+            assert recs[0]["sha_stats"] and len({r["sha_stats"] for r in recs}) == 1, (key, [(r["kernel"], r["sha_stats"][:12]) for r in recs])
+
+
+def test_the_hard_row_records_are_the_ones_design_md_tabulates(runs):
+    """DESIGN.md's second coverage table (the hard LayerNorm rows) against what the children ran."""
+    records = [r for k in gc.KERNELS for r in _record_list(runs, k)]
+    table = gc.coverage_table(records, hard=True)
+    assert table == gc.coverage_table(CASES, hard=True) and table in open(os.path.join(ROOT, "DESIGN.md")).read()
+    for k in gc.KERNELS:        # every tiled kernel ran every site that goes through one
+        assert {e for (kk, e, _) in gc.coverage(records, hard=True) if kk == k} == {0, 2, 3, 5}
+
+
+def _record_list(runs, kernel):
+    assert "not_run" not in runs[kernel], runs[kernel]["not_run"]
+    return runs[kernel]["records"]
 
 
 def test_the_records_cover_every_kernel_epilogue_pair_as_design_md_says(runs):
