@@ -1,0 +1,572 @@
+// crh_graph.hip -- the call graph beside the index: batched, bit-parallel, level-synchronous BFS over CSRs in
+// device memory, the listing of what it reached, the reached nodes as a row bitmap, and one shortest path.  gfx950 only.
+//
+// Bit q of a 64-bit word per node belongs to source set ("query") q, so one pass over the graph advances up to 64 searches:
+// the "lane q = query q" idiom of crh_lex.hip with the lanes inside a word.  Every result is a set or a minimum depth, and OR
+// does not depend on order: the outputs are exact and the same from run to run.
+//
+//   k_graph_sources   level 0 from the source lists (atomicOr: several queries may name one node)
+//   k_graph_level     one launch per level, PULL form: next[u] = (OR of front[v] over u's neighbours v in the CSR opposite to
+//                     the direction of travel) & ~seen[u].  next[u] and seen[u] have one writer, the lane that owns u; front is
+//                     the level the previous launch finished.  Nothing inside a launch waits for another workgroup.  A
+//                     workgroup ORs its new words together and makes one device-scope atomicOr into active[d]; the next
+//                     launch reads active[d - 1] first and leaves when it is 0, so the levels enqueued behind a dead frontier
+//                     cost a launch each and nothing else, and the host never waits between levels.
+//   k_graph_unself    without include_self: the source bits leave `seen` (they stay in level 0)
+//   k_graph_list      one workgroup per query: the nodes of levels first_level .. max_hops in (depth, node id) order, compacted
+//                     by ballots and a scan over the workgroup's waves; the exact count
+//   k_graph_row_words row -> node -> bit q of seen, as the validity words crh_index_row_mask writes
+//   k_graph_path      one wave walks back from the target's level, taking the smallest neighbour that lies in the level before
+//
+// One lane per node; a node whose adjacency list has CRH_GRAPH_WAVE_DEGREE entries or more is walked by its whole wave (64
+// entries per step, OR-reduced over the lanes), the shorter ones by their own lane.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "crh_common.h"
+
+namespace crh {
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr int kGraphThreads = 256;
+constexpr int kGraphWaves = kGraphThreads / 64;
+constexpr int kGraphListPerLane = 4;           // nodes a lane of k_graph_list looks at per step (1024 per workgroup)
+
+__device__ __forceinline__ u64 shfl64(u64 v, int src)
+{
+    const unsigned lo = __shfl((unsigned)v, src), hi = __shfl((unsigned)(v >> 32), src);
+    return ((u64)hi << 32) | lo;
+}
+
+__device__ __forceinline__ u64 wave_or(u64 v)
+{
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        lo |= __shfl_xor(lo, o);
+        hi |= __shfl_xor(hi, o);
+    }
+    return ((u64)hi << 32) | lo;
+}
+
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
+
+struct SourceArgs {
+    int64_t off[CRH_GRAPH_MAX_QUERIES + 1];   // by value: at most 65 offsets
+    const int32_t *nodes;
+    int nq;
+    int64_t n_nodes;
+    u64 *level0;
+    u64 *active0;
+};
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_sources(const SourceArgs a)
+{
+    const int64_t total = a.off[a.nq];
+    for (int64_t i = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t v = a.nodes[i];
+        if (v < 0 || v >= a.n_nodes) continue;                       // (-1: padding; a device list may hold anything)
+        int q = 0;
+        while (q + 1 < a.nq && a.off[q + 1] <= i) ++q;
+        atomicOr(a.level0 + v, 1ull << q);
+        atomicOr(a.active0, 1ull << q);
+    }
+}
+
+struct LevelArgs {
+    const int64_t *off[2];
+    const int32_t *adj[2];
+    int ncsr;
+    const u64 *front;
+    u64 *next;
+    u64 *seen;
+    const u64 *active_prev;
+    u64 *active_cur;
+    int64_t n;
+    u64 qmask;
+};
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_level(const LevelArgs a)
+{
+    if (*a.active_prev == 0ull) return;                              // (written by the launch before this one: the frontier died)
+    __shared__ u64 s_or[kGraphWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 mine = 0ull;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        const bool in = u < a.n;
+        const u64 sn = in ? a.seen[u] : ~0ull;
+        const bool want = (~sn & a.qmask) != 0ull;                   // (a node every query has seen already reads no list)
+        u64 acc = 0ull;
+        for (int c = 0; c < a.ncsr; ++c) {
+            int64_t b = 0, e = 0;
+            if (want) {
+                b = a.off[c][u];
+                e = a.off[c][u + 1];
+            }
+            const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
+            if (!wide)
+                for (int64_t i = b; i < e; ++i) acc |= a.front[a.adj[c][i]];
+            u64 m = __ballot(wide);
+            while (m) {
+                const int src = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
+                u64 part = 0ull;
+                for (int64_t i = bb + lane; i < ee; i += 64) part |= a.front[a.adj[c][i]];
+                part = wave_or(part);
+                if (lane == src) acc |= part;
+            }
+        }
+        const u64 nw = acc & ~sn;
+        if (nw) {                                                    // (the level was zeroed before the first launch)
+            a.next[u] = nw;
+            a.seen[u] = sn | nw;
+        }
+        mine |= nw;
+    }
+    mine = wave_or(mine);
+    if (lane == 0) s_or[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 all = 0ull;
+        for (int w = 0; w < kGraphWaves; ++w) all |= s_or[w];
+        if (all) atomicOr(a.active_cur, all);
+    }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_unself(const u64 *level0, u64 *seen, int64_t n)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) {
+        const u64 s = level0[v];
+        if (s) seen[v] &= ~s;
+    }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_list(const u64 *levels, int64_t n, int first_level, int max_hops, int limit,
+                                                              int32_t *out_nodes, int32_t *out_depth, int64_t *out_count)
+{
+    __shared__ int s_cnt[kGraphWaves];
+    const int q = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int64_t kStep = (int64_t)kGraphThreads * kGraphListPerLane;
+    int64_t total = 0;                                               // (the same in every thread)
+    for (int d = first_level; d <= max_hops; ++d) {
+        const u64 *lv = levels + (int64_t)d * n;
+        for (int64_t base = 0; base < n; base += kStep) {
+            // wave w takes the nodes base + w * 256 .. + 256, its pass j the 64 of them from j * 64: ascending node ids
+            const int64_t first = base + (int64_t)wave * 64 * kGraphListPerLane;
+            bool hit[kGraphListPerLane];
+            int before[kGraphListPerLane];
+            int wcount = 0;
+#pragma unroll
+            for (int j = 0; j < kGraphListPerLane; ++j) {
+                const int64_t v = first + j * 64 + lane;
+                hit[j] = v < n && ((lv[v] >> q) & 1ull);
+                const u64 bal = __ballot(hit[j]);
+                before[j] = wcount + __popcll(bal & ((1ull << lane) - 1ull));
+                wcount += __popcll(bal);
+            }
+            if (lane == 0) s_cnt[wave] = wcount;
+            __syncthreads();
+            int pre = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < kGraphWaves; ++w) {
+                if (w < wave) pre += s_cnt[w];
+                all += s_cnt[w];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < kGraphListPerLane; ++j) {
+                const int64_t pos = total + pre + before[j];
+                if (hit[j] && pos < limit) {
+                    out_nodes[(int64_t)q * limit + pos] = (int32_t)(first + j * 64 + lane);
+                    out_depth[(int64_t)q * limit + pos] = d;
+                }
+            }
+            total += all;
+        }
+    }
+    for (int64_t p = total + threadIdx.x; p < limit; p += kGraphThreads) {
+        out_nodes[(int64_t)q * limit + p] = -1;
+        out_depth[(int64_t)q * limit + p] = -1;
+    }
+    if (threadIdx.x == 0) out_count[q] = total;
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_row_words(const int32_t *row_node, int64_t n_rows, const u64 *seen, int64_t n_nodes,
+                                                                   int q, uint32_t *out, int64_t n_words)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t pairs = (n_words + 1) / 2;                         // a wave writes two words
+    for (int64_t p = (int64_t)blockIdx.x * kGraphWaves + (threadIdx.x >> 6); p < pairs; p += (int64_t)gridDim.x * kGraphWaves) {
+        const int64_t r = p * 64 + lane;
+        bool bit = false;
+        if (r < n_rows) {
+            const int64_t v = row_node[r];
+            bit = v >= 0 && v < n_nodes && ((seen[v] >> q) & 1ull);
+        }
+        const u64 bal = __ballot(bit);
+        if (lane == 0) out[2 * p] = (uint32_t)bal;
+        if (lane == 32 && 2 * p + 1 < n_words) out[2 * p + 1] = (uint32_t)(bal >> 32);
+    }
+}
+
+struct PathArgs {
+    const int64_t *off[2];
+    const int32_t *adj[2];
+    int ncsr;
+    const u64 *levels;
+    int64_t n;
+    int q;
+    int64_t target;
+    int max_hops;
+    int32_t *out;        // [CRH_GRAPH_MAX_HOPS + 2]: the length, then the nodes from the source to the target
+};
+
+__global__ __launch_bounds__(64) void k_graph_path(const PathArgs a)
+{
+    const int lane = threadIdx.x;
+    const bool at = lane <= a.max_hops && ((a.levels[(int64_t)lane * a.n + a.target] >> a.q) & 1ull);
+    const u64 where = __ballot(at);
+    if (!where) {
+        if (lane == 0) a.out[0] = 0;
+        return;
+    }
+    const int depth = __ffsll((long long)where) - 1;
+    int64_t cur = a.target;
+    if (lane == 0) {
+        a.out[0] = depth + 1;
+        a.out[1 + depth] = (int32_t)cur;
+    }
+    for (int d = depth; d >= 1; --d) {
+        const u64 *prev = a.levels + (int64_t)(d - 1) * a.n;
+        int best = 0x7fffffff;
+        for (int c = 0; c < a.ncsr; ++c) {
+            const int64_t b = a.off[c][cur], e = a.off[c][cur + 1];
+            for (int64_t i = b + lane; i < e; i += 64) {
+                const int p = a.adj[c][i];
+                if ((prev[p] >> a.q) & 1ull) best = min(best, p);
+            }
+        }
+        best = wave_min(best);
+        if (best == 0x7fffffff) {                                    // (levels that are not this graph's BFS: no path, never a wild index)
+            if (lane == 0) a.out[0] = 0;
+            return;
+        }
+        cur = best;
+        if (lane == 0) a.out[d] = best;
+    }
+}
+
+int graph_alloc(void **p, int64_t bytes)
+{
+    *p = nullptr;
+    CRH_HIP(hipMalloc(p, (size_t)std::max<int64_t>(bytes, 8)));
+    return CRH_OK;
+}
+
+int check_csr(const char *what, int64_t n_nodes, int64_t n_edges, const int64_t *off, const int32_t *adj)
+{
+    if (!off || (n_edges > 0 && !adj)) return fail(CRH_E_INVALID, "graph_set_relation: %s: NULL pointer", what);
+    if (off[0] != 0 || off[n_nodes] != n_edges)
+        return fail(CRH_E_INVALID, "graph_set_relation: %s offsets run from %lld to %lld, not 0 to %lld", what, (long long)off[0], (long long)off[n_nodes], (long long)n_edges);
+    for (int64_t v = 0; v < n_nodes; ++v)
+        if (off[v + 1] < off[v]) return fail(CRH_E_INVALID, "graph_set_relation: %s offsets decrease at node %lld", what, (long long)v);
+    for (int64_t i = 0; i < n_edges; ++i)
+        if (adj[i] < 0 || adj[i] >= n_nodes) return fail(CRH_E_INVALID, "graph_set_relation: %s entry %lld names node %d of %lld", what, (long long)i, adj[i], (long long)n_nodes);
+    return CRH_OK;
+}
+
+unsigned graph_blocks(int64_t items, int64_t per_block)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)current_device_cus() * 8));
+}
+
+}  // namespace
+}  // namespace crh
+
+struct crh_graph_relation {
+    bool set = false;
+    int64_t n_edges = 0;
+    int64_t *off[2] = {nullptr, nullptr};    // 0: along the edges (a node's targets), 1: against them (its sources)
+    int32_t *adj[2] = {nullptr, nullptr};
+};
+
+struct crh_graph {
+    int device = 0;
+    int64_t n_nodes = 0;
+    crh_graph_relation rel[CRH_GRAPH_MAX_RELATIONS];
+    int32_t *path = nullptr;                 // CRH_GRAPH_MAX_HOPS + 2 ints
+    int32_t *sources = nullptr;              // the upload of a host source list
+    int64_t cap_sources = 0;
+};
+
+using namespace crh;
+
+namespace {
+
+void graph_free_relation(crh_graph_relation &r)
+{
+    for (int c = 0; c < 2; ++c) {
+        if (r.off[c]) (void)hipFree(r.off[c]);
+        if (r.adj[c]) (void)hipFree(r.adj[c]);
+        r.off[c] = nullptr;
+        r.adj[c] = nullptr;
+    }
+    r.set = false;
+    r.n_edges = 0;
+}
+
+// The CSRs a traversal in `direction` PULLS through: travelling along the edges, a node looks at its sources (the reverse CSR).
+int graph_pull(const crh_graph *g, int rel, int direction, const int64_t **off, const int32_t **adj)
+{
+    const crh_graph_relation &r = g->rel[rel];
+    int n = 0;
+    if (direction == CRH_GRAPH_ALONG || direction == CRH_GRAPH_BOTH) {
+        off[n] = r.off[1];
+        adj[n++] = r.adj[1];
+    }
+    if (direction == CRH_GRAPH_AGAINST || direction == CRH_GRAPH_BOTH) {
+        off[n] = r.off[0];
+        adj[n++] = r.adj[0];
+    }
+    return n;
+}
+
+int graph_check_rel(const crh_graph *g, int rel, int direction, const char *who)
+{
+    if (!g) return fail(CRH_E_INVALID, "graph handle is NULL");
+    if (rel < 0 || rel >= CRH_GRAPH_MAX_RELATIONS || !g->rel[rel].set) return fail(CRH_E_INVALID, "%s: relation %d is not set", who, rel);
+    if (direction != CRH_GRAPH_ALONG && direction != CRH_GRAPH_AGAINST && direction != CRH_GRAPH_BOTH)
+        return fail(CRH_E_INVALID, "%s: direction=%d is none of CRH_GRAPH_ALONG / _AGAINST / _BOTH", who, direction);
+    return CRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crh_graph_create(int device, int64_t n_nodes, crh_graph **out)
+{
+    if (!out) return fail(CRH_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(CRH_E_NODEVICE, "no usable device %d", device);
+    DeviceGuard g(device);
+    if (!g.ok) return fail(CRH_E_NODEVICE, "hipSetDevice(%d) failed", device);
+    crh_graph *h = new crh_graph();
+    h->device = device;
+    h->n_nodes = n_nodes;
+    void *p = nullptr;
+    const int rc = graph_alloc(&p, 4 * (CRH_GRAPH_MAX_HOPS + 2));
+    h->path = static_cast<int32_t *>(p);
+    if (rc != CRH_OK) {
+        crh_graph_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return CRH_OK;
+}
+
+int crh_graph_destroy(crh_graph *g)
+{
+    if (!g) return CRH_OK;
+    DeviceGuard guard(g->device);
+    (void)hipDeviceSynchronize();
+    for (auto &r : g->rel) graph_free_relation(r);
+    if (g->path) (void)hipFree(g->path);
+    if (g->sources) (void)hipFree(g->sources);
+    delete g;
+    return CRH_OK;
+}
+
+int crh_graph_count(crh_graph *g, int rel, int64_t *nodes_out, int64_t *edges_out)
+{
+    if (!g) return fail(CRH_E_INVALID, "graph handle is NULL");
+    if (rel < 0 || rel >= CRH_GRAPH_MAX_RELATIONS) return fail(CRH_E_INVALID, "graph_count: relation %d outside 0..%d", rel, CRH_GRAPH_MAX_RELATIONS - 1);
+    if (nodes_out) *nodes_out = g->n_nodes;
+    if (edges_out) *edges_out = g->rel[rel].set ? g->rel[rel].n_edges : -1;
+    return CRH_OK;
+}
+
+int crh_graph_set_relation(crh_graph *g, int rel, int64_t n_edges, const int64_t *off_fwd_host, const int32_t *adj_fwd_host,
+                           const int64_t *off_rev_host, const int32_t *adj_rev_host)
+{
+    if (!g) return fail(CRH_E_INVALID, "graph handle is NULL");
+    if (rel < 0 || rel >= CRH_GRAPH_MAX_RELATIONS) return fail(CRH_E_INVALID, "graph_set_relation: relation %d outside 0..%d", rel, CRH_GRAPH_MAX_RELATIONS - 1);
+    if (n_edges < 0) return fail(CRH_E_INVALID, "graph_set_relation: n_edges=%lld is negative", (long long)n_edges);
+    CRH_TRY(check_csr("forward", g->n_nodes, n_edges, off_fwd_host, adj_fwd_host));
+    CRH_TRY(check_csr("reverse", g->n_nodes, n_edges, off_rev_host, adj_rev_host));
+    DeviceGuard guard(g->device);
+    CRH_HIP(hipDeviceSynchronize());       // (a traversal in flight reads the arrays this call releases)
+    crh_graph_relation fresh;
+    const int64_t *offs[2] = {off_fwd_host, off_rev_host};
+    const int32_t *adjs[2] = {adj_fwd_host, adj_rev_host};
+    int rc = CRH_OK;
+    for (int c = 0; c < 2 && rc == CRH_OK; ++c) {
+        void *po = nullptr, *pa = nullptr;
+        rc = graph_alloc(&po, (g->n_nodes + 1) * 8);
+        fresh.off[c] = static_cast<int64_t *>(po);
+        if (rc == CRH_OK) rc = graph_alloc(&pa, n_edges * 4);
+        fresh.adj[c] = static_cast<int32_t *>(pa);
+        if (rc == CRH_OK && hipMemcpy(fresh.off[c], offs[c], (size_t)(g->n_nodes + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(CRH_E_HIP, "graph_set_relation: the upload of the offsets failed");
+        if (rc == CRH_OK && n_edges > 0 && hipMemcpy(fresh.adj[c], adjs[c], (size_t)n_edges * 4, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(CRH_E_HIP, "graph_set_relation: the upload of the adjacency failed");
+    }
+    if (rc != CRH_OK) {
+        graph_free_relation(fresh);
+        return rc;                          // (the relation as it was stays)
+    }
+    graph_free_relation(g->rel[rel]);
+    fresh.set = true;
+    fresh.n_edges = n_edges;
+    g->rel[rel] = fresh;
+    return CRH_OK;
+}
+
+int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes, int sources_on_device,
+                  int max_hops, int include_self, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev, void *stream)
+{
+    CRH_TRY(graph_check_rel(g, rel, direction, "graph_bfs"));
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_bfs: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_bfs: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    if (!src_off_host) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
+    if (src_off_host[0] != 0) return fail(CRH_E_INVALID, "graph_bfs: src_off[0]=%lld, not 0", (long long)src_off_host[0]);
+    for (int q = 0; q < nq; ++q)
+        if (src_off_host[q + 1] < src_off_host[q]) return fail(CRH_E_INVALID, "graph_bfs: src_off decreases at query %d", q);
+    const int64_t total = src_off_host[nq];
+    if (total > 0 && !src_nodes) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
+    if (!sources_on_device)
+        for (int64_t i = 0; i < total; ++i)
+            if (src_nodes[i] < -1 || src_nodes[i] >= g->n_nodes)
+                return fail(CRH_E_INVALID, "graph_bfs: source %lld names node %d of %lld", (long long)i, src_nodes[i], (long long)g->n_nodes);
+    const int64_t n = g->n_nodes;
+    if (n == 0) return CRH_OK;
+    if (!levels_dev || !seen_dev || !active_dev) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u64 *levels = reinterpret_cast<u64 *>(levels_dev), *seen = reinterpret_cast<u64 *>(seen_dev), *active = reinterpret_cast<u64 *>(active_dev);
+    const int32_t *nodes_dev = src_nodes;
+    if (!sources_on_device && total > 0) {
+        if (g->cap_sources < total) {
+            CRH_HIP(hipStreamSynchronize(st));   // (a BFS in flight on this stream still reads the old upload)
+            if (g->sources) (void)hipFree(g->sources);
+            g->sources = nullptr;
+            g->cap_sources = 0;
+            void *p = nullptr;
+            CRH_TRY(graph_alloc(&p, std::max<int64_t>(total, 1024) * 4));
+            g->sources = static_cast<int32_t *>(p);
+            g->cap_sources = std::max<int64_t>(total, 1024);
+        }
+        CRH_HIP(hipMemcpyAsync(g->sources, src_nodes, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        CRH_HIP(hipStreamSynchronize(st));       // (the caller may free its list on return; pageable memory is staged anyway)
+        nodes_dev = g->sources;
+    }
+    CRH_HIP(hipMemsetAsync(levels, 0, (size_t)(max_hops + 1) * (size_t)n * 8, st));
+    CRH_HIP(hipMemsetAsync(active, 0, (size_t)(max_hops + 1) * 8, st));
+    if (total > 0) {
+        SourceArgs sa{};
+        for (int q = 0; q <= nq; ++q) sa.off[q] = src_off_host[q];
+        sa.nodes = nodes_dev;
+        sa.nq = nq;
+        sa.n_nodes = n;
+        sa.level0 = levels;
+        sa.active0 = active;
+        hipLaunchKernelGGL(k_graph_sources, dim3(graph_blocks(total, kGraphThreads)), dim3(kGraphThreads), 0, st, sa);
+    }
+    CRH_HIP(hipMemcpyAsync(seen, levels, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    LevelArgs la{};
+    la.ncsr = graph_pull(g, rel, direction, la.off, la.adj);
+    la.seen = seen;
+    la.n = n;
+    la.qmask = nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+    const unsigned blocks = graph_blocks(n, kGraphThreads);
+    for (int d = 1; d <= max_hops; ++d) {
+        la.front = levels + (int64_t)(d - 1) * n;
+        la.next = levels + (int64_t)d * n;
+        la.active_prev = active + (d - 1);
+        la.active_cur = active + d;
+        hipLaunchKernelGGL(k_graph_level, dim3(blocks), dim3(kGraphThreads), 0, st, la);
+    }
+    if (!include_self) hipLaunchKernelGGL(k_graph_unself, dim3(blocks), dim3(kGraphThreads), 0, st, levels, seen, n);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_list(crh_graph *g, int nq, const uint64_t *levels_dev, int max_hops, int first_level, int limit, int32_t *out_nodes_dev,
+                   int32_t *out_depth_dev, int64_t *out_count_dev, void *stream)
+{
+    if (!g) return fail(CRH_E_INVALID, "graph handle is NULL");
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_list: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_list: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    if (first_level < 0 || first_level > max_hops) return fail(CRH_E_INVALID, "graph_list: first_level=%d outside 0..%d", first_level, max_hops);
+    if (limit < 0 || limit > CRH_GRAPH_MAX_LIMIT) return fail(CRH_E_INVALID, "graph_list: limit=%d outside 0..%d", limit, CRH_GRAPH_MAX_LIMIT);
+    if (!out_count_dev || (limit > 0 && (!out_nodes_dev || !out_depth_dev)) || (g->n_nodes > 0 && !levels_dev))
+        return fail(CRH_E_INVALID, "graph_list: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_graph_list, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, reinterpret_cast<const u64 *>(levels_dev), g->n_nodes, first_level,
+                       max_hops, limit, out_nodes_dev, out_depth_dev, out_count_dev);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint64_t *seen_dev, int64_t n_nodes, int q, uint32_t *out_words_dev,
+                        int64_t n_words, void *stream)
+{
+    if (n_rows < 0 || n_rows >= (1LL << 31) || n_nodes < 0) return fail(CRH_E_INVALID, "graph_row_words: n_rows=%lld, n_nodes=%lld", (long long)n_rows, (long long)n_nodes);
+    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_row_words: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
+    if (n_words < ceil_div(n_rows, 32)) return fail(CRH_E_INVALID, "graph_row_words: %lld words for %lld rows", (long long)n_words, (long long)n_rows);
+    if (n_words == 0) return CRH_OK;
+    if (!out_words_dev || (n_rows > 0 && (!row_node_dev || (n_nodes > 0 && !seen_dev)))) return fail(CRH_E_INVALID, "graph_row_words: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_graph_row_words, dim3(graph_blocks((n_words + 1) / 2, kGraphWaves)), dim3(kGraphThreads), 0, st, row_node_dev, n_rows,
+                       reinterpret_cast<const u64 *>(seen_dev), n_nodes, q, out_words_dev, n_words);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_dev, int q, int64_t target, int max_hops, int32_t *out_nodes_host,
+                   int *out_len, void *stream)
+{
+    CRH_TRY(graph_check_rel(g, rel, direction, "graph_path"));
+    if (!out_len || !out_nodes_host) return fail(CRH_E_INVALID, "graph_path: NULL pointer");
+    *out_len = 0;
+    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_path: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_path: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    if (target < 0 || target >= g->n_nodes) return fail(CRH_E_INVALID, "graph_path: target=%lld is no node of %lld", (long long)target, (long long)g->n_nodes);
+    if (!levels_dev) return fail(CRH_E_INVALID, "graph_path: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PathArgs a{};
+    a.ncsr = graph_pull(g, rel, direction, a.off, a.adj);
+    a.levels = reinterpret_cast<const u64 *>(levels_dev);
+    a.n = g->n_nodes;
+    a.q = q;
+    a.target = target;
+    a.max_hops = max_hops;
+    a.out = g->path;
+    hipLaunchKernelGGL(k_graph_path, dim3(1), dim3(64), 0, st, a);
+    CRH_HIP(hipGetLastError());
+    int32_t got[CRH_GRAPH_MAX_HOPS + 2] = {};
+    CRH_HIP(hipMemcpyAsync(got, g->path, sizeof got, hipMemcpyDeviceToHost, st));
+    CRH_HIP(hipStreamSynchronize(st));
+    const int len = got[0];
+    if (len < 0 || len > max_hops + 1) return fail(CRH_E_INTERNAL, "graph_path: a path of %d nodes", len);
+    for (int i = 0; i < len; ++i) out_nodes_host[i] = got[1 + i];
+    *out_len = len;
+    return CRH_OK;
+}
+
+}  // extern "C"

@@ -37,6 +37,10 @@ REGEX_MAX_STATES, REGEX_MAX_TABLE_BYTES = 256, 32768   # CRH_REGEX_MAX_STATES / 
 FUZZY_MAX_EDITS = 3    # CRH_FUZZY_MAX_EDITS: byte edits one crh_text_fuzzy allows at most
 TEXT_ALL, TEXT_ANY = 0, 1   # CRH_TEXT_ALL / CRH_TEXT_ANY
 FACET_LDS_BINS = 8192       # CRH_FACET_LDS_BINS: up to this many bins crh_index_facet counts in LDS, above it by runs of equal codes
+GRAPH_MAX_RELATIONS, GRAPH_MAX_QUERIES, GRAPH_MAX_HOPS = 8, 64, 16   # CRH_GRAPH_MAX_RELATIONS / _MAX_QUERIES / _MAX_HOPS
+GRAPH_WAVE_DEGREE = 64      # CRH_GRAPH_WAVE_DEGREE: adjacency lists of at least so many entries are walked by a whole wave
+GRAPH_ALONG, GRAPH_AGAINST, GRAPH_BOTH = 0, 1, 2   # CRH_GRAPH_*: the direction of travel
+GRAPH_DIRECTIONS = {"callees": GRAPH_ALONG, "callers": GRAPH_AGAINST, "both": GRAPH_BOTH}
 FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
@@ -64,6 +68,8 @@ EXPORTS = (
     "crh_text_create", "crh_text_destroy", "crh_text_clear", "crh_text_count", "crh_text_append", "crh_text_match", "crh_text_regex",
     "crh_text_fuzzy",
     "crh_index_facet", "crh_search_range_facet", "crh_facet_select",
+    "crh_graph_create", "crh_graph_destroy", "crh_graph_count", "crh_graph_set_relation", "crh_graph_bfs", "crh_graph_list",
+    "crh_graph_row_words", "crh_graph_path",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
@@ -233,6 +239,14 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_index_facet.argtypes = [vp, i32, C.POINTER(Condition), i32, i32, vp, vp, vp]
     L.crh_search_range_facet.argtypes = [vp, i32, vp, i32, vp, C.POINTER(Condition), i32, i32, i32, vp, vp, vp]
     L.crh_facet_select.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
+    L.crh_graph_create.argtypes = [i32, i64, C.POINTER(vp)]
+    L.crh_graph_destroy.argtypes = [vp]
+    L.crh_graph_count.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64)]
+    L.crh_graph_set_relation.argtypes = [vp, i32, i64, vp, vp, vp, vp]
+    L.crh_graph_bfs.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.crh_graph_list.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.crh_graph_row_words.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp]
+    L.crh_graph_path.argtypes = [vp, i32, i32, vp, i32, i64, i32, vp, C.POINTER(i32), vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -1298,6 +1312,181 @@ class Text:
         check(lib().crh_text_fuzzy(self._handle(), data.ctypes.data if data.size else None, int(data.size), edits, int(bool(fold_case)),
                                    _ptr(mask), _ptr(out), c if count else None, stream))
         return out, ([int(v) for v in c[:levels]] if count else None)
+
+
+def gather_rows_i32(rows, row_base: int, col, fill: int = 0, stream: int = 0):
+    """``crh_gather_rows_i32``: ``out[i] = col[rows[i] - row_base]`` where this shard owns the row, ``fill`` elsewhere (padding
+    too); ``rows`` an int64 device tensor of GLOBAL rows, ``col`` the shard's int32 device column.  int32, the shape of ``rows``."""
+    import torch
+    _typed(rows, "int64", "rows")
+    _typed(col, "int32", "col")
+    if not _is_dev(rows) or not _is_dev(col):
+        raise NativeError(E_INVALID, "gather_rows_i32 takes device tensors")
+    out = torch.empty(tuple(rows.shape), dtype=torch.int32, device=rows.device)
+    use_device(rows.device.index)
+    check(lib().crh_gather_rows_i32(int(rows.numel()), _ptr(rows), int(row_base), int(col.numel()), _ptr(col) if col.numel() else None, int(fill),
+                                    _ptr(out), stream))
+    return out
+
+
+def graph_direction(direction) -> int:
+    """``"callees"`` / ``"callers"`` / ``"both"`` (or the CRH_GRAPH_* number) as ``crh_graph_bfs`` takes it."""
+    if isinstance(direction, str) and direction in GRAPH_DIRECTIONS:
+        return GRAPH_DIRECTIONS[direction]
+    if isinstance(direction, (int, np.integer)) and not isinstance(direction, bool) and int(direction) in GRAPH_DIRECTIONS.values():
+        return int(direction)
+    raise NativeError(E_INVALID, f"graph direction {direction!r} is not one of {sorted(GRAPH_DIRECTIONS)}")
+
+
+def graph_sources(sources) -> tuple[np.ndarray, np.ndarray]:
+    """Host source sets (an iterable of iterables of node ids) as the CSR ``crh_graph_bfs`` takes: (src_off int64 [nq + 1],
+    src_nodes int32)."""
+    sets = [np.asarray(list(s), np.int64).reshape(-1) for s in sources]
+    off = np.zeros(len(sets) + 1, np.int64)
+    np.cumsum([s.size for s in sets], out=off[1:])
+    nodes = np.concatenate(sets).astype(np.int32) if sets and off[-1] else np.zeros((0,), np.int32)
+    return off, nodes
+
+
+class Graph:
+    """Owning wrapper of one ``crh_graph`` handle: up to ``GRAPH_MAX_RELATIONS`` relations over ``n_nodes``
+    nodes, and the workspace of its traversals -- levels u64 [hops + 1, n_nodes], seen [n_nodes], active [GRAPH_MAX_HOPS + 1],
+    held as int64 device tensors, sized by the first BFS that needs them.  A BFS overwrites the workspace: list, row_words and
+    path read what the LAST bfs left unless they are handed tensors of their own."""
+    bfs_calls = 0         # crh_graph_bfs calls issued by all handles (tests count the traversals of a job)
+
+    def __init__(self, n_nodes: int, device: int = 0):
+        self.device, self.n_nodes = device, int(n_nodes)
+        h = C.c_void_p()
+        check(lib().crh_graph_create(device, int(n_nodes), C.byref(h)))
+        self._h = h
+        self.levels = self.seen = self.active = None
+        self.last = None      # (nq, max_hops) of the last bfs
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.crh_graph_destroy(self._h)
+            self._h = None
+            self.levels = self.seen = self.active = None
+
+    __del__ = close
+
+    def _handle(self):
+        if not self._h:
+            raise NativeError(E_INVALID, "graph handle is closed")
+        return self._h
+
+    def count(self, rel: int = 0) -> tuple[int, int]:
+        """(nodes, edges of relation ``rel``; -1: not set)."""
+        n, e = C.c_int64(0), C.c_int64(0)
+        check(lib().crh_graph_count(self._handle(), int(rel), C.byref(n), C.byref(e)))
+        return int(n.value), int(e.value)
+
+    def set_relation(self, rel: int, off_fwd, adj_fwd, off_rev, adj_rev) -> None:
+        """Relation ``rel`` from two host CSRs over the node ids (``graph.build_csr`` makes them); replaces what was there."""
+        of, orv = (np.ascontiguousarray(o, dtype=np.int64).reshape(-1) for o in (off_fwd, off_rev))
+        af, ar = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (adj_fwd, adj_rev))
+        if of.size != self.n_nodes + 1 or orv.size != self.n_nodes + 1 or af.size != ar.size:
+            raise NativeError(E_INVALID, f"set_relation: offsets of {of.size} / {orv.size} entries for {self.n_nodes} nodes, {af.size} / {ar.size} edges")
+        check(lib().crh_graph_set_relation(self._handle(), int(rel), int(af.size), of.ctypes.data, af.ctypes.data if af.size else None,
+                                           orv.ctypes.data, ar.ctypes.data if ar.size else None))
+
+    def _workspace(self, max_hops: int):
+        import torch
+        dev = f"cuda:{self.device}"
+        if self.levels is None or int(self.levels.shape[0]) < max_hops + 1:
+            self.levels = None                                         # (released before the larger one is taken)
+            self.levels = torch.empty((max_hops + 1, self.n_nodes), dtype=torch.int64, device=dev)
+        if self.seen is None:
+            self.seen = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
+            self.active = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
+
+    def bfs(self, rel: int, direction, sources, max_hops: int, include_self: bool = False, stream: int = 0):
+        """``crh_graph_bfs`` from up to ``GRAPH_MAX_QUERIES`` source sets: ``sources`` is an iterable of iterables of node ids
+        (host), or an int32 device tensor [nq, k] whose rows are the sets (-1: padding), complete on ``stream``.  Returns
+        ``(levels [max_hops + 1, n_nodes], seen [n_nodes], active [max_hops + 1])``: int64 device tensors holding the u64
+        words, views of the handle's workspace.  Only enqueues."""
+        max_hops = int(max_hops)
+        on_dev = _is_dev(sources)
+        if on_dev:
+            _typed(sources, "int32", "sources")
+            if sources.ndim != 2:
+                raise NativeError(E_INVALID, "device sources must be an int32 tensor [nq, k]")
+            nq, k = int(sources.shape[0]), int(sources.shape[1])
+            off, nodes = np.arange(nq + 1, dtype=np.int64) * k, sources
+        else:
+            off, nodes = graph_sources(sources)
+            nq = off.size - 1
+        hops = max_hops if 1 <= max_hops <= GRAPH_MAX_HOPS else 1           # (a max_hops the library refuses allocates one level)
+        self._workspace(hops)
+        Graph.bfs_calls += 1
+        check(lib().crh_graph_bfs(self._handle(), int(rel), graph_direction(direction), nq, off.ctypes.data,
+                                  _ptr(nodes) if int(off[-1]) else None, on_dev, max_hops, int(bool(include_self)),
+                                  _ptr(self.levels), _ptr(self.seen), _ptr(self.active), stream))
+        self.last = (nq, max_hops)
+        return self.levels[: max_hops + 1], self.seen, self.active[: max_hops + 1]
+
+    def list(self, limit: int, first_level: int = 1, nq: int | None = None, max_hops: int | None = None, levels=None, stream: int = 0):
+        """``crh_graph_list`` over the last BFS's levels (or ``levels``, with ``nq`` and ``max_hops``): ``(nodes int32 [nq, limit],
+        depth int32 [nq, limit], count int64 [nq])`` device tensors; (depth, node id) order, padding -1, exact counts."""
+        import torch
+        if levels is None:
+            if self.last is None:
+                raise NativeError(E_INVALID, "list: no bfs has run on this graph")
+            levels = self.levels
+            nq = self.last[0] if nq is None else nq
+            max_hops = self.last[1] if max_hops is None else max_hops
+        _typed(levels, "int64", "levels")
+        if not _is_dev(levels) or levels.ndim != 2 or int(levels.shape[0]) < int(max_hops) + 1 or int(levels.shape[1]) != self.n_nodes:
+            raise NativeError(E_INVALID, f"levels must be a device tensor of at least {int(max_hops) + 1} levels x {self.n_nodes} nodes")
+        dev = f"cuda:{self.device}"
+        lim = max(int(limit), 0)
+        nodes = torch.empty((max(int(nq), 0), lim), dtype=torch.int32, device=dev)
+        depth = torch.empty((max(int(nq), 0), lim), dtype=torch.int32, device=dev)
+        count = torch.zeros((max(int(nq), 0),), dtype=torch.int64, device=dev)
+        check(lib().crh_graph_list(self._handle(), int(nq), _ptr(levels), int(max_hops), int(first_level), int(limit), _ptr(nodes), _ptr(depth),
+                                   _ptr(count), stream))
+        return nodes, depth, count
+
+    def row_words(self, row_node, q: int = 0, n_words: int | None = None, out=None, seen=None, stream: int = 0):
+        """``crh_graph_row_words``: the rows whose node (``row_node`` int32 device tensor, -1: none) query ``q`` of the last BFS
+        reached (``seen``: another seen tensor), as int32 validity words [``n_words``, default ceil(rows / 32)]."""
+        import torch
+        _typed(row_node, "int32", "row_node")
+        if not _is_dev(row_node) or row_node.ndim != 1:
+            raise NativeError(E_INVALID, "row_node must be a one-dimensional int32 device tensor")
+        seen = self.seen if seen is None else seen
+        if seen is None:
+            raise NativeError(E_INVALID, "row_words: no bfs has run on this graph")
+        _typed(seen, "int64", "seen")
+        if not _is_dev(seen) or int(seen.numel()) < self.n_nodes:
+            raise NativeError(E_INVALID, f"seen must be a device tensor of {self.n_nodes} words")
+        rows = int(row_node.shape[0])
+        words = (rows + 31) // 32 if n_words is None else int(n_words)
+        if out is None:
+            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.device}")
+        _typed(out, "int32", "out")
+        if not _is_dev(out) or out.ndim != 1 or int(out.shape[0]) < words:
+            raise NativeError(E_INVALID, f"out must be a device tensor of at least {words} words")
+        use_device(self.device)
+        check(lib().crh_graph_row_words(_ptr(row_node) if rows else None, rows, _ptr(seen), self.n_nodes, int(q), _ptr(out), words, stream))
+        return out
+
+    def path(self, rel: int, direction, q: int, target: int, max_hops: int | None = None, levels=None, stream: int = 0) -> np.ndarray:
+        """``crh_graph_path``: the nodes of one shortest path of query ``q`` of the last BFS (same ``rel`` and ``direction``) from
+        a source to ``target``, int32; empty when the target was not reached.  Waits on ``stream``."""
+        if levels is None:
+            if self.last is None:
+                raise NativeError(E_INVALID, "path: no bfs has run on this graph")
+            levels, max_hops = self.levels, self.last[1] if max_hops is None else max_hops
+        _typed(levels, "int64", "levels")
+        if not _is_dev(levels) or levels.ndim != 2 or int(levels.shape[0]) < int(max_hops) + 1 or int(levels.shape[1]) != self.n_nodes:
+            raise NativeError(E_INVALID, f"levels must be a device tensor of at least {int(max_hops) + 1} levels x {self.n_nodes} nodes")
+        out = np.full((GRAPH_MAX_HOPS + 1,), -1, np.int32)
+        n = C.c_int(0)
+        check(lib().crh_graph_path(self._handle(), int(rel), graph_direction(direction), _ptr(levels), int(q), int(target), int(max_hops),
+                                   out.ctypes.data, C.byref(n), stream))
+        return out[: int(n.value)].copy()
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

@@ -33,7 +33,9 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               fusion: str | None = None, like_ids: list[str] | None = None, unlike_ids: list[str] | None = None,
                               min_score: float | None = None, max_overlap: float | None = None, mode: str | None = None,
                               contains: str | list[str] | None = None, contains_case: bool | None = None,
-                              matches: str | None = None, fuzzy: str | None = None, edits: int | None = None) -> ToolResult:
+                              matches: str | None = None, fuzzy: str | None = None, edits: int | None = None,
+                              within_callers_of: str | list[str] | None = None, within_callees_of: str | list[str] | None = None,
+                              graph_hops: int | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -47,7 +49,9 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             extra = {k: v for k, v in (("diversity", diversity), ("candidates", candidates), ("max_per_file", max_per_file),
                                        ("extra_queries", extra_queries or None), ("fusion", fusion), ("min_score", min_score), ("max_overlap", max_overlap), ("mode", mode),
                                        ("contains", contains or None), ("contains_case", contains_case if contains or matches or fuzzy else None),
-                                       ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None)) if v is not None}   # (only when asked for)
+                                       ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None),
+                                       ("within_callers_of", within_callers_of or None), ("within_callees_of", within_callees_of or None),
+                                       ("graph_hops", graph_hops if within_callers_of or within_callees_of else None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -108,6 +112,55 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
             "edits": {"type": "integer", "description": "With fuzzy: how many single-character insertions, deletions or substitutions "
                                                         "are allowed, 0..3 (default: 1 for up to 5 characters, 2 above; a swapped pair "
                                                         "of characters counts as 2)", "required": False},
+            "within_callers_of": {"type": "string", "description": "A function or method name (or a list): only code that calls it, "
+                                                                   "directly or through other calls, is searched -- the named code itself "
+                                                                   "included", "required": False},
+            "within_callees_of": {"type": "string", "description": "A function or method name (or a list): only code reachable from it by "
+                                                                   "calls is searched ('timeout handling, but only under main')",
+                                  "required": False},
+            "graph_hops": {"type": "integer", "description": "With within_callers_of / within_callees_of: how many calls away code may "
+                                                             "be, 1..16 (default: 3)", "required": False},
+        },
+    }
+
+
+def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[str, Any]:
+    """MCP ``code_graph`` tool (the reference answers these from Memgraph, query/graph_reasoning/engine.py): what calls a
+    function, what it calls, and how one function reaches another -- answered on the device from the call edges beside the
+    vectors (``VectorSearcher.find_callers`` / ``find_callees`` / ``find_call_chain``)."""
+    async def code_graph(name: str, relation: str = "callers", target: str | None = None, max_hops: int | None = None,
+                         limit: int = 50) -> ToolResult:
+        logger.info(f"[Tool:CodeGraph] {relation} of '{name}'" + (f" -> '{target}'" if target else ""))
+        try:
+            searcher = vector_searcher_factory()
+            if relation == "chain":
+                if not target:
+                    raise ValueError("relation 'chain' needs a target")
+                paths = await searcher.find_call_chain(name, target, **({} if max_hops is None else {"max_hops": max_hops}))
+                message = (f"'{name}' reaches '{target}' in {paths[0]['total_length']} call(s)." if paths else
+                           f"No chain of calls from '{name}' to '{target}' within {8 if max_hops is None else max_hops} calls.")
+                return ToolResult(success=True, data=paths, message=message)
+            if relation not in ("callers", "callees"):
+                raise ValueError(f"relation {relation!r} is not one of 'callers', 'callees', 'chain'")
+            walk = searcher.find_callers if relation == "callers" else searcher.find_callees
+            nodes = await walk(name, **({} if max_hops is None else {"max_hops": max_hops}), limit=limit)
+            return ToolResult(success=True, data=nodes, message=f"Found {len(nodes)} transitive {relation} of '{name}'.")
+        except Exception as e:  # the catch-all of the reference's tools (tools.py:431-436)
+            logger.error(f"[Tool:CodeGraph] Error: {e}", exc_info=True)
+            return ToolResult(success=False, error=str(e))
+
+    return {
+        "name": "code_graph",
+        "description": ("Walk the call graph: what calls a function (transitively), what it calls, or how one function reaches "
+                        "another. Use it for impact analysis and for 'how does X get to Y'."),
+        "function": code_graph,
+        "parameters": {
+            "name": {"type": "string", "description": "The qualified name of the function, method or class to start from", "required": True},
+            "relation": {"type": "string", "description": "'callers' (the default: what calls it), 'callees' (what it calls) or 'chain' "
+                                                          "(one shortest chain of calls from name to target)", "required": False},
+            "target": {"type": "string", "description": "With relation 'chain': the qualified name to reach", "required": False},
+            "max_hops": {"type": "integer", "description": "How many calls away to look, 1..16 (default: 3; 8 for a chain)", "required": False},
+            "limit": {"type": "integer", "description": "Maximum number of callers / callees listed, nearest first (default: 50)", "required": False},
         },
     }
 

@@ -27,7 +27,7 @@ from typing import Any, NamedTuple
 
 import numpy as np
 
-from . import ffi, lexical, regex_dfa
+from . import ffi, graph as graph_mod, lexical, regex_dfa
 from .errors import VectorStoreError
 from .settings import get_settings
 from .shards import STRIDE as SHARD_STRIDE, AppendFailed, ShardSet, split_global
@@ -244,6 +244,59 @@ def has_text_condition(filters, must_not=None) -> bool:
     return False
 
 
+# -- reachability in the call graph as a filter condition
+GRAPH_KEY = "graph"      # filters={"graph": {"callers_of": "pkg.mod.f", "hops": 3}}: not a payload key, a condition on the row's node
+_GRAPH_WORDS = tuple(graph_mod.FILTER_WORDS) + ("hops", "relation", "include_self", "match")
+_GRAPH_CACHE = 8         # reachability results a collection keeps (a repeated query under the same graph filter runs no second BFS)
+
+
+class GraphSpec(NamedTuple):
+    """A ``{"callers_of" | "callees_of" | "connected_to": name or names, ...}`` filter value, checked: the direction of travel,
+    the distinct names sorted, the hops, the relation, whether the named nodes' own rows pass, and how names resolve."""
+    direction: str
+    names: tuple
+    hops: int
+    relation: str
+    include_self: bool
+    match: str
+
+
+def graph_spec(spec) -> GraphSpec:
+    """The value of a ``"graph"`` filter entry as a :class:`GraphSpec`; ``ValueError`` naming the key for anything else."""
+    if not isinstance(spec, Mapping):
+        raise ValueError(f"filter key {GRAPH_KEY!r} takes a mapping {{'callers_of' | 'callees_of' | 'connected_to': name or list of names, 'hops': 1..{ffi.GRAPH_MAX_HOPS}}}, not {spec!r}")
+    unknown = [k for k in spec if k not in _GRAPH_WORDS]
+    kinds = [k for k in spec if k in graph_mod.FILTER_WORDS]
+    if unknown or len(kinds) != 1:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: exactly one of {', '.join(graph_mod.FILTER_WORDS)} and any of hops, relation, include_self, match "
+                         f"(got {sorted(map(str, spec))})")
+    names = spec[kinds[0]]
+    names = [names] if isinstance(names, str) else list(names) if isinstance(names, _COLLECTIONS) else None
+    if not names or not all(isinstance(n, str) for n in names):
+        raise ValueError(f"filter key {GRAPH_KEY!r}: {kinds[0]} takes a node name or a non-empty list of them, not {spec[kinds[0]]!r}")
+    hops = spec.get("hops", 3)
+    if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= int(hops) <= ffi.GRAPH_MAX_HOPS:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: hops must be an int in 1..{ffi.GRAPH_MAX_HOPS}, not {hops!r}")
+    relation, match = spec.get("relation", "calls"), spec.get("match", "exact")
+    if not isinstance(relation, str) or match not in ("exact", "suffix"):
+        raise ValueError(f"filter key {GRAPH_KEY!r}: relation is a string and match 'exact' or 'suffix' (got {relation!r}, {match!r})")
+    return GraphSpec(graph_mod.FILTER_WORDS[kinds[0]], tuple(sorted(set(names))), int(hops), relation, bool(spec.get("include_self", True)), match)
+
+
+def has_graph_condition(filters, must_not=None) -> bool:
+    """Does a filter (a dict, None, or a per-query sequence of them) carry a ``"graph"`` entry?"""
+    for f in (filters, must_not):
+        for d in (f if isinstance(f, (list, tuple)) else [f]):
+            if isinstance(d, Mapping) and GRAPH_KEY in d:
+                return True
+    return False
+
+
+def _host(x) -> np.ndarray:
+    """A device tensor or a host array as a host array."""
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+
+
 _DTYPES = {"f32": ffi.DTYPE_F32, "fp32": ffi.DTYPE_F32, "float32": ffi.DTYPE_F32, "bf16": ffi.DTYPE_BF16,
            "bfloat16": ffi.DTYPE_BF16}
 
@@ -304,6 +357,18 @@ class _Collection:
         self._text: dict[str, dict[int, Any]] = {}
         self._text_cache: dict[tuple, tuple] = {}    # (key, spec, other conditions, collection state) -> (tag, words per index, count, the levels of an approximate match or None)
         self.text_match_calls = 0            # text conditions resolved by a grep so far (repeated filters reuse the words)
+        # call graph: the node names in order of first appearance (ids only grow), every relation's edges as
+        # node-id pairs -- the part a snapshot keeps --, and, DERIVED on first use: the device graph and, per owned shard, the
+        # row -> node column (the host array, its device copy)
+        self._graph_names: list[str] = []
+        self._graph_code: dict[str, int] = {}
+        self._graph_rel: dict[str, np.ndarray] = {}
+        self._graph = None
+        self._graph_version = 0              # bumped by every set_graph_edges: what the derived parts and the cache are keyed by
+        self._graph_rows: dict[int, tuple] = {}
+        self._graph_rows_state = None
+        self._graph_cache: dict[tuple, tuple] = {}   # (spec, graph version, collection state) -> (tag, words per index)
+        self.graph_bfs_calls = 0             # graph conditions resolved by a BFS so far (repeated filters reuse the words)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
@@ -417,7 +482,11 @@ class _Collection:
         and is dropped."""
         out: list[tuple] = []
         texts: list[tuple] = []                                          # (key, TextSpec, negate): resolved once the others are known
+        graphs: list[tuple] = []                                         # (GraphSpec, negate): resolved before the text conditions
         for key, value in (filters or {}).items():
+            if key == GRAPH_KEY:
+                graphs.append((graph_spec(value), False))
+                continue
             if self._text_entry(key, value, False, texts):
                 continue
             if key in self.numeric_keys:
@@ -438,6 +507,9 @@ class _Collection:
                     return None
                 out.append((col, code))
         for key, value in (must_not or {}).items():
+            if key == GRAPH_KEY:
+                graphs.append((graph_spec(value), True))
+                continue
             if self._text_entry(key, value, True, texts):
                 continue
             if key in self.numeric_keys:
@@ -450,6 +522,14 @@ class _Collection:
             codes = self._codes_of(key, value if isinstance(value, _COLLECTIONS) else [value])
             if codes:
                 out.append((col, codes, True))
+        if len(out) + len(graphs) > ffi.MAX_FILTERS:
+            raise ValueError(f"{len(out) + len(graphs)} filter conditions, the device takes {ffi.MAX_FILTERS} (a graph condition is one)")
+        for spec, negate in graphs:                                      # (before the text conditions: a grep skips the tiles they empty)
+            cond = self._graph_condition(spec, negate)
+            if cond is None and not negate:
+                return None                                              # (no name is a node: nothing is reachable)
+            if cond is not None:
+                out.append(cond)
         if texts:
             if len(out) + len(texts) > ffi.MAX_FILTERS:
                 raise ValueError(f"{len(out) + len(texts)} filter conditions, the device takes {ffi.MAX_FILTERS} (a text condition is one)")
@@ -570,6 +650,170 @@ class _Collection:
         self._text_cache[ck] = hit
         return hit
 
+    # -- call graph
+    def set_graph_edges(self, edges, relation: str = "calls", derive_degrees: bool = False) -> dict[str, Any]:
+        """Sets or replaces the edges of ``relation``: ``edges`` is an iterable of ``(source_name, target_name)``.  Nodes are
+        numbered in order of first appearance, over all relations of the collection; self-loops and repeats are dropped.
+        ``derive_degrees``: the re-rank's centrality table becomes the distinct in-degree + out-degree of this relation."""
+        if not isinstance(relation, str) or not relation:
+            raise ValueError(f"a graph relation is named by a non-empty string, not {relation!r}")
+        if relation not in self._graph_rel and len(self._graph_rel) >= graph_mod.MAX_RELATIONS:
+            raise ValueError(f"a collection holds at most {graph_mod.MAX_RELATIONS} graph relations ({', '.join(self._graph_rel)})")
+        n0 = len(self._graph_names)
+        try:
+            pairs = graph_mod.number_edges(edges, self._graph_code, self._graph_names)
+        except Exception:
+            for name in self._graph_names[n0:]:                          # all or nothing: the names of a refused list leave again
+                del self._graph_code[name]
+            del self._graph_names[n0:]
+            raise
+        self._graph_rel[relation] = graph_mod.unique_edges(pairs, len(self._graph_names))
+        self._graph_changed()
+        if derive_degrees:
+            deg = graph_mod.total_degrees(self._graph_rel[relation], len(self._graph_names))
+            self.set_degrees({self._graph_names[i]: int(d) for i, d in enumerate(deg) if d})
+        return self.graph_info()
+
+    def graph_info(self) -> dict[str, Any]:
+        return {"nodes": len(self._graph_names), "relations": {r: int(len(e)) for r, e in self._graph_rel.items()}}
+
+    def _graph_changed(self) -> None:
+        self._graph_version += 1
+        self._graph_drop()
+
+    def _graph_drop(self) -> None:
+        """Forgets what is derived (the device graph, the row -> node columns, the kept results); names and edges stay."""
+        if self._graph is not None:
+            self._graph.close()
+        self._graph, self._graph_rows, self._graph_rows_state, self._graph_cache = None, {}, None, {}
+
+    def _graph_ready(self, relation: str) -> tuple[Any, int]:
+        """(the device graph, built from the kept edges on first use; the number of ``relation`` in it)."""
+        if self.shards.backend == "dist":
+            raise VectorStoreError(f"the call graph ({GRAPH_KEY!r} filters, graph_neighbors, call_chain) is not available with shard_backend='dist' yet")
+        if relation not in self._graph_rel:
+            raise ValueError(f"collection {self.name!r} has no graph relation {relation!r} (set_graph_edges; known: {', '.join(self._graph_rel) or 'none'})")
+        if self._graph is None:
+            n = len(self._graph_names)
+            g = ffi.Graph(n, device=self._device)
+            try:
+                for r, pairs in enumerate(self._graph_rel.values()):
+                    g.set_relation(r, *graph_mod.build_csr(pairs, n))
+            except Exception:
+                g.close()
+                raise
+            self._graph = g
+        return self._graph, list(self._graph_rel).index(relation)
+
+    def _graph_row_nodes(self) -> dict[int, Any]:
+        """shard -> the row -> node column where the indexes live (int32, -1: the row's key is no node), by the re-rank's key
+        rule ``graph_node_id or entity_name``; derived from the payload table on first use, extended as rows are appended,
+        rebuilt after a compaction and after the graph's names changed."""
+        state = (self._graph_version, self.compactions)
+        if self._graph_rows_state != state:
+            self._graph_rows, self._graph_rows_state = {}, state
+        code, value = self._graph_code, self.payloads.value
+        for s in self.shards.owned:
+            host, dev = self._graph_rows.get(s, (np.zeros((0,), np.int32), None))
+            have, want = int(host.size), self.shards.rows[s]
+            if have < want or dev is None:
+                slots = np.arange(have, want) if self.shards.ns == 1 else self.slot_of[s][have:want]
+                new = np.fromiter((code.get(value(int(t), "graph_node_id") or value(int(t), "entity_name", "") or "", -1) if t >= 0 else -1
+                                   for t in slots), np.int32, want - have)
+                host = np.concatenate([host, new])
+                self._graph_rows[s] = (host, self.shards._local(host))
+        return {s: self._graph_rows[s][1] for s in self.shards.owned}
+
+    def _graph_condition(self, spec: GraphSpec, negate: bool) -> "ffi.RowWords | None":
+        """A graph condition as the row-bitmap condition of the device filter: ONE BFS with one query bit from the named nodes,
+        then per owned shard the reached nodes' rows (``crh_graph_row_words`` over the row -> node column) as
+        ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  None when no name is a node.  The last few results are kept, keyed by
+        what they were computed from; every result lives in buffers of its own under a tag of its own."""
+        graph, rel = self._graph_ready(spec.relation)
+        ids, _ = graph_mod.resolve(spec.names, self._graph_code, self._graph_names, spec.match)
+        if not ids:
+            return None
+        ck = (spec, self._graph_version, tuple(self.shards.rows), self.shards.count()[1], self.compactions)
+        hit = self._graph_cache.pop(ck, None)
+        if hit is None:
+            stream = self.shards._stream()
+            columns = self._graph_row_nodes()
+            graph.bfs(rel, spec.direction, [ids], spec.hops, include_self=spec.include_self, stream=stream)
+            self.graph_bfs_calls += 1
+            words = {id(self.shards.index[s]): graph.row_words(columns[s], 0, stream=stream) for s in self.shards.owned}
+            hit = (ffi.next_words_tag(), words)
+            while len(self._graph_cache) >= _GRAPH_CACHE:
+                self._graph_cache.pop(next(iter(self._graph_cache)))     # (the least recently used: hits are re-inserted below)
+        self._graph_cache[ck] = hit
+        return ffi.RowWords(hit[0], hit[1], negate)
+
+    def graph_nodes_of(self, rows_dev, stream: int = 0):
+        """The nodes of a table of GLOBAL rows (CUDA int64, -1: padding) as an int32 CUDA tensor of the same shape, -1 where the
+        row's key is no node: ``crh_gather_rows_i32`` over every owned shard's row -> node column (a shard answers 0 for the
+        rows of the others, so the gathers add up)."""
+        import torch
+        columns = self._graph_row_nodes()
+        total = None
+        for s in self.shards.owned:
+            part = ffi.gather_rows_i32(rows_dev, s * SHARD_STRIDE, columns[s], 0, stream)
+            total = part if total is None else total + part
+        return torch.where(rows_dev >= 0, total, torch.full_like(total, -1))
+
+    def search_expanded(self, queries: np.ndarray, limit: int, dfilt, direction: str, hops: int, related_limit: int, relation: str):
+        """Per 64 queries: the search, its hit rows gathered to nodes, those nodes as the source sets of ONE BFS, and the list of
+        what it reached beyond them -- all on the device; the host sees the finished tables.  Returns ``(scores [nq, limit],
+        slots [nq, limit], related nodes [nq, related_limit], their depths, related counts [nq])`` host arrays."""
+        import torch
+        graph, rel = self._graph_ready(relation)
+        stream = self.shards._stream()
+        out = []
+        for a in range(0, len(queries), ffi.GRAPH_MAX_QUERIES):
+            part = np.ascontiguousarray(queries[a:a + ffi.GRAPH_MAX_QUERIES])
+            s, r = self.shards.search_device(torch.from_numpy(part).to(torch.device("cuda", self._device)), limit, dfilt)
+            graph.bfs(rel, direction, self.graph_nodes_of(r, stream), hops, include_self=True, stream=stream)
+            nodes, depth, count = graph.list(related_limit, first_level=1, stream=stream)
+            out.append((_host(s), self._global_slots(_host(r)), _host(nodes), _host(depth), _host(count)))
+        return tuple(np.concatenate([o[i] for o in out]) for i in range(5))
+
+    def _graph_names_of(self, nodes, depth) -> list[dict[str, Any]]:
+        return [{"name": self._graph_names[int(v)], "depth": int(d)} for v, d in zip(nodes, depth) if v >= 0]
+
+    def graph_neighbors(self, name_sets, direction: str, relation: str, max_hops: int, limit: int, include_self: bool, match: str) -> list[dict[str, Any]]:
+        """Per name set: the nodes reached within ``max_hops`` as ``{"hits": [{"name", "depth"}], "count", "unresolved"}``, in
+        (depth, node id) order; 64 sets per BFS."""
+        if direction not in graph_mod.DIRECTIONS:
+            raise ValueError(f"graph direction {direction!r} is not one of {', '.join(graph_mod.DIRECTIONS)}")
+        if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or not 1 <= int(max_hops) <= ffi.GRAPH_MAX_HOPS:
+            raise ValueError(f"max_hops must be an int in 1..{ffi.GRAPH_MAX_HOPS}, not {max_hops!r}")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 0:
+            raise ValueError(f"limit must be a non-negative int, not {limit!r}")
+        graph, rel = self._graph_ready(relation)
+        resolved = [graph_mod.resolve(names, self._graph_code, self._graph_names, match) for names in name_sets]
+        stream = self.shards._stream()
+        out = []
+        for a in range(0, len(resolved), ffi.GRAPH_MAX_QUERIES):
+            part = resolved[a:a + ffi.GRAPH_MAX_QUERIES]
+            graph.bfs(rel, direction, [ids for ids, _ in part], int(max_hops), include_self=include_self, stream=stream)
+            nodes, depth, count = (_host(t) for t in graph.list(int(limit), first_level=0 if include_self else 1, stream=stream))
+            out += [{"hits": self._graph_names_of(nodes[q], depth[q]), "count": int(count[q]), "unresolved": missing}
+                    for q, (_, missing) in enumerate(part)]
+        return out
+
+    def call_chain(self, source: str, target: str, relation: str, max_hops: int) -> list[str] | None:
+        """One shortest chain ``source -> ... -> target`` along ``relation`` of at most ``max_hops`` edges, as names; None when
+        there is none or a name is no node.  Among equally short chains, every step back from the target takes the node that
+        ``set_graph_edges`` saw first."""
+        if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or not 1 <= int(max_hops) <= ffi.GRAPH_MAX_HOPS:
+            raise ValueError(f"max_hops must be an int in 1..{ffi.GRAPH_MAX_HOPS}, not {max_hops!r}")
+        graph, rel = self._graph_ready(relation)
+        a, b = self._graph_code.get(source), self._graph_code.get(target)
+        if a is None or b is None:
+            return None
+        stream = self.shards._stream()
+        graph.bfs(rel, "callees", [[a]], int(max_hops), include_self=True, stream=stream)
+        nodes = _host(graph.path(rel, "callees", 0, b, stream=stream))
+        return [self._graph_names[int(v)] for v in nodes] or None
+
     def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None, must_not: dict[str, Any] | None = None) -> np.ndarray:
         """Alive slots matching every condition, in insertion order -- resolved on the device from the code columns."""
         dfilt = self.device_filters(filters, must_not)
@@ -588,6 +832,8 @@ class _Collection:
     def delete(self, filters: dict[str, Any], must_not: dict[str, Any] | None = None) -> int:
         """client.py:159-169: every point matching the AND of the conditions.  An empty filter matches every point, as
         ``Filter(must=[])`` does."""
+        if has_graph_condition(filters, must_not):
+            raise ValueError(f"delete takes no {GRAPH_KEY!r} condition: fetch the matching points (search with query_vector=None) and delete by id or file")
         if has_text_condition(filters, must_not):
             raise ValueError("delete takes no text condition ({'contains': ...} / {'matches': ...} / {'fuzzy': ...}): fetch the matching points (search_text) and delete by id or file")
         dfilt = self.device_filters(filters, must_not)
@@ -1075,6 +1321,7 @@ class _Collection:
             self.compactions += 1
         self._lex_drop()                      # (derived: rebuilt from the payload tables on the next lexical call)
         self._text_drop()                     # (likewise: on the next text filter)
+        self._graph_rows, self._graph_rows_state, self._graph_cache = {}, None, {}    # (the row -> node columns: on the next graph filter)
         return int(before - keep.size)
 
     # -- persistence
@@ -1103,6 +1350,16 @@ class _Collection:
                 self.payloads.save(tmp)
             self.row_shard.tofile(os.path.join(tmp, "rows.shard.i32"))
             self.row_local.tofile(os.path.join(tmp, "rows.local.i64"))
+            # the call graph is not derivable from the payloads: its node names (a JSON list, in id order) and every relation's
+            # edges (raw int32 [edges, 2] node ids) lie beside the tables, named by an optional "graph" entry of collection.json
+            graph_meta = None
+            if self._graph_rel:
+                with open(os.path.join(tmp, "graph.names.json"), "w") as f:
+                    json.dump(self._graph_names, f)
+                graph_meta = {"names": "graph.names.json", "nodes": len(self._graph_names), "relations": []}
+                for r, (rel, pairs) in enumerate(self._graph_rel.items()):
+                    np.ascontiguousarray(pairs, dtype=np.int32).tofile(os.path.join(tmp, f"graph.{r}.edges.i32"))
+                    graph_meta["relations"].append({"name": rel, "file": f"graph.{r}.edges.i32", "edges": int(len(pairs))})
             with open(os.path.join(tmp, "collection.json"), "w") as f:
                 # format 4: says where the payload tables are ("text_tables": "per_rank" = tables{rank}/ hold the text of that
                 # rank's rows only, written by one process per shard; "root" = one complete table)
@@ -1110,7 +1367,7 @@ class _Collection:
                 json.dump({"name": self.name, "keys": list(self.keys), "numeric_keys": list(self.numeric_keys), "format": 5,
                            "slots": self.payloads.n, "shards": self.shards.ns,
                            "shard_rows": list(self.shards.rows), "degrees": self._degrees,
-                           "text_tables": "per_rank" if self.partial else "root"}, f, default=repr)
+                           "text_tables": "per_rank" if self.partial else "root", **({"graph": graph_meta} if graph_meta else {})}, f, default=repr)
         self.shards.barrier()
         if primary:
             shutil.rmtree(directory, ignore_errors=True)
@@ -1171,10 +1428,25 @@ class _Collection:
         self._lex_drop()
         self._text_drop()
         self._degrees = meta.get("degrees")
+        self._graph_names, self._graph_code, self._graph_rel = [], {}, {}
+        graph_meta = meta.get("graph")
+        if graph_meta:
+            with open(os.path.join(directory, graph_meta["names"])) as f:
+                self._graph_names = [str(v) for v in json.load(f)]
+            self._graph_code = {v: i for i, v in enumerate(self._graph_names)}
+            if len(self._graph_names) != int(graph_meta["nodes"]) or len(self._graph_code) != len(self._graph_names):
+                raise ValueError(f"snapshot of {self.name}: {len(self._graph_names)} graph node names ({len(self._graph_code)} distinct), collection.json says {graph_meta['nodes']}")
+            for r in graph_meta["relations"]:
+                pairs = np.fromfile(os.path.join(directory, r["file"]), np.int32).reshape(-1, 2)
+                if len(pairs) != int(r["edges"]):
+                    raise ValueError(f"snapshot of {self.name}: relation {r['name']!r} holds {len(pairs)} edges, collection.json says {r['edges']}")
+                self._graph_rel[str(r["name"])] = graph_mod.unique_edges(pairs, len(self._graph_names))
+        self._graph_changed()
 
     def close(self) -> None:
         self._lex_drop()
         self._text_drop()
+        self._graph_drop()
         self.shards.close()
 
 
@@ -1595,6 +1867,8 @@ class HipVectorStore:
         nq = queries.shape[0]
         per = _per_query(filters, must_not, nq)
         if per is not None:
+            if has_graph_condition(filters, must_not):
+                raise ValueError(f"a per-query filter list cannot carry a {GRAPH_KEY!r} condition: it is one BFS and one row bitmap for the whole batch -- pass ONE filter dict")
             if has_text_condition(filters, must_not):
                 raise ValueError("a per-query filter list cannot carry a text condition ({'contains': ...} / {'matches': ...} / {'fuzzy': ...}): a text condition is "
                                  "one grep for the whole batch -- pass ONE filter dict")
@@ -1947,7 +2221,13 @@ class HipVectorStore:
         ``case=False``: ``re.IGNORECASE``) finds the expression, matched on the device by a DFA.
         ``{"fuzzy": string, "edits": 0..3}`` -- alone or beside the other two, then all must hold -- keeps the points whose text
         holds the string within that many insertions, deletions or substitutions of one BYTE (``edits`` left out: 1 up to 5
-        bytes, 2 above), matched on the device by a bit-parallel edit-distance walk."""
+        bytes, 2 above), matched on the device by a bit-parallel edit-distance walk.
+        ``filters`` / ``must_not`` may also carry the key ``"graph"`` (no payload key: a condition on the point's node,
+        ``graph_node_id or entity_name``): ``{"callers_of" | "callees_of" | "connected_to": name or list of names, "hops": 3,
+        "relation": "calls", "include_self": True, "match": "exact" | "suffix"}`` keeps the points whose node calls / is called
+        from / is connected to the named nodes within ``hops`` (1..16) edges given to :meth:`set_graph_edges` -- one BFS on the
+        device, the result a row bitmap like a text condition's, combinable with everything a filter combines
+        with except per-query filter lists; under ``must_not`` those points are excluded.  Names that are no node match nothing."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -1994,7 +2274,7 @@ class HipVectorStore:
         name = collection.value if isinstance(collection, CollectionName) else collection
         vec = np.asarray(query_vector, dtype=np.float32).reshape(-1)
         fut: asyncio.Future = loop.create_future()
-        if self._coalesce_filters and diversity is None and group is None and not has_text_condition(filters, must_not):
+        if self._coalesce_filters and diversity is None and group is None and not has_text_condition(filters, must_not) and not has_graph_condition(filters, must_not):
             # (a text condition is one grep per pass, not one per query: such calls are keyed by their filter below)
             # plain calls of one collection travel together whatever their filters: each entry carries its own
             key = (name, "any filter")
@@ -2559,6 +2839,103 @@ class HipVectorStore:
         """``{graph_node_id or entity_name: total_degree}`` for the device re-rank's centrality signal (the reference asks
         Memgraph per query, query/engine.py:348-377; a store that keeps the degrees beside the vectors answers on the device)."""
         await self._run(lambda: self._col(collection).set_degrees(total_degree))
+
+    # ------------------------------------------------------------------ the call graph on the device (DESIGN.md 3.27)
+    async def set_graph_edges(self, collection: str, edges, relation: str = "calls", derive_degrees: bool = False) -> dict[str, Any]:
+        """The edges of one named relation of the collection's graph (the reference keeps them in Memgraph): ``edges`` is an
+        iterable of ``(source_name, target_name)``; a node is named like the chunks' key ``graph_node_id or entity_name``.  A
+        call REPLACES that relation; up to 8 relations share one node numbering, in order of first appearance; repeats and
+        self-loops are dropped.  ``derive_degrees``: the re-rank's centrality table (:meth:`set_graph_degrees`) is filled
+        with every node's distinct in-degree + out-degree in this relation (GET_ENTITY_CENTRALITY's ``total_degree``).
+        Returns :meth:`graph_info`."""
+        try:
+            edges = list(edges)
+            return await self._run(lambda: self._col(collection).set_graph_edges(edges, relation, derive_degrees))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to set the graph edges of {collection}", cause=e)
+
+    async def graph_info(self, collection: str) -> dict[str, Any]:
+        """``{"nodes": n, "relations": {name: edges}}``."""
+        return await self._run(lambda: self._col(collection).graph_info())
+
+    async def graph_neighbors_batch(self, collection: str, name_sets, direction: str = "callers", relation: str = "calls", max_hops: int = 3,
+                                    limit: int = 50, include_self: bool = False, match: str = "exact") -> list[dict[str, Any]]:
+        """:meth:`graph_neighbors` for a list of name sets (each a name or a list of names): one device BFS per 64 sets."""
+        try:
+            sets = [[s] if isinstance(s, str) else list(s) for s in name_sets]
+            return await self._run(lambda: self._col(collection).graph_neighbors(sets, direction, relation, max_hops, limit, include_self, match))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to walk the graph of {collection}", cause=e)
+
+    async def graph_neighbors(self, collection: str, names, direction: str = "callers", relation: str = "calls", max_hops: int = 3,
+                              limit: int = 50, include_self: bool = False, match: str = "exact") -> dict[str, Any]:
+        """What reaches (``direction="callers"``), is reached from (``"callees"``) or is connected to (``"both"``) the named
+        nodes within ``max_hops`` (1..16) edges of ``relation``: FIND_TRANSITIVE_CALLERS / _CALLEES of the reference's
+        query/graph_reasoning/queries.py, as a bit-parallel BFS on the device.  Returns ``{"hits": [{"name", "depth"}], "count",
+        "unresolved"}``: every reached node ONCE, at its minimum depth (the Cypher's DISTINCT over (node, depth) lists a node
+        once per path length), ordered by (depth, order of first appearance in :meth:`set_graph_edges`), the first ``limit``
+        of them; ``count`` is how many there are, never clipped; ``unresolved`` the names that are no node.  ``names``: one
+        name or several (their union is the source set).  ``match="suffix"``: a name also stands for every node whose name ends
+        in ``"." + name``.  ``include_self``: the sources themselves lead the list at depth 0."""
+        return (await self.graph_neighbors_batch(collection, [names], direction, relation, max_hops, limit, include_self, match))[0]
+
+    async def call_chain(self, collection: str, source: str, target: str, relation: str = "calls", max_hops: int = 8) -> list[str] | None:
+        """One shortest chain of ``relation`` edges from ``source`` to ``target`` (FIND_CALL_CHAIN; at most ``max_hops`` edges,
+        1..16) as the list of node names, both ends included -- or None.  ONE chain per pair: where several are equally short,
+        each step back from the target takes the node :meth:`set_graph_edges` saw first."""
+        try:
+            return await self._run(lambda: self._col(collection).call_chain(source, target, relation, max_hops))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to walk the graph of {collection}", cause=e)
+
+    async def search_expanded_batch(self, collection: str, query_vectors, limit: int = 10, graph_expand: dict[str, Any] | None = None,
+                                    filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:
+        """:meth:`search_batch` plus, per query, the graph neighbourhood of its hits: ``[{"hits": [...], "related": [{"name",
+        "depth"}], "related_count": n}]``.  ``graph_expand`` = ``{"direction": "both", "hops": 1, "limit": 10, "relation":
+        "calls"}`` (any key may be left out): ``related`` holds the nodes reached within ``hops`` edges from the nodes of the
+        query's hits (a hit's node is its ``graph_node_id or entity_name``), the hits' own nodes left out, in (depth, order of
+        first appearance) order, the first ``limit`` of them; ``related_count`` is how many there are.  The hit rows become BFS
+        sources on the device, 64 queries per BFS: nothing returns to the host between the search and the list."""
+        try:
+            ex = dict(graph_expand or {})
+            unknown = [k for k in ex if k not in ("direction", "hops", "limit", "relation")]
+            direction, hops, rlimit, relation = ex.get("direction", "both"), ex.get("hops", 1), ex.get("limit", 10), ex.get("relation", "calls")
+            if unknown or direction not in graph_mod.DIRECTIONS or not isinstance(relation, str):
+                raise ValueError(f"graph_expand takes direction (one of {', '.join(graph_mod.DIRECTIONS)}), hops, limit and relation, not {graph_expand!r}")
+            for what, v, lo, hi in (("hops", hops, 1, ffi.GRAPH_MAX_HOPS), ("limit", rlimit, 0, 2 ** 20)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                    raise ValueError(f"graph_expand: {what} must be an int in {lo}..{hi}, not {v!r}")
+            if has_graph_condition(filters, must_not) and (isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple))):
+                raise ValueError(f"a per-query filter list cannot carry a {GRAPH_KEY!r} condition -- pass ONE filter dict")
+            if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+                raise ValueError("search_expanded takes ONE filter dict for the whole batch")
+            q = np.ascontiguousarray(np.asarray(query_vectors, dtype=np.float32))
+            if q.size == 0:
+                return []
+            q = q.reshape(-1, q.shape[-1]) if q.ndim != 2 else q
+            if limit > ffi.MAX_K:
+                raise ValueError(f"limit {limit} exceeds the index's maximum k of {ffi.MAX_K}")
+
+            def work():
+                col = self._col(collection)
+                if q.shape[1] != col.shards.dim:
+                    raise ValueError(f"query dim {q.shape[1]} != index dim {col.shards.dim}")
+                col._graph_ready(relation)
+                dfilt = col.device_filters(filters, must_not)
+                if dfilt is None or limit <= 0 or not len(q):
+                    return [{"hits": [], "related": [], "related_count": 0} for _ in range(len(q))]
+                self.search_passes += 1
+                scores, slots, nodes, depth, count = col.search_expanded(q, int(limit), dfilt, direction, int(hops), int(rlimit), relation)
+                return [{"hits": h, "related": col._graph_names_of(nodes[i], depth[i]), "related_count": int(count[i])}
+                        for i, h in enumerate(self._hit_lists(col, slots, scores))]
+            return await self._run(work)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_expanded(self, collection: str, query_vector, limit: int = 10, graph_expand: dict[str, Any] | None = None,
+                              filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> dict[str, Any]:
+        """:meth:`search_expanded_batch` for one query: ``{"hits", "related", "related_count"}``."""
+        return (await self.search_expanded_batch(collection, [query_vector], limit, graph_expand, filters, must_not))[0]
 
     async def search_rerank_batch(self, collection: str, query_vectors, plans, reranker, limit: int = 20,
                                   filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None):

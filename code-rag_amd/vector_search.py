@@ -121,6 +121,22 @@ def _contains_filter(key: str, contains, contains_case: bool, matches: str | Non
     return {key: spec}
 
 
+def _graph_filter(within_callers_of, within_callees_of, graph_hops: int | None) -> dict:
+    """``within_callers_of`` / ``within_callees_of`` (a node name or a list of them) as the store's ``"graph"`` condition: only
+    code that calls / is called from those nodes, transitively within ``graph_hops`` edges (the store's default: 3), the named
+    nodes' own chunks included -- ``{}`` without either: the call is then the one issued before."""
+    if within_callers_of is None and within_callees_of is None:
+        if graph_hops is not None:
+            raise QueryError("graph_hops stands beside within_callers_of or within_callees_of")
+        return {}
+    if within_callers_of is not None and within_callees_of is not None:
+        raise QueryError("within_callers_of and within_callees_of cannot be combined (one graph condition per search)")
+    spec = {"callers_of": within_callers_of} if within_callers_of is not None else {"callees_of": within_callees_of}
+    if graph_hops is not None:
+        spec["hops"] = graph_hops
+    return {"graph": spec}
+
+
 def _transform_similar_code_result(hit: dict) -> dict:
     """A store hit in the result shape of ``find_similar_code`` (vector_search.py:199-216); a recommend hit under strategy
     "best" keeps its two extra keys."""
@@ -219,7 +235,8 @@ class VectorSearcher:
                           extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                           max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
                           contains_case: bool = True, matches: str | None = None,
-                          fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
+                          fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
+                          within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -248,11 +265,17 @@ class VectorSearcher:
         must hold within ``edits`` BYTE insertions, deletions or substitutions (0..3; default 1 for up to 5 bytes, 2 above) --
         ``parse_retry_aftr`` finds ``parse_retry_after`` -- matched exactly on the device; beside the other two
         all must hold, and ``contains_case`` governs it too.  :meth:`search_summaries`, :meth:`find_similar_code`,
-        :meth:`facet_code` and :meth:`search_code_batch` take ``fuzzy`` / ``edits`` the same way."""
+        :meth:`facet_code` and :meth:`search_code_batch` take ``fuzzy`` / ``edits`` the same way.
+        ``within_callers_of`` / ``within_callees_of`` (not in the reference, which would need Memgraph and a second query): a
+        node name or a list of them -- only code that calls / is called from them, transitively within ``graph_hops`` edges
+        (default 3), counts: "timeout handling, but only in code reachable from ``main``".  Resolved by a BFS on the device
+        over the edges given to ``HipVectorStore.set_graph_edges``, in every mode and beside every other
+        argument; :meth:`search_summaries`, :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way."""
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops))
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -263,7 +286,8 @@ class VectorSearcher:
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,
                                extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                                mode: str = "semantic", contains: str | list[str] | None = None, contains_case: bool = True,
-                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
+                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
+                               within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
         ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`; ``contains`` / ``contains_case`` /
         ``matches`` likewise, over the ``summary`` text."""
@@ -272,6 +296,8 @@ class VectorSearcher:
         filters = {"project_name": project_name} if project_name else None
         if contains is not None or matches is not None or fuzzy is not None or edits is not None:
             filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case, matches, fuzzy, edits))
+        if within_callers_of is not None or within_callees_of is not None or graph_hops is not None:
+            filters = dict(filters or {}, **_graph_filter(within_callers_of, within_callees_of, graph_hops))
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -283,7 +309,8 @@ class VectorSearcher:
                                 max_per_file: int | None = None, min_score: float | None = None,
                                 max_overlap: float | None = None, contains: str | list[str] | None = None,
                                 contains_case: bool = True, matches: str | None = None,
-                                fuzzy: str | None = None, edits: int | None = None) -> list[dict]:
+                                fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
+                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
@@ -296,7 +323,8 @@ class VectorSearcher:
         on_device = bool(exact_exclude and exclude_file)
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch,
-                                  _contains_filter("content", contains, contains_case, matches, fuzzy, edits) or _NO_FILTER_KWARG,
+                                  {**_contains_filter("content", contains, contains_case, matches, fuzzy, edits),
+                                   **_graph_filter(within_callers_of, within_callees_of, graph_hops)} or _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
@@ -376,6 +404,44 @@ class VectorSearcher:
             logger.error(f"Vector store error: {e}")
             raise QueryError("Failed to count code by value", cause=e)
 
+    # ------------------------------------------------------------------ the call graph (query/graph_reasoning/engine.py's shapes)
+    async def _graph_walk(self, name: str, direction: str, max_hops: int, limit: int) -> list[dict]:
+        if not name or not name.strip():
+            raise QueryError("Entity name cannot be empty")
+        try:
+            got = await self.qdrant.graph_neighbors(collection=CollectionName.CODE_CHUNKS.value, names=name, direction=direction,
+                                                    max_hops=max_hops, limit=limit)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError(f"Failed to find transitive {direction}", cause=e)
+        return [{"name": h["name"].rsplit(".", 1)[-1], "qualified_name": h["name"], "metadata": {"depth": h["depth"]}} for h in got["hits"]]
+
+    async def find_callers(self, name: str, max_hops: int = 3, limit: int = 50) -> list[dict]:
+        """What calls ``name``, transitively (``GraphReasoningEngine.find_transitive_callers``): the fields of its ``GraphNode``
+        this store knows -- ``[{"name", "qualified_name", "metadata": {"depth"}}]`` -- by (depth, order of indexing), every
+        caller once, at its least depth -- answered by the device
+        BFS over the store's ``"calls"`` edges (``HipVectorStore.graph_neighbors``), no graph database asked."""
+        return await self._graph_walk(name, "callers", max_hops, limit)
+
+    async def find_callees(self, name: str, max_hops: int = 3, limit: int = 50) -> list[dict]:
+        """What ``name`` calls, transitively (``find_transitive_callees``); the shape of :meth:`find_callers`."""
+        return await self._graph_walk(name, "callees", max_hops, limit)
+
+    async def find_call_chain(self, source: str, target: str, max_hops: int = 8) -> list[dict]:
+        """How ``source`` reaches ``target`` (``find_call_chain``, whose ``GraphPath`` fields these are): ``[{"nodes": [names],
+        "relationships": ["CALLS", ...], "total_length", "path_type": "call_chain"}]`` with ONE shortest chain of calls, both
+        ends included -- or ``[]`` when there is none within ``max_hops`` calls (``HipVectorStore.call_chain``)."""
+        if not source or not target:
+            raise QueryError("find_call_chain needs a source and a target")
+        try:
+            chain = await self.qdrant.call_chain(collection=CollectionName.CODE_CHUNKS.value, source=source, target=target, max_hops=max_hops)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to find a call chain", cause=e)
+        if not chain:
+            return []
+        return [{"nodes": chain, "relationships": ["CALLS"] * (len(chain) - 1), "total_length": len(chain) - 1, "path_type": "call_chain"}]
+
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
@@ -384,7 +450,8 @@ class VectorSearcher:
                                 filters_per_query: list[dict | None] | None = None, min_score=None,
                                 max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
                                 contains_case: bool = True, matches: str | None = None,
-                                fuzzy: str | None = None, edits: int | None = None) -> list[list[dict]]:
+                                fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
+                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
         ``candidates`` only).
@@ -399,6 +466,9 @@ class VectorSearcher:
         if (contains is not None or matches is not None or fuzzy is not None or edits is not None) and filters_per_query is not None:
             raise QueryError("contains / matches / fuzzy cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
+        if (within_callers_of is not None or within_callees_of is not None) and filters_per_query is not None:
+            raise QueryError("within_callers_of / within_callees_of cannot be combined with filters_per_query (a graph condition is one BFS for the whole batch)")
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops))
         if filters_per_query is not None:
             if filters:
                 raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")

@@ -724,6 +724,70 @@ int crh_text_fuzzy(crh_text *t, const uint8_t *pat_host, int len, int max_edits,
                    const uint32_t *mask_dev /* or NULL */, uint32_t *out_words_dev /* [max_edits + 1][ceil(rows / 32)] */,
                    int64_t *out_counts_host /* [max_edits + 1] or NULL */, void *stream);
 
+/* ---- the call graph on the device.  The reference keeps it in Memgraph (query/graph_reasoning/queries.py:
+ * FIND_TRANSITIVE_CALLERS / _CALLEES, FIND_CALL_CHAIN); here it lies beside the index, and a set of reached nodes becomes a row
+ * bitmap a search takes as CRH_COND_WORDS.  Every result is a set or a minimum depth: exact, and the same from run to run.
+ *
+ * A crh_graph holds up to CRH_GRAPH_MAX_RELATIONS relations ("calls", "extends", ...: the caller numbers them) over ONE node id
+ * space 0 .. n_nodes - 1.  A relation is two CSRs in device memory: the forward one lists a node's targets (along the edges),
+ * the reverse one its sources (against them); offsets int64 [n_nodes + 1], adjacency int32 [n_edges]. */
+typedef struct crh_graph crh_graph; /* opaque */
+#define CRH_GRAPH_MAX_RELATIONS 8
+#define CRH_GRAPH_MAX_QUERIES 64   /* source sets of one crh_graph_bfs: bit q of a node's word belongs to set q */
+#define CRH_GRAPH_MAX_HOPS 16
+#define CRH_GRAPH_MAX_LIMIT (1 << 24) /* list entries per query of one crh_graph_list */
+#define CRH_GRAPH_WAVE_DEGREE 64   /* an adjacency list of at least so many entries is walked by a whole wave, a shorter one by one lane */
+#define CRH_GRAPH_ALONG 0   /* travel along the edges: from a caller to what it calls (callees) */
+#define CRH_GRAPH_AGAINST 1 /* against them (callers) */
+#define CRH_GRAPH_BOTH 2    /* either way */
+
+int crh_graph_create(int device, int64_t n_nodes, crh_graph **out);
+int crh_graph_destroy(crh_graph *g);
+/* *nodes_out = n_nodes; *edges_out = the edges of relation `rel`, -1 while it is not set.  Either pointer may be NULL. */
+int crh_graph_count(crh_graph *g, int rel, int64_t *nodes_out, int64_t *edges_out);
+
+/* Sets or replaces relation `rel` (0 .. CRH_GRAPH_MAX_RELATIONS - 1) from host arrays.  Checked on the host, CRH_E_INVALID with the
+ * relation left as it was: both offset arrays start at 0, never decrease and end at n_edges; every adjacency entry is a node.
+ * That the two CSRs hold the same edges, without repeats, each list ascending, is the caller's business (a repeat costs time,
+ * never exactness; crh_graph_path's tie rule reads the lists as they are).  Synchronous. */
+int crh_graph_set_relation(crh_graph *g, int rel, int64_t n_edges, const int64_t *off_fwd_host, const int32_t *adj_fwd_host,
+                           const int64_t *off_rev_host, const int32_t *adj_rev_host);
+
+/* Breadth-first search from nq (1..CRH_GRAPH_MAX_QUERIES) SOURCE SETS at once.  Set q is src_nodes[src_off[q] .. src_off[q + 1]);
+ * src_off (int64 [nq + 1], from 0) is a HOST array always, src_nodes a host array (sources_on_device = 0; an entry that is
+ * neither a node nor -1 is CRH_E_INVALID) or a device array complete on `stream` (!= 0; an entry that is no node is skipped).
+ * -1 is padding; an empty set and a repeated source are fine.
+ *   levels_dev u64 [max_hops + 1][n_nodes]: bit q of levels[d][v] is set iff node v is at MINIMUM depth d from set q in
+ *     `direction` (CRH_GRAPH_*); level 0 holds the sources.  Every word is written.
+ *   seen_dev   u64 [n_nodes]: the OR of the levels; with include_self = 0 the bits of level 0 are cleared from it (they stay in
+ *     level 0; a source that lies on a cycle is not listed a second time at the cycle's length).
+ *   active_dev u64 [max_hops + 1]: the OR of level d's words.
+ * 1 <= max_hops <= CRH_GRAPH_MAX_HOPS.  One launch per level, none waits for another workgroup; a level behind a dead frontier
+ * leaves at once.  Enqueues on `stream` and returns (a host source list is uploaded first, and the call waits for that upload
+ * only).  One BFS per handle may be in flight.  A graph without nodes is CRH_OK with nothing launched. */
+int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes,
+                  int sources_on_device, int max_hops, int include_self, uint64_t *levels_dev, uint64_t *seen_dev,
+                  uint64_t *active_dev, void *stream);
+
+/* What a BFS reached, per query, from its levels: the nodes of levels first_level .. max_hops (1: without the sources) ordered by
+ * (depth, node id) into out_nodes_dev / out_depth_dev int32 [nq][limit], padding -1, every slot written; out_count_dev int64
+ * [nq] = how many there are, exact, never clipped at limit.  0 <= limit <= CRH_GRAPH_MAX_LIMIT (0: the counts alone).  Enqueues. */
+int crh_graph_list(crh_graph *g, int nq, const uint64_t *levels_dev, int max_hops, int first_level, int limit, int32_t *out_nodes_dev,
+                   int32_t *out_depth_dev, int64_t *out_count_dev, void *stream);
+
+/* The reached nodes of query q as a ROW BITMAP: bit i of word t is set iff 32 t + i < n_rows, v = row_node_dev[32 t + i] is a node
+ * (0 <= v < n_nodes; -1: the row's key is no node) and bit q of seen_dev[v] is set.  u32 [n_words], n_words >= ceil(n_rows / 32);
+ * the layout crh_index_row_mask writes; tail bits and the words beyond the rows are 0.  Runs on the CURRENT device; enqueues. */
+int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint64_t *seen_dev, int64_t n_nodes, int q,
+                        uint32_t *out_words_dev, int64_t n_words, void *stream);
+
+/* One shortest path of query q to `target`, from the levels of a crh_graph_bfs with the same rel, direction and max_hops: walks
+ * back from the target's level, at every step to the SMALLEST node id among the neighbours that lie in the level before.
+ * out_nodes_host int32 [max_hops + 1] receives the nodes from a source to the target, *out_len how many (1: the target is a
+ * source; 0: not reached within max_hops).  Waits on `stream`. */
+int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_dev, int q, int64_t target, int max_hops,
+                   int32_t *out_nodes_host, int *out_len, void *stream);
+
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
  * the HF RobertaModel it wraps).  All pointers are device pointers; activations bf16,
