@@ -70,6 +70,7 @@ EXPORTS = (
     "crh_index_facet", "crh_search_range_facet", "crh_facet_select",
     "crh_graph_create", "crh_graph_destroy", "crh_graph_count", "crh_graph_set_relation", "crh_graph_bfs", "crh_graph_list",
     "crh_graph_row_words", "crh_graph_path",
+    "crh_graph_node_rows", "crh_graph_candidates", "crh_rerank_hybrid",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
@@ -77,6 +78,9 @@ DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_
 DEBUG_LIB_PATH = Path(os.environ.get("CODERAG_HIP_DEBUG_LIB", PKG_DIR / "lib" / "libcoderag_hip_debug.so"))
 
 RR_NAME_BYTES, RR_MAX_ENTITIES, RR_ENTITY_BYTES = 64, 8, 48
+RR_MAX_HYBRID, RR_HYBRID_SIGNALS, RR_HYBRID_TABLE = 512, 7, 128   # CRH_RR_MAX_HYBRID / _HYBRID_SIGNALS / _HYBRID_TABLE
+ROLE_PRIMARY, ROLE_CALLER, ROLE_CALLEE, ROLE_METHOD, ROLE_PARENT, ROLE_CHILD = range(6)   # CRH_ROLE_*
+GRAPH_CAND_MAX_QUERIES = 1024   # CRH_GRAPH_CAND_MAX_QUERIES
 
 
 class NativeError(RuntimeError):
@@ -99,6 +103,16 @@ class RerankQuery(C.Structure):
     """``crh_rerank_query``: one query's weights and lower-cased entity names."""
     _fields_ = [("vector_weight", C.c_double), ("centrality_weight", C.c_double), ("n_entities", C.c_int32),
                 ("entity_len", C.c_int32 * 8), ("entity", (C.c_uint8 * 48) * 8), ("pad_", C.c_int32)]
+
+
+class RerankHybridQuery(C.Structure):
+    """``crh_rerank_hybrid_query``: ``crh_rerank_query`` + the graph branch's weights."""
+    _fields_ = [("base", RerankQuery), ("graph_weight", C.c_double), ("context_weight", C.c_double), ("relationship_bonus", C.c_double)]
+
+
+class GraphSegment(C.Structure):
+    """``crh_graph_segment``: an explicit node, or the first ``take`` entries of a list row, in one role of one query."""
+    _fields_ = [(n, C.c_int32) for n in ("query", "role", "node", "list_row", "take", "pad_")]
 
 
 class RerankColumns(C.Structure):
@@ -247,6 +261,10 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_graph_list.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
     L.crh_graph_row_words.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp]
     L.crh_graph_path.argtypes = [vp, i32, i32, vp, i32, i64, i32, vp, C.POINTER(i32), vp]
+    L.crh_graph_node_rows.argtypes = [i64, vp, vp, i64, i64, vp, vp]
+    L.crh_graph_candidates.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_rerank_hybrid.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, i32, i32, i32, i32,
+                                    vp, vp, vp, vp, vp, vp, vp]
     if debug or hasattr(L, "crh_debug_gemm_variant"):   # (CODERAG_HIP_LIB may point a tool's whole run at the debug build)
         debug = True
         L.crh_debug_gemm_variant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]

@@ -35,10 +35,29 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               contains: str | list[str] | None = None, contains_case: bool | None = None,
                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None,
                               within_callers_of: str | list[str] | None = None, within_callees_of: str | list[str] | None = None,
-                              graph_hops: int | None = None) -> ToolResult:
+                              graph_hops: int | None = None, rank: str | None = None, entities: list[str] | None = None,
+                              intent: str | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
+            if rank not in (None, "vector", "hybrid"):
+                raise ValueError(f"rank {rank!r} is neither 'vector' nor 'hybrid'")
+            if rank == "hybrid":                 # graph results and vector hits in one list, ranked on the device
+                import numpy as np
+                from .engine_helpers import search_and_rank_hybrid_batch_device
+                from .query_types import ExtractedEntity, QueryIntent, QueryPlan
+                from .ranking import HybridRanker
+                from .ranking.device import HybridDeviceReranker
+                if entity_type or like_ids or unlike_ids or mode not in (None, "semantic"):
+                    raise ValueError("rank='hybrid' takes query, limit, entities and intent only")
+                plan = QueryPlan(original_query=query, primary_intent=QueryIntent(intent or QueryIntent.SEARCH_FUNCTIONALITY.value),
+                                 entities=[ExtractedEntity(name=e, is_primary=True) for e in (entities or [])])
+                vector = np.asarray(await searcher.embedder.embed(query), dtype=np.float32)[None, :]
+                ranked = (await search_and_rank_hybrid_batch_device(searcher.qdrant, HybridDeviceReranker(), HybridRanker(), vector, [plan],
+                                                                    limit=max(limit, 20)))[0][:limit]
+                data = [vars(SearchResult(qualified_name=r.graph_node_id or r.entity_name, entity_type=r.entity_type, file_path=r.file_path,
+                                          score=r.final_score, summary=r.summary)) for r in ranked]
+                return ToolResult(success=True, data=data, message=f"Found {len(data)} graph and vector matches for '{query}'.")
             if like_ids or unlike_ids:           # recommend by example: the query text is not embedded
                 if not like_ids:
                     raise ValueError("unlike_ids needs like_ids")
@@ -120,6 +139,13 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                   "required": False},
             "graph_hops": {"type": "integer", "description": "With within_callers_of / within_callees_of: how many calls away code may "
                                                              "be, 1..16 (default: 3)", "required": False},
+            "rank": {"type": "string", "description": "'vector' (the default: the plain matches) or 'hybrid': the named entities' graph "
+                                                      "neighbourhood (callers, callees, class hierarchy) and the matches ranked as one "
+                                                      "list", "required": False},
+            "entities": {"type": "array", "description": "With rank='hybrid': names of the functions or classes the question is about",
+                         "required": False},
+            "intent": {"type": "string", "description": "With rank='hybrid': find_callers, find_callees, find_hierarchy, "
+                                                        "explain_implementation, ... (default: search_functionality)", "required": False},
         },
     }
 

@@ -775,6 +775,134 @@ class _Collection:
             out.append((_host(s), self._global_slots(_host(r)), _host(nodes), _host(depth), _host(count)))
         return tuple(np.concatenate([o[i] for o in out]) for i in range(5))
 
+    # -- the hybrid re-rank with graph results
+    def richness_columns(self) -> dict[int, Any]:
+        """Per-shard richness bits (``ranking.device.RichnessColumn``) beside the side columns: derived from the payload table,
+        extended as rows are appended, rebuilt after a compaction."""
+        from .ranking.device import RichnessColumn
+        state = getattr(self, "_rich_state", None)
+        if state != self.compactions:
+            self._rich, self._rich_state = {}, self.compactions
+        for s in self.shards.owned:
+            col = self._rich.get(s)
+            if col is None:
+                col = self._rich[s] = RichnessColumn(self._device)
+            have, want = col.rows, self.shards.rows[s]
+            if have < want:
+                slots = np.arange(have, want) if self.shards.ns == 1 else self.slot_of[s][have:want]
+                col.append([self.payloads.get(int(t)) if t >= 0 else {} for t in slots])
+        return self._rich
+
+    def graph_node_rows(self):
+        """``(device int64 [nodes], host copy)``: every node's representative row -- the lowest alive GLOBAL row whose row -> node
+        entry is the node, -1 without one (``crh_graph_node_rows`` over every owned shard's column and alive words, into one
+        array).  Kept until rows are appended, deleted or compacted or the graph changes."""
+        from .ranking.device import graph_node_rows
+        key = (self._graph_version, tuple(self.shards.rows), self.shards.count()[1], self.compactions)
+        kept = getattr(self, "_node_rows", None)
+        if kept is None or kept[0] != key:
+            stream = self.shards._stream()
+            columns = self._graph_row_nodes()
+            out = None
+            for s in self.shards.owned:
+                alive = self.shards.index[s].row_mask(None, stream=stream)
+                out = graph_node_rows(columns[s], len(self._graph_names), alive, row_base=s * SHARD_STRIDE, out=out, stream=stream)
+            kept = self._node_rows = (key, out, _host(out))
+            self.graph_node_rows_builds = getattr(self, "graph_node_rows_builds", 0) + 1
+        return kept[1], kept[2]
+
+    def _graph_role_info(self):
+        """What ``engine_helpers.plan_graph_roles`` asks of this collection's graph."""
+        col, (_, rows_host) = self, self.graph_node_rows()
+
+        class Info:
+            relations = set(col._graph_rel)
+
+            @staticmethod
+            def resolve(name, match):
+                return graph_mod.resolve(name, col._graph_code, col._graph_names, match)[0]
+
+            @staticmethod
+            def is_class(node):
+                row = int(rows_host[node])
+                if row < 0:
+                    return False
+                slot = int(col._global_slots(np.asarray([row], np.int64))[0])
+                return str(col.payloads.value(slot, "entity_type", "") or "").lower() == "class"
+        return Info
+
+    def search_rerank_hybrid(self, queries: np.ndarray, plans, reranker, limit: int, dfilt, relation: str):
+        """Per 64 queries: the search (left on the device), the primaries of every query as one-node source sets of one BFS per
+        (relation, direction, hops) on the one stream, ``crh_graph_list``, the kept representative rows, ``crh_graph_candidates``,
+        the gathers and ``crh_rerank_hybrid`` -- the host sees the finished tables.  Returns per batch ``(output, slots [nq, k],
+        scores, graph slots [nq, G], graph nodes [nq, G], declined)``; ``declined[q]`` (count -1, or a graph list that does not fit
+        CRH_RR_MAX_HYBRID beside the hits) holds the query's graph lists ``[(role, node, depth)]`` for the host ranker."""
+        import torch
+        from .engine_helpers import plan_graph_roles
+        from .ranking.device import graph_candidates, segment_table
+        graph, _ = self._graph_ready(relation)
+        stream = self.shards._stream()
+        dev = torch.device("cuda", self._device)
+        node_rows, node_rows_host = self.graph_node_rows()
+        info = self._graph_role_info()
+        width = 50                                                       # MAX_RESULTS_PER_QUERY: the widest list a walk asks for
+        out = []
+        for a in range(0, len(plans), ffi.GRAPH_MAX_QUERIES):
+            part_plans = plans[a:a + ffi.GRAPH_MAX_QUERIES]
+            nq = len(part_plans)
+            if dfilt is not None and limit > 0:
+                s, r = self.shards.search_device(torch.from_numpy(np.ascontiguousarray(queries[a:a + nq])).to(dev), limit, dfilt)
+            else:
+                s = torch.full((nq, max(limit, 0)), float("-inf"), dtype=torch.float32, device=dev)
+                r = torch.full((nq, max(limit, 0)), -1, dtype=torch.int64, device=dev)
+            k = int(r.shape[1])
+            roles = [plan_graph_roles(p, info) for p in part_plans]
+            groups: dict[tuple, list] = {}                               # (relation, direction, hops) -> [(query, walk)]
+            for q, rp in enumerate(roles):
+                for w in rp.walks:
+                    groups.setdefault((w.relation, w.direction, w.hops), []).append((q, w))
+            per_query = [[(ffi.ROLE_PRIMARY, v, -1, 0) for v in rp.primaries] for rp in roles]
+            lists_n, lists_d, n_lists = [], [], 0
+            for (rel_name, direction, hops), members in groups.items():
+                rel = list(self._graph_rel).index(rel_name)
+                for b in range(0, len(members), ffi.GRAPH_MAX_QUERIES):   # one bit per (query, primary), 64 bits per BFS
+                    chunk = members[b:b + ffi.GRAPH_MAX_QUERIES]
+                    graph.bfs(rel, direction, [[w.source] for _, w in chunk], hops, include_self=False, stream=stream)
+                    nodes, depth, _ = graph.list(width, first_level=1, stream=stream)
+                    lists_n.append(nodes.clone())
+                    lists_d.append(depth.clone())
+                    for i, (q, w) in enumerate(chunk):
+                        per_query[q].append((w.role, -1, n_lists + i, min(w.limit, width)))
+                    n_lists += len(chunk)
+            segs, G_all = segment_table(per_query)
+            G = max(0, min(G_all, ffi.RR_MAX_HYBRID - k))
+            ln = torch.cat(lists_n) if lists_n else None
+            ld = torch.cat(lists_d) if lists_d else None
+            table = graph_candidates(segs, nq, G, node_rows, ln, ld, stream=stream) if G else None
+            g_cols = self.gather_side(table.row) if G else None
+            g_rich = None
+            if G:
+                rich = self.richness_columns()
+                for sh in self.shards.owned:
+                    part = rich[sh].gather(table.row, row_base=sh * SHARD_STRIDE, stream=stream)
+                    g_rich = part if g_rich is None else g_rich + part
+            res = reranker.rank(table, g_cols, g_rich, s if k else None, r if k else None, self.gather_side(r) if k else None, part_plans,
+                                stream=stream)
+            g_rows = _host(table.row) if G else np.zeros((nq, 0), np.int64)
+            g_nodes = _host(table.node) if G else np.zeros((nq, 0), np.int32)
+            declined = {}
+            too_long = [q for q in range(nq) if sum(1 if n >= 0 else t for _, n, _, t in per_query[q]) > G]
+            for q in sorted(set(too_long) | {q for q in range(nq) if res.count[q] < 0}):
+                res.count[q] = -1
+                ln_h, ld_h = (_host(ln), _host(ld)) if ln is not None else (None, None)
+                entries = []
+                for _, role, node, list_row, take in (sg for sg in segs if sg[0] == q):
+                    found = [(node, 0)] if node >= 0 else list(zip(ln_h[list_row][:take], ld_h[list_row][:take]))
+                    entries += [(role, int(v), int(d)) for v, d in found if v >= 0 and node_rows_host[int(v)] >= 0]
+                declined[q] = entries
+            out.append((res, self._global_slots(_host(r)) if k else np.zeros((nq, 0), np.int64), _host(s), self._global_slots(g_rows), g_nodes, declined))
+        return out
+
     def _graph_names_of(self, nodes, depth) -> list[dict[str, Any]]:
         return [{"name": self._graph_names[int(v)], "depth": int(d)} for v, d in zip(nodes, depth) if v >= 0]
 
@@ -2968,6 +3096,63 @@ class HipVectorStore:
                 wanted = sorted(wanted)
                 return RerankHits({t: (col.ids.get(t), p) for t, p in zip(wanted, col.payloads_of(wanted))}, col._degrees), out, slots, s.cpu().numpy()
             return await self._run(work)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    async def search_rerank_hybrid_batch(self, collection: str, query_vectors, plans, reranker, limit: int = 20,
+                                         filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, relation: str = "calls"):
+        """:meth:`search_rerank_batch` with the GRAPH branch of the ranker on the device as well (DESIGN.md 3.28;
+        ``ranking.device.HybridDeviceReranker``): per 64 queries the search, one BFS per direction from the plans' primary
+        entities (``engine_helpers.plan_graph_roles``), ``crh_graph_list``, the kept representative rows, ``crh_graph_candidates``,
+        the gathers and ``crh_rerank_hybrid`` -- nothing travels to the host before the finished tables.  Returns ``(hits, parts,
+        names)``: ``parts`` holds per batch of 64 ``(HybridRerankOutput, hit slots [nq, k], scores, graph slots [nq, G], graph nodes
+        [nq, G], declined)``, ``hits`` a :class:`RerankHits` answering for every slot a survivor, something it absorbed or a
+        declined query refers to, ``names`` the node id -> ``(name, slot of its representative row)`` table of those nodes.  ``declined[q]`` lists a declined
+        query's graph results ``[(role, node, depth)]`` for the host ranker.  One and several local shards; not available with
+        ``shard_backend="dist"``."""
+        try:
+            q = np.ascontiguousarray(np.asarray(query_vectors, dtype=np.float32))
+            q = q.reshape(-1, q.shape[-1]) if q.ndim != 2 else q
+            if len(plans) != len(q):
+                raise ValueError(f"{len(plans)} plans for {len(q)} query vectors")
+            if limit > ffi.RR_MAX_HYBRID:
+                raise ValueError(f"limit {limit} exceeds the {ffi.RR_MAX_HYBRID} candidates one hybrid re-rank takes")
+            if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+                raise ValueError("search_rerank_hybrid_batch takes ONE filter dict for the whole batch")
+
+            def work():
+                col = self._col(collection)
+                if len(q) and q.shape[1] != col.shards.dim:
+                    raise ValueError(f"query dim {q.shape[1]} != index dim {col.shards.dim}")
+                col._graph_ready(relation)
+                dfilt = col.device_filters(filters, must_not)
+                self.search_passes += 1
+                parts = col.search_rerank_hybrid(q, list(plans), reranker, int(limit), dfilt, relation)
+                wanted, nodes = set(), set()
+                for res, slots, _, g_slots, g_nodes, declined in parts:
+                    both = np.concatenate([g_slots, slots], axis=1)
+                    for qi in range(len(res.count)):
+                        c = int(res.count[qi])
+                        if c < 0:
+                            pos = np.flatnonzero(both[qi] >= 0)
+                            nodes.update(v for _, v, _ in declined[qi])
+                        else:
+                            pos = set(int(i) for i in res.index[qi, :c])
+                            for i, merged in zip(res.index[qi, :c], res.hybrid[qi, :c]):
+                                if merged:                                # what a survivor absorbed fills its missing fields
+                                    pos.update(int(j) for j in np.flatnonzero(res.key[qi] == res.key[qi, i]))
+                            pos = np.asarray(sorted(pos), np.int64)
+                        wanted.update(int(t) for t in both[qi, pos] if t >= 0)
+                        nodes.update(int(g_nodes[qi, i]) for i in pos if i < g_nodes.shape[1] and g_nodes[qi, i] >= 0)
+                order = sorted(nodes)
+                node_slots = col._global_slots(col.graph_node_rows()[1][order]) if order else []
+                wanted.update(int(t) for t in node_slots if t >= 0)      # (a declined query's lists may hold nodes beyond the table)
+                wanted = sorted(wanted)
+                hits = RerankHits({t: (col.ids.get(t), p) for t, p in zip(wanted, col.payloads_of(wanted))}, col._degrees)
+                return hits, parts, {v: (col._graph_names[v], int(t)) for v, t in zip(order, node_slots)}
+            return await self._run(work)
+        except VectorStoreError:
+            raise
         except Exception as e:
             raise VectorStoreError(f"Failed to search {collection}", cause=e)
 

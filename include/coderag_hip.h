@@ -788,6 +788,104 @@ int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint6
 int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_dev, int q, int64_t target, int max_hops,
                    int32_t *out_nodes_host, int *out_len, void *stream);
 
+/* ---- the hybrid re-rank with both branches on the device.  QueryEngine.search (query/engine.py:222-260) hands
+ * HybridRanker.rank_results a graph context AND the vector hits; crh_rerank_vector above covers lists of vector hits only.  The
+ * three entry points below turn the BFS lists of crh_graph_list into graph candidates and rank them together with the hits. */
+
+/* A node's REPRESENTATIVE ROW: the lowest alive global row (row_base + local) whose entry of the row -> node column is that
+ * node -- the row whose payload (file, lines, summary) stands for the node in a result.  row_node_dev int32 [n_rows] (-1 or
+ * anything outside 0 .. n_nodes - 1: the row's key is no node); alive_words_dev u32 [ceil(n_rows / 32)], bit i of word t =
+ * local row 32 t + i is alive (the layout crh_index_row_mask writes), or NULL: every row is alive.  node_rows_dev int64
+ * [n_nodes] is PRE-FILLED with -1 by the caller; one lane per row takes a 64-bit atomic minimum on the unsigned view, where -1
+ * is the maximum, so the shards of a collection call this one after the other on the same array and the result is exact
+ * whatever the order.  A node without an alive row keeps -1: it can never become a graph result.  Runs on the CURRENT device;
+ * enqueues. */
+int crh_graph_node_rows(int64_t n_rows, const int32_t *row_node_dev, const uint32_t *alive_words_dev, int64_t row_base, int64_t n_nodes,
+                        int64_t *node_rows_dev, void *stream);
+
+/* The roles of a graph result, in the order HybridRanker walks them (ranker.py:70-169: primary entities, callers, callees,
+ * methods, parent classes, child classes). */
+#define CRH_ROLE_PRIMARY 0
+#define CRH_ROLE_CALLER 1
+#define CRH_ROLE_CALLEE 2
+#define CRH_ROLE_METHOD 3
+#define CRH_ROLE_PARENT 4
+#define CRH_ROLE_CHILD 5
+#define CRH_GRAPH_CAND_MAX_QUERIES 1024
+#define CRH_GRAPH_CAND_MAX_SEGMENTS (1 << 20)
+
+/* One run of graph candidates of one query: an explicit node (node >= 0: a primary entity; list_row and take are not read), or
+ * the first `take` entries of row list_row of a crh_graph_list table (node < 0). */
+typedef struct crh_graph_segment {
+    int32_t query;
+    int32_t role;     /* CRH_ROLE_* */
+    int32_t node;
+    int32_t list_row;
+    int32_t take;
+    int32_t pad_;
+} crh_graph_segment;
+
+/* The per-query graph candidate table.  segments_host holds n_segments segments sorted by query; within a query they stand in
+ * the reference's order (all primaries, all caller lists in primary order, all callee lists, methods, parents, children).
+ * list_nodes_dev / list_depth_dev int32 [n_lists][limit] are what crh_graph_list wrote (several calls' tables laid end to
+ * end); node_rows_dev int64 [n_nodes] is crh_graph_node_rows' array.  Per query the entries of its segments are written in order
+ * into out_node / out_role / out_depth int32 [nq][G] and out_row int64 [nq][G] (the representative row); a -1 list entry and a
+ * node without a representative row are dropped IN PLACE (the order of the rest is kept), entries beyond G are cut, the slots
+ * behind the last entry are (-1, -1, -1, -1): every slot is written.  An explicit node has depth 0.  Checked on the host in the
+ * manner of crh_graph_set_relation, CRH_E_INVALID with nothing launched: queries ascending and < nq, roles, explicit nodes <
+ * n_nodes, list rows < n_lists, take >= 0 (a take beyond `limit` reads `limit` entries) -- no lane is handed an index outside
+ * its arrays.  segments_dev [n_segments] and seg_off_dev int32 [nq + 1] are caller-provided device scratch the call fills.  One
+ * wave per query.  nq <= CRH_GRAPH_CAND_MAX_QUERIES.  Runs on the CURRENT device; uploads the table on `stream`, waits for that
+ * upload only (segments_host is free on return, as crh_graph_bfs' source list) and enqueues the kernel. */
+int crh_graph_candidates(int nq, int G, int n_segments, const crh_graph_segment *segments_host, const int32_t *list_nodes_dev,
+                         const int32_t *list_depth_dev, int n_lists, int limit, const int64_t *node_rows_dev, int64_t n_nodes,
+                         crh_graph_segment *segments_dev, int32_t *seg_off_dev, int32_t *out_node_dev, int64_t *out_row_dev,
+                         int32_t *out_role_dev, int32_t *out_depth_dev, void *stream);
+
+#define CRH_RR_MAX_HYBRID 512      /* graph + vector candidates of one query: 84 bytes of LDS each, 42 KB */
+#define CRH_RR_HYBRID_SIGNALS 7    /* graph_match, query_entity_match, relationship_relevance, centrality, context_richness,
+                                      vector_similarity, code_quality -- the order of out_signals and of the presence bits */
+#define CRH_RR_HYBRID_TABLE 128    /* distinct centrality keys one query's table holds; more sends the query to the host */
+
+/* crh_rerank_query + what score_graph_result reads (scorer.py:9-77): the intent's graph and context weights
+ * (RankingConfig.weights_for) and RankingConfig.relationship_bonus. */
+typedef struct crh_rerank_hybrid_query {
+    crh_rerank_query base;
+    double graph_weight;
+    double context_weight;
+    double relationship_bonus;
+} crh_rerank_hybrid_query;
+
+/* HybridRanker.rank_results (ranker.py:24-54) for nq queries, one workgroup each.  A query's candidates are its G graph entries
+ * (g_rows_dev / g_role_dev / g_depth_dev [nq][G] as crh_graph_candidates wrote them, g_rows < 0 = padding; g_cols = the side
+ * columns of the representative rows, crh_gather_rerank_columns; g_rich_dev int32 [nq][G] = richness bits of those rows: bit 0
+ * summary, bit 1 docstring, bit 2 signature) FOLLOWED BY its k vector hits exactly as crh_rerank_vector takes them.  1 <= G + k <=
+ * CRH_RR_MAX_HYBRID, either may be 0 (its pointers are then not read); more is CRH_E_INVALID.
+ *   graph entry (scorer.py:9-77): graph_match = max(0.3, 1.0 - (depth - 1) * 0.2) for callers and callees (depth 0 counts as 1),
+ *     1.0 otherwise; relationship_relevance 1.0 / 0.8 / 0.7 / 0.5 (primary / caller / callee / other); query_entity_match and
+ *     centrality as for a hit; context_richness = 0.3 summary + 0.2 docstring + 0.2 signature summed in that order from 0.0 (a
+ *     graph node carries no content); score = the five products with graph_weight, entity_match_bonus, relationship_bonus,
+ *     centrality_weight, context_weight, summed left to right.
+ *   vector entry: crh_rerank_vector's formula (scorer.py:80-126).
+ *   centrality table (engine.py:348-377, insertion-ordered): the keys of the first primary_top PRIMARY graph entries, then of the
+ *     named ones among the first centrality_top hits, one entry per key, cut at centrality_limit keys; a key whose degree is < 0
+ *     answers no lookup.
+ *   merge (ranker.py:171-202): the first entry of a key absorbs the later ones in list order, c = (f + f_j) / 2; c = c * 1.1; the
+ *     signals are a UNION, the larger value where both carry one; any merge makes the result "hybrid".
+ *   stable descending sort, per-file cap, total cap as in crh_rerank_vector.
+ * Outputs per query in final order, [nq][max_total]: out_index (position in the concatenated list; < G: a graph entry, whose
+ * role and depth the caller reads there), out_score f64, out_signals f64 [..][CRH_RR_HYBRID_SIGNALS] with out_mask's bit t set
+ * iff signal t is PRESENT (absent is not 0.0), out_flags bit 0 = hybrid, bit 1 = the first entry was a graph entry.
+ * out_count[q] = survivors, or -1: the host must rank this query (entities outside 0..CRH_RR_MAX_ENTITIES, a name longer than
+ * CRH_RR_NAME_BYTES, more than CRH_RR_HYBRID_TABLE centrality keys).  The slots behind the survivors are written (-1, 0, ...).
+ * All arithmetic in f64 in the reference's operand order.  Runs on the CURRENT device; enqueues. */
+int crh_rerank_hybrid(int nq, int G, int k, const int64_t *g_rows_dev, const int32_t *g_role_dev, const int32_t *g_depth_dev,
+                      const crh_rerank_columns *g_cols, const int32_t *g_rich_dev, const float *scores_dev, const int64_t *rows_dev,
+                      const crh_rerank_columns *cols, const crh_rerank_hybrid_query *queries_dev, double entity_match_bonus,
+                      int max_per_file, int max_total, int primary_top, int centrality_top, int centrality_limit, int32_t *out_index_dev,
+                      double *out_score_dev, double *out_signals_dev, int32_t *out_mask_dev, int32_t *out_count_dev, int32_t *out_flags_dev,
+                      void *stream);
+
 /* ------------------------------------------------------------- encoder --------- */
 /* UniXcoder = RoBERTa-base geometry encoder (providers/unixcoder_provider.py:137-155 and
  * the HF RobertaModel it wraps).  All pointers are device pointers; activations bf16,
