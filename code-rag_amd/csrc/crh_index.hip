@@ -77,6 +77,7 @@ struct Pending {
     float *out_s;
     int64_t *out_r;
     int slot;
+    hipStream_t stream;   // the stream the batch was enqueued on: what a finish waits for, and where the batch is run again
     bool multi;     // a mixed-filter batch (crh_search_multi): key is the classes' keys behind their number, cls the queries' classes
     QueryClasses cls;
     bool range;     // a range batch (crh_search_range): thr the queries' thresholds, counts their in-range totals (device; nullptr: list only)
@@ -177,6 +178,8 @@ struct crh_index {
     std::vector<Pending> pending;
     int next_slot = 0;
     crh_search_stats stats{};
+    bool stats_carry = false;       // a mutation completed pending batches: their stats stay until the caller's own finish
+    hipEvent_t order_ev = nullptr;  // puts a call behind the pending batches of ANOTHER stream (they share the workspace); made on first use
 
     // optional HIP-event timing of the dominant kernel (bench.py's roofline figure)
     bool profiling = false;
@@ -1044,21 +1047,31 @@ int enqueue_pending(crh_index *h, crh_index::Workspace &w, const Pending &p, int
     return enqueue_batch(h, w, p.q_dev, p.nq, p.k, mask, p.row_base, p.out_s, p.out_r, slot, st, path_out);
 }
 
-int finish_pending(crh_index *h, hipStream_t st)
+// Completes every pending batch.  A batch is final only once its status slot has been read: the wait is for every stream a
+// pending batch was enqueued on -- not for the caller's, which may be another one -- and a batch whose candidate buffers
+// overflowed or whose one-launch scan timed out is run again on ITS stream.  Every entry point that changes what such a
+// re-run would read (rows, alive words, code columns, capacity) comes through here first, so a re-run always answers for
+// the index the batch was enqueued on.
+int finish_pending(crh_index *h)
 {
     if (h->pending.empty()) return CRH_OK;
-    CRH_HIP(hipStreamSynchronize(st));
+    std::vector<hipStream_t> streams;
+    for (const Pending &p : h->pending)
+        if (std::find(streams.begin(), streams.end(), p.stream) == streams.end()) streams.push_back(p.stream);
+    for (hipStream_t s : streams) CRH_HIP(hipStreamSynchronize(s));
+    hipStream_t cst = streams.back();
     const int used = std::max(1, std::min(h->next_slot, kStatusSlots));   // slots are handed out in order from 0
     std::vector<SearchStatus> host((size_t)used);
-    // (copies of the search path go through `st`, not through hipMemcpy: that one runs on the NULL stream and would wait for everything
+    // (copies of the search path go through a stream of the batches, not through hipMemcpy: that one runs on the NULL stream and would wait for everything
     // another thread has queued there -- an encoder forward under way on torch's default stream held every answer back ~13 ms)
-    CRH_HIP(hipMemcpyAsync(host.data(), h->status, sizeof(SearchStatus) * (size_t)used, hipMemcpyDeviceToHost, st));
-    CRH_HIP(hipStreamSynchronize(st));
+    CRH_HIP(hipMemcpyAsync(host.data(), h->status, sizeof(SearchStatus) * (size_t)used, hipMemcpyDeviceToHost, cst));
+    CRH_HIP(hipStreamSynchronize(cst));
     std::vector<Pending> todo;
     todo.swap(h->pending);
     h->next_slot = 0;
-    crh_index::Workspace &w = h->ws;   // (everything is idle: a batch that overflowed is re-run alone on `st`)
+    crh_index::Workspace &w = h->ws;   // (everything is idle: a batch that overflowed is re-run alone on its stream)
     for (const Pending &p : todo) {
+        hipStream_t st = p.stream;
         SearchStatus s = host[p.slot];
         if (h->profiling && h->count > 0) {
             float ms = 0.f;
@@ -1135,6 +1148,18 @@ int finish_pending(crh_index *h, hipStream_t st)
     return CRH_OK;
 }
 
+// What every entry point that changes rows, alive words, code columns or capacity does first: the pending batches are
+// completed against the index they were enqueued on (one wait for their streams; nothing pending: this test alone).  Their
+// stats stay readable until the caller's own crh_search_finish.
+int complete_pending(crh_index *h)
+{
+    if (h->pending.empty()) return CRH_OK;
+    DeviceGuard g(h->device);
+    CRH_TRY(finish_pending(h));
+    h->stats_carry = true;
+    return CRH_OK;
+}
+
 // the device staging of a call's lists: host outputs are copied from it, crh_search_range_facet leaves its k = 1 lists in it
 int ensure_stage_out(crh_index *h, int64_t elems)
 {
@@ -1194,10 +1219,17 @@ int search_batches(crh_index *h, int nq, const float *queries, int queries_on_de
         os = h->stage_os;
         orow = h->stage_or;
     }
-    if (h->pending.empty()) h->stats = crh_search_stats{};
+    if (h->pending.empty() && !h->stats_carry) h->stats = crh_search_stats{};
+    // Batches pending on ANOTHER stream use the same workspace (query images, thresholds, candidate lists): this call's work
+    // goes behind them.  One stream -- every caller in this repository -- never gets here.
+    if (!h->pending.empty() && h->pending.back().stream != st) {
+        if (!h->order_ev) CRH_HIP(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
+        CRH_HIP(hipEventRecord(h->order_ev, h->pending.back().stream));
+        CRH_HIP(hipStreamWaitEvent(st, h->order_ev, 0));
+    }
 
     for (int q0 = 0; q0 < nq;) {
-        if (h->next_slot >= kStatusSlots) CRH_TRY(finish_pending(h, st));
+        if (h->next_slot >= kStatusSlots) CRH_TRY(complete_pending(h));   // (every stream's batches: the slots are the index's)
         Pending p{};
         CRH_TRY(plan(p, q0, nq - q0, st));
         p.k = k;
@@ -1207,12 +1239,14 @@ int search_batches(crh_index *h, int nq, const float *queries, int queries_on_de
         p.out_s = os + (int64_t)q0 * k;
         p.out_r = orow + (int64_t)q0 * k;
         p.slot = h->next_slot++;
+        p.stream = st;
         CRH_TRY(enqueue_pending(h, h->ws, p, p.slot, st, &p.path));
         h->pending.push_back(p);
         q0 += p.nq;
     }
     if (!out_on_device || !queries_on_device) {
-        CRH_TRY(finish_pending(h, st));
+        CRH_TRY(finish_pending(h));
+        h->stats_carry = false;
         if (!out_on_device) {
             CRH_HIP(hipMemcpyAsync(out_scores, h->stage_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
             CRH_HIP(hipMemcpyAsync(out_rows, h->stage_or, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
@@ -1415,6 +1449,7 @@ int crh_index_destroy(crh_index *h)
     dev_free(h->stage_cnt);
     if (h->stage_in) (void)hipFree(h->stage_in);
     for (auto &e : h->ev) (void)hipEventDestroy(e);
+    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     delete h;
     return CRH_OK;
 }
@@ -1446,6 +1481,7 @@ static int append_impl(crh_index *h, int64_t n, const float *vecs, int on_device
     if (h->count + n > h->cap_rows)
         return fail(CRH_E_CAPACITY, "append of %lld rows exceeds capacity (%lld of %lld used)", (long long)n, (long long)h->count,
                     (long long)h->cap_rows);
+    CRH_TRY(complete_pending(h));   // (a pending batch that is run again must not see these rows)
     DeviceGuard g(h->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t chunk = 65536;
@@ -1493,6 +1529,7 @@ int crh_index_tombstone(crh_index *h, int64_t n, const int64_t *rows)
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
     if (n <= 0) return CRH_OK;
     if (!rows) return fail(CRH_E_INVALID, "rows is NULL");
+    CRH_TRY(complete_pending(h));   // (a pending batch that is run again must still see these rows)
     DeviceGuard g(h->device);
     CRH_TRY(ensure_stage_in(h, n * 8));
     CRH_HIP(hipMemcpy(h->stage_in, rows, (size_t)n * 8, hipMemcpyHostToDevice));
@@ -1510,6 +1547,7 @@ int crh_index_tombstone(crh_index *h, int64_t n, const int64_t *rows)
 static int tombstone_key(crh_index *h, const FilterKey &key, int64_t *n_cleared_out)
 {
     if (h->count == 0) return CRH_OK;
+    CRH_TRY(complete_pending(h));
     DeviceGuard g(h->device);
     CRH_HIP(hipDeviceSynchronize());   // searches in flight on other streams read `alive` / the shared mask buffer
     CRH_TRY(ensure_workspace0(h));
@@ -1683,6 +1721,7 @@ int crh_index_import(crh_index *h, int64_t first_tile, int64_t n_tiles, int64_t 
     if (!tiles_host || !alive_host) return fail(CRH_E_INVALID, "import: tiles and alive words are required");
     if ((h->xf32 != nullptr) != (master_host != nullptr)) return fail(CRH_E_INVALID, "import: the f32 master copy goes with dtype f32, and only with it");
     if ((h->ncols > 0) != (codes_host != nullptr)) return fail(CRH_E_INVALID, "import: index has %d code columns", h->ncols);
+    CRH_TRY(complete_pending(h));
     DeviceGuard g(h->device);
     CRH_HIP(hipDeviceSynchronize());
     const size_t tile_bytes = (size_t)h->ksteps * 1024;
@@ -1716,6 +1755,7 @@ int crh_index_count(crh_index *h, int64_t *rows_out, int64_t *alive_out)
 int crh_index_clear(crh_index *h)
 {
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
+    CRH_TRY(complete_pending(h));   // (the pending batches answer for the rows that are about to go)
     DeviceGuard g(h->device);
     CRH_HIP(hipDeviceSynchronize());
     const int64_t used_tiles = ceil_div(h->count, 32);
@@ -1727,8 +1767,6 @@ int crh_index_clear(crh_index *h)
     h->mutations += 1;
     h->i8_dirty_from = 0;
     h->alive_count = 0;
-    h->pending.clear();
-    h->next_slot = 0;
     return CRH_OK;
 }
 
@@ -1737,6 +1775,7 @@ int crh_index_reserve(crh_index *h, int64_t capacity_rows)
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
     if (capacity_rows <= h->cap_rows) return CRH_OK;
     if (capacity_rows > (1LL << 31)) return fail(CRH_E_INVALID, "capacity_rows %lld out of range", (long long)capacity_rows);
+    CRH_TRY(complete_pending(h));   // (rows and code columns move to new buffers, the kept masks are void)
     DeviceGuard g(h->device);
     CRH_HIP(hipDeviceSynchronize());
     const int64_t new_rows = (capacity_rows + 31) & ~31LL, new_tiles = new_rows / 32;
@@ -2200,7 +2239,10 @@ int crh_search_finish(crh_index *h, void *stream)
 {
     if (!h) return fail(CRH_E_INVALID, "index is NULL");
     DeviceGuard g(h->device);
-    return finish_pending(h, static_cast<hipStream_t>(stream));
+    (void)stream;   // (the batches know their streams; kept for the ABI and for callers that name the stream they work on)
+    const int rc = finish_pending(h);
+    h->stats_carry = false;
+    return rc;
 }
 
 int crh_index_set_profiling(crh_index *h, int enable)
@@ -2389,7 +2431,9 @@ int crh_search_range_facet(crh_index *h, int nq, const float *queries, int queri
     CRH_TRY(search_range_key(h, nq, queries, queries_on_device, 1, thresholds_host, key, 0, h->stage_os, h->stage_or, h->stage_cnt, 1, stream, col,
                              n_bins, reinterpret_cast<unsigned long long *>(out_bins_dev), reinterpret_cast<unsigned long long *>(out_info_dev)));
     DeviceGuard g(h->device);
-    return finish_pending(h, static_cast<hipStream_t>(stream));
+    const int rc = finish_pending(h);
+    h->stats_carry = false;
+    return rc;
 }
 
 }  // extern "C"

@@ -276,7 +276,20 @@ int crh_search_range(crh_index *h, int nq, const float *queries, int queries_on_
  * enable: 1 / 0, negative = keep; max_fraction_den: > 0 sets it, otherwise kept (default 4: DESIGN.md section 3). */
 int crh_index_set_sparse_route(crh_index *h, int enable, int max_fraction_den);
 
-/* Completes every crh_search enqueued with device outputs since the last finish. */
+/* Completes every search enqueued with device outputs since the last finish (crh_search, _cond, _multi, _range): waits for
+ * the streams those calls were enqueued on -- every one of them, whichever `stream` is passed here; the index remembers them
+ * -- reads each batch's status, and runs again, on the batch's own stream, every batch whose candidate buffers overflowed or
+ * whose one-launch scan timed out.  The outputs are final when the call returns.
+ * What the caller owes a pending search UNTIL then: its queries, its outputs, the out_counts buffer of a range search and the
+ * bitmap of a CRH_COND_WORDS condition stay allocated and untouched -- a batch that is run again reads and writes them again.
+ * Calls on several streams may be pending at once; a call on another stream than the pending call before it is put behind
+ * that one on the device (they share the index's workspace).
+ * The index itself may be changed while searches are pending: crh_index_append / _append_preprocessed, the three tombstone
+ * calls, crh_index_import, crh_index_reserve and crh_index_clear complete the pending searches FIRST -- as crh_search_finish
+ * does, at its cost: one wait for their streams -- so every search answers for the index as it was at its call, also when
+ * it had to run again.  With nothing pending that costs nothing.  crh_index_compact alone refuses (CRH_E_INVALID) while
+ * searches are pending: finish them first.  At most 1024 batches stay pending: the call that would enqueue one more completes
+ * them itself.  Batches completed that way, or by a mutation, stay in crh_search_stats until the caller's own finish. */
 int crh_search_finish(crh_index *h, void *stream);
 
 int crh_search_get_stats(crh_index *h, crh_search_stats *out);
