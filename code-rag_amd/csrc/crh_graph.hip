@@ -20,6 +20,9 @@
 //
 // One lane per node; a node whose adjacency list has CRH_GRAPH_WAVE_DEGREE entries or more is walked by its whole wave (64
 // entries per step, OR-reduced over the lanes), the shorter ones by their own lane.
+//
+// Personalised PageRank over the same CSRs stands behind the BFS kernels: k_ppr_inv, k_ppr_seed, k_ppr_step (one
+// launch per step, pull form, sums in list order), k_ppr_bins / k_ppr_bins_exclude, k_ppr_order.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -267,6 +270,203 @@ __global__ __launch_bounds__(64) void k_graph_path(const PathArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- personalised PageRank
+// (DESIGN.md 3.30).  State is f32 [n_nodes, QS], QS the smallest power of two >= nq: lane l of a wave owns node base + l / QS and
+// query l % QS.  Every sum has ONE writer and walks its pull list in list order, every operation is a separate f32 rounding
+// (the library is built with -ffp-contract=off) and subnormals are kept: the result is the same bits as the CPU restatement.
+
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_inv(const int64_t *off0, const int64_t *off1, int64_t n, float *inv)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) {
+        int64_t out = off0[v + 1] - off0[v];
+        if (off1) out += off1[v + 1] - off1[v];
+        inv[v] = out > 0 ? 1.0f / (float)out : 0.0f;                 // (correctly rounded: v_div_scale / _fmas / _fixup)
+    }
+}
+
+// One workgroup per query.  p0 and contrib0 were zeroed on the stream; the FIRST entry of a node takes the ordered sum of the
+// weights of all its entries, found by comparing against the earlier entries as the group select does.
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_seed(const int32_t *nodes, const float *weights, int c, int64_t n, int shift,
+                                                            const float *inv, float *p0, float *contrib)
+{
+    __shared__ int32_t s_node[CRH_MAX_K];
+    __shared__ float s_w[CRH_MAX_K];
+    __shared__ float s_sum;
+    const int q = blockIdx.x;
+    for (int i = threadIdx.x; i < c; i += kGraphThreads) {
+        const int64_t v = nodes[(int64_t)q * c + i];
+        const float w = weights ? weights[(int64_t)q * c + i] : 1.0f;
+        const bool real = v >= 0 && v < n && w > 0.0f && w < __builtin_inff();   // (a negative, NaN or infinite weight counts as +0)
+        s_node[i] = real ? (int32_t)v : -1;
+        s_w[i] = real ? w : 0.0f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float sum = 0.0f;
+        for (int i = 0; i < c; ++i) sum += s_w[i];                  // (list order; padding adds +0, which changes no bits)
+        s_sum = sum;
+    }
+    __syncthreads();
+    const float sum = s_sum;
+    const bool live = sum > 0.0f && sum < __builtin_inff();
+    for (int i = threadIdx.x; i < c; i += kGraphThreads) {
+        const int32_t v = s_node[i];
+        if (v < 0) continue;
+        bool first = true;
+        for (int j = 0; j < i && first; ++j) first = s_node[j] != v;
+        if (!first) continue;
+        float w = 0.0f;
+        for (int j = i; j < c; ++j)
+            if (s_node[j] == v) w += s_w[j];
+        const float p = live ? w / sum : 0.0f;
+        const int64_t at = ((int64_t)v << shift) | q;
+        p0[at] = p;
+        contrib[at] = p * inv[v];
+    }
+}
+
+struct PprStepArgs {
+    const int64_t *off[2];
+    const int32_t *adj[2];
+    int ncsr;
+    const float *p0, *inv, *contrib;   // contrib: what the launch before this one finished
+    float *next, *p;                   // contrib_{t+1}, p_{t+1}
+    int64_t n;
+    int shift;
+    float restart, a;
+};
+
+// One launch per step; a lane owns (node, query) and is the only writer of both outputs.  No list walk is skipped.  WIDE (QS =
+// 64): the wave owns one node, loads 64 adjacency entries at a time and reads one 256-byte row of contrib per neighbour.
+template <bool WIDE>
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_step(const PprStepArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int q = lane & ((1 << a.shift) - 1);
+    const int per = 64 >> a.shift;                                   // nodes of a wave
+    const int64_t groups = (a.n + per - 1) / per;
+    for (int64_t w = (int64_t)blockIdx.x * kGraphWaves + wave; w < groups; w += (int64_t)gridDim.x * kGraphWaves) {
+        const int64_t u = WIDE ? w : w * per + (lane >> a.shift);
+        const bool in = u < a.n;
+        float acc = 0.0f;
+        for (int c = 0; c < a.ncsr; ++c) {
+            const int32_t *adj = a.adj[c];
+            if (WIDE) {
+                const int64_t b = a.off[c][u], e = a.off[c][u + 1];
+                for (int64_t i = b; i < e; i += 64) {
+                    const int cnt = (int)(e - i < 64 ? e - i : 64);
+                    const int mine = lane < cnt ? adj[i + lane] : 0;
+                    int j = 0;
+                    for (; j + 16 <= cnt; j += 16) {                 // sixteen rows in flight; the additions keep the list's order
+                        float row[16];
+#pragma unroll
+                        for (int t = 0; t < 16; ++t) {
+                            const int64_t v = __shfl(mine, j + t);
+                            row[t] = a.contrib[(v << 6) | lane];
+                        }
+#pragma unroll
+                        for (int t = 0; t < 16; ++t) acc += row[t];
+                    }
+                    for (; j + 4 <= cnt; j += 4) {
+                        const int64_t v0 = __shfl(mine, j), v1 = __shfl(mine, j + 1), v2 = __shfl(mine, j + 2), v3 = __shfl(mine, j + 3);
+                        const float c0 = a.contrib[(v0 << 6) | lane], c1 = a.contrib[(v1 << 6) | lane];
+                        const float c2 = a.contrib[(v2 << 6) | lane], c3 = a.contrib[(v3 << 6) | lane];
+                        acc += c0;
+                        acc += c1;
+                        acc += c2;
+                        acc += c3;
+                    }
+                    for (; j < cnt; ++j) {
+                        const int64_t v = __shfl(mine, j);
+                        acc += a.contrib[(v << 6) | lane];
+                    }
+                }
+            } else if (in) {
+                const int64_t b = a.off[c][u], e = a.off[c][u + 1];
+                int64_t i = b;
+                for (; i + 8 <= e; i += 8) {                         // eight entries in flight, added in list order
+                    float part[8];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) part[t] = a.contrib[((int64_t)adj[i + t] << a.shift) | q];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) acc += part[t];
+                }
+                for (; i < e; ++i) acc += a.contrib[((int64_t)adj[i] << a.shift) | q];
+            }
+        }
+        if (in) {
+            const int64_t at = (u << a.shift) | q;
+            const float pn = (a.restart * a.p0[at]) + (a.a * acc);
+            a.p[at] = pn;
+            a.next[at] = pn * a.inv[u];
+        }
+    }
+}
+
+// bins[q, v] = the bit pattern of p[v, q] (order-preserving for >= +0): a 64-node tile is turned in LDS.
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_bins(const float *p, int64_t n, int shift, int nq, int64_t *bins)
+{
+    __shared__ uint32_t s_bits[64][65];
+    const int qs = 1 << shift;
+    for (int64_t base = (int64_t)blockIdx.x * 64; base < n; base += (int64_t)gridDim.x * 64) {
+        const int nodes = (int)(n - base < 64 ? n - base : 64);
+        for (int e = threadIdx.x; e < nodes * qs; e += kGraphThreads) s_bits[e >> shift][e & (qs - 1)] = __float_as_uint(p[base * qs + e]);
+        __syncthreads();
+        for (int e = threadIdx.x; e < nq * 64; e += kGraphThreads) {
+            const int q = e >> 6, v = e & 63;
+            if (v < nodes) bins[(int64_t)q * n + base + v] = (int64_t)s_bits[v][q];
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_bins_exclude(const int32_t *exclude, int nq, int c, int64_t n, int64_t *bins)
+{
+    const int64_t total = (int64_t)nq * c;
+    for (int64_t i = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t v = exclude[i];
+        if (v >= 0 && v < n) bins[(i / c) * n + v] = 0;              // (several entries may name one node: they all write 0)
+    }
+}
+
+// One workgroup per query: list 0 of the fuse table is the candidates as they stand, list 1 the candidates with graph_score > 0
+// by descending graph_score, ties to the earlier position (rank by counting), padded with (-1, -inf).
+__global__ __launch_bounds__(kGraphThreads) void k_ppr_order(const float *p, int64_t n, int shift, int c, const int64_t *rows, const float *cosine,
+                                                             const int32_t *nodes, float *out_scores, int64_t *out_rows, float *out_gs)
+{
+    __shared__ uint32_t s_key[CRH_MAX_K];
+    const int q = blockIdx.x;
+    const int64_t in = (int64_t)q * c, out0 = (int64_t)q * 2 * c, out1 = out0 + c;
+    for (int i = threadIdx.x; i < c; i += kGraphThreads) {
+        const int64_t r = rows[in + i], v = nodes[in + i];
+        const float g = (r >= 0 && v >= 0 && v < n) ? p[(v << shift) | q] : 0.0f;
+        const uint32_t key = g > 0.0f ? __float_as_uint(g) : 0u;
+        s_key[i] = key;
+        out_gs[in + i] = __uint_as_float(key);
+        out_scores[out0 + i] = cosine[in + i];
+        out_rows[out0 + i] = r;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < c; i += kGraphThreads) {
+        const uint32_t key = s_key[i];
+        int before = 0, zeros = 0, zeros_before = 0;
+        for (int j = 0; j < c; ++j) {
+            const uint32_t o = s_key[j];
+            before += (o > key || (o == key && j < i)) ? 1 : 0;
+            zeros += o == 0u ? 1 : 0;
+            zeros_before += (o == 0u && j < i) ? 1 : 0;
+        }
+        if (key) {
+            out_scores[out1 + before] = __uint_as_float(key);
+            out_rows[out1 + before] = rows[in + i];
+        } else {
+            out_scores[out1 + (c - zeros) + zeros_before] = -__builtin_inff();
+            out_rows[out1 + (c - zeros) + zeros_before] = -1;
+        }
+    }
+}
+
 int graph_alloc(void **p, int64_t bytes)
 {
     *p = nullptr;
@@ -308,6 +508,9 @@ struct crh_graph {
     int32_t *path = nullptr;                 // CRH_GRAPH_MAX_HOPS + 2 ints
     int32_t *sources = nullptr;              // the upload of a host source list
     int64_t cap_sources = 0;
+    float *inv[CRH_GRAPH_MAX_RELATIONS][3] = {};   // personalised PageRank: 1 / out(v) per (relation, direction), built on first use
+    void *seeds = nullptr;                   // the upload of a host seed list: nodes, then weights
+    int64_t cap_seeds = 0;
 };
 
 using namespace crh;
@@ -324,6 +527,21 @@ void graph_free_relation(crh_graph_relation &r)
     }
     r.set = false;
     r.n_edges = 0;
+}
+
+void graph_drop_inv(crh_graph *g, int rel)
+{
+    for (float *&p : g->inv[rel]) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+}
+
+int ppr_shift(int nq)
+{
+    int shift = 0;
+    while ((1 << shift) < nq) ++shift;
+    return shift;
 }
 
 // The CSRs a traversal in `direction` PULLS through: travelling along the edges, a node looks at its sources (the reverse CSR).
@@ -384,6 +602,8 @@ int crh_graph_destroy(crh_graph *g)
     DeviceGuard guard(g->device);
     (void)hipDeviceSynchronize();
     for (auto &r : g->rel) graph_free_relation(r);
+    for (int r = 0; r < CRH_GRAPH_MAX_RELATIONS; ++r) graph_drop_inv(g, r);
+    if (g->seeds) (void)hipFree(g->seeds);
     if (g->path) (void)hipFree(g->path);
     if (g->sources) (void)hipFree(g->sources);
     delete g;
@@ -429,6 +649,7 @@ int crh_graph_set_relation(crh_graph *g, int rel, int64_t n_edges, const int64_t
         return rc;                          // (the relation as it was stays)
     }
     graph_free_relation(g->rel[rel]);
+    graph_drop_inv(g, rel);                 // (1 / out(v) of the edges that leave)
     fresh.set = true;
     fresh.n_edges = n_edges;
     g->rel[rel] = fresh;
@@ -566,6 +787,119 @@ int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_
     if (len < 0 || len > max_hops + 1) return fail(CRH_E_INTERNAL, "graph_path: a path of %d nodes", len);
     for (int i = 0; i < len; ++i) out_nodes_host[i] = got[1 + i];
     *out_len = len;
+    return CRH_OK;
+}
+
+int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int32_t *seed_nodes, const float *seed_weights, int seeds_on_device,
+                  float restart, int steps, float *work_dev, float *out_dev, void *stream)
+{
+    CRH_TRY(graph_check_rel(g, rel, direction, "graph_ppr"));
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (c < 1 || c > CRH_MAX_K) return fail(CRH_E_INVALID, "graph_ppr: c=%d outside 1..%d", c, CRH_MAX_K);
+    if (steps < 1 || steps > CRH_GRAPH_PPR_MAX_STEPS) return fail(CRH_E_INVALID, "graph_ppr: steps=%d outside 1..%d", steps, CRH_GRAPH_PPR_MAX_STEPS);
+    if (!(restart > 0.0f && restart < 1.0f)) return fail(CRH_E_INVALID, "graph_ppr: restart=%g is not inside (0, 1)", (double)restart);
+    if (!seed_nodes) return fail(CRH_E_INVALID, "graph_ppr: NULL pointer");
+    const int64_t n = g->n_nodes, total = (int64_t)nq * c;
+    if (!seeds_on_device)
+        for (int64_t i = 0; i < total; ++i) {
+            if (seed_nodes[i] < -1 || seed_nodes[i] >= n)
+                return fail(CRH_E_INVALID, "graph_ppr: seed %lld names node %d of %lld", (long long)i, seed_nodes[i], (long long)n);
+            if (seed_weights && !(seed_weights[i] >= 0.0f && seed_weights[i] < __builtin_inff()))
+                return fail(CRH_E_INVALID, "graph_ppr: weight %lld is %g, not a finite value >= 0", (long long)i, (double)seed_weights[i]);
+        }
+    if (n == 0) return CRH_OK;
+    if (!work_dev || !out_dev) return fail(CRH_E_INVALID, "graph_ppr: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int shift = ppr_shift(nq);
+    const int64_t plane = n << shift;
+    float *&inv = g->inv[rel][direction];
+    if (!inv) {                              // built once per (relation, direction); crh_graph_set_relation drops it
+        void *p = nullptr;
+        CRH_TRY(graph_alloc(&p, n * 4));
+        const crh_graph_relation &r = g->rel[rel];
+        const int64_t *o0 = direction == CRH_GRAPH_AGAINST ? r.off[1] : r.off[0];            // out(v): the OPPOSITE list or lists
+        const int64_t *o1 = direction == CRH_GRAPH_BOTH ? r.off[1] : nullptr;
+        hipLaunchKernelGGL(k_ppr_inv, dim3(graph_blocks(n, kGraphThreads)), dim3(kGraphThreads), 0, st, o0, o1, n, static_cast<float *>(p));
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {     // (another stream may use it next)
+            (void)hipFree(p);
+            return fail(CRH_E_HIP, "graph_ppr: building 1 / out(v) failed");
+        }
+        inv = static_cast<float *>(p);
+    }
+    const int32_t *nodes_dev = seed_nodes;
+    const float *weights_dev = seed_weights;
+    if (!seeds_on_device) {
+        if (g->cap_seeds < total) {
+            CRH_HIP(hipStreamSynchronize(st));   // (a call in flight on this stream still reads the old upload)
+            if (g->seeds) (void)hipFree(g->seeds);
+            g->seeds = nullptr;
+            g->cap_seeds = 0;
+            const int64_t cap = std::max<int64_t>(total, 4096);
+            CRH_TRY(graph_alloc(&g->seeds, cap * 8));
+            g->cap_seeds = cap;
+        }
+        int32_t *up_nodes = static_cast<int32_t *>(g->seeds);
+        float *up_weights = reinterpret_cast<float *>(up_nodes + g->cap_seeds);
+        CRH_HIP(hipMemcpyAsync(up_nodes, seed_nodes, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        if (seed_weights) CRH_HIP(hipMemcpyAsync(up_weights, seed_weights, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        CRH_HIP(hipStreamSynchronize(st));       // (the caller may free its lists on return)
+        nodes_dev = up_nodes;
+        weights_dev = seed_weights ? up_weights : nullptr;
+    }
+    float *p0 = work_dev, *ping = work_dev + plane, *pong = work_dev + 2 * plane;
+    CRH_HIP(hipMemsetAsync(p0, 0, (size_t)plane * 2 * 4, st));       // p0 and contrib_0: +0 wherever no seed lands
+    hipLaunchKernelGGL(k_ppr_seed, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, nodes_dev, weights_dev, c, n, shift, inv, p0, ping);
+    PprStepArgs sa{};
+    sa.ncsr = graph_pull(g, rel, direction, sa.off, sa.adj);
+    sa.p0 = p0;
+    sa.inv = inv;
+    sa.p = out_dev;
+    sa.n = n;
+    sa.shift = shift;
+    sa.restart = restart;
+    sa.a = 1.0f - restart;
+    const unsigned blocks = graph_blocks(ceil_div(n, 64 >> shift), kGraphWaves);
+    for (int t = 0; t < steps; ++t) {
+        sa.contrib = (t & 1) ? pong : ping;
+        sa.next = (t & 1) ? ping : pong;
+        if (shift == 6)
+            hipLaunchKernelGGL(k_ppr_step<true>, dim3(blocks), dim3(kGraphThreads), 0, st, sa);
+        else
+            hipLaunchKernelGGL(k_ppr_step<false>, dim3(blocks), dim3(kGraphThreads), 0, st, sa);
+    }
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_ppr_bins(int64_t n_nodes, int nq, const float *scores_dev, int c, const int32_t *exclude_dev, int64_t *out_bins_dev, void *stream)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_ppr_bins: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr_bins: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (c < 0 || c > CRH_MAX_K || (c > 0 && !exclude_dev)) return fail(CRH_E_INVALID, "graph_ppr_bins: %d exclusions per query (0..%d) at %p", c, CRH_MAX_K, (const void *)exclude_dev);
+    if (n_nodes == 0) return CRH_OK;
+    if (!scores_dev || !out_bins_dev) return fail(CRH_E_INVALID, "graph_ppr_bins: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_ppr_bins, dim3(graph_blocks(n_nodes, 64)), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, ppr_shift(nq), nq, out_bins_dev);
+    if (c > 0)
+        hipLaunchKernelGGL(k_ppr_bins_exclude, dim3(graph_blocks((int64_t)nq * c, kGraphThreads)), dim3(kGraphThreads), 0, st, exclude_dev, nq, c, n_nodes,
+                           out_bins_dev);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_ppr_order(int64_t n_nodes, int nq, int c, const float *scores_dev, const int64_t *rows_dev, const float *cosine_dev,
+                        const int32_t *nodes_dev, float *out_fuse_scores_dev, int64_t *out_fuse_rows_dev, float *out_graph_score_dev, void *stream)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_ppr_order: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr_order: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (c < 1 || c > CRH_MAX_K) return fail(CRH_E_INVALID, "graph_ppr_order: c=%d outside 1..%d", c, CRH_MAX_K);
+    if (!rows_dev || !cosine_dev || !nodes_dev || !out_fuse_scores_dev || !out_fuse_rows_dev || !out_graph_score_dev || (n_nodes > 0 && !scores_dev))
+        return fail(CRH_E_INVALID, "graph_ppr_order: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_ppr_order, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, ppr_shift(nq), c, rows_dev, cosine_dev, nodes_dev,
+                       out_fuse_scores_dev, out_fuse_rows_dev, out_graph_score_dev);
+    CRH_HIP(hipGetLastError());
     return CRH_OK;
 }
 

@@ -41,6 +41,7 @@ GRAPH_MAX_RELATIONS, GRAPH_MAX_QUERIES, GRAPH_MAX_HOPS = 8, 64, 16   # CRH_GRAPH
 GRAPH_WAVE_DEGREE = 64      # CRH_GRAPH_WAVE_DEGREE: adjacency lists of at least so many entries are walked by a whole wave
 GRAPH_ALONG, GRAPH_AGAINST, GRAPH_BOTH = 0, 1, 2   # CRH_GRAPH_*: the direction of travel
 GRAPH_DIRECTIONS = {"callees": GRAPH_ALONG, "callers": GRAPH_AGAINST, "both": GRAPH_BOTH}
+GRAPH_PPR_MAX_STEPS = 64    # CRH_GRAPH_PPR_MAX_STEPS: steps of one crh_graph_ppr
 FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
@@ -71,6 +72,7 @@ EXPORTS = (
     "crh_graph_create", "crh_graph_destroy", "crh_graph_count", "crh_graph_set_relation", "crh_graph_bfs", "crh_graph_list",
     "crh_graph_row_words", "crh_graph_path",
     "crh_graph_node_rows", "crh_graph_candidates", "crh_rerank_hybrid",
+    "crh_graph_ppr", "crh_graph_ppr_bins", "crh_graph_ppr_order",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
@@ -262,6 +264,9 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_graph_row_words.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp]
     L.crh_graph_path.argtypes = [vp, i32, i32, vp, i32, i64, i32, vp, C.POINTER(i32), vp]
     L.crh_graph_node_rows.argtypes = [i64, vp, vp, i64, i64, vp, vp]
+    L.crh_graph_ppr.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, C.c_float, i32, vp, vp, vp]
+    L.crh_graph_ppr_bins.argtypes = [i64, i32, vp, i32, vp, vp, vp]
+    L.crh_graph_ppr_order.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.crh_graph_candidates.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.crh_rerank_hybrid.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, i32, i32, i32, i32,
                                     vp, vp, vp, vp, vp, vp, vp]
@@ -1380,12 +1385,14 @@ class Graph:
         self._h = h
         self.levels = self.seen = self.active = None
         self.last = None      # (nq, max_hops) of the last bfs
+        self.ppr_work = None  # f32 [4, n_nodes, QS]: p0, two contribution planes, the scores of the last ppr
+        self.ppr_last = None  # (nq, QS) of the last ppr
 
     def close(self) -> None:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.crh_graph_destroy(self._h)
             self._h = None
-            self.levels = self.seen = self.active = None
+            self.levels = self.seen = self.active = self.ppr_work = None
 
     __del__ = close
 
@@ -1505,6 +1512,106 @@ class Graph:
         check(lib().crh_graph_path(self._handle(), int(rel), graph_direction(direction), _ptr(levels), int(q), int(target), int(max_hops),
                                    out.ctypes.data, C.byref(n), stream))
         return out[: int(n.value)].copy()
+
+    # -- personalised PageRank
+    def _ppr_workspace(self, qs: int):
+        import torch
+        need = 4 * self.n_nodes * qs                                    # p0, two contribution planes, the scores
+        if self.ppr_work is None or int(self.ppr_work.numel()) < need:
+            self.ppr_work = None                                       # (released before the larger one is taken)
+            self.ppr_work = torch.empty((max(need, 1),), dtype=torch.float32, device=f"cuda:{self.device}")
+        return self.ppr_work
+
+    def ppr(self, rel: int, direction, seeds, weights=None, restart: float = 0.15, steps: int = 16, stream: int = 0):
+        """``crh_graph_ppr``: personalised PageRank from up to ``GRAPH_MAX_QUERIES`` seed lists.  ``seeds`` is an iterable of
+        iterables of node ids with ``weights`` alike (host; ``None``: every weight 1), or an int32 device tensor [nq, c] with an
+        f32 device tensor [nq, c] (-1 / 0: padding), complete on ``stream``.  Returns the scores, f32 [n_nodes, nq]: a view of
+        the handle's workspace that the next ``ppr`` overwrites.  Only enqueues."""
+        on_dev = _is_dev(seeds)
+        if on_dev:
+            _typed(seeds, "int32", "seeds")
+            if seeds.ndim != 2:
+                raise NativeError(E_INVALID, "device seeds must be an int32 tensor [nq, c]")
+            nq, c = int(seeds.shape[0]), int(seeds.shape[1])
+            if weights is not None:
+                if not _is_dev(weights):
+                    raise NativeError(E_INVALID, "device seeds take device weights")
+                _out(weights, "float32", "weights", (nq, c))
+            nodes, w = seeds, weights
+        else:
+            sets = [np.asarray(list(s), np.int64).reshape(-1) for s in seeds]
+            nq, c = len(sets), max([int(s.size) for s in sets] + [1])
+            nodes = np.full((nq, c), -1, np.int32)
+            for q, s in enumerate(sets):
+                nodes[q, : s.size] = s
+            w = None
+            if weights is not None:
+                w = np.zeros((nq, c), np.float32)
+                given = [np.asarray(list(x), np.float32).reshape(-1) for x in weights]
+                if [int(x.size) for x in given] != [int(s.size) for s in sets]:
+                    raise NativeError(E_INVALID, "ppr: weights must have the shape of seeds")
+                for q, x in enumerate(given):
+                    w[q, : x.size] = x
+        qs = 1
+        while qs < min(max(nq, 1), GRAPH_MAX_QUERIES):
+            qs *= 2
+        work = self._ppr_workspace(qs)
+        plane = self.n_nodes * qs
+        check(lib().crh_graph_ppr(self._handle(), int(rel), graph_direction(direction), nq, c, _ptr(nodes), _ptr(w), on_dev, float(restart),
+                                  int(steps), _ptr(work), _ptr(work) + 12 * plane, stream))
+        self.ppr_last = (nq, qs)
+        return work[3 * plane: 4 * plane].view(self.n_nodes, qs)[:, :nq]
+
+    def _ppr_state(self, what: str):
+        if self.ppr_last is None:
+            raise NativeError(E_INVALID, f"{what}: no ppr has run on this graph")
+        nq, qs = self.ppr_last
+        plane = self.n_nodes * qs
+        return nq, self.ppr_work[3 * plane: 4 * plane]
+
+    def ppr_top(self, k: int, exclude=None, stream: int = 0):
+        """The top ``k`` nodes of the last ``ppr`` per query: ``crh_graph_ppr_bins`` (``exclude``: an int32 device tensor [nq, c]
+        of nodes to leave out, -1: padding) and ``crh_facet_select``.  Returns device tensors ``(nodes int32 [nq, k], scores f32
+        [nq, k])`` by descending score, ties to the lower node id, a zero score never returned; the tail is ``(-1, 0)``."""
+        import torch
+        nq, scores = self._ppr_state("ppr_top")
+        c = 0
+        if exclude is not None:
+            _typed(exclude, "int32", "exclude")
+            if not _is_dev(exclude) or exclude.ndim != 2 or int(exclude.shape[0]) != nq:
+                raise NativeError(E_INVALID, f"exclude must be an int32 device tensor [{nq}, c]")
+            c = int(exclude.shape[1])
+        bins = torch.empty((nq, max(self.n_nodes, 1)), dtype=torch.int64, device=f"cuda:{self.device}")
+        if self.n_nodes == 0:
+            bins.zero_()
+        use_device(self.device)
+        check(lib().crh_graph_ppr_bins(self.n_nodes, nq, _ptr(scores), c, _ptr(exclude) if c else None, _ptr(bins), stream))
+        codes, counts, _ = facet_select(bins, k, stream)
+        return codes, counts.to(torch.int32).view(torch.float32)
+
+    def ppr_order(self, rows, cosine, nodes, stream: int = 0):
+        """``crh_graph_ppr_order`` over the last ``ppr``: a candidate table (``rows`` int64, ``cosine`` f32, ``nodes`` int32, each
+        a device tensor [nq, c]) as ``(scores f32 [nq, 2, c], rows int64 [nq, 2, c], graph_score f32 [nq, c])`` -- the two lists
+        ``fuse_select(scores, rows, 2, k)`` takes (the table itself; its candidates with a positive graph score by descending
+        graph score, ties to the earlier position) and every candidate's graph score."""
+        import torch
+        nq, scores = self._ppr_state("ppr_order")
+        for x, what in ((rows, "rows"), (cosine, "cosine"), (nodes, "nodes")):
+            if not _is_dev(x):
+                raise NativeError(E_INVALID, f"{what} must be a device tensor")
+        if rows.ndim != 2 or int(rows.shape[0]) != nq:
+            raise NativeError(E_INVALID, f"rows must be [{nq}, c]")
+        c = int(rows.shape[1])
+        _typed(rows, "int64", "rows")
+        _out(cosine, "float32", "cosine", (nq, c))
+        _out(nodes, "int32", "nodes", (nq, c))
+        dev = f"cuda:{self.device}"
+        fs = torch.empty((nq, 2, c), dtype=torch.float32, device=dev)
+        fr = torch.empty((nq, 2, c), dtype=torch.int64, device=dev)
+        gs = torch.empty((nq, c), dtype=torch.float32, device=dev)
+        use_device(self.device)
+        check(lib().crh_graph_ppr_order(self.n_nodes, nq, c, _ptr(scores), _ptr(rows), _ptr(cosine), _ptr(nodes), _ptr(fs), _ptr(fr), _ptr(gs), stream))
+        return fs, fr, gs
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

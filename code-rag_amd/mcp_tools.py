@@ -40,8 +40,25 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
-            if rank not in (None, "vector", "hybrid"):
-                raise ValueError(f"rank {rank!r} is neither 'vector' nor 'hybrid'")
+            if rank not in (None, "vector", "hybrid", "propagated"):
+                raise ValueError(f"rank {rank!r} is none of 'vector', 'hybrid', 'propagated'")
+            if rank == "propagated":             # the matches re-ranked by a random walk over the call graph
+                if like_ids or unlike_ids or entities or intent:
+                    raise ValueError("rank='propagated' takes the arguments of a plain search, not like_ids, unlike_ids, entities or intent")
+                extra = {k: v for k, v in (("diversity", diversity), ("max_per_file", max_per_file), ("extra_queries", extra_queries or None),
+                                           ("min_score", min_score), ("max_overlap", max_overlap), ("candidates", candidates),
+                                           ("contains", contains or None), ("matches", matches or None), ("fuzzy", fuzzy or None),
+                                           ("edits", edits if fuzzy else None), ("within_callers_of", within_callers_of or None),
+                                           ("within_callees_of", within_callees_of or None),
+                                           ("graph_hops", graph_hops if within_callers_of or within_callees_of else None)) if v is not None}
+                if contains_case is not None and (contains or matches or fuzzy):
+                    extra["contains_case"] = contains_case
+                got = await searcher.search_code_propagated(query=query, limit=limit, entity_type=entity_type, mode=mode or "semantic", **extra)
+                data = [vars(SearchResult(qualified_name=h.get("graph_node_id") or h.get("entity_name"), entity_type=h.get("entity_type"),
+                                          file_path=h.get("file_path"), score=h.get("score"), summary=None)) for h in got["results"]]
+                related = ", ".join(r["qualified_name"] for r in got["related"])
+                return ToolResult(success=True, data=data, message=f"Found {len(data)} matches for '{query}', ordered by similarity and call-graph "
+                                  "relevance." + (f" Related code the query text did not find: {related}." if related else ""))
             if rank == "hybrid":                 # graph results and vector hits in one list, ranked on the device
                 import numpy as np
                 from .engine_helpers import search_and_rank_hybrid_batch_device
@@ -139,9 +156,11 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                   "required": False},
             "graph_hops": {"type": "integer", "description": "With within_callers_of / within_callees_of: how many calls away code may "
                                                              "be, 1..16 (default: 3)", "required": False},
-            "rank": {"type": "string", "description": "'vector' (the default: the plain matches) or 'hybrid': the named entities' graph "
+            "rank": {"type": "string", "description": "'vector' (the default: the plain matches), 'hybrid': the named entities' graph "
                                                       "neighbourhood (callers, callees, class hierarchy) and the matches ranked as one "
-                                                      "list", "required": False},
+                                                      "list, or 'propagated': the matches re-ordered by how central they are in the code "
+                                                      "the matches call and are called from, with the related functions the text did "
+                                                      "not find named in the message", "required": False},
             "entities": {"type": "array", "description": "With rank='hybrid': names of the functions or classes the question is about",
                          "required": False},
             "intent": {"type": "string", "description": "With rank='hybrid': find_callers, find_callees, find_hierarchy, "
@@ -155,10 +174,17 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
     function, what it calls, and how one function reaches another -- answered on the device from the call edges beside the
     vectors (``VectorSearcher.find_callers`` / ``find_callees`` / ``find_call_chain``)."""
     async def code_graph(name: str, relation: str = "callers", target: str | None = None, max_hops: int | None = None,
-                         limit: int = 50) -> ToolResult:
-        logger.info(f"[Tool:CodeGraph] {relation} of '{name}'" + (f" -> '{target}'" if target else ""))
+                         limit: int = 50, op: str | None = None) -> ToolResult:
+        logger.info(f"[Tool:CodeGraph] {op or relation} of '{name}'" + (f" -> '{target}'" if target else ""))
         try:
             searcher = vector_searcher_factory()
+            if op is not None:
+                if op != "important_near":
+                    raise ValueError(f"op {op!r} is not 'important_near'")
+                if target or max_hops is not None:
+                    raise ValueError("op 'important_near' takes name and limit only")
+                nodes = await searcher.find_important_near(name, limit=limit)
+                return ToolResult(success=True, data=nodes, message=f"Found {len(nodes)} nodes that matter around '{name}'.")
             if relation == "chain":
                 if not target:
                     raise ValueError("relation 'chain' needs a target")
@@ -187,6 +213,9 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
             "target": {"type": "string", "description": "With relation 'chain': the qualified name to reach", "required": False},
             "max_hops": {"type": "integer", "description": "How many calls away to look, 1..16 (default: 3; 8 for a chain)", "required": False},
             "limit": {"type": "integer", "description": "Maximum number of callers / callees listed, nearest first (default: 50)", "required": False},
+            "op": {"type": "string", "description": "'important_near': instead of a walk, rank the code around name by a random walk with "
+                                                    "restart over the calls, both ways (personalised PageRank): what matters near it, "
+                                                    "best first", "required": False},
         },
     }
 

@@ -369,6 +369,7 @@ class _Collection:
         self._graph_rows_state = None
         self._graph_cache: dict[tuple, tuple] = {}   # (spec, graph version, collection state) -> (tag, words per index)
         self.graph_bfs_calls = 0             # graph conditions resolved by a BFS so far (repeated filters reuse the words)
+        self.graph_ppr_calls = 0             # personalised PageRank passes run so far (64 queries or name sets each)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
@@ -751,8 +752,15 @@ class _Collection:
         """The nodes of a table of GLOBAL rows (CUDA int64, -1: padding) as an int32 CUDA tensor of the same shape, -1 where the
         row's key is no node: ``crh_gather_rows_i32`` over every owned shard's row -> node column (a shard answers 0 for the
         rows of the others, so the gathers add up)."""
-        import torch
         columns = self._graph_row_nodes()
+        if not self.shards._native():                                    # injected indexes: host arrays all the way
+            shard, local = split_global(np.asarray(rows_dev, np.int64))
+            out = np.full(local.shape, -1, np.int32)
+            for s in self.shards.owned:
+                mine = (local >= 0) & (shard == s)
+                out[mine] = columns[s][local[mine]]
+            return out
+        import torch
         total = None
         for s in self.shards.owned:
             part = ffi.gather_rows_i32(rows_dev, s * SHARD_STRIDE, columns[s], 0, stream)
@@ -774,6 +782,75 @@ class _Collection:
             nodes, depth, count = graph.list(related_limit, first_level=1, stream=stream)
             out.append((_host(s), self._global_slots(_host(r)), _host(nodes), _host(depth), _host(count)))
         return tuple(np.concatenate([o[i] for o in out]) for i in range(5))
+
+    # -- graph-propagated relevance (personalised PageRank)
+    def _node_slots(self, nodes: np.ndarray) -> np.ndarray:
+        """The slots of the representative rows of a host table of nodes (-1: padding), -1 for a node without an alive row."""
+        rows_host = self.graph_node_rows()[1]
+        nodes = np.asarray(nodes, np.int64)
+        rows = np.where(nodes >= 0, rows_host[np.maximum(nodes, 0)], -1) if rows_host.size else np.full(nodes.shape, -1, np.int64)
+        return self._global_slots(rows)
+
+    def search_propagated(self, queries: np.ndarray, limit: int, candidates: int, dfilt, prop: dict[str, Any], related_limit: int):
+        """Per 64 queries, all on the device: the exact top-``candidates``, their rows gathered to nodes, those nodes as the
+        seeds of ONE personalised PageRank (weights ``max(cos, +0)``, or 1), the candidates ordered by graph score and fused
+        with the cosine list (``crh_graph_ppr_order`` + ``crh_fuse_select``, m = 2), and the best nodes that are no candidate's
+        node (``crh_graph_ppr_bins`` + ``crh_facet_select``).  Returns host arrays ``(slots [nq, limit], fused, cosine,
+        graph_score, related nodes [nq, related_limit], their scores, their representative slots)``; -1 is padding."""
+        graph, rel = self._graph_ready(prop["relation"])
+        stream = self.shards._stream()
+        out = []
+        for a in range(0, len(queries), ffi.GRAPH_MAX_QUERIES):
+            part = np.ascontiguousarray(queries[a:a + ffi.GRAPH_MAX_QUERIES])
+            cs, cr = self.shards._candidates(part, candidates, dfilt)
+            nodes = self.graph_nodes_of(cr, stream)
+            weights = cs.clip(min=0) if prop["seed_weight"] == "cosine" else None
+            graph.ppr(rel, prop["direction"], nodes, weights, prop["restart"], prop["steps"], stream=stream)
+            self.graph_ppr_calls += 1
+            fs, fr, gs = graph.ppr_order(cr, cs, nodes, stream=stream)
+            fused = ffi.fuse_select(fs, fr, 2, limit, "rrf", prop["rrf_k"], stream=stream)
+            rows, score, first = _host(fused[0]), _host(fused[1]), _host(fused[4])
+            at = np.maximum(first, 0)                                    # (a row's first entry lies in list 0: its position there)
+            cos = np.where(rows >= 0, np.take_along_axis(_host(cs), at, 1), -np.inf).astype(np.float32)
+            gsc = np.where(rows >= 0, np.take_along_axis(_host(gs), at, 1), 0).astype(np.float32)
+            if related_limit:
+                top, top_scores = (_host(t) for t in graph.ppr_top(related_limit, exclude=nodes, stream=stream))
+            else:
+                top, top_scores = np.zeros((len(part), 0), np.int32), np.zeros((len(part), 0), np.float32)
+            out.append((self._global_slots(rows), score, cos, gsc, top, top_scores, self._node_slots(top)))
+        return tuple(np.concatenate([o[i] for o in out]) for i in range(7))
+
+    def graph_rank(self, name_sets, weight_sets, relation: str, direction: str, restart: float, steps: int, limit: int, match: str,
+                   include_seeds: bool):
+        """Per name set: personalised PageRank seeded by the named nodes (a name's weight goes to every node it stands for), 64
+        sets per pass, and its ``limit`` best nodes.  Returns ``[(nodes, scores, slots, unresolved)]``: host arrays of the nodes
+        with a positive score, best first, and the slots of their representative rows (-1: none)."""
+        graph, rel = self._graph_ready(relation)
+        stream = self.shards._stream()
+        resolved = []
+        for names, ws in zip(name_sets, weight_sets):
+            ids, w, missing = [], [], []
+            for j, name in enumerate(names):
+                got, miss = graph_mod.resolve([name], self._graph_code, self._graph_names, match)
+                missing += miss
+                ids += got
+                w += [1.0 if ws is None else float(ws[j])] * len(got)
+            if len(ids) > ffi.MAX_K:
+                raise ValueError(f"a seed set of {len(ids)} nodes exceeds the maximum of {ffi.MAX_K}")
+            resolved.append((ids, w, missing))
+        out = []
+        for a in range(0, len(resolved), ffi.GRAPH_MAX_QUERIES):
+            part = resolved[a:a + ffi.GRAPH_MAX_QUERIES]
+            graph.ppr(rel, direction, [ids for ids, _, _ in part], [w for _, w, _ in part], restart, steps, stream=stream)
+            self.graph_ppr_calls += 1
+            exclude = None
+            if not include_seeds:
+                c = max(max(len(ids) for ids, _, _ in part), 1)
+                exclude = self.shards._local(np.asarray([ids + [-1] * (c - len(ids)) for ids, _, _ in part], np.int32).reshape(len(part), c))
+            nodes, scores = (_host(t) for t in graph.ppr_top(limit, exclude=exclude, stream=stream))
+            slots = self._node_slots(nodes)
+            out += [(nodes[q][nodes[q] >= 0], scores[q][nodes[q] >= 0], slots[q][nodes[q] >= 0], missing) for q, (_, _, missing) in enumerate(part)]
+        return out
 
     # -- the hybrid re-rank with graph results (DESIGN.md 3.28)
     def richness_columns(self) -> dict[int, Any]:
@@ -804,9 +881,16 @@ class _Collection:
             stream = self.shards._stream()
             columns = self._graph_row_nodes()
             out = None
-            for s in self.shards.owned:
+            for s in self.shards.owned if self.shards._native() else ():
                 alive = self.shards.index[s].row_mask(None, stream=stream)
                 out = graph_node_rows(columns[s], len(self._graph_names), alive, row_base=s * SHARD_STRIDE, out=out, stream=stream)
+            if out is None:                                              # injected indexes: the same minimum on the host
+                out = np.full((len(self._graph_names),), -1, np.int64)
+                for s in sorted(self.shards.owned, reverse=True):
+                    alive = np.unpackbits(np.asarray(self.shards.index[s].row_mask(None)).view(np.uint8), bitorder="little").astype(bool)
+                    for r in range(len(columns[s]) - 1, -1, -1):
+                        if alive[r] and columns[s][r] >= 0:
+                            out[columns[s][r]] = s * SHARD_STRIDE + r
             kept = self._node_rows = (key, out, _host(out))
             self.graph_node_rows_builds = getattr(self, "graph_node_rows_builds", 0) + 1
         return kept[1], kept[2]
@@ -3064,6 +3148,160 @@ class HipVectorStore:
                               filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> dict[str, Any]:
         """:meth:`search_expanded_batch` for one query: ``{"hits", "related", "related_count"}``."""
         return (await self.search_expanded_batch(collection, [query_vector], limit, graph_expand, filters, must_not))[0]
+
+    # ------------------------------------------------------------------ graph-propagated relevance (DESIGN.md 3.30)
+    PROPAGATE_DEFAULTS = {"relation": "calls", "direction": "both", "restart": 0.15, "steps": 16, "seed_weight": "cosine", "rrf_k": 60}
+
+    @classmethod
+    def _propagate_args(cls, propagate, what: str = "propagate") -> dict[str, Any]:
+        """The checked settings of one personalised PageRank: the defaults with the caller's keys over them; ``ValueError`` for
+        the caller alone, before anything runs."""
+        given = {} if propagate is None or propagate is True else propagate
+        if not isinstance(given, dict) or any(k not in cls.PROPAGATE_DEFAULTS for k in given):
+            raise ValueError(f"{what} takes {', '.join(cls.PROPAGATE_DEFAULTS)}, not {propagate!r}")
+        p = {**cls.PROPAGATE_DEFAULTS, **given}
+        if not isinstance(p["relation"], str) or not p["relation"]:
+            raise ValueError(f"{what}: relation must be a non-empty string, not {p['relation']!r}")
+        if p["direction"] not in graph_mod.DIRECTIONS:
+            raise ValueError(f"{what}: direction must be one of {', '.join(graph_mod.DIRECTIONS)}, not {p['direction']!r}")
+        if p["seed_weight"] not in ("cosine", "uniform"):
+            raise ValueError(f"{what}: seed_weight must be 'cosine' or 'uniform', not {p['seed_weight']!r}")
+        for key, lo, hi in (("steps", 1, ffi.GRAPH_PPR_MAX_STEPS), ("rrf_k", 0, 2 ** 31 - 1)):
+            if isinstance(p[key], bool) or not isinstance(p[key], (int, np.integer)) or not lo <= int(p[key]) <= hi:
+                raise ValueError(f"{what}: {key} must be an int in {lo}..{hi}, not {p[key]!r}")
+            p[key] = int(p[key])
+        r = p["restart"]
+        if isinstance(r, bool) or not isinstance(r, (int, float, np.floating)) or not 0.0 < float(np.float32(r)) < 1.0:
+            raise ValueError(f"{what}: restart must be a number inside (0, 1), not {r!r}")
+        p["restart"] = float(r)
+        return p
+
+    async def search_propagated_batch(self, collection: str, query_vectors, limit: int = 10, candidates: int | None = None,
+                                      propagate: dict[str, Any] | None = None, related_limit: int = 10,
+                                      filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, **others) -> list[dict[str, Any]]:
+        """Vector search re-ranked and extended by graph-propagated relevance: ``[{"hits": [...], "related": [...]}]``.  Per
+        query the exact top-``candidates`` (default ``4 * limit``, at most 512) seed a personalised PageRank over the
+        collection's graph -- a random walk with restart from the candidates' nodes, weighted ``max(cosine, 0)`` -- and
+
+        * ``hits`` are the first ``limit`` candidates under reciprocal-rank fusion of the cosine order and the graph-score
+          order (a candidate without a node, or with graph score 0, stands in the cosine list only); each carries ``score``
+          (fused), ``cosine`` and ``graph_score``;
+        * ``related`` are the ``related_limit`` nodes with the highest graph score that are NO candidate's node -- what the
+          query is about beyond what the embedding found -- as ``{"node", "graph_score", "payload"}``, ``payload`` being that of
+          the node's representative chunk (its first alive one) or None.
+
+        ``propagate`` = ``{"relation": "calls", "direction": "both", "restart": 0.15, "steps": 16, "seed_weight": "cosine" |
+        "uniform", "rrf_k": 60}`` (any key may be left out).  64 queries per pass; nothing returns to the host between the
+        search and the finished tables.  The definition is exact and deterministic."""
+        try:
+            used = [name for name in ("diversity", "group_by", "max_overlap", "score_threshold") if others.get(name) is not None]
+            unknown = [name for name in others if name not in ("diversity", "group_by", "max_overlap", "score_threshold")]
+            if unknown:
+                raise TypeError(f"search_propagated got unexpected arguments: {', '.join(unknown)}")
+            if isinstance(filters, (list, tuple)) or isinstance(must_not, (list, tuple)):
+                used.append("per-query filter lists")
+            if used:
+                raise ValueError(f"search_propagated cannot be combined with {', '.join(used)} (it takes ONE filter dict, and fuses two "
+                                 "orders of one candidate list)")
+            if self._shard_backend == "dist":
+                raise ValueError("search_propagated is not available with shard_backend='dist' yet")
+            prop = self._propagate_args(propagate)
+            for what, v, lo, hi in (("limit", limit, 0, ffi.MAX_K // 2), ("related_limit", related_limit, 0, ffi.MAX_K)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                    raise ValueError(f"search_propagated: {what} must be an int in {lo}..{hi}, not {v!r}")
+            limit, related_limit = int(limit), int(related_limit)
+            if candidates is None:
+                candidates = min(ffi.MAX_K // 2, 4 * max(limit, 1))
+            if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or not max(limit, 1) <= int(candidates) <= ffi.MAX_K // 2:
+                raise ValueError(f"search_propagated: candidates must be an int in {max(limit, 1)}..{ffi.MAX_K // 2} (>= limit), not {candidates!r}")
+            candidates = int(candidates)
+            q = np.ascontiguousarray(np.asarray(query_vectors, dtype=np.float32))
+            if q.size == 0:
+                return []
+            q = q.reshape(-1, q.shape[-1]) if q.ndim != 2 else q
+
+            def work():
+                col = self._col(collection)
+                if q.shape[1] != col.shards.dim:
+                    raise ValueError(f"query dim {q.shape[1]} != index dim {col.shards.dim}")
+                col._graph_ready(prop["relation"])
+                dfilt = col.device_filters(filters, must_not)
+                if dfilt is None or limit <= 0:
+                    return [{"hits": [], "related": []} for _ in range(len(q))]
+                self.search_passes += (len(q) + 63) // 64
+                slots, fused, cos, gsc, top, top_scores, top_slots = col.search_propagated(q, limit, candidates, dfilt, prop, related_limit)
+
+                def decorate(hits, keep):
+                    for h, cv, gv in zip(hits, cos[keep].tolist(), gsc[keep].tolist()):
+                        h["cosine"], h["graph_score"] = cv, gv
+                return [{"hits": h, "related": self._node_list(col, top[i], top_scores[i], top_slots[i])}
+                        for i, h in enumerate(self._hit_lists(col, slots, fused, decorate=decorate))]
+            return await self._run(work)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to search {collection}", cause=e)
+
+    @staticmethod
+    def _node_list(col: _Collection, nodes, scores, slots) -> list[dict[str, Any]]:
+        """``[{"node", "graph_score", "payload"}]`` of one query's ranked nodes (-1: padding); a node without an alive chunk has
+        payload None.  Runs inside the worker job, like :meth:`_hit_lists`."""
+        keep = np.asarray(nodes) >= 0
+        have = [int(t) for t in np.asarray(slots)[keep] if t >= 0]
+        pays = iter(col.payloads_of(have)) if have else iter(())
+        return [{"node": col._graph_names[int(v)], "graph_score": float(g), "payload": next(pays) if t >= 0 else None}
+                for v, g, t in zip(np.asarray(nodes)[keep], np.asarray(scores)[keep], np.asarray(slots)[keep])]
+
+    async def search_propagated(self, collection: str, query_vector, limit: int = 10, candidates: int | None = None,
+                                propagate: dict[str, Any] | None = None, related_limit: int = 10,
+                                filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None, **others) -> dict[str, Any]:
+        """:meth:`search_propagated_batch` for one query: ``{"hits", "related"}``."""
+        return (await self.search_propagated_batch(collection, [query_vector], limit, candidates, propagate, related_limit, filters, must_not,
+                                                   **others))[0]
+
+    async def graph_rank_batch(self, collection: str, name_sets, weights=None, direction: str = "both", relation: str = "calls",
+                               restart: float = 0.15, steps: int = 16, limit: int = 10, match: str = "exact",
+                               include_seeds: bool = True) -> list[dict[str, Any]]:
+        """:meth:`graph_rank` for a list of name sets (each a name or a list of names; ``weights``: None, or per set None or one
+        number per name): one personalised PageRank per 64 sets."""
+        try:
+            sets = [[s] if isinstance(s, str) else list(s) for s in name_sets]
+            wsets = [None] * len(sets) if weights is None else list(weights)
+            if len(wsets) != len(sets):
+                raise ValueError(f"{len(wsets)} weight lists for {len(sets)} name sets")
+            checked = []
+            for names, ws in zip(sets, wsets):
+                if ws is not None:
+                    ws = [ws] if isinstance(ws, (int, float)) else list(ws)
+                    if len(ws) != len(names) or any(isinstance(w, bool) or not isinstance(w, (int, float, np.floating, np.integer))
+                                                     or not np.isfinite(np.float32(w)) or w < 0 for w in ws):
+                        raise ValueError(f"weights must be one finite number >= 0 per name, not {ws!r} for {names!r}")
+                checked.append(ws)
+            prop = self._propagate_args({"relation": relation, "direction": direction, "restart": restart, "steps": steps}, "graph_rank")
+            if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= int(limit) <= ffi.MAX_K:
+                raise ValueError(f"graph_rank: limit must be an int in 1..{ffi.MAX_K}, not {limit!r}")
+            if self._shard_backend == "dist":
+                raise ValueError("graph_rank is not available with shard_backend='dist' yet")
+
+            def work():
+                col = self._col(collection)
+                ranked = col.graph_rank(sets, checked, prop["relation"], prop["direction"], prop["restart"], prop["steps"], int(limit), match,
+                                        bool(include_seeds))
+                return [{"hits": self._node_list(col, nodes, scores, slots), "unresolved": missing} for nodes, scores, slots, missing in ranked]
+            return await self._run(work)
+        except Exception as e:
+            raise VectorStoreError(f"Failed to rank the graph of {collection}", cause=e)
+
+    async def graph_rank(self, collection: str, names, weights=None, direction: str = "both", relation: str = "calls",
+                         restart: float = 0.15, steps: int = 16, limit: int = 10, match: str = "exact",
+                         include_seeds: bool = True) -> dict[str, Any]:
+        """What matters around the named nodes: personalised PageRank over ``relation`` seeded by them (``weights``: one number
+        >= 0 per name, default 1; ``match="suffix"``: a name also stands for every node whose name ends in ``"." + name``, each
+        with the name's weight), ``steps`` (1..64) steps with restart probability ``restart``.  ``direction``: the way the walk
+        travels -- ``"callees"`` follows the calls, ``"callers"`` goes against them, ``"both"`` either way.  Returns ``{"hits":
+        [{"node", "graph_score", "payload"}], "unresolved"}``: the ``limit`` nodes with the highest score (> 0), ties to the
+        node :meth:`set_graph_edges` saw first; ``include_seeds=False`` leaves the named nodes out; ``payload`` is that of the
+        node's first alive chunk, or None.  Exact and deterministic."""
+        return (await self.graph_rank_batch(collection, [names], None if weights is None else [weights], direction, relation, restart, steps,
+                                            limit, match, include_seeds))[0]
 
     async def search_rerank_batch(self, collection: str, query_vectors, plans, reranker, limit: int = 20,
                                   filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None):

@@ -137,6 +137,14 @@ def _graph_filter(within_callers_of, within_callees_of, graph_hops: int | None) 
     return {"graph": spec}
 
 
+def _node_row(ranked: dict) -> dict:
+    """A ranked graph node of the store (``{"node", "graph_score", "payload"}``) as a result row; a node without a chunk has
+    its names and score only."""
+    pay = ranked.get("payload") or {}
+    return {"name": ranked["node"].rsplit(".", 1)[-1], "qualified_name": ranked["node"], "graph_score": ranked["graph_score"],
+            "file_path": pay.get("file_path"), "entity_type": pay.get("entity_type"), "start_line": pay.get("start_line")}
+
+
 def _transform_similar_code_result(hit: dict) -> dict:
     """A store hit in the result shape of ``find_similar_code`` (vector_search.py:199-216); a recommend hit under strategy
     "best" keeps its two extra keys."""
@@ -236,7 +244,8 @@ class VectorSearcher:
                           max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
                           contains_case: bool = True, matches: str | None = None,
                           fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
-                          within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
+                          within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
+                          propagate: bool | dict | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -270,7 +279,19 @@ class VectorSearcher:
         node name or a list of them -- only code that calls / is called from them, transitively within ``graph_hops`` edges
         (default 3), counts: "timeout handling, but only in code reachable from ``main``".  Resolved by a BFS on the device
         over the edges given to ``HipVectorStore.set_graph_edges``, in every mode and beside every other
-        argument; :meth:`search_summaries`, :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way."""
+        argument; :meth:`search_summaries`, :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way.
+        ``propagate`` (not in the reference): ``True``, or the settings of ``HipVectorStore.search_propagated`` -- the best
+        ``candidates`` matches seed a random walk with restart over the call graph (personalised PageRank) and
+        the results are ordered by reciprocal-rank fusion of similarity and graph score: of the matches, those in the middle of
+        the code the others call come first.  Every result then also carries ``cosine`` and ``graph_score``;
+        :meth:`search_code_propagated` returns the related nodes as well.  Semantic mode only, beside the filters and
+        ``candidates``."""
+        if propagate is not None and propagate is not False:
+            return (await self.search_code_propagated(
+                query, limit, language, entity_type, project_name, candidates=candidates, propagate=propagate, related_limit=0,
+                contains=contains, contains_case=contains_case, matches=matches, fuzzy=fuzzy, edits=edits, within_callers_of=within_callers_of,
+                within_callees_of=within_callees_of, graph_hops=graph_hops, diversity=diversity, max_per_file=max_per_file,
+                extra_queries=extra_queries, min_score=min_score, max_overlap=max_overlap, mode=mode))["results"]
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
@@ -281,6 +302,58 @@ class VectorSearcher:
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
                                   max_overlap=max_overlap, **_mode_kwargs(mode))
         return [_project(h, _CODE_KEYS + _fused_keys(h)) for h in hits]
+
+    async def search_code_propagated(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
+                                     entity_type: str | None = None, project_name: str | list[str] | None = None, *,
+                                     candidates: int | None = None, propagate: bool | dict | None = None, related_limit: int = 10,
+                                     contains: str | list[str] | None = None, contains_case: bool = True, matches: str | None = None,
+                                     fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
+                                     within_callees_of: str | list[str] | None = None, graph_hops: int | None = None, mode: str = "semantic",
+                                     **others) -> dict:
+        """:meth:`search_code` with graph-propagated relevance (``HipVectorStore.search_propagated``; not in the reference):
+        ``{"results": [...], "related": [...]}``.  ``results`` have :meth:`search_code`'s shape plus ``cosine`` and
+        ``graph_score``, ``score`` being the fused one; ``related`` -- ``[{"name", "qualified_name", "graph_score", "file_path",
+        "entity_type", "start_line"}]`` -- are the nodes the walk from the matches ends up at that are no match themselves: the
+        function all three retry wrappers call, whose body never says "retry".  The filters apply to the matches (the seeds),
+        not to ``related``."""
+        if not query or not query.strip():
+            raise QueryError("Search query cannot be empty")
+        used = [k for k, v in others.items() if v is not None] + ([] if mode == "semantic" else [f"mode={mode!r}"])
+        if used:
+            raise ValueError(f"propagate cannot be combined with {', '.join(used)}")
+        filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
+        filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops))
+        try:
+            vector = await self.embedder.embed(query)
+            got = await self.qdrant.search_propagated(collection=CollectionName.CODE_CHUNKS.value, query_vector=vector, limit=limit,
+                                                      candidates=candidates, propagate=None if propagate is True else propagate,
+                                                      related_limit=related_limit, filters=filters or None)
+        except EmbeddingError as e:
+            logger.error(f"Embedding error: {e}")
+            raise QueryError("Failed to embed search query", cause=e)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to search code", cause=e)
+        results = [dict(_project(h, _CODE_KEYS), cosine=h["cosine"], graph_score=h["graph_score"]) for h in got["hits"]]
+        return {"results": results, "related": [_node_row(r) for r in got["related"]]}
+
+    async def find_important_near(self, names, limit: int = 10, direction: str = "both", weights=None, restart: float = 0.15,
+                                  steps: int = 16, include_seeds: bool = False, match: str = "exact") -> list[dict]:
+        """What matters around ``names`` (one name or several): personalised PageRank over the store's ``"calls"`` edges seeded
+        by them (``HipVectorStore.graph_rank``; not in the reference, whose only graded graph signal is a global degree count)
+        -- ``[{"name", "qualified_name", "graph_score", "file_path", "entity_type", "start_line"}]``, best first, the named
+        nodes themselves left out unless ``include_seeds``."""
+        wanted = [names] if isinstance(names, str) else list(names or [])
+        if not wanted or not all(isinstance(n, str) and n.strip() for n in wanted):
+            raise QueryError("Entity name cannot be empty")
+        try:
+            got = await self.qdrant.graph_rank(collection=CollectionName.CODE_CHUNKS.value, names=wanted, weights=weights, direction=direction,
+                                               restart=restart, steps=steps, limit=limit, match=match, include_seeds=include_seeds)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to rank the call graph", cause=e)
+        return [_node_row(r) for r in got["hits"]]
 
     async def search_summaries(self, query: str, limit: int = DEFAULT_SEARCH_LIMIT, project_name: str | None = None, *,
                                diversity: float | None = None, candidates: int | None = None, max_per_file: int | None = None,

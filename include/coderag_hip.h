@@ -801,6 +801,57 @@ int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint6
 int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_dev, int q, int64_t target, int max_hops,
                    int32_t *out_nodes_host, int *out_len, void *stream);
 
+/* ---- graph-propagated relevance: personalised PageRank seeded by hits or by named nodes.  The definition is
+ * this repository's own, and it is exact: the device result is the same BITS as a CPU restatement that follows the text below.
+ *
+ * For a relation and a direction, node u's PULL LIST is the one crh_graph_bfs pulls through: ALONG its sources (the reverse
+ * CSR's list), AGAINST its targets (the forward list), BOTH the reverse list, then the forward list, multiplicity kept.  out(v)
+ * is the length of the OPPOSITE list or lists (ALONG: v's forward list; AGAINST: its reverse list; BOTH: the sum of the two);
+ * inv[v] = 1.0f / (float)out(v), 0 where out(v) == 0.
+ *   Seeds.  Query q has c entries (node, weight), 1 <= c <= CRH_MAX_K; node == -1 or weight == 0 is padding.  w_q[v] = the f32 sum
+ *     of the weights of v's entries in list order, S_q = the f32 sum of all real weights in list order, p0[v] = w_q[v] / S_q.
+ *     A query whose S_q is not a finite value > 0 has p0 = 0 everywhere, and every score 0.  A HOST list is checked (a node
+ *     outside -1 .. n_nodes - 1, a weight that is not finite and >= 0: CRH_E_INVALID); a DEVICE list is clamped by the kernel:
+ *     an entry that is no node is padding, a negative, NaN or infinite weight counts as +0.  seed_weights NULL: every weight 1.
+ *   Steps.  restart is an f32 inside (0, 1), a = 1.0f - restart in f32.  For t = 0 .. steps - 1, 1 <= steps <= CRH_GRAPH_PPR_MAX_STEPS:
+ *       contrib[v] = p_t[v] * inv[v]
+ *       acc[u]     = 0.0f, then += contrib[v] for v in u's pull list, IN LIST ORDER, each addition rounded to f32
+ *       p_{t+1}[u] = (restart * p0[u]) + (a * acc[u])
+ *     Every operation is a separate f32 rounding (no fused multiply-add); subnormals are kept.  The mass of a node with out == 0
+ *     is dropped: at the fixed point that ranks like "dangling nodes jump back to the seeds" (the two solutions are
+ *     proportional) and needs no grid-wide sum.  The result is p_steps; every score is >= +0.
+ *   No float atomics, no tree or strided reduction of a pull list (a hub's list is walked in order by the lanes that own the
+ *   hub), nothing grid-wide inside a launch: one launch per step over ping-pong buffers.
+ *
+ * State layout: f32 [n_nodes][QS], QS the smallest power of two >= nq (1 .. 64); column q belongs to query q, the columns from
+ * nq on are 0.  work_dev holds 3 * n_nodes * QS floats, out_dev n_nodes * QS; both are caller-owned and overwritten (every word
+ * of out_dev is written).  Seeds int32 / f32 [nq][c], on the host (seeds_on_device = 0; uploaded first, and the call waits for
+ * that upload only) or on the device, complete on `stream`.  The first call for a (relation, direction) builds inv and waits
+ * for it; crh_graph_set_relation drops it.  Enqueues.  Any bad argument is CRH_E_INVALID with nothing launched; a graph without
+ * nodes is CRH_OK with nothing launched.  One PPR per handle may be in flight with host seeds. */
+#define CRH_GRAPH_PPR_MAX_STEPS 64
+int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int32_t *seed_nodes /* [nq, c] */,
+                  const float *seed_weights /* [nq, c] or NULL */, int seeds_on_device, float restart, int steps,
+                  float *work_dev /* [3, n_nodes, QS] */, float *out_dev /* [n_nodes, QS] */, void *stream);
+
+/* The scores of a crh_graph_ppr (same nq) as the histograms crh_facet_select takes: out_bins_dev int64 [nq][n_nodes], bins[q][v]
+ * = the bit pattern of p[v][q], which orders like the value for every f32 >= +0.  exclude_dev int32 [nq][c] (c 0..CRH_MAX_K; NULL
+ * with c = 0): the nodes named in row q get 0 in query q; an entry that is no node is skipped.  crh_facet_select over these bins
+ * is the top-k nodes by descending score, ties to the lower node id, a zero score never returned.  Runs on the CURRENT device;
+ * enqueues. */
+int crh_graph_ppr_bins(int64_t n_nodes, int nq, const float *scores_dev /* [n_nodes, QS] */, int c,
+                       const int32_t *exclude_dev /* [nq, c] or NULL */, int64_t *out_bins_dev /* [nq, n_nodes] */, void *stream);
+
+/* A candidate table (rows int64 / cosine f32 as a search returns them, rows < 0 = padding; nodes int32, -1: the row's key is no
+ * node; each [nq][c], 1 <= c <= CRH_MAX_K) as the TWO lists crh_fuse_select fuses with m = 2, out_fuse_scores_dev f32 /
+ * out_fuse_rows_dev int64 [nq][2][c]: list 0 is the table as it stands; list 1 holds the candidates with graph_score > 0 by
+ * descending graph_score, ties to the EARLIER position, padded with (-1, -inf).  graph_score[i] = p[node_i][q], 0 for padding and
+ * for a row without a node; out_graph_score_dev f32 [nq][c] keeps it per position (crh_fuse_select's out_first of a row is its
+ * position in list 0).  One workgroup per query, rank by counting.  Runs on the CURRENT device; enqueues. */
+int crh_graph_ppr_order(int64_t n_nodes, int nq, int c, const float *scores_dev /* [n_nodes, QS] */, const int64_t *rows_dev,
+                        const float *cosine_dev, const int32_t *nodes_dev, float *out_fuse_scores_dev, int64_t *out_fuse_rows_dev,
+                        float *out_graph_score_dev, void *stream);
+
 /* ---- the hybrid re-rank with both branches on the device.  QueryEngine.search (query/engine.py:222-260) hands
  * HybridRanker.rank_results a graph context AND the vector hits; crh_rerank_vector above covers lists of vector hits only.  The
  * three entry points below turn the BFS lists of crh_graph_list into graph candidates and rank them together with the hits. */
