@@ -467,6 +467,256 @@ __global__ __launch_bounds__(kGraphThreads) void k_ppr_order(const float *p, int
     }
 }
 
+// ------------------------------------------------------------------------------- components and layers
+// Integer sweeps over the same CSRs, one lane per node, one launch per sweep.  Every sweep is MONOTONE (a label is set once, a
+// colour only falls, a layer only rises) towards a fixed point that does not depend on the order of the updates, so a sweep
+// works in place: a value another lane wrote earlier in the same launch is as good as last launch's.  A sweep ORs its flags
+// (bit 0: something changed, bit 1: an unassigned node is left) into ONE word with one atomicOr per workgroup; the next launch
+// reads that word first and leaves when bit 0 is clear, so the host enqueues kSweepBatch sweeps per read-back.
+
+constexpr int kSweepBatch = 16;                // sweeps enqueued per read-back of the flag words
+constexpr int kSccCounters = 24;               // the extra words of the work arrays: flags [kSweepBatch + 1] from 0, four counters from here
+constexpr int kNoColour = 0x7fffffff;
+
+// The minimum of f(adj[i]) over the list [b, e) of the lane's node: walked by the lane itself below CRH_GRAPH_WAVE_DEGREE
+// entries, by the whole wave from there on.  `key` is what f needs to know about the node that owns the list (the lanes that help
+// with another lane's list get that lane's).  Every lane of the wave calls it (b == e: nothing to walk).
+template <class F>
+__device__ __forceinline__ int list_min(const int32_t *adj, int64_t b, int64_t e, int lane, int key, F f)
+{
+    int acc = kNoColour;
+    const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
+    if (!wide)
+        for (int64_t i = b; i < e; ++i) acc = min(acc, f(adj[i], key));
+    u64 m = __ballot(wide);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
+        const int owner = __shfl(key, src);
+        int part = kNoColour;
+        for (int64_t i = bb + lane; i < ee; i += 64) part = min(part, f(adj[i], owner));
+        part = wave_min(part);
+        if (lane == src) acc = part;
+    }
+    return acc;
+}
+
+// One atomicOr per workgroup: the OR of the lanes' flag bits 0 and 1.
+__device__ __forceinline__ void sweep_flags(unsigned mine, unsigned *flag)
+{
+    __shared__ unsigned s_flag[kGraphWaves];
+    const unsigned w = (__ballot(mine & 1u) ? 1u : 0u) | (__ballot(mine & 2u) ? 2u : 0u);
+    if ((threadIdx.x & 63) == 0) s_flag[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned all = 0u;
+        for (int i = 0; i < kGraphWaves; ++i) all |= s_flag[i];
+        if (all) atomicOr(flag, all);
+    }
+}
+
+struct SccArgs {
+    const int64_t *off_out, *off_in;           // the forward CSR (a node's targets) and the reverse one (its sources)
+    const int32_t *adj_out, *adj_in;
+    int32_t *comp;                             // -1: unassigned
+    int32_t *colour;
+    int64_t n;
+    const unsigned *prev;
+    unsigned *cur;
+};
+
+// Trim: an unassigned node without an unassigned in-neighbour, or without an unassigned out-neighbour, is a component by itself.
+__global__ __launch_bounds__(kGraphThreads) void k_scc_trim(const SccArgs a)
+{
+    if ((*a.prev & 1u) == 0u) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0u;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        const bool in = u < a.n;
+        const bool open = in && a.comp[u] < 0;
+        const int32_t *comp = a.comp;
+        const int self = (int)u;
+        auto open_other = [comp](int v, int owner) { return v != owner && comp[v] < 0 ? 0 : 1; };
+        const int no_in = list_min(a.adj_in, open ? a.off_in[u] : 0, open ? a.off_in[u + 1] : 0, lane, self, open_other);   // 0: there is one
+        const int no_out = list_min(a.adj_out, open ? a.off_out[u] : 0, open ? a.off_out[u + 1] : 0, lane, self, open_other);
+        if (open) {
+            if (no_in != 0 || no_out != 0) {
+                a.comp[u] = self;
+                mine |= 1u;
+            } else {
+                mine |= 2u;
+            }
+        }
+    }
+    sweep_flags(mine, a.cur);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_scc_colour_init(const int32_t *comp, int32_t *colour, int64_t n)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads)
+        colour[v] = comp[v] < 0 ? (int32_t)v : kNoColour;           // (an assigned node never lowers a neighbour's colour)
+}
+
+// Colour: the smallest id among the unassigned nodes that reach the node.
+__global__ __launch_bounds__(kGraphThreads) void k_scc_colour(const SccArgs a)
+{
+    if ((*a.prev & 1u) == 0u) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0u;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        const bool in = u < a.n;
+        const bool open = in && a.comp[u] < 0;
+        const int32_t *colour = a.colour;
+        const int least = list_min(a.adj_in, open ? a.off_in[u] : 0, open ? a.off_in[u + 1] : 0, lane, 0, [colour](int v, int) { return (int)colour[v]; });
+        if (open && least < a.colour[u]) {
+            a.colour[u] = least;
+            mine |= 1u;
+        }
+    }
+    sweep_flags(mine, a.cur);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_scc_roots(int32_t *comp, const int32_t *colour, int64_t n)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads)
+        if (comp[v] < 0 && colour[v] == (int32_t)v) comp[v] = (int32_t)v;
+}
+
+// Back-mark: an unassigned node of colour c joins component c once one of its out-neighbours has.
+__global__ __launch_bounds__(kGraphThreads) void k_scc_mark(const SccArgs a)
+{
+    if ((*a.prev & 1u) == 0u) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0u;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        const bool in = u < a.n;
+        const bool open = in && a.comp[u] < 0;
+        const int32_t *comp = a.comp;
+        const int c = open ? (int)a.colour[u] : -2;
+        const int hit = list_min(a.adj_out, open ? a.off_out[u] : 0, open ? a.off_out[u + 1] : 0, lane, c,
+                                 [comp](int v, int mine_c) { return comp[v] == mine_c ? 0 : 1; });
+        if (open && hit == 0) {
+            a.comp[u] = c;
+            mine |= 1u;
+        }
+    }
+    sweep_flags(mine, a.cur);
+}
+
+// counters: [0] components, [1] components of two nodes or more, [2] nodes that are not their component's label.  `big` was zeroed.
+__global__ __launch_bounds__(kGraphThreads) void k_scc_members(const int32_t *comp, int32_t *big, int64_t n, unsigned *counters)
+{
+    unsigned mine = 0u;
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t c = comp[v];
+        if (c != v && c >= 0 && c < n) {
+            big[c] = 1;                                              // (every member writes the same value)
+            ++mine;
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(counters + 2, mine);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_scc_count(const int32_t *comp, const int32_t *big, int64_t n, unsigned *counters)
+{
+    unsigned roots = 0u, bigs = 0u;
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads)
+        if (comp[v] == (int32_t)v) {
+            ++roots;
+            bigs += big[v] ? 1u : 0u;
+        }
+    for (int o = 32; o >= 1; o >>= 1) {
+        roots += __shfl_xor(roots, o);
+        bigs += __shfl_xor(bigs, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (roots) atomicAdd(counters + 0, roots);
+        if (bigs) atomicAdd(counters + 1, bigs);
+    }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_scc_bins_count(const int32_t *comp, int64_t n, u64 *bins)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t c = comp[v];
+        if (c >= 0 && c < n) atomicAdd(bins + c, 1ull);              // (a label that is no node counts nowhere)
+    }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_scc_bins_keep(const int32_t *self_nodes, int64_t n_self, int64_t n, u64 *bins)
+{
+    for (int64_t c = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; c < n; c += (int64_t)gridDim.x * kGraphThreads) {
+        const u64 size = bins[c];
+        if (size != 1ull) continue;                                  // (0 stays 0; two nodes or more are a cycle)
+        int64_t lo = 0, hi = n_self;                                 // the one member is c itself: is it in the sorted list?
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (self_nodes[mid] < c) lo = mid + 1; else hi = mid;
+        }
+        if (!(lo < n_self && self_nodes[lo] == c)) bins[c] = 0ull;
+    }
+}
+
+struct LayerArgs {
+    const int64_t *off;                        // the pull CSR: ALONG the reverse one, AGAINST the forward one
+    const int32_t *adj;
+    const int32_t *comp;
+    int32_t *layer;
+    int64_t n;
+    const unsigned *prev;
+    unsigned *cur;
+};
+
+// layer[u] = max over the pull list of layer[v] + (comp[v] != comp[u]), from zeros: the longest path of the condensation.
+__global__ __launch_bounds__(kGraphThreads) void k_graph_layer(const LayerArgs a)
+{
+    if ((*a.prev & 1u) == 0u) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0u;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        const bool in = u < a.n;
+        const int32_t *comp = a.comp, *layer = a.layer;
+        const int cu = in ? (int)comp[u] : 0;
+        const int best = -list_min(a.adj, in ? a.off[u] : 0, in ? a.off[u + 1] : 0, lane, cu,
+                                   [comp, layer](int v, int own) { return -((int)layer[v] + (comp[v] != own ? 1 : 0)); });
+        if (in && best != -kNoColour && best > a.layer[u]) {
+            a.layer[u] = best;
+            mine |= 1u;
+        }
+    }
+    sweep_flags(mine, a.cur);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_layer_max(const int32_t *layer, int64_t n, int *out)
+{
+    int best = 0;
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) best = max(best, (int)layer[v]);
+    best = -wave_min(-best);
+    if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_node_words(int64_t n, int mode, const int32_t *values, const int64_t *bins, int64_t lo, int64_t hi,
+                                                                    int q, u64 *out)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < n; v += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t x = values[v];
+        bool hit;
+        if (mode == CRH_GRAPH_WORDS_IN_CYCLE)
+            hit = x >= 0 && x < n && bins[x] > 0;
+        else if (mode == CRH_GRAPH_WORDS_SAME_COMPONENT)
+            hit = x == lo;
+        else
+            hit = lo <= x && x <= hi;
+        out[v] = hit ? 1ull << q : 0ull;
+    }
+}
+
 int graph_alloc(void **p, int64_t bytes)
 {
     *p = nullptr;
@@ -899,6 +1149,179 @@ int crh_graph_ppr_order(int64_t n_nodes, int nq, int c, const float *scores_dev,
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_ppr_order, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, ppr_shift(nq), c, rows_dev, cosine_dev, nodes_dev,
                        out_fuse_scores_dev, out_fuse_rows_dev, out_graph_score_dev);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Enqueues sweeps, kSweepBatch per read-back of their flag words, until one changes nothing.  `launch(prev, cur)` enqueues one
+// sweep that leaves at once when bit 0 of *prev is clear and ORs its own flags into *cur.  `ran` counts the sweeps that did
+// run, `launched` all of them; the loop never goes past `cap` sweeps that ran (CRH_E_INTERNAL).  *last = the flags of the sweep
+// that changed nothing.
+template <class L>
+int sweep_to_fixed_point(L launch, unsigned *flags, hipStream_t st, int64_t cap, int64_t &ran, int64_t &launched, unsigned *last, const char *who)
+{
+    unsigned host[kSweepBatch + 1];
+    while (ran < cap) {                                              // (every pass adds at least one to `ran`)
+        const int batch = (int)std::min<int64_t>(kSweepBatch, cap - ran);
+        CRH_HIP(hipMemsetAsync(flags, 0, sizeof host, st));
+        CRH_HIP(hipMemsetAsync(flags, 1, 4, st));                    // flags[0] != 0: the first sweep of a batch always runs
+        for (int i = 0; i < batch; ++i) launch(flags + i, flags + i + 1);
+        launched += batch;
+        CRH_HIP(hipGetLastError());
+        CRH_HIP(hipMemcpyAsync(host, flags, sizeof host, hipMemcpyDeviceToHost, st));
+        CRH_HIP(hipStreamSynchronize(st));
+        for (int i = 1; i <= batch; ++i) {
+            ++ran;
+            if ((host[i] & 1u) == 0u) {
+                *last = host[i];
+                return CRH_OK;
+            }
+        }
+    }
+    return fail(CRH_E_INTERNAL, "%s: no fixed point within %lld sweeps", who, (long long)cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int crh_graph_scc(crh_graph *g, int rel, int32_t *comp_out_dev, int32_t *work_dev, int64_t *info_host, void *stream)
+{
+    CRH_TRY(graph_check_rel(g, rel, CRH_GRAPH_ALONG, "graph_scc"));
+    if (!info_host) return fail(CRH_E_INVALID, "graph_scc: NULL pointer");
+    info_host[0] = info_host[1] = info_host[2] = info_host[3] = 0;
+    const int64_t n = g->n_nodes;
+    if (n == 0) return CRH_OK;
+    if (!comp_out_dev || !work_dev) return fail(CRH_E_INVALID, "graph_scc: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const crh_graph_relation &r = g->rel[rel];
+    SccArgs a{};
+    a.off_out = r.off[0];
+    a.adj_out = r.adj[0];
+    a.off_in = r.off[1];
+    a.adj_in = r.adj[1];
+    a.comp = comp_out_dev;
+    a.colour = work_dev;
+    a.n = n;
+    unsigned *flags = reinterpret_cast<unsigned *>(work_dev + n);
+    unsigned *counters = reinterpret_cast<unsigned *>(work_dev + n) + kSccCounters;
+    const unsigned blocks = graph_blocks(n, kGraphThreads);
+    const int64_t cap = CRH_GRAPH_SCC_MAX_SWEEPS(n);
+    int64_t ran = 0, launched = 0;
+    auto sweep = [&](void (*kernel)(const SccArgs)) {
+        return [&, kernel](const unsigned *prev, unsigned *cur) {
+            a.prev = prev;
+            a.cur = cur;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kGraphThreads), 0, st, a);
+        };
+    };
+    CRH_HIP(hipMemsetAsync(comp_out_dev, 0xff, (size_t)n * 4, st));  // -1: unassigned
+    bool done = false;
+    for (int64_t round = 0; round <= n && !done; ++round) {          // (a round that finds a node left assigns its colour's root at least)
+        unsigned last = 0u;
+        CRH_TRY(sweep_to_fixed_point(sweep(k_scc_trim), flags, st, cap, ran, launched, &last, "graph_scc"));
+        if ((last & 2u) == 0u) {
+            done = true;
+            break;
+        }
+        hipLaunchKernelGGL(k_scc_colour_init, dim3(blocks), dim3(kGraphThreads), 0, st, comp_out_dev, work_dev, n);
+        CRH_TRY(sweep_to_fixed_point(sweep(k_scc_colour), flags, st, cap, ran, launched, &last, "graph_scc"));
+        hipLaunchKernelGGL(k_scc_roots, dim3(blocks), dim3(kGraphThreads), 0, st, comp_out_dev, work_dev, n);
+        CRH_TRY(sweep_to_fixed_point(sweep(k_scc_mark), flags, st, cap, ran, launched, &last, "graph_scc"));
+    }
+    if (!done) return fail(CRH_E_INTERNAL, "graph_scc: nodes left after %lld rounds", (long long)n + 1);
+    CRH_HIP(hipMemsetAsync(work_dev, 0, (size_t)n * 4, st));         // the colours are spent: which labels have a second member
+    CRH_HIP(hipMemsetAsync(counters, 0, 16, st));
+    hipLaunchKernelGGL(k_scc_members, dim3(blocks), dim3(kGraphThreads), 0, st, comp_out_dev, work_dev, n, counters);
+    hipLaunchKernelGGL(k_scc_count, dim3(blocks), dim3(kGraphThreads), 0, st, comp_out_dev, work_dev, n, counters);
+    CRH_HIP(hipGetLastError());
+    unsigned got[4] = {};
+    CRH_HIP(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, st));
+    CRH_HIP(hipStreamSynchronize(st));
+    info_host[0] = got[0];
+    info_host[1] = got[1];
+    info_host[2] = (int64_t)got[1] + got[2];                         // a component of two or more: its label and the others
+    info_host[3] = launched;
+    return CRH_OK;
+}
+
+int crh_graph_scc_bins(int64_t n_nodes, const int32_t *comp_dev, const int32_t *self_nodes_dev, int64_t n_self, int64_t *out_bins_dev, void *stream)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_scc_bins: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    if (n_self < 0 || n_self > n_nodes || (n_self > 0 && !self_nodes_dev))
+        return fail(CRH_E_INVALID, "graph_scc_bins: %lld self-loop nodes (0..%lld) at %p", (long long)n_self, (long long)n_nodes, (const void *)self_nodes_dev);
+    if (n_nodes == 0) return CRH_OK;
+    if (!comp_dev || !out_bins_dev) return fail(CRH_E_INVALID, "graph_scc_bins: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u64 *bins = reinterpret_cast<u64 *>(out_bins_dev);
+    CRH_HIP(hipMemsetAsync(bins, 0, (size_t)n_nodes * 8, st));
+    const unsigned blocks = graph_blocks(n_nodes, kGraphThreads);
+    hipLaunchKernelGGL(k_scc_bins_count, dim3(blocks), dim3(kGraphThreads), 0, st, comp_dev, n_nodes, bins);
+    hipLaunchKernelGGL(k_scc_bins_keep, dim3(blocks), dim3(kGraphThreads), 0, st, self_nodes_dev, n_self, n_nodes, bins);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_layers(crh_graph *g, int rel, int direction, const int32_t *comp_dev, int32_t *out_dev, int32_t *work_dev, int64_t *info_host, void *stream)
+{
+    CRH_TRY(graph_check_rel(g, rel, direction, "graph_layers"));
+    if (direction == CRH_GRAPH_BOTH) return fail(CRH_E_INVALID, "graph_layers: direction is CRH_GRAPH_ALONG or CRH_GRAPH_AGAINST (taken both ways every edge lies on a cycle)");
+    if (!info_host) return fail(CRH_E_INVALID, "graph_layers: NULL pointer");
+    info_host[0] = info_host[1] = 0;
+    const int64_t n = g->n_nodes;
+    if (n == 0) return CRH_OK;
+    if (!comp_dev || !out_dev || !work_dev) return fail(CRH_E_INVALID, "graph_layers: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const crh_graph_relation &r = g->rel[rel];
+    const int c = direction == CRH_GRAPH_ALONG ? 1 : 0;              // ALONG pulls through a node's sources
+    LayerArgs a{};
+    a.off = r.off[c];
+    a.adj = r.adj[c];
+    a.comp = comp_dev;
+    a.layer = out_dev;
+    a.n = n;
+    unsigned *flags = reinterpret_cast<unsigned *>(work_dev);
+    int *most = reinterpret_cast<int *>(work_dev) + kSccCounters;
+    const unsigned blocks = graph_blocks(n, kGraphThreads);
+    int64_t ran = 0, launched = 0;
+    unsigned last = 0u;
+    CRH_HIP(hipMemsetAsync(out_dev, 0, (size_t)n * 4, st));
+    CRH_TRY(sweep_to_fixed_point(
+        [&](const unsigned *prev, unsigned *cur) {
+            a.prev = prev;
+            a.cur = cur;
+            hipLaunchKernelGGL(k_graph_layer, dim3(blocks), dim3(kGraphThreads), 0, st, a);
+        },
+        flags, st, CRH_GRAPH_LAYERS_MAX_SWEEPS(n), ran, launched, &last, "graph_layers"));
+    CRH_HIP(hipMemsetAsync(most, 0, 4, st));
+    hipLaunchKernelGGL(k_graph_layer_max, dim3(blocks), dim3(kGraphThreads), 0, st, out_dev, n, most);
+    CRH_HIP(hipGetLastError());
+    int got = 0;
+    CRH_HIP(hipMemcpyAsync(&got, most, 4, hipMemcpyDeviceToHost, st));
+    CRH_HIP(hipStreamSynchronize(st));
+    info_host[0] = (int64_t)got + 1;
+    info_host[1] = launched;
+    return CRH_OK;
+}
+
+int crh_graph_node_words(int64_t n_nodes, int mode, const int32_t *values_dev, const int64_t *bins_dev, int64_t lo, int64_t hi, int q,
+                         uint64_t *out_words_dev, void *stream)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_node_words: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    if (mode != CRH_GRAPH_WORDS_IN_CYCLE && mode != CRH_GRAPH_WORDS_SAME_COMPONENT && mode != CRH_GRAPH_WORDS_RANGE)
+        return fail(CRH_E_INVALID, "graph_node_words: mode=%d is none of CRH_GRAPH_WORDS_*", mode);
+    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_node_words: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
+    if (n_nodes == 0) return CRH_OK;
+    if (!values_dev || !out_words_dev || (mode == CRH_GRAPH_WORDS_IN_CYCLE && !bins_dev)) return fail(CRH_E_INVALID, "graph_node_words: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_graph_node_words, dim3(graph_blocks(n_nodes, kGraphThreads)), dim3(kGraphThreads), 0, st, n_nodes, mode, values_dev, bins_dev, lo, hi, q,
+                       reinterpret_cast<u64 *>(out_words_dev));
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }

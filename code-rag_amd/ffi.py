@@ -41,6 +41,8 @@ GRAPH_MAX_RELATIONS, GRAPH_MAX_QUERIES, GRAPH_MAX_HOPS = 8, 64, 16   # CRH_GRAPH
 GRAPH_WAVE_DEGREE = 64      # CRH_GRAPH_WAVE_DEGREE: adjacency lists of at least so many entries are walked by a whole wave
 GRAPH_ALONG, GRAPH_AGAINST, GRAPH_BOTH = 0, 1, 2   # CRH_GRAPH_*: the direction of travel
 GRAPH_DIRECTIONS = {"callees": GRAPH_ALONG, "callers": GRAPH_AGAINST, "both": GRAPH_BOTH}
+GRAPH_SCC_WORK_EXTRA = 32   # CRH_GRAPH_SCC_WORK_EXTRA: int32 words of crh_graph_scc's work array beyond one per node
+GRAPH_WORDS = {"in_cycle": 0, "same_component": 1, "range": 2}    # CRH_GRAPH_WORDS_*: the conditions of crh_graph_node_words
 GRAPH_PPR_MAX_STEPS = 64    # CRH_GRAPH_PPR_MAX_STEPS: steps of one crh_graph_ppr
 FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
 
@@ -73,6 +75,7 @@ EXPORTS = (
     "crh_graph_row_words", "crh_graph_path",
     "crh_graph_node_rows", "crh_graph_candidates", "crh_rerank_hybrid",
     "crh_graph_ppr", "crh_graph_ppr_bins", "crh_graph_ppr_order",
+    "crh_graph_scc", "crh_graph_scc_bins", "crh_graph_layers", "crh_graph_node_words",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
@@ -267,6 +270,10 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_graph_ppr.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, C.c_float, i32, vp, vp, vp]
     L.crh_graph_ppr_bins.argtypes = [i64, i32, vp, i32, vp, vp, vp]
     L.crh_graph_ppr_order.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.crh_graph_scc.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.crh_graph_scc_bins.argtypes = [i64, vp, vp, i64, vp, vp]
+    L.crh_graph_layers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.crh_graph_node_words.argtypes = [i64, i32, vp, vp, i64, i64, i32, vp, vp]
     L.crh_graph_candidates.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.crh_rerank_hybrid.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, i32, i32, i32, i32,
                                     vp, vp, vp, vp, vp, vp, vp]
@@ -1377,6 +1384,7 @@ class Graph:
     held as int64 device tensors, sized by the first BFS that needs them.  A BFS overwrites the workspace: list, row_words and
     path read what the LAST bfs left unless they are handed tensors of their own."""
     bfs_calls = 0         # crh_graph_bfs calls issued by all handles (tests count the traversals of a job)
+    scc_calls = 0         # crh_graph_scc calls likewise
 
     def __init__(self, n_nodes: int, device: int = 0):
         self.device, self.n_nodes = device, int(n_nodes)
@@ -1612,6 +1620,76 @@ class Graph:
         use_device(self.device)
         check(lib().crh_graph_ppr_order(self.n_nodes, nq, c, _ptr(scores), _ptr(rows), _ptr(cosine), _ptr(nodes), _ptr(fs), _ptr(fr), _ptr(gs), stream))
         return fs, fr, gs
+
+    # -- components and layers
+    def _node_array(self, x, want: str, what: str):
+        _typed(x, want, what)
+        if not _is_dev(x) or x.ndim != 1 or int(x.shape[0]) != self.n_nodes:
+            raise NativeError(E_INVALID, f"{what} must be a {want} device tensor of {self.n_nodes} entries")
+        return x
+
+    def scc(self, rel: int, stream: int = 0):
+        """``crh_graph_scc``: ``(comp, info)`` -- ``comp`` an int32 device tensor [n_nodes] of its own, ``comp[v]`` = the smallest
+        node id of v's strongly connected component in relation ``rel``; ``info`` a host int64 [4] = (components, components of
+        two nodes or more, nodes in those, sweeps launched).  Waits on ``stream``."""
+        import torch
+        dev = f"cuda:{self.device}"
+        comp = torch.empty((self.n_nodes,), dtype=torch.int32, device=dev)
+        work = torch.empty((self.n_nodes + GRAPH_SCC_WORK_EXTRA,), dtype=torch.int32, device=dev)
+        info = np.zeros((4,), np.int64)
+        Graph.scc_calls += 1
+        check(lib().crh_graph_scc(self._handle(), int(rel), _ptr(comp), _ptr(work), info.ctypes.data, stream))
+        return comp, info
+
+    def scc_bins(self, comp, self_nodes=None, stream: int = 0):
+        """``crh_graph_scc_bins``: int64 device tensor [n_nodes], ``bins[c]`` = the size of component ``c`` when it is cyclic (two
+        nodes or more, or one node that is in ``self_nodes``: a sorted, distinct int32 host array or device tensor of the nodes
+        with a self-loop), 0 otherwise.  ``facet_select(bins, k)`` then lists the largest cyclic components."""
+        import torch
+        self._node_array(comp, "int32", "comp")
+        dev = f"cuda:{self.device}"
+        n_self = 0
+        if self_nodes is not None:
+            if not _is_dev(self_nodes):
+                self_nodes = torch.from_numpy(np.ascontiguousarray(self_nodes, dtype=np.int32).reshape(-1)).to(dev)
+            _typed(self_nodes, "int32", "self_nodes")
+            n_self = int(self_nodes.numel())
+        bins = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
+        use_device(self.device)
+        check(lib().crh_graph_scc_bins(self.n_nodes, _ptr(comp), _ptr(self_nodes) if n_self else None, n_self, _ptr(bins), stream))
+        return bins
+
+    def layers(self, rel: int, direction, comp, stream: int = 0):
+        """``crh_graph_layers``: ``(layer, info)`` -- ``layer`` an int32 device tensor [n_nodes], the longest-path layer of every
+        node's component in the condensation, travelling ``"callees"`` (along the edges: the DEPTH below the entry points) or
+        ``"callers"`` (against them: the HEIGHT above the leaves); ``info`` a host int64 [2] = (layers, sweeps launched).  Waits
+        on ``stream``."""
+        import torch
+        self._node_array(comp, "int32", "comp")
+        dev = f"cuda:{self.device}"
+        out = torch.empty((self.n_nodes,), dtype=torch.int32, device=dev)
+        work = torch.empty((GRAPH_SCC_WORK_EXTRA,), dtype=torch.int32, device=dev)
+        info = np.zeros((2,), np.int64)
+        check(lib().crh_graph_layers(self._handle(), int(rel), graph_direction(direction), _ptr(comp), _ptr(out), _ptr(work), info.ctypes.data, stream))
+        return out, info
+
+    def node_words(self, mode, values, bins=None, lo: int = 0, hi: int = 0, q: int = 0, out=None, stream: int = 0):
+        """``crh_graph_node_words``: a condition on every node as int64 ``seen`` words [n_nodes] (bit ``q`` where it holds), which
+        :meth:`row_words` takes as ``seen=``.  ``mode`` ``"in_cycle"`` (``values`` = components, ``bins`` = :meth:`scc_bins`),
+        ``"same_component"`` (``values`` = components, ``lo`` = a label) or ``"range"`` (``lo <= values[v] <= hi``)."""
+        import torch
+        if mode not in GRAPH_WORDS and mode not in GRAPH_WORDS.values():
+            raise NativeError(E_INVALID, f"node_words mode {mode!r} is not one of {sorted(GRAPH_WORDS)}")
+        mode = GRAPH_WORDS.get(mode, mode)
+        self._node_array(values, "int32", "values")
+        if bins is not None:
+            self._node_array(bins, "int64", "bins")
+        if out is None:
+            out = torch.empty((self.n_nodes,), dtype=torch.int64, device=f"cuda:{self.device}")
+        self._node_array(out, "int64", "out")
+        use_device(self.device)
+        check(lib().crh_graph_node_words(self.n_nodes, int(mode), _ptr(values), _ptr(bins), int(lo), int(hi), int(q), _ptr(out), stream))
+        return out
 
 
 def _list_stride(x, want: str, what: str, nl: int, nq: int, k: int) -> int:

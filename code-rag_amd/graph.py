@@ -10,6 +10,7 @@ import numpy as np
 MAX_RELATIONS = 8          # CRH_GRAPH_MAX_RELATIONS: named relations one collection holds
 DIRECTIONS = ("callers", "callees", "both")
 FILTER_WORDS = {"callers_of": "callers", "callees_of": "callees", "connected_to": "both"}    # the filter's key -> the direction of travel
+STRUCTURE_WORDS = ("in_cycle", "same_cycle_as", "depth", "height")    # filter keys on the graph as a whole
 
 
 def number_edges(edges: Iterable, code: dict, names: list) -> np.ndarray:
@@ -36,6 +37,15 @@ def unique_edges(pairs: np.ndarray, n_nodes: int) -> np.ndarray:
     pairs = pairs[pairs[:, 0] != pairs[:, 1]]
     keys = np.unique(pairs[:, 0] * max(n_nodes, 1) + pairs[:, 1])
     return np.stack([keys // max(n_nodes, 1), keys % max(n_nodes, 1)], axis=1).astype(np.int32)
+
+
+def self_loops(pairs: np.ndarray, n_nodes: int) -> np.ndarray:
+    """The nodes that carry a self-loop, int32, ascending without repeats: what :func:`unique_edges` drops and a listing of the
+    recursive functions needs (a function that calls itself is a cycle of one node)."""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= n_nodes):
+        raise ValueError(f"an edge names a node outside 0..{n_nodes - 1}")
+    return np.unique(pairs[pairs[:, 0] == pairs[:, 1], 0]).astype(np.int32)
 
 
 def build_csr(pairs: np.ndarray, n_nodes: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

@@ -36,7 +36,7 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None,
                               within_callers_of: str | list[str] | None = None, within_callees_of: str | list[str] | None = None,
                               graph_hops: int | None = None, rank: str | None = None, entities: list[str] | None = None,
-                              intent: str | None = None) -> ToolResult:
+                              intent: str | None = None, in_cycle: bool | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -87,7 +87,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                        ("contains", contains or None), ("contains_case", contains_case if contains or matches or fuzzy else None),
                                        ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None),
                                        ("within_callers_of", within_callers_of or None), ("within_callees_of", within_callees_of or None),
-                                       ("graph_hops", graph_hops if within_callers_of or within_callees_of else None)) if v is not None}   # (only when asked for)
+                                       ("graph_hops", graph_hops if within_callers_of or within_callees_of else None),
+                                       ("in_cycle", True if in_cycle else None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -156,6 +157,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                   "required": False},
             "graph_hops": {"type": "integer", "description": "With within_callers_of / within_callees_of: how many calls away code may "
                                                              "be, 1..16 (default: 3)", "required": False},
+            "in_cycle": {"type": "boolean", "description": "true: only code that lies in a call cycle is searched -- recursive functions "
+                                                           "and groups of functions that call each other", "required": False},
             "rank": {"type": "string", "description": "'vector' (the default: the plain matches), 'hybrid': the named entities' graph "
                                                       "neighbourhood (callers, callees, class hierarchy) and the matches ranked as one "
                                                       "list, or 'propagated': the matches re-ordered by how central they are in the code "
@@ -173,14 +176,26 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
     """MCP ``code_graph`` tool (the reference answers these from Memgraph, query/graph_reasoning/engine.py): what calls a
     function, what it calls, and how one function reaches another -- answered on the device from the call edges beside the
     vectors (``VectorSearcher.find_callers`` / ``find_callees`` / ``find_call_chain``)."""
-    async def code_graph(name: str, relation: str = "callers", target: str | None = None, max_hops: int | None = None,
+    async def code_graph(name: str = "", relation: str = "callers", target: str | None = None, max_hops: int | None = None,
                          limit: int = 50, op: str | None = None) -> ToolResult:
         logger.info(f"[Tool:CodeGraph] {op or relation} of '{name}'" + (f" -> '{target}'" if target else ""))
         try:
             searcher = vector_searcher_factory()
+            if op in ("cycles", "layers"):       # questions about the graph as a whole (DESIGN.md 3.31)
+                if target or max_hops is not None:
+                    raise ValueError(f"op {op!r} takes name and limit only")
+                if op == "cycles":
+                    if name:
+                        raise ValueError("op 'cycles' lists the cycles of the whole graph: it takes no name (search with in_cycle for code inside them)")
+                    got = await searcher.find_cycles(limit=limit)
+                    return ToolResult(success=True, data=got["cycles"], message=f"Found {got['count']} call cycle(s) over {got['nodes']} function(s); the "
+                                      f"{len(got['cycles'])} largest are listed.")
+                got = await searcher.find_layers(names=name or None, match="suffix")
+                return ToolResult(success=True, data=got["nodes"], message=f"The call graph has {got['layers']} layer(s); by depth below the entry points "
+                                  f"they hold {got['histogram']['depth']} functions, by height above the leaves {got['histogram']['height']}.")
             if op is not None:
                 if op != "important_near":
-                    raise ValueError(f"op {op!r} is not 'important_near'")
+                    raise ValueError(f"op {op!r} is not one of 'important_near', 'cycles', 'layers'")
                 if target or max_hops is not None:
                     raise ValueError("op 'important_near' takes name and limit only")
                 nodes = await searcher.find_important_near(name, limit=limit)
@@ -207,7 +222,8 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
                         "another. Use it for impact analysis and for 'how does X get to Y'."),
         "function": code_graph,
         "parameters": {
-            "name": {"type": "string", "description": "The qualified name of the function, method or class to start from", "required": True},
+            "name": {"type": "string", "description": "The qualified name of the function, method or class to start from (none for op "
+                                                      "'cycles'; optional for op 'layers')", "required": True},
             "relation": {"type": "string", "description": "'callers' (the default: what calls it), 'callees' (what it calls) or 'chain' "
                                                           "(one shortest chain of calls from name to target)", "required": False},
             "target": {"type": "string", "description": "With relation 'chain': the qualified name to reach", "required": False},
@@ -215,7 +231,10 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
             "limit": {"type": "integer", "description": "Maximum number of callers / callees listed, nearest first (default: 50)", "required": False},
             "op": {"type": "string", "description": "'important_near': instead of a walk, rank the code around name by a random walk with "
                                                     "restart over the calls, both ways (personalised PageRank): what matters near it, "
-                                                    "best first", "required": False},
+                                                    "best first.  'cycles': the groups of functions that call each other in a circle "
+                                                    "(recursion, mutual recursion), largest first; takes limit only.  'layers': how deep "
+                                                    "below the entry points and how high above the leaf helpers name lies (without a name: "
+                                                    "how many functions each layer holds)", "required": False},
         },
     }
 

@@ -261,10 +261,56 @@ class GraphSpec(NamedTuple):
     match: str
 
 
-def graph_spec(spec) -> GraphSpec:
+class GraphStructureSpec(NamedTuple):
+    """A ``{"in_cycle": True}`` / ``{"same_cycle_as": name}`` / ``{"depth" | "height": int or range}`` filter value, checked
+    (DESIGN.md 3.31): the kind, its argument (True, the name, or inclusive ``(lo, hi)``), the relation and how a name resolves."""
+    kind: str
+    arg: Any
+    relation: str
+    match: str
+
+
+def _graph_structure_spec(spec) -> GraphStructureSpec:
+    kinds = [k for k in spec if k in graph_mod.STRUCTURE_WORDS]
+    allowed = ("relation", "match") if kinds == ["same_cycle_as"] else ("relation",)
+    unknown = [k for k in spec if k not in kinds and k not in allowed]
+    if unknown or len(kinds) != 1:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: exactly one of {', '.join(graph_mod.STRUCTURE_WORDS)} (or of {', '.join(graph_mod.FILTER_WORDS)}) "
+                         f"and 'relation' (got {sorted(map(str, spec))})")
+    kind, value = kinds[0], spec[kinds[0]]
+    relation, match = spec.get("relation", "calls"), spec.get("match", "exact")
+    if not isinstance(relation, str) or match not in ("exact", "suffix"):
+        raise ValueError(f"filter key {GRAPH_KEY!r}: relation is a string and match 'exact' or 'suffix' (got {relation!r}, {match!r})")
+    if kind == "in_cycle":
+        if value is not True:
+            raise ValueError(f"filter key {GRAPH_KEY!r}: in_cycle takes True (exclude the cycles with must_not), not {value!r}")
+        arg = True
+    elif kind == "same_cycle_as":
+        if not isinstance(value, str) or not value:
+            raise ValueError(f"filter key {GRAPH_KEY!r}: same_cycle_as takes one node name, not {value!r}")
+        arg = value
+    elif isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+        if value < 0:
+            raise ValueError(f"filter key {GRAPH_KEY!r}: {kind} is a layer number >= 0, not {value!r}")
+        arg = (int(value), int(value))
+    elif isinstance(value, Mapping):
+        if any(v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))) for v in value.values()):
+            raise ValueError(f"filter key {GRAPH_KEY!r}: the bounds of a {kind} range are ints, not {dict(value)!r}")
+        try:
+            arg = range_bounds(kind, value)
+        except ValueError as e:
+            raise ValueError(f"filter key {GRAPH_KEY!r}: {e}") from None
+    else:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: {kind} takes an int or a range mapping ({', '.join(_RANGE_WORDS)}), not {value!r}")
+    return GraphStructureSpec(kind, arg, relation, match)
+
+
+def graph_spec(spec) -> "GraphSpec | GraphStructureSpec":
     """The value of a ``"graph"`` filter entry as a :class:`GraphSpec`; ``ValueError`` naming the key for anything else."""
     if not isinstance(spec, Mapping):
         raise ValueError(f"filter key {GRAPH_KEY!r} takes a mapping {{'callers_of' | 'callees_of' | 'connected_to': name or list of names, 'hops': 1..{ffi.GRAPH_MAX_HOPS}}}, not {spec!r}")
+    if any(k in graph_mod.STRUCTURE_WORDS for k in spec):
+        return _graph_structure_spec(spec)
     unknown = [k for k in spec if k not in _GRAPH_WORDS]
     kinds = [k for k in spec if k in graph_mod.FILTER_WORDS]
     if unknown or len(kinds) != 1:
@@ -363,6 +409,8 @@ class _Collection:
         self._graph_names: list[str] = []
         self._graph_code: dict[str, int] = {}
         self._graph_rel: dict[str, np.ndarray] = {}
+        self._graph_self: dict[str, np.ndarray] = {}   # relation -> the nodes that carried a self-loop (the CSRs keep none): sorted int32
+        self._graph_struct: dict[str, dict] = {}       # relation -> components, cyclic bins, layers on the device: DERIVED
         self._graph = None
         self._graph_version = 0              # bumped by every set_graph_edges: what the derived parts and the cache are keyed by
         self._graph_rows: dict[int, tuple] = {}
@@ -370,6 +418,7 @@ class _Collection:
         self._graph_cache: dict[tuple, tuple] = {}   # (spec, graph version, collection state) -> (tag, words per index)
         self.graph_bfs_calls = 0             # graph conditions resolved by a BFS so far (repeated filters reuse the words)
         self.graph_ppr_calls = 0             # personalised PageRank passes run so far (64 queries or name sets each)
+        self.graph_scc_calls = 0             # component computations run so far (one per relation and graph version)
         self.compact_dead_fraction, self.compact_min_dead = compact_dead_fraction, compact_min_dead
         self.compactions = 0
         self.group_rounds = {"queries": 0, "round2": 0, "exclusion": 0}    # search_grouped: queries asked / sent to round 2 / exclusion rounds run
@@ -654,7 +703,8 @@ class _Collection:
     # -- call graph
     def set_graph_edges(self, edges, relation: str = "calls", derive_degrees: bool = False) -> dict[str, Any]:
         """Sets or replaces the edges of ``relation``: ``edges`` is an iterable of ``(source_name, target_name)``.  Nodes are
-        numbered in order of first appearance, over all relations of the collection; self-loops and repeats are dropped.
+        numbered in order of first appearance, over all relations of the collection; self-loops and repeats are dropped from
+        the edges, the nodes that carried a self-loop are kept beside them (sorted int32, ``_graph_self``).
         ``derive_degrees``: the re-rank's centrality table becomes the distinct in-degree + out-degree of this relation."""
         if not isinstance(relation, str) or not relation:
             raise ValueError(f"a graph relation is named by a non-empty string, not {relation!r}")
@@ -669,6 +719,7 @@ class _Collection:
             del self._graph_names[n0:]
             raise
         self._graph_rel[relation] = graph_mod.unique_edges(pairs, len(self._graph_names))
+        self._graph_self[relation] = graph_mod.self_loops(pairs, len(self._graph_names))
         self._graph_changed()
         if derive_degrees:
             deg = graph_mod.total_degrees(self._graph_rel[relation], len(self._graph_names))
@@ -686,7 +737,7 @@ class _Collection:
         """Forgets what is derived (the device graph, the row -> node columns, the kept results); names and edges stay."""
         if self._graph is not None:
             self._graph.close()
-        self._graph, self._graph_rows, self._graph_rows_state, self._graph_cache = None, {}, None, {}
+        self._graph, self._graph_rows, self._graph_rows_state, self._graph_cache, self._graph_struct = None, {}, None, {}, {}
 
     def _graph_ready(self, relation: str) -> tuple[Any, int]:
         """(the device graph, built from the kept edges on first use; the number of ``relation`` in it)."""
@@ -730,23 +781,119 @@ class _Collection:
         then per owned shard the reached nodes' rows (``crh_graph_row_words`` over the row -> node column) as
         ``CRH_COND_WORDS`` (``negate``: ``_NOT_WORDS``).  None when no name is a node.  The last few results are kept, keyed by
         what they were computed from; every result lives in buffers of its own under a tag of its own."""
+        if isinstance(spec, GraphStructureSpec):
+            return self._graph_structure_condition(spec, negate)
         graph, rel = self._graph_ready(spec.relation)
         ids, _ = graph_mod.resolve(spec.names, self._graph_code, self._graph_names, spec.match)
         if not ids:
             return None
+        def reached(stream):
+            self.graph_bfs_calls += 1
+            return graph.bfs(rel, spec.direction, [ids], spec.hops, include_self=spec.include_self, stream=stream)[1]
+        return self._graph_row_words(spec, negate, graph, reached)
+
+    def _graph_row_words(self, spec, negate: bool, graph, node_words) -> "ffi.RowWords":
+        """The rows of the nodes whose word ``node_words(stream)`` (the ``seen`` words of a BFS, or ``crh_graph_node_words``')
+        carries bit 0, per owned shard, kept in the LRU under ``spec`` and what the rows were computed from."""
         ck = (spec, self._graph_version, tuple(self.shards.rows), self.shards.count()[1], self.compactions)
         hit = self._graph_cache.pop(ck, None)
         if hit is None:
             stream = self.shards._stream()
             columns = self._graph_row_nodes()
-            graph.bfs(rel, spec.direction, [ids], spec.hops, include_self=spec.include_self, stream=stream)
-            self.graph_bfs_calls += 1
-            words = {id(self.shards.index[s]): graph.row_words(columns[s], 0, stream=stream) for s in self.shards.owned}
+            seen = node_words(stream)
+            words = {id(self.shards.index[s]): graph.row_words(columns[s], 0, seen=seen, stream=stream) for s in self.shards.owned}
             hit = (ffi.next_words_tag(), words)
             while len(self._graph_cache) >= _GRAPH_CACHE:
                 self._graph_cache.pop(next(iter(self._graph_cache)))     # (the least recently used: hits are re-inserted below)
         self._graph_cache[ck] = hit
         return ffi.RowWords(hit[0], hit[1], negate)
+
+    # -- the graph as a whole: cycles, components, layers (DESIGN.md 3.31)
+    def _graph_structure(self, relation: str, layers: bool = False) -> tuple[Any, dict]:
+        """(the device graph, the derived state of ``relation``): ``comp`` int32 / ``bins`` int64 [nodes] on the device and
+        ``info``; with ``layers`` also ``depth`` / ``height`` int32 [nodes] and ``layers``.  Computed on first use, once per
+        relation and graph version; :meth:`_graph_drop` forgets it."""
+        graph, rel = self._graph_ready(relation)
+        st = self._graph_struct.get(relation)
+        stream = self.shards._stream()
+        if st is None:
+            comp, info = graph.scc(rel, stream=stream)
+            self.graph_scc_calls += 1
+            loops = self._graph_self.get(relation)
+            bins = graph.scc_bins(comp, loops if loops is not None and loops.size else None, stream=stream)
+            st = self._graph_struct[relation] = {"comp": comp, "bins": bins, "info": [int(v) for v in info]}
+        if layers and "depth" not in st:
+            depth, info = graph.layers(rel, "callees", st["comp"], stream=stream)
+            st["height"], _ = graph.layers(rel, "callers", st["comp"], stream=stream)
+            st["depth"], st["layers"] = depth, int(info[0])
+        return graph, st
+
+    def _graph_structure_host(self, st: dict, what: str) -> np.ndarray:
+        """A derived array on the host (4 or 8 bytes per node: the listings' output formatting), copied once."""
+        host = st.setdefault("host", {})
+        if what not in host:
+            host[what] = _host(st[what])
+        return host[what]
+
+    def _graph_structure_condition(self, spec: GraphStructureSpec, negate: bool) -> "ffi.RowWords | None":
+        """A condition on the node's place in the whole graph as the row-bitmap condition of the device filter:
+        ``crh_graph_node_words`` over the kept components or layers, then :meth:`_graph_row_words` (the LRU of the walk
+        conditions).  None when ``same_cycle_as`` names no node."""
+        graph, st = self._graph_structure(spec.relation, layers=spec.kind in ("depth", "height"))
+        if spec.kind == "in_cycle":
+            args = ("in_cycle", st["comp"], st["bins"], 0, 0)
+        elif spec.kind == "same_cycle_as":
+            ids, _ = graph_mod.resolve([spec.arg], self._graph_code, self._graph_names, spec.match)
+            if not ids:
+                return None
+            if len(ids) > 1:
+                raise ValueError(f"filter key {GRAPH_KEY!r}: same_cycle_as={spec.arg!r} names {len(ids)} nodes ({', '.join(self._graph_names[i] for i in ids[:4])}, ...): name one")
+            args = ("same_component", st["comp"], None, int(self._graph_structure_host(st, "comp")[ids[0]]), 0)
+        else:
+            args = ("range", st[spec.kind], None, spec.arg[0], spec.arg[1])
+        return self._graph_row_words(spec, negate, graph, lambda stream: graph.node_words(args[0], args[1], bins=args[2], lo=args[3], hi=args[4], q=0, stream=stream))
+
+    def graph_cycles(self, relation: str, limit: int, members: int) -> dict[str, Any]:
+        """The cyclic components of ``relation``, largest first (ties to the node seen first): see ``HipVectorStore.graph_cycles``."""
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= ffi.MAX_K:
+            raise ValueError(f"graph_cycles: limit must be an int in 1..{ffi.MAX_K}, not {limit!r}")
+        if isinstance(members, bool) or not isinstance(members, (int, np.integer)) or members < 0:
+            raise ValueError(f"graph_cycles: members must be a non-negative int, not {members!r}")
+        graph, st = self._graph_structure(relation)
+        names, n = self._graph_names, len(self._graph_names)
+        if n == 0:
+            return {"components": [], "count": 0, "nodes": 0, "self_recursive": []}
+        codes, counts, info = (_host(t) for t in ffi.facet_select(st["bins"], int(limit), self.shards._stream()))
+        comp = self._graph_structure_host(st, "comp")
+        loops = self._graph_self.get(relation, np.zeros((0,), np.int32))
+        looped = set(loops.tolist())
+        out = []
+        for c, size in zip(codes.reshape(-1).tolist(), counts.reshape(-1).tolist()):
+            if c < 0:
+                break
+            nodes = np.flatnonzero(comp == c)
+            out.append({"id": names[c], "size": int(size), "nodes": [names[v] for v in nodes[:members].tolist()],
+                        "self_recursive": [names[v] for v in nodes.tolist() if v in looped][:members]})
+        bins = self._graph_structure_host(st, "bins")
+        alone = [names[v] for v in loops.tolist() if bins[comp[v]] == 1]
+        return {"components": out, "count": int(info.reshape(-1)[0]), "nodes": int(info.reshape(-1)[1]),
+                "self_recursive": alone if len(alone) <= members else len(alone)}
+
+    def graph_layers(self, relation: str, names, match: str) -> dict[str, Any]:
+        """The layers of the condensation of ``relation``: see ``HipVectorStore.graph_layers``."""
+        graph, st = self._graph_structure(relation, layers=True)
+        n = len(self._graph_names)
+        depth, height = self._graph_structure_host(st, "depth"), self._graph_structure_host(st, "height")
+        layers = st["layers"] if n else 0
+        out = {"layers": layers, "histogram": {"depth": np.bincount(depth, minlength=layers).tolist() if n else [],
+                                               "height": np.bincount(height, minlength=layers).tolist() if n else []}, "nodes": []}
+        if names is not None:
+            ids, missing = graph_mod.resolve(names, self._graph_code, self._graph_names, match)
+            comp, bins = self._graph_structure_host(st, "comp"), self._graph_structure_host(st, "bins")
+            out["nodes"] = [{"name": self._graph_names[v], "depth": int(depth[v]), "height": int(height[v]), "component": self._graph_names[int(comp[v])],
+                             "cyclic": bool(bins[comp[v]] > 0)} for v in ids]
+            out["unresolved"] = missing
+        return out
 
     def graph_nodes_of(self, rows_dev, stream: int = 0):
         """The nodes of a table of GLOBAL rows (CUDA int64, -1: padding) as an int32 CUDA tensor of the same shape, -1 where the
@@ -1572,6 +1719,10 @@ class _Collection:
                 for r, (rel, pairs) in enumerate(self._graph_rel.items()):
                     np.ascontiguousarray(pairs, dtype=np.int32).tofile(os.path.join(tmp, f"graph.{r}.edges.i32"))
                     graph_meta["relations"].append({"name": rel, "file": f"graph.{r}.edges.i32", "edges": int(len(pairs))})
+                    loops = self._graph_self.get(rel)
+                    if loops is not None and loops.size:                  # optional: the nodes that carried a self-loop (sorted int32)
+                        np.ascontiguousarray(loops, dtype=np.int32).tofile(os.path.join(tmp, f"graph.{r}.self.i32"))
+                        graph_meta["relations"][-1]["self"] = f"graph.{r}.self.i32"
             with open(os.path.join(tmp, "collection.json"), "w") as f:
                 # format 4: says where the payload tables are ("text_tables": "per_rank" = tables{rank}/ hold the text of that
                 # rank's rows only, written by one process per shard; "root" = one complete table)
@@ -1640,7 +1791,7 @@ class _Collection:
         self._lex_drop()
         self._text_drop()
         self._degrees = meta.get("degrees")
-        self._graph_names, self._graph_code, self._graph_rel = [], {}, {}
+        self._graph_names, self._graph_code, self._graph_rel, self._graph_self = [], {}, {}, {}
         graph_meta = meta.get("graph")
         if graph_meta:
             with open(os.path.join(directory, graph_meta["names"])) as f:
@@ -1653,6 +1804,8 @@ class _Collection:
                 if len(pairs) != int(r["edges"]):
                     raise ValueError(f"snapshot of {self.name}: relation {r['name']!r} holds {len(pairs)} edges, collection.json says {r['edges']}")
                 self._graph_rel[str(r["name"])] = graph_mod.unique_edges(pairs, len(self._graph_names))
+                loops = np.fromfile(os.path.join(directory, r["self"]), np.int32) if r.get("self") else np.zeros((0,), np.int32)
+                self._graph_self[str(r["name"])] = graph_mod.self_loops(np.stack([loops, loops], axis=1), len(self._graph_names))
         self._graph_changed()
 
     def close(self) -> None:
@@ -2439,7 +2592,12 @@ class HipVectorStore:
         "relation": "calls", "include_self": True, "match": "exact" | "suffix"}`` keeps the points whose node calls / is called
         from / is connected to the named nodes within ``hops`` (1..16) edges given to :meth:`set_graph_edges` -- one BFS on the
         device, the result a row bitmap like a text condition's, combinable with everything a filter combines
-        with except per-query filter lists; under ``must_not`` those points are excluded.  Names that are no node match nothing."""
+        with except per-query filter lists; under ``must_not`` those points are excluded.  Names that are no node match nothing.
+        Instead of a walk the entry may ask about the node's place in the WHOLE graph, with ``"relation"``
+        beside it: ``{"in_cycle": True}`` -- the node lies in a cycle of the relation (it calls itself, or is one of several
+        nodes that all reach each other) --, ``{"same_cycle_as": name}``, or ``{"depth" | "height": int or range mapping}`` --
+        its layer below the entry points / above the leaves (:meth:`graph_layers`).  Components and layers are found on the
+        device once per relation and graph version."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -3057,7 +3215,8 @@ class HipVectorStore:
         """The edges of one named relation of the collection's graph (the reference keeps them in Memgraph): ``edges`` is an
         iterable of ``(source_name, target_name)``; a node is named like the chunks' key ``graph_node_id or entity_name``.  A
         call REPLACES that relation; up to 8 relations share one node numbering, in order of first appearance; repeats and
-        self-loops are dropped.  ``derive_degrees``: the re-rank's centrality table (:meth:`set_graph_degrees`) is filled
+        self-loops are dropped from the edges (WHICH nodes carried a self-loop is kept: :meth:`graph_cycles` reports a function
+        that calls itself).  ``derive_degrees``: the re-rank's centrality table (:meth:`set_graph_degrees`) is filled
         with every node's distinct in-degree + out-degree in this relation (GET_ENTITY_CENTRALITY's ``total_degree``).
         Returns :meth:`graph_info`."""
         try:
@@ -3099,6 +3258,32 @@ class HipVectorStore:
             return await self._run(lambda: self._col(collection).call_chain(source, target, relation, max_hops))
         except Exception as e:
             raise VectorStoreError(f"Failed to walk the graph of {collection}", cause=e)
+
+    # ------------------------------------------------------------------ the graph as a whole
+    async def graph_cycles(self, collection: str, relation: str = "calls", limit: int = 10, members: int = 50) -> dict[str, Any]:
+        """Which functions are (mutually) recursive, which modules import each other in a circle: the CYCLIC strongly connected
+        components of ``relation`` -- two nodes or more that all reach each other, or one node with an edge to itself -- found on
+        the device (trim, colouring, back-mark; the ``limit`` largest chosen by ``crh_facet_select``).  Returns ``{"components":
+        [{"id", "size", "nodes", "self_recursive"}], "count", "nodes", "self_recursive"}``: the components largest first, ties
+        to the one whose first node :meth:`set_graph_edges` saw first; ``id`` is that first node's name, ``nodes`` the members in
+        order of first appearance (at most ``members``), ``self_recursive`` those of them that also call themselves; ``count``
+        and ``nodes`` are the number of cyclic components and of nodes in them, never clipped; the outer ``self_recursive``
+        names the nodes that are cyclic ONLY by their own self-loop (their number when there are more than ``members``)."""
+        try:
+            return await self._run(lambda: self._col(collection).graph_cycles(relation, limit, members))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to list the cycles of {collection}", cause=e)
+
+    async def graph_layers(self, collection: str, relation: str = "calls", names=None, match: str = "exact") -> dict[str, Any]:
+        """Entry points, leaf utilities and a reading or build order: the longest-path layers of the CONDENSATION of ``relation``
+        (every cycle shrunk to one node), both ways.  ``depth`` is 0 for a node nobody outside its own cycle calls, ``height`` 0
+        for one that calls nothing outside its own cycle.  Returns ``{"layers": n, "histogram": {"depth": [nodes per layer],
+        "height": [...]}, "nodes": [{"name", "depth", "height", "component", "cyclic"}]}`` -- ``nodes`` for the named ones
+        (``names``: a name or a list, resolved as in :meth:`graph_neighbors`; ``"unresolved"`` lists the rest)."""
+        try:
+            return await self._run(lambda: self._col(collection).graph_layers(relation, names, match))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to layer the graph of {collection}", cause=e)
 
     async def search_expanded_batch(self, collection: str, query_vectors, limit: int = 10, graph_expand: dict[str, Any] | None = None,
                                     filters: dict[str, Any] | None = None, must_not: dict[str, Any] | None = None) -> list[dict[str, Any]]:

@@ -121,10 +121,16 @@ def _contains_filter(key: str, contains, contains_case: bool, matches: str | Non
     return {key: spec}
 
 
-def _graph_filter(within_callers_of, within_callees_of, graph_hops: int | None) -> dict:
+def _graph_filter(within_callers_of, within_callees_of, graph_hops: int | None, in_cycle: bool | None = None, graph_depth=None,
+                  graph_height=None) -> dict:
     """``within_callers_of`` / ``within_callees_of`` (a node name or a list of them) as the store's ``"graph"`` condition: only
     code that calls / is called from those nodes, transitively within ``graph_hops`` edges (the store's default: 3), the named
     nodes' own chunks included -- ``{}`` without either: the call is then the one issued before."""
+    whole = {k: v for k, v in (("in_cycle", True if in_cycle else None), ("depth", graph_depth), ("height", graph_height)) if v is not None}
+    if whole:                                                            # the node's place in the whole graph (DESIGN.md 3.31)
+        if len(whole) > 1 or within_callers_of is not None or within_callees_of is not None or graph_hops is not None:
+            raise QueryError("in_cycle, graph_depth, graph_height, within_callers_of and within_callees_of cannot be combined (one graph condition per search)")
+        return {"graph": whole}
     if within_callers_of is None and within_callees_of is None:
         if graph_hops is not None:
             raise QueryError("graph_hops stands beside within_callers_of or within_callees_of")
@@ -245,7 +251,8 @@ class VectorSearcher:
                           contains_case: bool = True, matches: str | None = None,
                           fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
                           within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
-                          propagate: bool | dict | None = None) -> list[dict]:
+                          propagate: bool | dict | None = None, in_cycle: bool | None = None, graph_depth: int | dict | None = None,
+                          graph_height: int | dict | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -280,6 +287,11 @@ class VectorSearcher:
         (default 3), counts: "timeout handling, but only in code reachable from ``main``".  Resolved by a BFS on the device
         over the edges given to ``HipVectorStore.set_graph_edges``, in every mode and beside every other
         argument; :meth:`search_summaries`, :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way.
+        ``in_cycle=True`` / ``graph_depth`` / ``graph_height`` (not in the reference) instead: only code whose node lies in a
+        call cycle -- a recursive function, or several that call each other -- / at that depth below the entry points / at
+        that height above the leaf helpers (an int, or a range such as ``{"lte": 1}``): "retry handling, but only in leaf
+        helpers" is ``graph_height=0``.  Components and layers of the whole graph are found on the device once per graph
+        (DESIGN.md 3.31); :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way.
         ``propagate`` (not in the reference): ``True``, or the settings of ``HipVectorStore.search_propagated`` -- the best
         ``candidates`` matches seed a random walk with restart over the call graph (personalised PageRank) and
         the results are ordered by reciprocal-rank fusion of similarity and graph score: of the matches, those in the middle of
@@ -291,12 +303,13 @@ class VectorSearcher:
                 query, limit, language, entity_type, project_name, candidates=candidates, propagate=propagate, related_limit=0,
                 contains=contains, contains_case=contains_case, matches=matches, fuzzy=fuzzy, edits=edits, within_callers_of=within_callers_of,
                 within_callees_of=within_callees_of, graph_hops=graph_hops, diversity=diversity, max_per_file=max_per_file,
-                extra_queries=extra_queries, min_score=min_score, max_overlap=max_overlap, mode=mode))["results"]
+                extra_queries=extra_queries, min_score=min_score, max_overlap=max_overlap, mode=mode, in_cycle=in_cycle or None,
+                graph_depth=graph_depth, graph_height=graph_height))["results"]
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
-        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops))
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height))
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -383,21 +396,23 @@ class VectorSearcher:
                                 max_overlap: float | None = None, contains: str | list[str] | None = None,
                                 contains_case: bool = True, matches: str | None = None,
                                 fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
-                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
+                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
+                                in_cycle: bool | None = None, graph_depth: int | dict | None = None,
+                                graph_height: int | dict | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
         ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet.  ``max_overlap`` as in
         :meth:`search_code`: no chunk repeats more than that share of a better chunk's lines.  ``contains`` / ``contains_case``
         as in :meth:`search_code`: only chunks that hold the literal string(s); ``matches`` likewise: only chunks the regular
-        expression matches."""
+        expression matches.  ``in_cycle`` / ``graph_depth`` / ``graph_height`` as in :meth:`search_code`."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
         on_device = bool(exact_exclude and exclude_file)
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch,
                                   {**_contains_filter("content", contains, contains_case, matches, fuzzy, edits),
-                                   **_graph_filter(within_callers_of, within_callees_of, graph_hops)} or _NO_FILTER_KWARG,
+                                   **_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height)} or _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
@@ -515,6 +530,32 @@ class VectorSearcher:
             return []
         return [{"nodes": chain, "relationships": ["CALLS"] * (len(chain) - 1), "total_length": len(chain) - 1, "path_type": "call_chain"}]
 
+    async def find_cycles(self, limit: int = 10, relation: str = "calls", members: int = 50) -> dict:
+        """Which functions are (mutually) recursive -- with ``relation="imports"``: which modules depend on each other in a
+        circle (``HipVectorStore.graph_cycles``; not in the reference, whose Cypher has no query for it): ``{"cycles": [{"name",
+        "qualified_name", "size", "members": [qualified names], "self_recursive": [...]}], "count", "nodes", "self_recursive"}``,
+        the largest cycle first; ``name`` is that of the member indexed first."""
+        try:
+            got = await self.qdrant.graph_cycles(collection=CollectionName.CODE_CHUNKS.value, relation=relation, limit=limit, members=members)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to find the call cycles", cause=e)
+        cycles = [{"name": c["id"].rsplit(".", 1)[-1], "qualified_name": c["id"], "size": c["size"], "members": c["nodes"],
+                   "self_recursive": c["self_recursive"]} for c in got["components"]]
+        return {"cycles": cycles, "count": got["count"], "nodes": got["nodes"], "self_recursive": got["self_recursive"]}
+
+    async def find_layers(self, names=None, relation: str = "calls", match: str = "exact") -> dict:
+        """Entry points, leaf utilities, a reading order (``HipVectorStore.graph_layers``; not in the reference): ``{"layers",
+        "histogram": {"depth", "height"}, "nodes": [{"name", "qualified_name", "depth", "height", "component", "cyclic"}]}`` --
+        ``depth`` 0: nobody outside its own cycle calls it; ``height`` 0: it calls nothing outside its own cycle."""
+        try:
+            got = await self.qdrant.graph_layers(collection=CollectionName.CODE_CHUNKS.value, relation=relation, names=names, match=match)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to layer the call graph", cause=e)
+        nodes = [dict(n, name=n["name"].rsplit(".", 1)[-1], qualified_name=n["name"]) for n in got["nodes"]]
+        return {**got, "nodes": nodes}
+
     # ------------------------------------------------------------------ batch entry (not in the reference)
     async def search_code_batch(self, queries, limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None,
                                 entity_type: str | None = None, project_name: str | list[str] | None = None, *,
@@ -524,7 +565,9 @@ class VectorSearcher:
                                 max_overlap: float | None = None, mode: str = "semantic", contains: str | list[str] | None = None,
                                 contains_case: bool = True, matches: str | None = None,
                                 fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
-                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[list[dict]]:
+                                within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
+                                in_cycle: bool | None = None, graph_depth: int | dict | None = None,
+                                graph_height: int | dict | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
         ``candidates`` only).
@@ -541,7 +584,9 @@ class VectorSearcher:
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
         if (within_callers_of is not None or within_callees_of is not None) and filters_per_query is not None:
             raise QueryError("within_callers_of / within_callees_of cannot be combined with filters_per_query (a graph condition is one BFS for the whole batch)")
-        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops))
+        if (in_cycle or graph_depth is not None or graph_height is not None) and filters_per_query is not None:
+            raise QueryError("in_cycle / graph_depth / graph_height cannot be combined with filters_per_query (a graph condition is one bitmap for the whole batch)")
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height))
         if filters_per_query is not None:
             if filters:
                 raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")

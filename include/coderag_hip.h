@@ -852,6 +852,71 @@ int crh_graph_ppr_order(int64_t n_nodes, int nq, int c, const float *scores_dev 
                         const float *cosine_dev, const int32_t *nodes_dev, float *out_fuse_scores_dev, int64_t *out_fuse_rows_dev,
                         float *out_graph_score_dev, void *stream);
 
+/* ---- the structure of the whole graph: strongly connected components and the layers of the condensation.
+ * Every result is a uniquely defined integer: exact, and the same from run to run.  Every phase is a sequence of SWEEPS, one
+ * launch each, one lane per node (a list of CRH_GRAPH_WAVE_DEGREE entries or more is walked by the node's whole wave), none of
+ * which waits for another workgroup.  A sweep is monotone towards a fixed point that does not depend on the order of updates,
+ * so it updates in place; it makes one atomicOr per workgroup into a `changed` word, the next launch reads that word and leaves
+ * at once when it is 0, and the host reads the words back once per 16 sweeps.
+ *
+ * crh_graph_scc: comp_out_dev int32 [n_nodes], comp[v] = the SMALLEST node id of v's strongly connected component in relation
+ * `rel` (both CSRs are read; an entry u == v of a list is ignored).  Rounds of
+ *   trim      an unassigned node without an unassigned in-neighbour, or without an unassigned out-neighbour: comp[v] = v;
+ *   colour    colour[v] = v, then min with the colours of the unassigned in-neighbours: the smallest unassigned id that reaches v;
+ *   back-mark colour[r] == r: comp[r] = r; then an unassigned v joins comp[v] = colour[v] once an out-neighbour w has
+ *             comp[w] == colour[v]
+ * each to its fixed point, until a trim leaves no node unassigned.  work_dev int32 [n_nodes + CRH_GRAPH_SCC_WORK_EXTRA],
+ * caller-owned, overwritten.  info_host int64 [4] = (components, components of two nodes or more, the nodes in those, sweeps
+ * launched, those that left at once included); a self-loop is unknown here: crh_graph_scc_bins counts with them.
+ * BOUND.  A trim sweep that changes something assigns a node (at most n of them in all) and each of the at most n + 1 rounds
+ * ends with one that changes nothing; with m nodes left, a colour or a label travels a simple path, so the colour and the
+ * back-mark phase change something in at most m - 1 sweeps each and run one more; every round assigns its smallest id at
+ * least, so m <= n, n - 1, ...: in all at most n + (n + 1) + n (n + 1) < CRH_GRAPH_SCC_MAX_SWEEPS(n) sweeps that run.  The host
+ * loop stops there with CRH_E_INTERNAL (unreachable for CSRs that hold the same edges) and never loops on.
+ * WAITS on `stream` (it reads the changed words between batches of sweeps), unlike the "enqueues" calls.  Any bad argument is
+ * CRH_E_INVALID with nothing launched, info zeroed where there is one; a graph without nodes is CRH_OK with nothing launched. */
+#define CRH_GRAPH_SCC_WORK_EXTRA 32
+#define CRH_GRAPH_SCC_MAX_SWEEPS(n) (((int64_t)(n) + 2) * ((int64_t)(n) + 2))
+#define CRH_GRAPH_LAYERS_MAX_SWEEPS(n) ((int64_t)(n) + 1)
+int crh_graph_scc(crh_graph *g, int rel, int32_t *comp_out_dev /* [n_nodes] */, int32_t *work_dev /* [n_nodes + CRH_GRAPH_SCC_WORK_EXTRA] */,
+                  int64_t *info_host /* [4] */, void *stream);
+
+/* The CYCLIC components as the histogram crh_facet_select takes: out_bins_dev int64 [n_nodes], bins[c] = the number of nodes v
+ * with comp[v] == c when that number is at least 2, or is 1 and c is in self_nodes_dev (int32, sorted ascending, distinct; NULL
+ * with n_self = 0: the nodes that carry a self-loop, which the CSRs do not keep); 0 otherwise.  A label outside 0 .. n_nodes - 1
+ * counts nowhere.  Integer atomics: exact whatever the order.  crh_facet_select(1, n_nodes, k, bins, ...) is then the k largest
+ * cyclic components, ties to the lower label, and its info (cyclic components, nodes in them).  Runs on the CURRENT device;
+ * enqueues; every bin is written.  Bad arguments (n_self outside 0 .. n_nodes, NULL pointers) are CRH_E_INVALID with nothing
+ * launched; n_nodes = 0 is CRH_OK with nothing launched. */
+int crh_graph_scc_bins(int64_t n_nodes, const int32_t *comp_dev, const int32_t *self_nodes_dev /* or NULL */, int64_t n_self,
+                       int64_t *out_bins_dev /* [n_nodes] */, void *stream);
+
+/* The longest-path layer of every node's component in the CONDENSATION (every component shrunk to one node), comp_dev as
+ * crh_graph_scc wrote it for the same relation: out_dev int32 [n_nodes] = the least fixed point, from zeros, of
+ *   layer[v] = max over u of layer[u] + (comp[u] != comp[v]),
+ * u running over v's in-neighbours for CRH_GRAPH_ALONG (DEPTH: 0 for a node nobody outside its own cycle calls) and over its
+ * out-neighbours for CRH_GRAPH_AGAINST (HEIGHT: 0 for a node that calls nothing outside its own cycle); CRH_GRAPH_BOTH is
+ * CRH_E_INVALID.  Bellman-Ford with weights 0 and 1: a longest walk can be taken simple (a cycle lies inside a component and
+ * weighs 0), so a value travels at most n - 1 edges: at most n sweeps run, and the host loop stops at
+ * CRH_GRAPH_LAYERS_MAX_SWEEPS(n) with CRH_E_INTERNAL -- which is what labels that are no components of this relation get.
+ * Labels are compared, never used as an index.  work_dev int32 [CRH_GRAPH_SCC_WORK_EXTRA].  info_host int64 [2] = (layers =
+ * the largest value + 1, sweeps launched).  WAITS on `stream`.  Argument handling as crh_graph_scc. */
+int crh_graph_layers(crh_graph *g, int rel, int direction, const int32_t *comp_dev, int32_t *out_dev /* [n_nodes] */,
+                     int32_t *work_dev /* [CRH_GRAPH_SCC_WORK_EXTRA] */, int64_t *info_host /* [2] */, void *stream);
+
+/* A condition on every node as the `seen` words of a BFS, for crh_graph_row_words: out_words_dev u64 [n_nodes], word v = 1 << q
+ * where the condition holds and 0 elsewhere (every word is written), x = values_dev[v] (int32 [n_nodes]):
+ *   CRH_GRAPH_WORDS_IN_CYCLE        0 <= x < n_nodes and bins_dev[x] > 0 (values = components, bins = crh_graph_scc_bins')
+ *   CRH_GRAPH_WORDS_SAME_COMPONENT  x == lo                               (values = components, lo = a label)
+ *   CRH_GRAPH_WORDS_RANGE           lo <= x <= hi                         (values = layers; lo > hi is an empty range)
+ * bins_dev is read by the first mode only and may be NULL otherwise.  0 <= q < CRH_GRAPH_MAX_QUERIES.  Runs on the CURRENT
+ * device; enqueues.  Bad arguments are CRH_E_INVALID with nothing launched; n_nodes = 0 is CRH_OK with nothing launched. */
+#define CRH_GRAPH_WORDS_IN_CYCLE 0
+#define CRH_GRAPH_WORDS_SAME_COMPONENT 1
+#define CRH_GRAPH_WORDS_RANGE 2
+int crh_graph_node_words(int64_t n_nodes, int mode, const int32_t *values_dev, const int64_t *bins_dev /* or NULL */, int64_t lo,
+                         int64_t hi, int q, uint64_t *out_words_dev /* [n_nodes] */, void *stream);
+
 /* ---- the hybrid re-rank with both branches on the device.  QueryEngine.search (query/engine.py:222-260) hands
  * HybridRanker.rank_results a graph context AND the vector hits; crh_rerank_vector above covers lists of vector hits only.  The
  * three entry points below turn the BFS lists of crh_graph_list into graph candidates and rank them together with the hits. */
