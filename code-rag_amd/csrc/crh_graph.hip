@@ -23,6 +23,11 @@
 //
 // Personalised PageRank over the same CSRs stands behind the BFS kernels: k_ppr_inv, k_ppr_seed, k_ppr_step (one
 // launch per step, pull form, sums in list order), k_ppr_bins / k_ppr_bins_exclude, k_ppr_order.
+//
+// Chains in full read the levels of a BFS: k_sigma_init / k_sigma_level (the number of shortest chains per node
+// and query, saturating u64, one launch per level), k_graph_chains (one wave unranks one chain), k_between_meet / k_between_out
+// (the nodes on a way from one set to another); k_graph_sources<true> / k_graph_level<true> are the BFS with an avoided node
+// per query.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -69,8 +74,10 @@ struct SourceArgs {
     int64_t n_nodes;
     u64 *level0;
     u64 *active0;
+    const u64 *avoid;                         // AVOID only: bit q at v = query q never enters v
 };
 
+template <bool AVOID>
 __global__ __launch_bounds__(kGraphThreads) void k_graph_sources(const SourceArgs a)
 {
     const int64_t total = a.off[a.nq];
@@ -79,6 +86,7 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_sources(const SourceArg
         if (v < 0 || v >= a.n_nodes) continue;                       // (-1: padding; a device list may hold anything)
         int q = 0;
         while (q + 1 < a.nq && a.off[q + 1] <= i) ++q;
+        if (AVOID && ((a.avoid[v] >> q) & 1ull)) continue;           // (an avoided source is no source)
         atomicOr(a.level0 + v, 1ull << q);
         atomicOr(a.active0, 1ull << q);
     }
@@ -95,8 +103,10 @@ struct LevelArgs {
     u64 *active_cur;
     int64_t n;
     u64 qmask;
+    const u64 *avoid;                         // AVOID only
 };
 
+template <bool AVOID>
 __global__ __launch_bounds__(kGraphThreads) void k_graph_level(const LevelArgs a)
 {
     if (*a.active_prev == 0ull) return;                              // (written by the launch before this one: the frontier died)
@@ -106,7 +116,7 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_level(const LevelArgs a
     for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
         const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
         const bool in = u < a.n;
-        const u64 sn = in ? a.seen[u] : ~0ull;
+        const u64 sn = in ? (AVOID ? a.seen[u] | a.avoid[u] : a.seen[u]) : ~0ull;   // (a query that avoids u counts as having seen it)
         const bool want = (~sn & a.qmask) != 0ull;                   // (a node every query has seen already reads no list)
         u64 acc = 0ull;
         for (int c = 0; c < a.ncsr; ++c) {
@@ -132,7 +142,7 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_level(const LevelArgs a
         const u64 nw = acc & ~sn;
         if (nw) {                                                    // (the level was zeroed before the first launch)
             a.next[u] = nw;
-            a.seen[u] = sn | nw;
+            a.seen[u] = AVOID ? a.seen[u] | nw : sn | nw;
         }
         mine |= nw;
     }
@@ -717,6 +727,267 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_node_words(int64_t n, i
     }
 }
 
+// ------------------------------------------------------------------- chains in full: counts, the K first, between
+// Exact integers over the levels of a BFS.  sigma is u64 [n_nodes, QS] in the layout of the PageRank state: lane l of a wave owns
+// node base + l / QS and query l % QS.  Sums SATURATE at 2^64 - 1; every term is >= 0, so min(true sum, 2^64 - 1) is the same in
+// whatever order the terms are added, and a long list may be split over the wave.
+
+__device__ __forceinline__ u64 sat_add(u64 a, u64 b)
+{
+    const u64 s = a + b;
+    return s < a ? ~0ull : s;
+}
+
+__device__ __forceinline__ u64 wave_sat_sum(u64 v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = sat_add(v, shfl64(v, (int)(threadIdx.x & 63) ^ o));
+    return v;
+}
+
+// Level 0, and every other word zeroed: sigma[v][q] = bit q of levels[0][v] for q < nq.
+__global__ __launch_bounds__(kGraphThreads) void k_sigma_init(const u64 *level0, int64_t n, int shift, u64 qmask, u64 *sigma)
+{
+    const int64_t total = n << shift;
+    for (int64_t i = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kGraphThreads)
+        sigma[i] = ((level0[i >> shift] & qmask) >> (i & ((1 << shift) - 1))) & 1ull;
+}
+
+struct SigmaArgs {
+    const int64_t *off;                        // the pull CSR
+    const int32_t *adj;
+    const u64 *cur, *prev;                     // levels[d], levels[d - 1]
+    const u64 *active;                         // &active[d]
+    u64 *sigma;
+    int64_t n;
+    int shift;
+    u64 qmask;                                 // the queries there are: a column from nq on stays 0
+};
+
+// One launch per level d >= 1; a lane owns (node, query) and is the only writer of its entry.  It writes entries of level d
+// and reads entries of level d - 1 only, so one buffer serves.  WIDE (QS = 64): the wave owns one node, loads 64 adjacency
+// entries and their level words at a time and reads one 512-byte row of sigma per neighbour that any wanted query passed
+// through.  Otherwise a lane walks its own list, and a list of CRH_GRAPH_WAVE_DEGREE entries or more is walked by the whole
+// wave for that lane's query.
+template <bool WIDE>
+__global__ __launch_bounds__(kGraphThreads) void k_sigma_level(const SigmaArgs a)
+{
+    if (*a.active == 0ull) return;                                   // (nothing lies at this depth)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int q = lane & ((1 << a.shift) - 1);
+    const int per = 64 >> a.shift;                                   // nodes of a wave
+    const int64_t groups = (a.n + per - 1) / per;
+    for (int64_t w = (int64_t)blockIdx.x * kGraphWaves + wave; w < groups; w += (int64_t)gridDim.x * kGraphWaves) {
+        if (WIDE) {
+            const int64_t u = w;                                     // (w < groups = n)
+            const u64 uw = a.cur[u] & a.qmask;
+            if (uw == 0ull) continue;                                // (the wave's: all lanes leave together)
+            const int64_t b = a.off[u], e = a.off[u + 1];
+            u64 acc = 0ull;
+            for (int64_t i = b; i < e; i += 64) {
+                const bool have = i + lane < e;
+                const int mine = have ? a.adj[i + lane] : 0;
+                const u64 pw = have ? a.prev[mine] & uw : 0ull;
+                u64 m = __ballot(pw != 0ull);
+                while (m) {
+                    const int j = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const int64_t v = __shfl(mine, j);
+                    const u64 pv = shfl64(pw, j);
+                    if ((pv >> lane) & 1ull) acc = sat_add(acc, a.sigma[(v << 6) | lane]);
+                }
+            }
+            if ((uw >> lane) & 1ull) a.sigma[(u << 6) | lane] = acc;
+        } else {
+            const int64_t u = w * per + (lane >> a.shift);
+            const bool mineq = u < a.n && (((a.cur[u] & a.qmask) >> q) & 1ull);
+            int64_t b = 0, e = 0;
+            if (mineq) {
+                b = a.off[u];
+                e = a.off[u + 1];
+            }
+            const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
+            u64 acc = 0ull;
+            if (!wide)
+                for (int64_t i = b; i < e; ++i) {
+                    const int64_t v = a.adj[i];
+                    if ((a.prev[v] >> q) & 1ull) acc = sat_add(acc, a.sigma[(v << a.shift) | q]);
+                }
+            u64 m = __ballot(wide);
+            while (m) {
+                const int src = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
+                const int qq = __shfl(q, src);
+                u64 part = 0ull;
+                for (int64_t i = bb + lane; i < ee; i += 64) {
+                    const int64_t v = a.adj[i];
+                    if ((a.prev[v] >> qq) & 1ull) part = sat_add(part, a.sigma[(v << a.shift) | qq]);
+                }
+                part = wave_sat_sum(part);
+                if (lane == src) acc = part;
+            }
+            if (mineq) a.sigma[(u << a.shift) | q] = acc;
+        }
+    }
+}
+
+struct ChainArgs {
+    const int64_t *off;                        // the pull CSR
+    const int32_t *adj;
+    const u64 *levels, *sigma;
+    int64_t n;
+    int shift, nq, max_hops, K;
+    int32_t host_targets[CRH_GRAPH_MAX_QUERIES];   // by value, as the source offsets of the BFS
+    const int32_t *dev_targets;                // or NULL: host_targets
+    int32_t *out_nodes;                        // [nq][K][max_hops + 1]
+    int32_t *out_len;                          // [nq]
+    u64 *out_count;                            // [nq]
+};
+
+// One wave per (query, rank): unranks chain `rank` in the order of the node sequences read backwards from the target.  A step
+// reads 64 entries of the pull list; an inclusive saturating scan of the qualifying entries' sigma finds the first entry whose
+// running sum exceeds what is left of the rank (rank < K <= 64, so a saturated sum compares as the true one would).
+__global__ __launch_bounds__(kGraphThreads) void k_graph_chains(const ChainArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * kGraphWaves + (threadIdx.x >> 6);
+    if (slot >= (int64_t)a.nq * a.K) return;
+    const int q = (int)(slot / a.K), rank = (int)(slot % a.K);
+    const int64_t t = a.dev_targets ? a.dev_targets[q] : a.host_targets[q];
+    const bool node = t >= 0 && t < a.n;
+    const bool at = node && lane <= a.max_hops && ((a.levels[(int64_t)lane * a.n + t] >> q) & 1ull);
+    const u64 where = __ballot(at);
+    const int depth = where ? __ffsll((long long)where) - 1 : -1;
+    const u64 count = where ? a.sigma[(t << a.shift) | q] : 0ull;
+    if (rank == 0 && lane == 0) {
+        a.out_count[q] = count;
+        a.out_len[q] = depth + 1;
+    }
+    int mine = -1;                                                   // lane l holds the chain's node l, -1 beyond it
+    bool ok = (u64)rank < count;
+    if (ok) {
+        if (lane == depth) mine = (int)t;
+        u64 rem = (u64)rank;
+        int64_t u = t;
+        for (int d = depth; d >= 1 && ok; --d) {
+            const u64 *prev = a.levels + (int64_t)(d - 1) * a.n;
+            const int64_t b = a.off[u], e = a.off[u + 1];
+            int next = -1;
+            for (int64_t i = b; i < e && next < 0; i += 64) {
+                const bool have = i + lane < e;
+                const int v = have ? a.adj[i + lane] : 0;
+                const bool qual = have && ((prev[v] >> q) & 1ull);
+                const u64 s = qual ? a.sigma[((int64_t)v << a.shift) | q] : 0ull;
+                u64 incl = s;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const u64 up = shfl64(incl, lane >= o ? lane - o : lane);
+                    if (lane >= o) incl = sat_add(incl, up);
+                }
+                const u64 hit = __ballot(qual && rem < incl);
+                if (hit) {
+                    const int j = __ffsll((long long)hit) - 1;
+                    const u64 before = j ? shfl64(incl, j - 1) : 0ull;   // (<= rem: exact, never saturated)
+                    rem -= before;
+                    next = __shfl(v, j);
+                } else {
+                    rem -= shfl64(incl, 63);                         // (<= rem likewise)
+                }
+            }
+            if (next < 0) {                                          // (levels and sigma that are not this graph's: no chain, never a wild index)
+                ok = false;
+                break;
+            }
+            if (lane == d - 1) mine = next;
+            u = next;
+        }
+    }
+    if (lane <= a.max_hops) a.out_nodes[slot * (a.max_hops + 1) + lane] = ok ? mine : -1;
+}
+
+struct BetweenArgs {
+    const u64 *fwd, *back;                     // levels of the two searches, [max_hops + 1][n]
+    int64_t n;
+    int max_hops, mode, nq;
+    u64 *meet;                                 // [max_hops + 1]
+    u64 *out;                                  // [n]
+    int32_t *dist;                             // [nq] or NULL
+};
+
+constexpr int kLevels = CRH_GRAPH_MAX_HOPS + 1;
+
+// meet[d] = OR over v and i + j = d of F[i][v] & B[j][v], d <= max_hops: one atomicOr per workgroup and distance.  meet was zeroed.
+__global__ __launch_bounds__(kGraphThreads) void k_between_meet(const BetweenArgs a)
+{
+    __shared__ u64 s_meet[kGraphWaves][kLevels];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 m[kLevels];
+#pragma unroll
+    for (int d = 0; d < kLevels; ++d) m[d] = 0ull;
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < a.n; v += (int64_t)gridDim.x * kGraphThreads) {
+        u64 f[kLevels], bk[kLevels], anyf = 0ull, anyb = 0ull;
+#pragma unroll
+        for (int i = 0; i < kLevels; ++i) {
+            f[i] = i <= a.max_hops ? a.fwd[(int64_t)i * a.n + v] : 0ull;
+            bk[i] = i <= a.max_hops ? a.back[(int64_t)i * a.n + v] : 0ull;
+            anyf |= f[i];
+            anyb |= bk[i];
+        }
+        if ((anyf & anyb) == 0ull) continue;
+#pragma unroll
+        for (int i = 0; i < kLevels; ++i)
+#pragma unroll
+            for (int j = 0; j < kLevels - i; ++j) m[i + j] |= f[i] & bk[j];
+    }
+#pragma unroll
+    for (int d = 0; d < kLevels; ++d) {
+        const u64 w = wave_or(m[d]);
+        if (lane == 0) s_meet[wave][d] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x <= a.max_hops) {
+        u64 all = 0ull;
+        for (int w = 0; w < kGraphWaves; ++w) all |= s_meet[w][threadIdx.x];
+        if (all) atomicOr(a.meet + threadIdx.x, all);
+    }
+}
+
+// out[v] = OR over i + j <= max_hops of F[i][v] & B[j][v] & M[i + j]; M[d] = every query (mode 0) or the queries whose sets
+// first meet at distance d (mode 1).  dist[q] = that distance, -1 when the sets never meet within max_hops.
+__global__ __launch_bounds__(kGraphThreads) void k_between_out(const BetweenArgs a)
+{
+    u64 mask[kLevels], earlier = 0ull;
+    const u64 qmask = a.nq == 64 ? ~0ull : (1ull << a.nq) - 1ull;
+#pragma unroll
+    for (int d = 0; d < kLevels; ++d) {
+        const u64 md = d <= a.max_hops ? a.meet[d] : 0ull;
+        mask[d] = d > a.max_hops ? 0ull : a.mode == 0 ? qmask : md & ~earlier;
+        earlier |= md;
+    }
+    if (a.dist && blockIdx.x == 0 && (int)threadIdx.x < a.nq) {
+        int dq = -1;
+        for (int d = a.max_hops; d >= 0; --d)
+            if ((a.meet[d] >> threadIdx.x) & 1ull) dq = d;
+        a.dist[threadIdx.x] = dq;
+    }
+    for (int64_t v = (int64_t)blockIdx.x * kGraphThreads + threadIdx.x; v < a.n; v += (int64_t)gridDim.x * kGraphThreads) {
+        u64 f[kLevels], bk[kLevels];
+#pragma unroll
+        for (int i = 0; i < kLevels; ++i) {
+            f[i] = i <= a.max_hops ? a.fwd[(int64_t)i * a.n + v] : 0ull;
+            bk[i] = i <= a.max_hops ? a.back[(int64_t)i * a.n + v] : 0ull;
+        }
+        u64 acc = 0ull;
+#pragma unroll
+        for (int i = 0; i < kLevels; ++i)
+#pragma unroll
+            for (int j = 0; j < kLevels - i; ++j) acc |= f[i] & bk[j] & mask[i + j];
+        a.out[v] = acc;
+    }
+}
+
 int graph_alloc(void **p, int64_t bytes)
 {
     *p = nullptr;
@@ -906,25 +1177,30 @@ int crh_graph_set_relation(crh_graph *g, int rel, int64_t n_edges, const int64_t
     return CRH_OK;
 }
 
-int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes, int sources_on_device,
-                  int max_hops, int include_self, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev, void *stream)
+}  // extern "C"
+
+namespace {
+
+// crh_graph_bfs and crh_graph_bfs_avoiding: `avoid` NULL launches the kernels without the avoided-node test.
+int graph_bfs_run(const char *who, crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes, int sources_on_device,
+                  int max_hops, int include_self, const uint64_t *avoid_dev, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev, void *stream)
 {
-    CRH_TRY(graph_check_rel(g, rel, direction, "graph_bfs"));
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_bfs: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_bfs: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
-    if (!src_off_host) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
-    if (src_off_host[0] != 0) return fail(CRH_E_INVALID, "graph_bfs: src_off[0]=%lld, not 0", (long long)src_off_host[0]);
+    CRH_TRY(graph_check_rel(g, rel, direction, who));
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: nq=%d outside 1..%d", who, nq, CRH_GRAPH_MAX_QUERIES);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "%s: max_hops=%d outside 1..%d", who, max_hops, CRH_GRAPH_MAX_HOPS);
+    if (!src_off_host) return fail(CRH_E_INVALID, "%s: NULL pointer", who);
+    if (src_off_host[0] != 0) return fail(CRH_E_INVALID, "%s: src_off[0]=%lld, not 0", who, (long long)src_off_host[0]);
     for (int q = 0; q < nq; ++q)
-        if (src_off_host[q + 1] < src_off_host[q]) return fail(CRH_E_INVALID, "graph_bfs: src_off decreases at query %d", q);
+        if (src_off_host[q + 1] < src_off_host[q]) return fail(CRH_E_INVALID, "%s: src_off decreases at query %d", who, q);
     const int64_t total = src_off_host[nq];
-    if (total > 0 && !src_nodes) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
+    if (total > 0 && !src_nodes) return fail(CRH_E_INVALID, "%s: NULL pointer", who);
     if (!sources_on_device)
         for (int64_t i = 0; i < total; ++i)
             if (src_nodes[i] < -1 || src_nodes[i] >= g->n_nodes)
-                return fail(CRH_E_INVALID, "graph_bfs: source %lld names node %d of %lld", (long long)i, src_nodes[i], (long long)g->n_nodes);
+                return fail(CRH_E_INVALID, "%s: source %lld names node %d of %lld", who, (long long)i, src_nodes[i], (long long)g->n_nodes);
     const int64_t n = g->n_nodes;
     if (n == 0) return CRH_OK;
-    if (!levels_dev || !seen_dev || !active_dev) return fail(CRH_E_INVALID, "graph_bfs: NULL pointer");
+    if (!levels_dev || !seen_dev || !active_dev) return fail(CRH_E_INVALID, "%s: NULL pointer", who);
     DeviceGuard guard(g->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     u64 *levels = reinterpret_cast<u64 *>(levels_dev), *seen = reinterpret_cast<u64 *>(seen_dev), *active = reinterpret_cast<u64 *>(active_dev);
@@ -954,7 +1230,11 @@ int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *s
         sa.n_nodes = n;
         sa.level0 = levels;
         sa.active0 = active;
-        hipLaunchKernelGGL(k_graph_sources, dim3(graph_blocks(total, kGraphThreads)), dim3(kGraphThreads), 0, st, sa);
+        sa.avoid = reinterpret_cast<const u64 *>(avoid_dev);
+        if (avoid_dev)
+            hipLaunchKernelGGL(k_graph_sources<true>, dim3(graph_blocks(total, kGraphThreads)), dim3(kGraphThreads), 0, st, sa);
+        else
+            hipLaunchKernelGGL(k_graph_sources<false>, dim3(graph_blocks(total, kGraphThreads)), dim3(kGraphThreads), 0, st, sa);
     }
     CRH_HIP(hipMemcpyAsync(seen, levels, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
     LevelArgs la{};
@@ -962,17 +1242,41 @@ int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *s
     la.seen = seen;
     la.n = n;
     la.qmask = nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+    la.avoid = reinterpret_cast<const u64 *>(avoid_dev);
     const unsigned blocks = graph_blocks(n, kGraphThreads);
     for (int d = 1; d <= max_hops; ++d) {
         la.front = levels + (int64_t)(d - 1) * n;
         la.next = levels + (int64_t)d * n;
         la.active_prev = active + (d - 1);
         la.active_cur = active + d;
-        hipLaunchKernelGGL(k_graph_level, dim3(blocks), dim3(kGraphThreads), 0, st, la);
+        if (avoid_dev)
+            hipLaunchKernelGGL(k_graph_level<true>, dim3(blocks), dim3(kGraphThreads), 0, st, la);
+        else
+            hipLaunchKernelGGL(k_graph_level<false>, dim3(blocks), dim3(kGraphThreads), 0, st, la);
     }
     if (!include_self) hipLaunchKernelGGL(k_graph_unself, dim3(blocks), dim3(kGraphThreads), 0, st, levels, seen, n);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crh_graph_bfs(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes, int sources_on_device,
+                  int max_hops, int include_self, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev, void *stream)
+{
+    return graph_bfs_run("graph_bfs", g, rel, direction, nq, src_off_host, src_nodes, sources_on_device, max_hops, include_self, nullptr, levels_dev, seen_dev,
+                         active_dev, stream);
+}
+
+int crh_graph_bfs_avoiding(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes, int sources_on_device,
+                           int max_hops, int include_self, const uint64_t *avoid_dev, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev,
+                           void *stream)
+{
+    if (g && g->n_nodes > 0 && !avoid_dev) return fail(CRH_E_INVALID, "graph_bfs_avoiding: NULL pointer");
+    return graph_bfs_run("graph_bfs_avoiding", g, rel, direction, nq, src_off_host, src_nodes, sources_on_device, max_hops, include_self, avoid_dev, levels_dev,
+                         seen_dev, active_dev, stream);
 }
 
 int crh_graph_list(crh_graph *g, int nq, const uint64_t *levels_dev, int max_hops, int first_level, int limit, int32_t *out_nodes_dev,
@@ -1322,6 +1626,130 @@ int crh_graph_node_words(int64_t n_nodes, int mode, const int32_t *values_dev, c
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_graph_node_words, dim3(graph_blocks(n_nodes, kGraphThreads)), dim3(kGraphThreads), 0, st, n_nodes, mode, values_dev, bins_dev, lo, hi, q,
                        reinterpret_cast<u64 *>(out_words_dev));
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+}  // extern "C"
+
+// ---- chains in full
+
+namespace {
+
+// What the chain calls share: a set relation, ALONG or AGAINST, 1..64 queries, 1..16 hops.
+int chains_check(const char *who, crh_graph *g, int rel, int direction, int nq, int max_hops)
+{
+    CRH_TRY(graph_check_rel(g, rel, direction, who));
+    if (direction == CRH_GRAPH_BOTH)
+        return fail(CRH_E_INVALID, "%s: direction is CRH_GRAPH_ALONG or CRH_GRAPH_AGAINST (taken both ways a chain may turn back on itself)", who);
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: nq=%d outside 1..%d", who, nq, CRH_GRAPH_MAX_QUERIES);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "%s: max_hops=%d outside 1..%d", who, max_hops, CRH_GRAPH_MAX_HOPS);
+    return CRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crh_graph_sigma(crh_graph *g, int rel, int direction, int nq, const uint64_t *levels_dev, const uint64_t *active_dev, int max_hops,
+                    uint64_t *sigma_out_dev, void *stream)
+{
+    CRH_TRY(chains_check("graph_sigma", g, rel, direction, nq, max_hops));
+    const int64_t n = g->n_nodes;
+    if (n == 0) return CRH_OK;
+    if (!levels_dev || !active_dev || !sigma_out_dev) return fail(CRH_E_INVALID, "graph_sigma: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const u64 *levels = reinterpret_cast<const u64 *>(levels_dev);
+    SigmaArgs a{};
+    const int64_t *off[2];
+    const int32_t *adj[2];
+    (void)graph_pull(g, rel, direction, off, adj);
+    a.off = off[0];
+    a.adj = adj[0];
+    a.sigma = reinterpret_cast<u64 *>(sigma_out_dev);
+    a.n = n;
+    a.shift = ppr_shift(nq);
+    a.qmask = nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+    hipLaunchKernelGGL(k_sigma_init, dim3(graph_blocks(n << a.shift, kGraphThreads)), dim3(kGraphThreads), 0, st, levels, n, a.shift, a.qmask, a.sigma);
+    const unsigned blocks = graph_blocks(ceil_div(n, 64 >> a.shift), kGraphWaves);
+    for (int d = 1; d <= max_hops; ++d) {
+        a.cur = levels + (int64_t)d * n;
+        a.prev = levels + (int64_t)(d - 1) * n;
+        a.active = reinterpret_cast<const u64 *>(active_dev) + d;
+        if (a.shift == 6)
+            hipLaunchKernelGGL(k_sigma_level<true>, dim3(blocks), dim3(kGraphThreads), 0, st, a);
+        else
+            hipLaunchKernelGGL(k_sigma_level<false>, dim3(blocks), dim3(kGraphThreads), 0, st, a);
+    }
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_chains(crh_graph *g, int rel, int direction, int nq, const uint64_t *levels_dev, const uint64_t *sigma_dev, int max_hops,
+                     const int32_t *targets, int targets_on_device, int K, int32_t *out_nodes_dev, int32_t *out_len_dev, uint64_t *out_count_dev,
+                     void *stream)
+{
+    CRH_TRY(chains_check("graph_chains", g, rel, direction, nq, max_hops));
+    if (K < 1 || K > CRH_GRAPH_MAX_CHAINS) return fail(CRH_E_INVALID, "graph_chains: K=%d outside 1..%d", K, CRH_GRAPH_MAX_CHAINS);
+    if (!targets) return fail(CRH_E_INVALID, "graph_chains: NULL pointer");
+    const int64_t n = g->n_nodes;
+    if (!targets_on_device)
+        for (int q = 0; q < nq; ++q)
+            if (targets[q] < -1 || targets[q] >= n) return fail(CRH_E_INVALID, "graph_chains: target %d names node %d of %lld", q, targets[q], (long long)n);
+    if (n == 0) return CRH_OK;
+    if (!levels_dev || !sigma_dev || !out_nodes_dev || !out_len_dev || !out_count_dev) return fail(CRH_E_INVALID, "graph_chains: NULL pointer");
+    DeviceGuard guard(g->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ChainArgs a{};
+    const int64_t *off[2];
+    const int32_t *adj[2];
+    (void)graph_pull(g, rel, direction, off, adj);
+    a.off = off[0];
+    a.adj = adj[0];
+    a.levels = reinterpret_cast<const u64 *>(levels_dev);
+    a.sigma = reinterpret_cast<const u64 *>(sigma_dev);
+    a.n = n;
+    a.shift = ppr_shift(nq);
+    a.nq = nq;
+    a.max_hops = max_hops;
+    a.K = K;
+    if (targets_on_device)
+        a.dev_targets = targets;
+    else
+        for (int q = 0; q < nq; ++q) a.host_targets[q] = targets[q];
+    a.out_nodes = out_nodes_dev;
+    a.out_len = out_len_dev;
+    a.out_count = reinterpret_cast<u64 *>(out_count_dev);
+    hipLaunchKernelGGL(k_graph_chains, dim3((unsigned)ceil_div((int64_t)nq * K, kGraphWaves)), dim3(kGraphThreads), 0, st, a);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int crh_graph_between(int64_t n_nodes, int nq, const uint64_t *levels_fwd_dev, const uint64_t *levels_back_dev, int max_hops, int mode, uint64_t *meet_dev,
+                      uint64_t *out_words_dev, int32_t *out_dist_dev, void *stream)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_between: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_between: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_between: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    if (mode != CRH_GRAPH_BETWEEN_ANY && mode != CRH_GRAPH_BETWEEN_SHORTEST) return fail(CRH_E_INVALID, "graph_between: mode=%d is none of CRH_GRAPH_BETWEEN_*", mode);
+    if (n_nodes == 0) return CRH_OK;
+    if (!levels_fwd_dev || !levels_back_dev || !meet_dev || !out_words_dev) return fail(CRH_E_INVALID, "graph_between: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    BetweenArgs a{};
+    a.fwd = reinterpret_cast<const u64 *>(levels_fwd_dev);
+    a.back = reinterpret_cast<const u64 *>(levels_back_dev);
+    a.n = n_nodes;
+    a.max_hops = max_hops;
+    a.mode = mode;
+    a.nq = nq;
+    a.meet = reinterpret_cast<u64 *>(meet_dev);
+    a.out = reinterpret_cast<u64 *>(out_words_dev);
+    a.dist = out_dist_dev;
+    CRH_HIP(hipMemsetAsync(a.meet, 0, (size_t)(max_hops + 1) * 8, st));
+    const unsigned blocks = graph_blocks(n_nodes, kGraphThreads);
+    hipLaunchKernelGGL(k_between_meet, dim3(blocks), dim3(kGraphThreads), 0, st, a);
+    hipLaunchKernelGGL(k_between_out, dim3(blocks), dim3(kGraphThreads), 0, st, a);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }

@@ -44,6 +44,9 @@ GRAPH_DIRECTIONS = {"callees": GRAPH_ALONG, "callers": GRAPH_AGAINST, "both": GR
 GRAPH_SCC_WORK_EXTRA = 32   # CRH_GRAPH_SCC_WORK_EXTRA: int32 words of crh_graph_scc's work array beyond one per node
 GRAPH_WORDS = {"in_cycle": 0, "same_component": 1, "range": 2}    # CRH_GRAPH_WORDS_*: the conditions of crh_graph_node_words
 GRAPH_PPR_MAX_STEPS = 64    # CRH_GRAPH_PPR_MAX_STEPS: steps of one crh_graph_ppr
+GRAPH_MAX_CHAINS = 64       # CRH_GRAPH_MAX_CHAINS: chains per query of one crh_graph_chains
+GRAPH_SATURATED = 2 ** 64 - 1   # a chain count of crh_graph_sigma that means "at least that many"
+GRAPH_BETWEEN = {"any": 0, "shortest": 1}   # CRH_GRAPH_BETWEEN_*: the modes of crh_graph_between
 FACET_MAX_ENTRIES = 2 ** 26  # bin entries (queries x bins) one semantic facet call may ask of a shard set: 512 MB of int64 per slab
 
 # every symbol include/coderag_hip.h declares (tests check the library exports all of them)
@@ -76,6 +79,7 @@ EXPORTS = (
     "crh_graph_node_rows", "crh_graph_candidates", "crh_rerank_hybrid",
     "crh_graph_ppr", "crh_graph_ppr_bins", "crh_graph_ppr_order",
     "crh_graph_scc", "crh_graph_scc_bins", "crh_graph_layers", "crh_graph_node_words",
+    "crh_graph_sigma", "crh_graph_chains", "crh_graph_between", "crh_graph_bfs_avoiding",
 )
 # exported by lib/libcoderag_hip_debug.so only (same sources built with -DCRH_ENABLE_DEBUG; tools/ and kernel tests)
 DEBUG_EXPORTS = ("crh_debug_gemm_variant", "crh_debug_read_ceiling", "crh_debug_i8_move", "crh_debug_i8_intervals",
@@ -274,6 +278,10 @@ def _bind(path: Path, debug: bool) -> C.CDLL:
     L.crh_graph_scc_bins.argtypes = [i64, vp, vp, i64, vp, vp]
     L.crh_graph_layers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.crh_graph_node_words.argtypes = [i64, i32, vp, vp, i64, i64, i32, vp, vp]
+    L.crh_graph_sigma.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp]
+    L.crh_graph_chains.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.crh_graph_between.argtypes = [i64, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.crh_graph_bfs_avoiding.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.crh_graph_candidates.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.crh_rerank_hybrid.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32, i32, i32, i32, i32,
                                     vp, vp, vp, vp, vp, vp, vp]
@@ -1395,12 +1403,17 @@ class Graph:
         self.last = None      # (nq, max_hops) of the last bfs
         self.ppr_work = None  # f32 [4, n_nodes, QS]: p0, two contribution planes, the scores of the last ppr
         self.ppr_last = None  # (nq, QS) of the last ppr
+        self.levels_back = self.seen_back = self.active_back = None   # the second workspace: bfs(..., back=True)
+        self.last_back = None   # (nq, max_hops) of the last bfs there
+        self.sigma_buf = None   # u64 [n_nodes, QS] as int64: the chain counts of the last sigma
+        self.sigma_last = None  # (nq, max_hops, the tensor it wrote)
 
     def close(self) -> None:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.crh_graph_destroy(self._h)
             self._h = None
             self.levels = self.seen = self.active = self.ppr_work = None
+            self.levels_back = self.seen_back = self.active_back = self.sigma_buf = self.sigma_last = None
 
     __del__ = close
 
@@ -1434,11 +1447,24 @@ class Graph:
             self.seen = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
             self.active = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
 
-    def bfs(self, rel: int, direction, sources, max_hops: int, include_self: bool = False, stream: int = 0):
+    def _workspace_back(self, max_hops: int):
+        """The second workspace: the search from the other end, which ``between`` reads beside the first."""
+        import torch
+        dev = f"cuda:{self.device}"
+        if self.levels_back is None or int(self.levels_back.shape[0]) < max_hops + 1:
+            self.levels_back = None                                    # (released before the larger one is taken)
+            self.levels_back = torch.empty((max_hops + 1, self.n_nodes), dtype=torch.int64, device=dev)
+        if self.seen_back is None:
+            self.seen_back = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
+            self.active_back = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
+
+    def bfs(self, rel: int, direction, sources, max_hops: int, include_self: bool = False, stream: int = 0, back: bool = False, avoid=None):
         """``crh_graph_bfs`` from up to ``GRAPH_MAX_QUERIES`` source sets: ``sources`` is an iterable of iterables of node ids
         (host), or an int32 device tensor [nq, k] whose rows are the sets (-1: padding), complete on ``stream``.  Returns
         ``(levels [max_hops + 1, n_nodes], seen [n_nodes], active [max_hops + 1])``: int64 device tensors holding the u64
-        words, views of the handle's workspace.  Only enqueues."""
+        words, views of the handle's workspace.  Only enqueues.  ``back``: the search runs in the SECOND workspace and leaves
+        the first (and what ``list`` / ``path`` / ``sigma`` read by default) alone.  ``avoid`` (:meth:`bfs_avoiding`): an
+        int64 device tensor [n_nodes], bit q at v = query q never enters v."""
         max_hops = int(max_hops)
         on_dev = _is_dev(sources)
         if on_dev:
@@ -1451,13 +1477,180 @@ class Graph:
             off, nodes = graph_sources(sources)
             nq = off.size - 1
         hops = max_hops if 1 <= max_hops <= GRAPH_MAX_HOPS else 1           # (a max_hops the library refuses allocates one level)
-        self._workspace(hops)
+        if back:
+            self._workspace_back(hops)
+            levels, seen, active = self.levels_back, self.seen_back, self.active_back
+        else:
+            self._workspace(hops)
+            levels, seen, active = self.levels, self.seen, self.active
         Graph.bfs_calls += 1
-        check(lib().crh_graph_bfs(self._handle(), int(rel), graph_direction(direction), nq, off.ctypes.data,
-                                  _ptr(nodes) if int(off[-1]) else None, on_dev, max_hops, int(bool(include_self)),
-                                  _ptr(self.levels), _ptr(self.seen), _ptr(self.active), stream))
-        self.last = (nq, max_hops)
-        return self.levels[: max_hops + 1], self.seen, self.active[: max_hops + 1]
+        head = (self._handle(), int(rel), graph_direction(direction), nq, off.ctypes.data, _ptr(nodes) if int(off[-1]) else None, on_dev, max_hops,
+                int(bool(include_self)))
+        if avoid is None:
+            check(lib().crh_graph_bfs(*head, _ptr(levels), _ptr(seen), _ptr(active), stream))
+        else:
+            self._node_array(avoid, "int64", "avoid")
+            check(lib().crh_graph_bfs_avoiding(*head, _ptr(avoid), _ptr(levels), _ptr(seen), _ptr(active), stream))
+        if back:
+            self.last_back = (nq, max_hops)
+        else:
+            self.last = (nq, max_hops)
+        return levels[: max_hops + 1], seen, active[: max_hops + 1]
+
+    # -- chains in full
+    def avoid_words(self, nodes):
+        """The ``avoid`` words of :meth:`bfs_avoiding` from one node per query (a host sequence, -1: the query avoids nothing):
+        an int64 device tensor [n_nodes] with bit q set at ``nodes[q]``."""
+        import torch
+        nodes = np.asarray(list(nodes), np.int64).reshape(-1)
+        if nodes.size > GRAPH_MAX_QUERIES or (nodes.size and (nodes.min() < -1 or nodes.max() >= self.n_nodes)):
+            raise NativeError(E_INVALID, f"avoid: at most {GRAPH_MAX_QUERIES} nodes of 0..{self.n_nodes - 1} (or -1)")
+        dev = f"cuda:{self.device}"
+        out = torch.zeros((self.n_nodes,), dtype=torch.int64, device=dev)
+        keep = np.flatnonzero(nodes >= 0)
+        if keep.size:
+            bits = (np.uint64(1) << keep.astype(np.uint64)).view(np.int64)
+            out.index_add_(0, torch.from_numpy(nodes[keep]).to(dev), torch.from_numpy(bits).to(dev))   # (distinct bits: the sum is the OR)
+        return out
+
+    def bfs_avoiding(self, rel: int, direction, sources, max_hops: int, avoid, include_self: bool = False, stream: int = 0, back: bool = False):
+        """``crh_graph_bfs_avoiding``: :meth:`bfs` in which query q never enters the nodes whose ``avoid`` word carries bit q
+        (an avoided source is no source).  ``avoid``: an int64 device tensor [n_nodes], or one node per query as
+        :meth:`avoid_words` takes them."""
+        if not _is_dev(avoid):
+            avoid = self.avoid_words(avoid)
+        return self.bfs(rel, direction, sources, max_hops, include_self=include_self, stream=stream, back=back, avoid=avoid)
+
+    def seen_bits(self, nodes, seen=None) -> np.ndarray:
+        """Bit q of ``seen[nodes[q]]`` per query q (host bool [len(nodes)]; False for -1): gathered on the device, so the host
+        sees the finished bits only.  ``seen``: default the last :meth:`bfs`'s.  Waits for the device."""
+        import torch
+        nodes = np.asarray(list(nodes), np.int64).reshape(-1)
+        seen = self.seen if seen is None else seen
+        if seen is None or nodes.size > GRAPH_MAX_QUERIES or (nodes.size and (nodes.min() < -1 or nodes.max() >= self.n_nodes)):
+            raise NativeError(E_INVALID, f"seen_bits: a bfs first, then at most {GRAPH_MAX_QUERIES} nodes of 0..{self.n_nodes - 1} (or -1)")
+        if not nodes.size or not self.n_nodes:
+            return np.zeros((nodes.size,), bool)
+        at = torch.from_numpy(np.maximum(nodes, 0)).to(seen.device)
+        got = (seen.index_select(0, at) >> torch.arange(nodes.size, device=seen.device)) & 1
+        return (got.cpu().numpy() != 0) & (nodes >= 0)
+
+    def _levels_arg(self, levels, nq, max_hops, what: str, back: bool = False):
+        if levels is None:
+            last = self.last_back if back else self.last
+            if last is None:
+                raise NativeError(E_INVALID, f"{what}: no bfs has run on this graph")
+            levels = self.levels_back if back else self.levels
+            nq = last[0] if nq is None else nq
+            max_hops = last[1] if max_hops is None else max_hops
+        if nq is None or max_hops is None:
+            raise NativeError(E_INVALID, f"{what}: levels of its own need nq and max_hops")
+        _typed(levels, "int64", "levels")
+        hops = int(max_hops) if 1 <= int(max_hops) <= GRAPH_MAX_HOPS else 1   # (a max_hops the library refuses needs one level)
+        if not _is_dev(levels) or levels.ndim != 2 or int(levels.shape[0]) < hops + 1 or int(levels.shape[1]) != self.n_nodes:
+            raise NativeError(E_INVALID, f"levels must be a device tensor of at least {hops + 1} levels x {self.n_nodes} nodes")
+        return levels, int(nq), int(max_hops)
+
+    @staticmethod
+    def _qs(nq: int) -> int:
+        qs = 1
+        while qs < min(max(nq, 1), GRAPH_MAX_QUERIES):
+            qs *= 2
+        return qs
+
+    def sigma(self, rel: int, direction, nq: int | None = None, max_hops: int | None = None, levels=None, active=None, out=None, stream: int = 0):
+        """``crh_graph_sigma`` over the last BFS (same ``rel`` and ``direction``, ``include_self=True``; or ``levels`` and
+        ``active`` with ``nq`` and ``max_hops``): the number of SHORTEST chains from source set q to every node, saturating at
+        ``GRAPH_SATURATED``.  Returns an int64 device tensor [n_nodes, QS] holding the u64 words (QS: the power of two >= nq;
+        the columns from nq on are 0), the handle's own unless ``out`` is given.  Only enqueues."""
+        import torch
+        if (levels is None) != (active is None):
+            raise NativeError(E_INVALID, "sigma: levels and active come together")
+        active = self.active if active is None else active
+        levels, nq, max_hops = self._levels_arg(levels, nq, max_hops, "sigma")
+        _typed(active, "int64", "active")
+        if not _is_dev(active) or int(active.numel()) < min(max(max_hops, 1), GRAPH_MAX_HOPS) + 1:
+            raise NativeError(E_INVALID, "active must be a device tensor of max_hops + 1 words")
+        qs = self._qs(nq)
+        if out is None:
+            if self.sigma_buf is None or int(self.sigma_buf.numel()) < self.n_nodes * qs:
+                self.sigma_buf = None                                  # (released before the larger one is taken)
+                self.sigma_buf = torch.empty((max(self.n_nodes * qs, 1),), dtype=torch.int64, device=f"cuda:{self.device}")
+            out = self.sigma_buf[: self.n_nodes * qs].view(self.n_nodes, qs)
+        _out(out, "int64", "out", (self.n_nodes, qs))
+        check(lib().crh_graph_sigma(self._handle(), int(rel), graph_direction(direction), nq, _ptr(levels), _ptr(active), max_hops, _ptr(out), stream))
+        self.sigma_last = (nq, max_hops, out)
+        return out
+
+    def chains(self, rel: int, direction, targets, k: int, nq: int | None = None, max_hops: int | None = None, levels=None, sigma=None, out=None,
+               stream: int = 0):
+        """``crh_graph_chains``: the ``k`` (1..``GRAPH_MAX_CHAINS``) first shortest chains of every query to its target, in the
+        order of the node ids read backwards from the target.  ``targets``: one node per query, a host sequence (-1: none) or
+        an int32 device tensor [nq].  ``sigma``: default the last :meth:`sigma`'s.  Returns device tensors ``(nodes int32 [nq,
+        k, max_hops + 1]`` from a source to the target, padding -1, ``length int32 [nq]`` (0: not reached), ``count int64
+        [nq])`` -- the u64 words: ``count.cpu().numpy().view(np.uint64)``; ``out``: three tensors to write instead."""
+        import torch
+        levels, nq, max_hops = self._levels_arg(levels, nq, max_hops, "chains")
+        if sigma is None:
+            if self.sigma_last is None:
+                raise NativeError(E_INVALID, "chains: no sigma has run on this graph")
+            sigma = self.sigma_last[2]
+        _out(sigma, "int64", "sigma", (self.n_nodes, self._qs(nq)))
+        on_dev = _is_dev(targets)
+        if on_dev:
+            _out(targets, "int32", "targets", (nq,))
+        else:
+            targets = np.ascontiguousarray(np.asarray(list(targets), np.int64).reshape(-1).astype(np.int32))
+            if targets.size != nq:
+                raise NativeError(E_INVALID, f"chains: {targets.size} targets for {nq} queries")
+        kk = int(k) if 1 <= int(k) <= GRAPH_MAX_CHAINS else 1               # (a k the library refuses allocates one chain)
+        hops = max_hops if 1 <= max_hops <= GRAPH_MAX_HOPS else 1
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = (torch.empty((nq, kk, hops + 1), dtype=torch.int32, device=dev), torch.empty((nq,), dtype=torch.int32, device=dev),
+                   torch.empty((nq,), dtype=torch.int64, device=dev))
+            if self.n_nodes == 0:
+                out[0].fill_(-1), out[1].zero_(), out[2].zero_()
+        nodes, length, count = out
+        _out(nodes, "int32", "out nodes", (nq, kk, hops + 1))
+        _out(length, "int32", "out length", (nq,))
+        _out(count, "int64", "out count", (nq,))
+        for t in out:
+            if not _is_dev(t):
+                raise NativeError(E_INVALID, "chains: out takes device tensors")
+        check(lib().crh_graph_chains(self._handle(), int(rel), graph_direction(direction), nq, _ptr(levels), _ptr(sigma), max_hops, _ptr(targets),
+                                     on_dev, int(k), _ptr(nodes), _ptr(length), _ptr(count), stream))
+        return nodes, length, count
+
+    def between(self, levels_back=None, mode="any", nq: int | None = None, max_hops: int | None = None, levels=None, out=None, dist=None,
+                stream: int = 0):
+        """``crh_graph_between``: the nodes between the source sets of the last :meth:`bfs` and the target sets of the last
+        ``bfs(..., back=True)`` in the opposite direction (both ``include_self=True``, the same ``max_hops``; or ``levels`` /
+        ``levels_back`` with ``nq`` and ``max_hops``).  ``mode`` ``"any"``: on a WALK of at most ``max_hops`` edges from the one
+        set to the other; ``"shortest"``: on a shortest chain.  Returns ``(words, dist)``: int64 ``seen``-style words [n_nodes]
+        (bit q; :meth:`row_words` takes them as ``seen=``) and int32 [nq] = the distance of the sets, -1 where they do not
+        meet.  Both are tensors of the call's own (``out`` / ``dist``: tensors to write): no level is overwritten."""
+        import torch
+        if mode not in GRAPH_BETWEEN and mode not in GRAPH_BETWEEN.values():
+            raise NativeError(E_INVALID, f"between mode {mode!r} is not one of {sorted(GRAPH_BETWEEN)}")
+        mode = GRAPH_BETWEEN.get(mode, mode)
+        if levels is None and levels_back is None and self.last is not None and self.last_back is not None and self.last != self.last_back:
+            raise NativeError(E_INVALID, f"between: the two searches ran with (nq, max_hops) = {self.last} and {self.last_back}")
+        levels, nq, max_hops = self._levels_arg(levels, nq, max_hops, "between")
+        levels_back, _, _ = self._levels_arg(levels_back, nq, max_hops, "between", back=True)
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
+        self._node_array(out, "int64", "out")
+        if dist is None:
+            dist = torch.full((nq,), -1, dtype=torch.int32, device=dev)
+        _out(dist, "int32", "dist", (nq,))
+        if not _is_dev(dist):
+            raise NativeError(E_INVALID, "between: dist takes a device tensor")
+        meet = torch.empty((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
+        use_device(self.device)
+        check(lib().crh_graph_between(self.n_nodes, nq, _ptr(levels), _ptr(levels_back), max_hops, int(mode), _ptr(meet), _ptr(out), _ptr(dist), stream))
+        return out, dist
 
     def list(self, limit: int, first_level: int = 1, nq: int | None = None, max_hops: int | None = None, levels=None, stream: int = 0):
         """``crh_graph_list`` over the last BFS's levels (or ``levels``, with ``nq`` and ``max_hops``): ``(nodes int32 [nq, limit],

@@ -11,6 +11,7 @@ MAX_RELATIONS = 8          # CRH_GRAPH_MAX_RELATIONS: named relations one collec
 DIRECTIONS = ("callers", "callees", "both")
 FILTER_WORDS = {"callers_of": "callers", "callees_of": "callees", "connected_to": "both"}    # the filter's key -> the direction of travel
 STRUCTURE_WORDS = ("in_cycle", "same_cycle_as", "depth", "height")    # filter keys on the graph as a whole
+BETWEEN_WORD = "between"   # the filter key of the nodes on a way from one node set to another
 
 
 def number_edges(edges: Iterable, code: dict, names: list) -> np.ndarray:

@@ -36,7 +36,7 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                               matches: str | None = None, fuzzy: str | None = None, edits: int | None = None,
                               within_callers_of: str | list[str] | None = None, within_callees_of: str | list[str] | None = None,
                               graph_hops: int | None = None, rank: str | None = None, entities: list[str] | None = None,
-                              intent: str | None = None, in_cycle: bool | None = None) -> ToolResult:
+                              intent: str | None = None, in_cycle: bool | None = None, between: list | None = None) -> ToolResult:
         logger.info(f"[Tool:SemanticSearch] Query: '{query}'")
         try:
             searcher = vector_searcher_factory()
@@ -87,8 +87,8 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                        ("contains", contains or None), ("contains_case", contains_case if contains or matches or fuzzy else None),
                                        ("matches", matches or None), ("fuzzy", fuzzy or None), ("edits", edits if fuzzy else None),
                                        ("within_callers_of", within_callers_of or None), ("within_callees_of", within_callees_of or None),
-                                       ("graph_hops", graph_hops if within_callers_of or within_callees_of else None),
-                                       ("in_cycle", True if in_cycle else None)) if v is not None}   # (only when asked for)
+                                       ("graph_hops", graph_hops if within_callers_of or within_callees_of or between else None),
+                                       ("in_cycle", True if in_cycle else None), ("between", tuple(between) if between else None)) if v is not None}   # (only when asked for)
             hits = await searcher.search_code(query=query, limit=limit, entity_type=entity_type, **extra)
             rows = []
             for h in hits:
@@ -156,7 +156,11 @@ def create_semantic_search_tool(vector_searcher_factory: Callable[[], Any]) -> d
                                                                    "calls is searched ('timeout handling, but only under main')",
                                   "required": False},
             "graph_hops": {"type": "integer", "description": "With within_callers_of / within_callees_of: how many calls away code may "
-                                                             "be, 1..16 (default: 3)", "required": False},
+                                                             "be, 1..16 (default: 3); with between: how long a way may be (default: 8)",
+                           "required": False},
+            "between": {"type": "array", "description": "Two function names [a, b] (either may be a list of names): only code that lies on "
+                                                        "a way of calls from a to b is searched ('retry handling, but only between "
+                                                        "handle_request and db.execute')", "required": False},
             "in_cycle": {"type": "boolean", "description": "true: only code that lies in a call cycle is searched -- recursive functions "
                                                            "and groups of functions that call each other", "required": False},
             "rank": {"type": "string", "description": "'vector' (the default: the plain matches), 'hybrid': the named entities' graph "
@@ -193,9 +197,19 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
                 got = await searcher.find_layers(names=name or None, match="suffix")
                 return ToolResult(success=True, data=got["nodes"], message=f"The call graph has {got['layers']} layer(s); by depth below the entry points "
                                   f"they hold {got['histogram']['depth']} functions, by height above the leaves {got['histogram']['height']}.")
+            if op == "chains":                   # every shortest chain, and what none of them avoids
+                if not name or not target:
+                    raise ValueError("op 'chains' needs a name and a target")
+                got = await searcher.find_call_chains(name, target, **({} if max_hops is None else {"max_hops": max_hops}), limit=min(limit, 64))
+                if not got["count"]:
+                    message = f"No chain of calls from '{name}' to '{target}' within {8 if max_hops is None else max_hops} calls."
+                else:
+                    message = (f"'{name}' reaches '{target}' by {'at least ' if got['saturated'] else ''}{got['count']} shortest chain(s) of {got['length']} call(s); "
+                               f"{len(got['chains'])} listed. " + (f"Every way passes {', '.join(got['must_pass'])}." if got["must_pass"] else "No function lies on every way."))
+                return ToolResult(success=True, data=got["chains"], message=message)
             if op is not None:
                 if op != "important_near":
-                    raise ValueError(f"op {op!r} is not one of 'important_near', 'cycles', 'layers'")
+                    raise ValueError(f"op {op!r} is not one of 'important_near', 'cycles', 'layers', 'chains'")
                 if target or max_hops is not None:
                     raise ValueError("op 'important_near' takes name and limit only")
                 nodes = await searcher.find_important_near(name, limit=limit)
@@ -226,7 +240,7 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
                                                       "'cycles'; optional for op 'layers')", "required": True},
             "relation": {"type": "string", "description": "'callers' (the default: what calls it), 'callees' (what it calls) or 'chain' "
                                                           "(one shortest chain of calls from name to target)", "required": False},
-            "target": {"type": "string", "description": "With relation 'chain': the qualified name to reach", "required": False},
+            "target": {"type": "string", "description": "With relation 'chain' or op 'chains': the qualified name to reach", "required": False},
             "max_hops": {"type": "integer", "description": "How many calls away to look, 1..16 (default: 3; 8 for a chain)", "required": False},
             "limit": {"type": "integer", "description": "Maximum number of callers / callees listed, nearest first (default: 50)", "required": False},
             "op": {"type": "string", "description": "'important_near': instead of a walk, rank the code around name by a random walk with "
@@ -234,7 +248,9 @@ def create_code_graph_tool(vector_searcher_factory: Callable[[], Any]) -> dict[s
                                                     "best first.  'cycles': the groups of functions that call each other in a circle "
                                                     "(recursion, mutual recursion), largest first; takes limit only.  'layers': how deep "
                                                     "below the entry points and how high above the leaf helpers name lies (without a name: "
-                                                    "how many functions each layer holds)", "required": False},
+                                                    "how many functions each layer holds).  'chains': with target, HOW MANY shortest chains "
+                                                    "of calls lead from name to target, the first `limit` of them, and the functions every "
+                                                    "way of at most max_hops calls passes", "required": False},
         },
     }
 

@@ -270,6 +270,43 @@ class GraphStructureSpec(NamedTuple):
     match: str
 
 
+class GraphBetweenSpec(NamedTuple):
+    """A ``{"between": [source or names, target or names], "hops": 8, "shortest": False, ...}`` filter value, checked (DESIGN.md
+    3.32): the distinct names of either end sorted, the hop budget, whether only shortest chains count, the relation and how
+    names resolve."""
+    sources: tuple
+    targets: tuple
+    hops: int
+    shortest: bool
+    relation: str
+    match: str
+
+
+def _graph_between_spec(spec) -> GraphBetweenSpec:
+    word = graph_mod.BETWEEN_WORD
+    unknown = [k for k in spec if k not in (word, "hops", "shortest", "relation", "match")]
+    if unknown:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: {word} stands alone beside any of hops, shortest, relation, match (got {sorted(map(str, spec))})")
+    ends = spec[word]
+    if not isinstance(ends, (list, tuple)) or len(ends) != 2:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: {word} takes [source or names, target or names], not {ends!r}")
+    sides = []
+    for names in ends:
+        names = [names] if isinstance(names, str) else list(names) if isinstance(names, _COLLECTIONS) else None
+        if not names or not all(isinstance(n, str) for n in names):
+            raise ValueError(f"filter key {GRAPH_KEY!r}: either end of {word} is a node name or a non-empty list of them, not {ends!r}")
+        sides.append(tuple(sorted(set(names))))
+    hops, shortest = spec.get("hops", 8), spec.get("shortest", False)
+    if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= int(hops) <= ffi.GRAPH_MAX_HOPS:
+        raise ValueError(f"filter key {GRAPH_KEY!r}: hops must be an int in 1..{ffi.GRAPH_MAX_HOPS}, not {hops!r}")
+    if not isinstance(shortest, bool):
+        raise ValueError(f"filter key {GRAPH_KEY!r}: shortest is True or False, not {shortest!r}")
+    relation, match = spec.get("relation", "calls"), spec.get("match", "exact")
+    if not isinstance(relation, str) or match not in ("exact", "suffix"):
+        raise ValueError(f"filter key {GRAPH_KEY!r}: relation is a string and match 'exact' or 'suffix' (got {relation!r}, {match!r})")
+    return GraphBetweenSpec(sides[0], sides[1], int(hops), shortest, relation, match)
+
+
 def _graph_structure_spec(spec) -> GraphStructureSpec:
     kinds = [k for k in spec if k in graph_mod.STRUCTURE_WORDS]
     allowed = ("relation", "match") if kinds == ["same_cycle_as"] else ("relation",)
@@ -305,10 +342,12 @@ def _graph_structure_spec(spec) -> GraphStructureSpec:
     return GraphStructureSpec(kind, arg, relation, match)
 
 
-def graph_spec(spec) -> "GraphSpec | GraphStructureSpec":
+def graph_spec(spec) -> "GraphSpec | GraphStructureSpec | GraphBetweenSpec":
     """The value of a ``"graph"`` filter entry as a :class:`GraphSpec`; ``ValueError`` naming the key for anything else."""
     if not isinstance(spec, Mapping):
         raise ValueError(f"filter key {GRAPH_KEY!r} takes a mapping {{'callers_of' | 'callees_of' | 'connected_to': name or list of names, 'hops': 1..{ffi.GRAPH_MAX_HOPS}}}, not {spec!r}")
+    if graph_mod.BETWEEN_WORD in spec:
+        return _graph_between_spec(spec)
     if any(k in graph_mod.STRUCTURE_WORDS for k in spec):
         return _graph_structure_spec(spec)
     unknown = [k for k in spec if k not in _GRAPH_WORDS]
@@ -783,6 +822,8 @@ class _Collection:
         what they were computed from; every result lives in buffers of its own under a tag of its own."""
         if isinstance(spec, GraphStructureSpec):
             return self._graph_structure_condition(spec, negate)
+        if isinstance(spec, GraphBetweenSpec):
+            return self._graph_between_condition(spec, negate)
         graph, rel = self._graph_ready(spec.relation)
         ids, _ = graph_mod.resolve(spec.names, self._graph_code, self._graph_names, spec.match)
         if not ids:
@@ -807,6 +848,22 @@ class _Collection:
                 self._graph_cache.pop(next(iter(self._graph_cache)))     # (the least recently used: hits are re-inserted below)
         self._graph_cache[ck] = hit
         return ffi.RowWords(hit[0], hit[1], negate)
+
+    def _graph_between_condition(self, spec: GraphBetweenSpec, negate: bool) -> "ffi.RowWords | None":
+        """The rows of the nodes that lie on a way of at most ``hops`` edges from the one named set to the other:
+        a BFS along the edges from the sources, one against them from the targets in the second workspace, and
+        ``crh_graph_between`` over the two, then :meth:`_graph_row_words`.  None when either end names no node."""
+        graph, rel = self._graph_ready(spec.relation)
+        src, _ = graph_mod.resolve(spec.sources, self._graph_code, self._graph_names, spec.match)
+        dst, _ = graph_mod.resolve(spec.targets, self._graph_code, self._graph_names, spec.match)
+        if not src or not dst:
+            return None
+        def between(stream):
+            self.graph_bfs_calls += 2
+            graph.bfs(rel, "callees", [src], spec.hops, include_self=True, stream=stream)
+            graph.bfs(rel, "callers", [dst], spec.hops, include_self=True, stream=stream, back=True)
+            return graph.between(mode="shortest" if spec.shortest else "any", stream=stream)[0]
+        return self._graph_row_words(spec, negate, graph, between)
 
     # -- the graph as a whole: cycles, components, layers (DESIGN.md 3.31)
     def _graph_structure(self, relation: str, layers: bool = False) -> tuple[Any, dict]:
@@ -1172,6 +1229,51 @@ class _Collection:
         graph.bfs(rel, "callees", [[a]], int(max_hops), include_self=True, stream=stream)
         nodes = _host(graph.path(rel, "callees", 0, b, stream=stream))
         return [self._graph_names[int(v)] for v in nodes] or None
+
+    def call_chains(self, pairs, relation: str, max_hops: int, limit: int, must_pass: bool, match: str) -> list[dict[str, Any]]:
+        """Per ``(source or names, target)`` pair: how many shortest chains lead from the source set to the target, the first
+        ``limit`` of them and the nodes no chain of at most ``max_hops`` edges can avoid -- see ``HipVectorStore.call_chains``.
+        64 pairs per pass: one BFS, ``crh_graph_sigma``, ``crh_graph_chains``; then the (pair, interior node of chain 0)
+        candidates, 64 per ``crh_graph_bfs_avoiding``, of which the host reads the targets' finished bits only."""
+        if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or not 1 <= int(max_hops) <= ffi.GRAPH_MAX_HOPS:
+            raise ValueError(f"max_hops must be an int in 1..{ffi.GRAPH_MAX_HOPS}, not {max_hops!r}")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 0 <= int(limit) <= ffi.GRAPH_MAX_CHAINS:
+            raise ValueError(f"limit must be an int in 0..{ffi.GRAPH_MAX_CHAINS}, not {limit!r}")
+        graph, rel = self._graph_ready(relation)
+        names, hops = self._graph_names, int(max_hops)
+        resolved = []
+        for pair in pairs:
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2 or not isinstance(pair[1], str):
+                raise ValueError(f"a chain is asked for by a (source or names, target) pair, not {pair!r}")
+            src, missing = graph_mod.resolve(pair[0], self._graph_code, names, match)
+            dst, gone = graph_mod.resolve([pair[1]], self._graph_code, names, match)
+            if len(dst) > 1:
+                raise ValueError(f"target {pair[1]!r} names {len(dst)} nodes ({', '.join(names[i] for i in dst[:4])}, ...): name one")
+            resolved.append((src, dst[0] if dst else -1, missing + gone))
+        stream = self.shards._stream()
+        out = []
+        for a in range(0, len(resolved), ffi.GRAPH_MAX_QUERIES):
+            part = resolved[a:a + ffi.GRAPH_MAX_QUERIES]
+            graph.bfs(rel, "callees", [src for src, _, _ in part], hops, include_self=True, stream=stream)
+            graph.sigma(rel, "callees", stream=stream)
+            nodes, length, count = (_host(t) for t in graph.chains(rel, "callees", [t for _, t, _ in part], max(int(limit), 1), stream=stream))
+            count = count.view(np.uint64)
+            found = [[] for _ in part]
+            if must_pass:
+                cand = [(q, int(v)) for q in range(len(part)) for v in nodes[q, 0, 1:max(int(length[q]) - 1, 1)]]
+                for b in range(0, len(cand), ffi.GRAPH_MAX_QUERIES):
+                    some = cand[b:b + ffi.GRAPH_MAX_QUERIES]
+                    graph.bfs_avoiding(rel, "callees", [part[q][0] for q, _ in some], hops, [v for _, v in some], include_self=True, stream=stream)
+                    reached = graph.seen_bits([part[q][1] for q, _ in some])
+                    for (q, v), still in zip(some, reached):
+                        if not still:
+                            found[q].append(v)
+            for q, (_, _, missing) in enumerate(part):
+                n, c = int(length[q]), int(count[q])
+                out.append({"count": c, "saturated": c == ffi.GRAPH_SATURATED, "length": n - 1 if n else None,
+                            "chains": [[names[int(v)] for v in nodes[q, r, :n]] for r in range(min(c, int(limit)))],
+                            "must_pass": [names[v] for v in found[q]], "unresolved": missing})
+        return out
 
     def matching_slots(self, filters: dict[str, Any] | None, limit: int | None = None, must_not: dict[str, Any] | None = None) -> np.ndarray:
         """Alive slots matching every condition, in insertion order -- resolved on the device from the code columns."""
@@ -2597,7 +2699,11 @@ class HipVectorStore:
         beside it: ``{"in_cycle": True}`` -- the node lies in a cycle of the relation (it calls itself, or is one of several
         nodes that all reach each other) --, ``{"same_cycle_as": name}``, or ``{"depth" | "height": int or range mapping}`` --
         its layer below the entry points / above the leaves (:meth:`graph_layers`).  Components and layers are found on the
-        device once per relation and graph version."""
+        device once per relation and graph version.  Or it asks for the code BETWEEN two node sets:
+        ``{"between": [source or names, target or names], "hops": 8, "shortest": False, "relation": "calls", "match":
+        "exact"}`` keeps the points whose node lies on a WALK of at most ``hops`` edges from a source to a target, both ends
+        included (a walk, not a simple path: its two halves may share a node); ``"shortest": True`` keeps the nodes of the
+        shortest chains only."""
         try:
             if score_threshold is not None:
                 if query_vector is None:
@@ -3258,6 +3364,30 @@ class HipVectorStore:
             return await self._run(lambda: self._col(collection).call_chain(source, target, relation, max_hops))
         except Exception as e:
             raise VectorStoreError(f"Failed to walk the graph of {collection}", cause=e)
+
+    async def call_chains_batch(self, collection: str, pairs, relation: str = "calls", max_hops: int = 8, limit: int = 10, must_pass: bool = True,
+                                match: str = "exact") -> list[dict[str, Any]]:
+        """:meth:`call_chains` for a list of ``(source or names, target)`` pairs: 64 pairs per pass over the graph."""
+        try:
+            pairs = list(pairs)
+            return await self._run(lambda: self._col(collection).call_chains(pairs, relation, max_hops, limit, must_pass, match))
+        except Exception as e:
+            raise VectorStoreError(f"Failed to walk the graph of {collection}", cause=e)
+
+    async def call_chains(self, collection: str, source, target: str, relation: str = "calls", max_hops: int = 8, limit: int = 10,
+                          must_pass: bool = True, match: str = "exact") -> dict[str, Any]:
+        """How ``source`` reaches ``target`` over ``relation``, in full (:meth:`call_chain` returns one chain):
+        ``{"count", "saturated", "length", "chains", "must_pass", "unresolved"}``.  ``count`` is the number of SHORTEST chains
+        of at most ``max_hops`` (1..16) edges, exact up to 2^64 - 1 (``saturated``: at least that many); ``length`` their number
+        of edges, None when there is no chain; ``chains`` the first ``limit`` (0..64) of them as lists of names from a source
+        to the target, ordered by the nodes read BACKWARDS from the target in the order :meth:`set_graph_edges` saw them --
+        ``chains[0]`` is :meth:`call_chain`'s; longer chains than the shortest are not listed (the reference's FIND_ALL_PATHS
+        lists every path up to its bound).  ``must_pass`` (``must_pass=False`` skips it): the nodes other than the ends that
+        EVERY way of at most ``max_hops`` edges passes, in chain order -- the bound is part of the statement: a detour longer
+        than ``max_hops`` does not count.  ``source``: a name or several (together the source set); ``target`` must name
+        exactly one node (``match="suffix"`` may find several: a ValueError lists them).  ``unresolved``: the names that are
+        no node."""
+        return (await self.call_chains_batch(collection, [(source, target)], relation, max_hops, limit, must_pass, match))[0]
 
     # ------------------------------------------------------------------ the graph as a whole (DESIGN.md 3.31)
     async def graph_cycles(self, collection: str, relation: str = "calls", limit: int = 10, members: int = 50) -> dict[str, Any]:

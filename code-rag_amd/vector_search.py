@@ -122,11 +122,22 @@ def _contains_filter(key: str, contains, contains_case: bool, matches: str | Non
 
 
 def _graph_filter(within_callers_of, within_callees_of, graph_hops: int | None, in_cycle: bool | None = None, graph_depth=None,
-                  graph_height=None) -> dict:
+                  graph_height=None, between=None) -> dict:
     """``within_callers_of`` / ``within_callees_of`` (a node name or a list of them) as the store's ``"graph"`` condition: only
     code that calls / is called from those nodes, transitively within ``graph_hops`` edges (the store's default: 3), the named
-    nodes' own chunks included -- ``{}`` without either: the call is then the one issued before."""
+    nodes' own chunks included -- ``{}`` without either: the call is then the one issued before.  ``between``
+    = ``(a, b)``, each a name or a list of them: only code on a way of at most ``graph_hops`` (default 8) calls from ``a`` to
+    ``b``."""
     whole = {k: v for k, v in (("in_cycle", True if in_cycle else None), ("depth", graph_depth), ("height", graph_height)) if v is not None}
+    if between is not None:
+        if whole or within_callers_of is not None or within_callees_of is not None:
+            raise QueryError("between, in_cycle, graph_depth, graph_height, within_callers_of and within_callees_of cannot be combined (one graph condition per search)")
+        if isinstance(between, str) or not isinstance(between, (list, tuple)) or len(between) != 2:
+            raise QueryError("between takes a pair (a, b): a node name or a list of names for either end")
+        spec = {"between": [list(e) if isinstance(e, (list, tuple, set, frozenset)) else e for e in between]}
+        if graph_hops is not None:
+            spec["hops"] = graph_hops
+        return {"graph": spec}
     if whole:                                                            # the node's place in the whole graph (DESIGN.md 3.31)
         if len(whole) > 1 or within_callers_of is not None or within_callees_of is not None or graph_hops is not None:
             raise QueryError("in_cycle, graph_depth, graph_height, within_callers_of and within_callees_of cannot be combined (one graph condition per search)")
@@ -252,7 +263,7 @@ class VectorSearcher:
                           fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
                           within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
                           propagate: bool | dict | None = None, in_cycle: bool | None = None, graph_depth: int | dict | None = None,
-                          graph_height: int | dict | None = None) -> list[dict]:
+                          graph_height: int | dict | None = None, between: tuple | list | None = None) -> list[dict]:
         """vector_search.py:60-116.  ``mode`` (not in the reference): "semantic" -- the default, everything below --,
         "lexical" -- exact keyword search (BM25) of ``query``, nothing embedded: where is ``parse_retry_after`` -- or "hybrid"
         -- both, fused by reciprocal rank (``HipVectorStore.search_hybrid``): every result then also carries ``cosine``,
@@ -292,6 +303,10 @@ class VectorSearcher:
         that height above the leaf helpers (an int, or a range such as ``{"lte": 1}``): "retry handling, but only in leaf
         helpers" is ``graph_height=0``.  Components and layers of the whole graph are found on the device once per graph
         (DESIGN.md 3.31); :meth:`find_similar_code` and :meth:`search_code_batch` take them the same way.
+        ``between=(a, b)`` (not in the reference) instead, each end a node name or a list of them: only code that lies on a way
+        of at most ``graph_hops`` (default 8) calls from ``a`` to ``b`` -- "retry handling, but only between ``handle_request``
+        and ``db.execute``" (DESIGN.md 3.32); :meth:`search_summaries`, :meth:`find_similar_code`, :meth:`search_code_batch`
+        and :meth:`facet_code` take it the same way.
         ``propagate`` (not in the reference): ``True``, or the settings of ``HipVectorStore.search_propagated`` -- the best
         ``candidates`` matches seed a random walk with restart over the call graph (personalised PageRank) and
         the results are ordered by reciprocal-rank fusion of similarity and graph score: of the matches, those in the middle of
@@ -304,12 +319,12 @@ class VectorSearcher:
                 contains=contains, contains_case=contains_case, matches=matches, fuzzy=fuzzy, edits=edits, within_callers_of=within_callers_of,
                 within_callees_of=within_callees_of, graph_hops=graph_hops, diversity=diversity, max_per_file=max_per_file,
                 extra_queries=extra_queries, min_score=min_score, max_overlap=max_overlap, mode=mode, in_cycle=in_cycle or None,
-                graph_depth=graph_depth, graph_height=graph_height))["results"]
+                graph_depth=graph_depth, graph_height=graph_height, between=between))["results"]
         if not query or not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
-        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height))
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height, between))
         hits = await self._lookup(query, CollectionName.CODE_CHUNKS.value, limit, filters or None,
                                   "Failed to embed search query", "Failed to search code", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -373,7 +388,8 @@ class VectorSearcher:
                                extra_queries: list[str] | None = None, fusion: str = "rrf", min_score: float | None = None,
                                mode: str = "semantic", contains: str | list[str] | None = None, contains_case: bool = True,
                                matches: str | None = None, fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
-                               within_callees_of: str | list[str] | None = None, graph_hops: int | None = None) -> list[dict]:
+                               within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
+                               between: tuple | list | None = None) -> list[dict]:
         """vector_search.py:118-166 (filters on ``project_name``, which summary payloads never carry: quirk Q6).
         ``extra_queries`` / ``fusion`` / ``min_score`` / ``mode`` as in :meth:`search_code`; ``contains`` / ``contains_case`` /
         ``matches`` likewise, over the ``summary`` text."""
@@ -382,8 +398,8 @@ class VectorSearcher:
         filters = {"project_name": project_name} if project_name else None
         if contains is not None or matches is not None or fuzzy is not None or edits is not None:
             filters = dict(filters or {}, **_contains_filter("summary", contains, contains_case, matches, fuzzy, edits))
-        if within_callers_of is not None or within_callees_of is not None or graph_hops is not None:
-            filters = dict(filters or {}, **_graph_filter(within_callers_of, within_callees_of, graph_hops))
+        if within_callers_of is not None or within_callees_of is not None or graph_hops is not None or between is not None:
+            filters = dict(filters or {}, **_graph_filter(within_callers_of, within_callees_of, graph_hops, between=between))
         hits = await self._lookup(query, CollectionName.SUMMARIES.value, limit, filters,
                                   "Failed to embed search query", "Failed to search summaries", diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, extra_queries=extra_queries, fusion=fusion, min_score=min_score,
@@ -398,21 +414,21 @@ class VectorSearcher:
                                 fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
                                 within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
                                 in_cycle: bool | None = None, graph_depth: int | dict | None = None,
-                                graph_height: int | dict | None = None) -> list[dict]:
+                                graph_height: int | dict | None = None, between: tuple | list | None = None) -> list[dict]:
         """vector_search.py:168-219: over-fetch by 5 when a file is excluded, drop its chunks, keep ``limit`` -- which comes
         back short when the excluded file owns more than 5 of the best hits.  ``exact_exclude=True`` (not in the reference)
         excludes the file on the device instead (``must_not={"file_path": exclude_file}``) and fetches exactly ``limit``.
         ``min_score`` as in :meth:`search_code`: only chunks at least that similar to the snippet.  ``max_overlap`` as in
         :meth:`search_code`: no chunk repeats more than that share of a better chunk's lines.  ``contains`` / ``contains_case``
         as in :meth:`search_code`: only chunks that hold the literal string(s); ``matches`` likewise: only chunks the regular
-        expression matches.  ``in_cycle`` / ``graph_depth`` / ``graph_height`` as in :meth:`search_code`."""
+        expression matches.  ``in_cycle`` / ``graph_depth`` / ``graph_height`` / ``between`` as in :meth:`search_code`."""
         if not code_snippet or not code_snippet.strip():
             raise QueryError("Code snippet cannot be empty")
         on_device = bool(exact_exclude and exclude_file)
         fetch = limit + EXCLUDE_FILE_BUFFER if exclude_file and not on_device else limit
         hits = await self._lookup(code_snippet, CollectionName.CODE_CHUNKS.value, fetch,
                                   {**_contains_filter("content", contains, contains_case, matches, fuzzy, edits),
-                                   **_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height)} or _NO_FILTER_KWARG,
+                                   **_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height, between)} or _NO_FILTER_KWARG,
                                   "Failed to embed code snippet", "Failed to find similar code",
                                   must_not={"file_path": exclude_file} if on_device else None, diversity=diversity, candidates=candidates,
                                   max_per_file=max_per_file, min_score=min_score, max_overlap=max_overlap)
@@ -467,19 +483,22 @@ class VectorSearcher:
                          limit: int = DEFAULT_SEARCH_LIMIT, language: str | list[str] | None = None, entity_type: str | None = None,
                          project_name: str | list[str] | None = None, contains: str | list[str] | None = None,
                          contains_case: bool = True, matches: str | None = None, fuzzy: str | None = None,
-                         edits: int | None = None) -> dict:
+                         edits: int | None = None, between: tuple | list | None = None, graph_hops: int | None = None) -> dict:
         """WHERE something lives, not which chunks (not in the reference, whose callers fetch hits and count them in Python):
         the ``limit`` most frequent values of ``key`` -- a file path, a language, an entity type -- among the code chunks that
         pass the filters, with their counts (``HipVectorStore.facet``): ``{"hits": [{"value", "count"}], "values", "total",
         "missing"}``.  ``contains`` / ``contains_case`` / ``matches`` / ``fuzzy`` / ``edits`` as in :meth:`search_code`: how many
         chunks per file hold ``TODO(``.  With ``query`` and ``min_score`` -- both or neither -- ``query`` is embedded and only chunks at least that
-        similar to it count: in which files does this concept live.  Counts are exact; ties go to the value indexed first."""
+        similar to it count: in which files does this concept live.  Counts are exact; ties go to the value indexed first.
+        ``between`` / ``graph_hops`` as in :meth:`search_code`: which files hold the code between two functions."""
         if (query is None) != (min_score is None):
             raise QueryError("facet_code: query and min_score come together or not at all")
         if query is not None and not query.strip():
             raise QueryError("Search query cannot be empty")
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         filters.update(_contains_filter("content", contains, contains_case, matches, fuzzy, edits))
+        if between is not None or graph_hops is not None:
+            filters.update(_graph_filter(None, None, graph_hops, between=between))
         try:
             kwargs = {}
             if query is not None:
@@ -530,6 +549,21 @@ class VectorSearcher:
             return []
         return [{"nodes": chain, "relationships": ["CALLS"] * (len(chain) - 1), "total_length": len(chain) - 1, "path_type": "call_chain"}]
 
+    async def find_call_chains(self, source, target: str, max_hops: int = 8, limit: int = 10, must_pass: bool = True, relation: str = "calls",
+                               match: str = "exact") -> dict:
+        """How ``source`` (a name or several) reaches ``target``, in full (``HipVectorStore.call_chains``; the reference's
+        FIND_ALL_PATHS lists every path up to its bound, this the SHORTEST ones): ``{"count", "saturated", "length", "chains":
+        [[names]], "must_pass": [names], "unresolved"}`` -- how many shortest chains of at most ``max_hops`` calls there are,
+        the first ``limit`` of them, and the functions no way of at most ``max_hops`` calls avoids."""
+        if not source or not target:
+            raise QueryError("find_call_chains needs a source and a target")
+        try:
+            return await self.qdrant.call_chains(collection=CollectionName.CODE_CHUNKS.value, source=source, target=target, relation=relation,
+                                                 max_hops=max_hops, limit=limit, must_pass=must_pass, match=match)
+        except VectorStoreError as e:
+            logger.error(f"Vector store error: {e}")
+            raise QueryError("Failed to find the call chains", cause=e)
+
     async def find_cycles(self, limit: int = 10, relation: str = "calls", members: int = 50) -> dict:
         """Which functions are (mutually) recursive -- with ``relation="imports"``: which modules depend on each other in a
         circle (``HipVectorStore.graph_cycles``; not in the reference, whose Cypher has no query for it): ``{"cycles": [{"name",
@@ -567,7 +601,7 @@ class VectorSearcher:
                                 fuzzy: str | None = None, edits: int | None = None, within_callers_of: str | list[str] | None = None,
                                 within_callees_of: str | list[str] | None = None, graph_hops: int | None = None,
                                 in_cycle: bool | None = None, graph_depth: int | dict | None = None,
-                                graph_height: int | dict | None = None) -> list[list[dict]]:
+                                graph_height: int | dict | None = None, between: tuple | list | None = None) -> list[list[dict]]:
         """``queries``: list of strings (embedded in one provider batch) or an array [B, dim] of ready vectors.
         ``mode`` "lexical" / "hybrid" as in :meth:`search_code` (``queries`` must be strings then; the filters and
         ``candidates`` only).
@@ -577,7 +611,8 @@ class VectorSearcher:
         means "any of"; not combinable with ``diversity`` / ``max_per_file`` yet.  ``min_score``: one number or one per query, as in
         :meth:`search_code`; not together with ``filters_per_query`` either.  ``max_overlap`` as in :meth:`search_code`; not
         together with ``filters_per_query``, ``diversity``, ``max_per_file`` or ``min_score``.  ``contains`` / ``contains_case`` as in
-        :meth:`search_code`, one text condition for the whole batch; not together with ``filters_per_query``.  ``matches`` likewise."""
+        :meth:`search_code`, one text condition for the whole batch; not together with ``filters_per_query``.  ``matches`` likewise;
+        ``between`` likewise: one graph condition for the whole batch."""
         filters = {k: v for k, v in (("language", language), ("entity_type", entity_type), ("project_name", project_name)) if v}
         if (contains is not None or matches is not None or fuzzy is not None or edits is not None) and filters_per_query is not None:
             raise QueryError("contains / matches / fuzzy cannot be combined with filters_per_query (a text condition is one grep for the whole batch)")
@@ -586,7 +621,9 @@ class VectorSearcher:
             raise QueryError("within_callers_of / within_callees_of cannot be combined with filters_per_query (a graph condition is one BFS for the whole batch)")
         if (in_cycle or graph_depth is not None or graph_height is not None) and filters_per_query is not None:
             raise QueryError("in_cycle / graph_depth / graph_height cannot be combined with filters_per_query (a graph condition is one bitmap for the whole batch)")
-        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height))
+        if between is not None and filters_per_query is not None:
+            raise QueryError("between cannot be combined with filters_per_query (a graph condition is one bitmap for the whole batch)")
+        filters.update(_graph_filter(within_callers_of, within_callees_of, graph_hops, in_cycle, graph_depth, graph_height, between))
         if filters_per_query is not None:
             if filters:
                 raise QueryError("filters_per_query cannot be combined with language / entity_type / project_name")

@@ -801,6 +801,66 @@ int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint6
 int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_dev, int q, int64_t target, int max_hops,
                    int32_t *out_nodes_host, int *out_len, void *stream);
 
+/* ---- chains in full: how many shortest chains, the K first of them, the nodes between two sets, a BFS that avoids a node
+ * (DESIGN.md 3.32).  Exact integers over the levels of a crh_graph_bfs(rel, direction, ..., max_hops, include_self = 1); the
+ * definitions are this repository's own and a CPU restatement of the text below gives the same words.  direction is
+ * CRH_GRAPH_ALONG or CRH_GRAPH_AGAINST: CRH_GRAPH_BOTH is CRH_E_INVALID.  "u's pull list" is the list that BFS pulls through
+ * (ALONG: u's sources, the reverse CSR; AGAINST: its targets), read as it is; the host builder makes every list ascending.
+ * Every call enqueues on `stream`; a bad argument is CRH_E_INVALID with nothing launched, a graph without nodes CRH_OK with
+ * nothing launched.
+ *
+ * crh_graph_sigma: sigma_out_dev u64 [n_nodes][QS], QS the smallest power of two >= nq, column q = query q, the columns from nq
+ * on 0, every word written.  sigma[v][q] = 1 where bit q of levels[0][v] is set; for d = 1 .. max_hops and u with bit q in
+ * levels[d][u], sigma[u][q] = the SATURATING sum, min(true sum, 2^64 - 1), of sigma[v][q] over the entries v of u's pull list
+ * with bit q in levels[d - 1][v]; 0 everywhere else.  All terms are >= 0, so the saturated sum does not depend on the order of
+ * addition.  sigma[t][q] is the number of SHORTEST chains from source set q to t (0: not reached within max_hops; 2^64 - 1: at
+ * least that many).  active_dev is the BFS's: a level whose word is 0 leaves at once.  One launch for level 0 and the zeros,
+ * one per level after it; an entry has one writer. */
+int crh_graph_sigma(crh_graph *g, int rel, int direction, int nq, const uint64_t *levels_dev, const uint64_t *active_dev, int max_hops,
+                    uint64_t *sigma_out_dev, void *stream);
+
+/* The K first shortest chains of every query q to its target t_q (targets: int32 [nq], a host array -- an entry that is
+ * neither a node nor -1 is CRH_E_INVALID, -1 has no chain -- or, targets_on_device != 0, a device array complete on `stream`,
+ * where an entry that is no node yields count 0).  levels_dev and sigma_dev are crh_graph_bfs' and crh_graph_sigma's for the
+ * same rel, direction, nq and max_hops.  Chains are ORDERED by their node ids read BACKWARDS from the target: the node before
+ * the target first, then the one before that.  Chain r, 0 <= r < min(K, count), is found by unranking: rem = r, u = t_q, d =
+ * the target's level; while d > 0 walk u's pull list in order over the entries v with bit q in levels[d - 1][v] -- if rem <
+ * sigma[v][q] step to v (d - 1), otherwise rem -= sigma[v][q].  A saturated sigma compares as the true one would, since rem <
+ * K <= CRH_GRAPH_MAX_CHAINS.  Chain 0 is, node for node, crh_graph_path's.
+ *   out_nodes_dev int32 [nq][K][max_hops + 1]: from a source to the target, padded with -1; every slot written.
+ *   out_len_dev   int32 [nq]: the nodes of each chain (1: the target is a source), 0 when the target is not reached.
+ *   out_count_dev u64 [nq]: sigma[t_q][q].
+ * One wave per (query, rank), 64 list entries per step. */
+#define CRH_GRAPH_MAX_CHAINS 64
+int crh_graph_chains(crh_graph *g, int rel, int direction, int nq, const uint64_t *levels_dev, const uint64_t *sigma_dev, int max_hops,
+                     const int32_t *targets, int targets_on_device, int K, int32_t *out_nodes_dev, int32_t *out_len_dev,
+                     uint64_t *out_count_dev, void *stream);
+
+/* The nodes BETWEEN source set q and target set q.  levels_fwd_dev: a BFS from the source sets; levels_back_dev: a BFS in the
+ * OPPOSITE direction from the target sets; both with this max_hops and include_self = 1.  With dF and dB a node's two minimum
+ * depths, bit q of out_words_dev[v] (u64 [n_nodes], the layout of seen_dev, which crh_graph_row_words takes) is set iff both
+ * exist and
+ *   CRH_GRAPH_BETWEEN_ANY       dF + dB <= max_hops: v lies on a WALK of at most max_hops edges from the one set to the other
+ *                               (a walk, not a simple path: the two halves may share a node); the ends are included
+ *   CRH_GRAPH_BETWEEN_SHORTEST  dF + dB == D_q, the least dF + dB over all nodes, where that is <= max_hops: v lies on a
+ *                               shortest chain
+ * out_dist_dev int32 [nq], or NULL: D_q, -1 where the sets do not meet within max_hops.  meet_dev u64 [max_hops + 1] is the
+ * caller's work array (meet[d] = the queries with a node at dF + dB = d).  Two launches; runs on the CURRENT device. */
+#define CRH_GRAPH_BETWEEN_ANY 0
+#define CRH_GRAPH_BETWEEN_SHORTEST 1
+int crh_graph_between(int64_t n_nodes, int nq, const uint64_t *levels_fwd_dev, const uint64_t *levels_back_dev, int max_hops, int mode,
+                      uint64_t *meet_dev /* u64 [max_hops + 1], caller-owned */, uint64_t *out_words_dev, int32_t *out_dist_dev /* or NULL */,
+                      void *stream);
+
+/* crh_graph_bfs with an AVOIDED node set per query: avoid_dev u64 [n_nodes], bit q at v = query q never enters v.  Level 0 =
+ * sources & ~avoid, next[u] = pulled & ~seen[u] & ~avoid[u]; everything else as crh_graph_bfs.  With it "v is a MUST-PASS node
+ * of (S, t)" is decided: v is neither t nor a source, t is reached from S within max_hops, and is not once v may not be
+ * entered.  The statement is bounded by max_hops: a detour longer than that does not count.  Such a v lies on every chain,
+ * hence on chain 0: its interior nodes are the candidates. */
+int crh_graph_bfs_avoiding(crh_graph *g, int rel, int direction, int nq, const int64_t *src_off_host, const int32_t *src_nodes,
+                           int sources_on_device, int max_hops, int include_self, const uint64_t *avoid_dev, uint64_t *levels_dev,
+                           uint64_t *seen_dev, uint64_t *active_dev, void *stream);
+
 /* ---- graph-propagated relevance: personalised PageRank seeded by hits or by named nodes.  The definition is
  * this repository's own, and it is exact: the device result is the same BITS as a CPU restatement that follows the text below.
  *
