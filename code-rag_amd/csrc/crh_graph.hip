@@ -18,11 +18,17 @@
 //   k_graph_row_words row -> node -> bit q of seen, as the validity words crh_index_row_mask writes
 //   k_graph_path      one wave walks back from the target's level, taking the smallest neighbour that lies in the level before
 //
-// One lane per node; a node whose adjacency list has CRH_GRAPH_WAVE_DEGREE entries or more is walked by its whole wave (64
-// entries per step, OR-reduced over the lanes), the shorter ones by their own lane.
+// One lane per node; list_reduce is the one walk of an adjacency list: a list of CRH_GRAPH_WAVE_DEGREE entries or more is walked
+// by its whole wave (64 entries per step, reduced over the lanes), the shorter ones by their own lane.  The four sweeps below
+// (minimum, through list_min) and the narrow k_sigma_level (saturating sum) go through it; k_graph_level has the same walk
+// written out with OR (it measured slower through the helper).
 //
 // Personalised PageRank over the same CSRs stands behind the BFS kernels: k_ppr_inv, k_ppr_seed, k_ppr_step (one
-// launch per step, pull form, sums in list order), k_ppr_bins / k_ppr_bins_exclude, k_ppr_order.
+// launch per step, pull form, sums in list order: its own loops, never list_reduce), k_ppr_bins / k_ppr_bins_exclude, k_ppr_order.
+//
+// Components and layers are monotone sweeps to a fixed point, one launch per sweep, all in the one frame
+// sweep_nodes: k_scc_trim, k_scc_colour, k_scc_mark, k_graph_layer; beside them k_scc_colour_init, k_scc_roots, k_scc_members,
+// k_scc_count, k_scc_bins_count / k_scc_bins_keep, k_graph_layer_max, k_graph_node_words.
 //
 // Chains in full read the levels of a BFS: k_sigma_init / k_sigma_level (the number of shortest chains per node
 // and query, saturating u64, one launch per level), k_graph_chains (one wave unranks one chain), k_between_meet / k_between_out
@@ -65,6 +71,41 @@ __device__ __forceinline__ int wave_min(int v)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
     return v;
+}
+
+// The bits of the queries there are.
+__host__ __device__ __forceinline__ u64 query_mask(int nq)
+{
+    return nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+}
+
+// The one walk of an adjacency list: combine(...) of f(adj[i], key) over the list [b, e) of the lane's node, `identity` for an
+// empty one.  The lane walks a list of fewer than CRH_GRAPH_WAVE_DEGREE entries itself; the longer ones are handed round by
+// ballot, each walked by the whole wave 64 entries per step and reduced by wave_combine, and the result goes to the lane that
+// owns the list.  `key` is what f needs to know about the node that owns the list (the lanes that help with another lane's list
+// get that lane's).  EVERY lane of the wave calls it, with b == e when it has nothing to walk: the ballot and the shuffles
+// inside are the whole wave's.  The terms are combined in whatever order the split gives, so the reduction must not depend on
+// order: OR, a minimum, a saturating sum of terms >= 0.  k_ppr_step does NOT come here: its f32 sums are in list order by design
+// (bit-equal to the CPU restatement).
+template <class T, class F, class C, class W>
+__device__ __forceinline__ T list_reduce(const int32_t *adj, int64_t b, int64_t e, int lane, int key, T identity, F f, C combine, W wave_combine)
+{
+    T acc = identity;
+    const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
+    if (!wide)
+        for (int64_t i = b; i < e; ++i) acc = combine(acc, f(adj[i], key));
+    u64 m = __ballot(wide);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
+        const int owner = __shfl(key, src);
+        T part = identity;
+        for (int64_t i = bb + lane; i < ee; i += 64) part = combine(part, f(adj[i], owner));
+        part = wave_combine(part);
+        if (lane == src) acc = part;
+    }
+    return acc;
 }
 
 struct SourceArgs {
@@ -125,6 +166,9 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_level(const LevelArgs a
                 b = a.off[c][u];
                 e = a.off[c][u + 1];
             }
+            // list_reduce written out with OR, every list ORed straight into the node's word: through the helper the kernel
+            // took two registers more and the avoiding BFS of a small graph measured slower (profiles/graph_refactor.md).
+            // The same contract holds: every lane reaches the ballot, with b == e when it has nothing to walk.
             const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
             if (!wide)
                 for (int64_t i = b; i < e; ++i) acc |= a.front[a.adj[c][i]];
@@ -488,28 +532,11 @@ constexpr int kSweepBatch = 16;                // sweeps enqueued per read-back 
 constexpr int kSccCounters = 24;               // the extra words of the work arrays: flags [kSweepBatch + 1] from 0, four counters from here
 constexpr int kNoColour = 0x7fffffff;
 
-// The minimum of f(adj[i]) over the list [b, e) of the lane's node: walked by the lane itself below CRH_GRAPH_WAVE_DEGREE
-// entries, by the whole wave from there on.  `key` is what f needs to know about the node that owns the list (the lanes that help
-// with another lane's list get that lane's).  Every lane of the wave calls it (b == e: nothing to walk).
+// The minimum of f(adj[i], key) over the list [b, e) of the lane's node, kNoColour for an empty one: list_reduce, under its contract.
 template <class F>
 __device__ __forceinline__ int list_min(const int32_t *adj, int64_t b, int64_t e, int lane, int key, F f)
 {
-    int acc = kNoColour;
-    const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
-    if (!wide)
-        for (int64_t i = b; i < e; ++i) acc = min(acc, f(adj[i], key));
-    u64 m = __ballot(wide);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
-        const int owner = __shfl(key, src);
-        int part = kNoColour;
-        for (int64_t i = bb + lane; i < ee; i += 64) part = min(part, f(adj[i], owner));
-        part = wave_min(part);
-        if (lane == src) acc = part;
-    }
-    return acc;
+    return list_reduce(adj, b, e, lane, key, kNoColour, f, [](int x, int y) { return min(x, y); }, [](int x) { return wave_min(x); });
 }
 
 // One atomicOr per workgroup: the OR of the lanes' flag bits 0 and 1.
@@ -526,6 +553,22 @@ __device__ __forceinline__ void sweep_flags(unsigned mine, unsigned *flag)
     }
 }
 
+// The frame of a sweep: it leaves at once when the sweep before it changed nothing, gives every node to one lane, and ORs the
+// flag bits that body(u, in, lane) returns (`in`: u is a node) into *cur.  The nodes are handed out by the wave, and a lane
+// past the last node still calls body: what body does with a list (list_min) is the whole wave's.
+template <class B>
+__device__ __forceinline__ void sweep_nodes(int64_t n, const unsigned *prev, unsigned *cur, B body)
+{
+    if ((*prev & 1u) == 0u) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0u;
+    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < n; base += (int64_t)gridDim.x * kGraphThreads) {
+        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
+        mine |= body(u, u < n, lane);
+    }
+    sweep_flags(mine, cur);
+}
+
 struct SccArgs {
     const int64_t *off_out, *off_in;           // the forward CSR (a node's targets) and the reverse one (its sources)
     const int32_t *adj_out, *adj_in;
@@ -539,28 +582,18 @@ struct SccArgs {
 // Trim: an unassigned node without an unassigned in-neighbour, or without an unassigned out-neighbour, is a component by itself.
 __global__ __launch_bounds__(kGraphThreads) void k_scc_trim(const SccArgs a)
 {
-    if ((*a.prev & 1u) == 0u) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned mine = 0u;
-    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
-        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
-        const bool in = u < a.n;
+    sweep_nodes(a.n, a.prev, a.cur, [&a](int64_t u, bool in, int lane) {
         const bool open = in && a.comp[u] < 0;
         const int32_t *comp = a.comp;
         const int self = (int)u;
         auto open_other = [comp](int v, int owner) { return v != owner && comp[v] < 0 ? 0 : 1; };
         const int no_in = list_min(a.adj_in, open ? a.off_in[u] : 0, open ? a.off_in[u + 1] : 0, lane, self, open_other);   // 0: there is one
         const int no_out = list_min(a.adj_out, open ? a.off_out[u] : 0, open ? a.off_out[u + 1] : 0, lane, self, open_other);
-        if (open) {
-            if (no_in != 0 || no_out != 0) {
-                a.comp[u] = self;
-                mine |= 1u;
-            } else {
-                mine |= 2u;
-            }
-        }
-    }
-    sweep_flags(mine, a.cur);
+        if (!open) return 0u;
+        if (no_in == 0 && no_out == 0) return 2u;
+        a.comp[u] = self;
+        return 1u;
+    });
 }
 
 __global__ __launch_bounds__(kGraphThreads) void k_scc_colour_init(const int32_t *comp, int32_t *colour, int64_t n)
@@ -572,21 +605,14 @@ __global__ __launch_bounds__(kGraphThreads) void k_scc_colour_init(const int32_t
 // Colour: the smallest id among the unassigned nodes that reach the node.
 __global__ __launch_bounds__(kGraphThreads) void k_scc_colour(const SccArgs a)
 {
-    if ((*a.prev & 1u) == 0u) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned mine = 0u;
-    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
-        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
-        const bool in = u < a.n;
+    sweep_nodes(a.n, a.prev, a.cur, [&a](int64_t u, bool in, int lane) {
         const bool open = in && a.comp[u] < 0;
         const int32_t *colour = a.colour;
         const int least = list_min(a.adj_in, open ? a.off_in[u] : 0, open ? a.off_in[u + 1] : 0, lane, 0, [colour](int v, int) { return (int)colour[v]; });
-        if (open && least < a.colour[u]) {
-            a.colour[u] = least;
-            mine |= 1u;
-        }
-    }
-    sweep_flags(mine, a.cur);
+        if (!open || least >= a.colour[u]) return 0u;
+        a.colour[u] = least;
+        return 1u;
+    });
 }
 
 __global__ __launch_bounds__(kGraphThreads) void k_scc_roots(int32_t *comp, const int32_t *colour, int64_t n)
@@ -598,23 +624,16 @@ __global__ __launch_bounds__(kGraphThreads) void k_scc_roots(int32_t *comp, cons
 // Back-mark: an unassigned node of colour c joins component c once one of its out-neighbours has.
 __global__ __launch_bounds__(kGraphThreads) void k_scc_mark(const SccArgs a)
 {
-    if ((*a.prev & 1u) == 0u) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned mine = 0u;
-    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
-        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
-        const bool in = u < a.n;
+    sweep_nodes(a.n, a.prev, a.cur, [&a](int64_t u, bool in, int lane) {
         const bool open = in && a.comp[u] < 0;
         const int32_t *comp = a.comp;
         const int c = open ? (int)a.colour[u] : -2;
         const int hit = list_min(a.adj_out, open ? a.off_out[u] : 0, open ? a.off_out[u + 1] : 0, lane, c,
                                  [comp](int v, int mine_c) { return comp[v] == mine_c ? 0 : 1; });
-        if (open && hit == 0) {
-            a.comp[u] = c;
-            mine |= 1u;
-        }
-    }
-    sweep_flags(mine, a.cur);
+        if (!open || hit != 0) return 0u;
+        a.comp[u] = c;
+        return 1u;
+    });
 }
 
 // counters: [0] components, [1] components of two nodes or more, [2] nodes that are not their component's label.  `big` was zeroed.
@@ -685,22 +704,15 @@ struct LayerArgs {
 // layer[u] = max over the pull list of layer[v] + (comp[v] != comp[u]), from zeros: the longest path of the condensation.
 __global__ __launch_bounds__(kGraphThreads) void k_graph_layer(const LayerArgs a)
 {
-    if ((*a.prev & 1u) == 0u) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned mine = 0u;
-    for (int64_t base = ((int64_t)blockIdx.x * kGraphWaves + wave) * 64; base < a.n; base += (int64_t)gridDim.x * kGraphThreads) {
-        const int64_t u = base + lane;                               // (base is the wave's: its lanes stay together)
-        const bool in = u < a.n;
+    sweep_nodes(a.n, a.prev, a.cur, [&a](int64_t u, bool in, int lane) {
         const int32_t *comp = a.comp, *layer = a.layer;
         const int cu = in ? (int)comp[u] : 0;
         const int best = -list_min(a.adj, in ? a.off[u] : 0, in ? a.off[u + 1] : 0, lane, cu,
                                    [comp, layer](int v, int own) { return -((int)layer[v] + (comp[v] != own ? 1 : 0)); });
-        if (in && best != -kNoColour && best > a.layer[u]) {
-            a.layer[u] = best;
-            mine |= 1u;
-        }
-    }
-    sweep_flags(mine, a.cur);
+        if (!in || best == -kNoColour || best <= a.layer[u]) return 0u;
+        a.layer[u] = best;
+        return 1u;
+    });
 }
 
 __global__ __launch_bounds__(kGraphThreads) void k_graph_layer_max(const int32_t *layer, int64_t n, int *out)
@@ -767,8 +779,8 @@ struct SigmaArgs {
 // One launch per level d >= 1; a lane owns (node, query) and is the only writer of its entry.  It writes entries of level d
 // and reads entries of level d - 1 only, so one buffer serves.  WIDE (QS = 64): the wave owns one node, loads 64 adjacency
 // entries and their level words at a time and reads one 512-byte row of sigma per neighbour that any wanted query passed
-// through.  Otherwise a lane walks its own list, and a list of CRH_GRAPH_WAVE_DEGREE entries or more is walked by the whole
-// wave for that lane's query.
+// through.  Otherwise a lane walks its own list by list_reduce, which has the whole wave walk a list of CRH_GRAPH_WAVE_DEGREE
+// entries or more for that lane's query (the key).
 template <bool WIDE>
 __global__ __launch_bounds__(kGraphThreads) void k_sigma_level(const SigmaArgs a)
 {
@@ -807,27 +819,11 @@ __global__ __launch_bounds__(kGraphThreads) void k_sigma_level(const SigmaArgs a
                 b = a.off[u];
                 e = a.off[u + 1];
             }
-            const bool wide = e - b >= CRH_GRAPH_WAVE_DEGREE;
-            u64 acc = 0ull;
-            if (!wide)
-                for (int64_t i = b; i < e; ++i) {
-                    const int64_t v = a.adj[i];
-                    if ((a.prev[v] >> q) & 1ull) acc = sat_add(acc, a.sigma[(v << a.shift) | q]);
-                }
-            u64 m = __ballot(wide);
-            while (m) {
-                const int src = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const int64_t bb = (int64_t)shfl64((u64)b, src), ee = (int64_t)shfl64((u64)e, src);
-                const int qq = __shfl(q, src);
-                u64 part = 0ull;
-                for (int64_t i = bb + lane; i < ee; i += 64) {
-                    const int64_t v = a.adj[i];
-                    if ((a.prev[v] >> qq) & 1ull) part = sat_add(part, a.sigma[(v << a.shift) | qq]);
-                }
-                part = wave_sat_sum(part);
-                if (lane == src) acc = part;
-            }
+            const u64 *prev = a.prev, *sigma = a.sigma;
+            const int shift = a.shift;
+            const u64 acc = list_reduce(a.adj, b, e, lane, q, 0ull,
+                                        [prev, sigma, shift](int64_t v, int qq) { return (prev[v] >> qq) & 1ull ? sigma[(v << shift) | qq] : 0ull; },
+                                        [](u64 x, u64 y) { return sat_add(x, y); }, [](u64 x) { return wave_sat_sum(x); });
             if (mineq) a.sigma[(u << a.shift) | q] = acc;
         }
     }
@@ -959,7 +955,7 @@ __global__ __launch_bounds__(kGraphThreads) void k_between_meet(const BetweenArg
 __global__ __launch_bounds__(kGraphThreads) void k_between_out(const BetweenArgs a)
 {
     u64 mask[kLevels], earlier = 0ull;
-    const u64 qmask = a.nq == 64 ? ~0ull : (1ull << a.nq) - 1ull;
+    const u64 qmask = query_mask(a.nq);
 #pragma unroll
     for (int d = 0; d < kLevels; ++d) {
         const u64 md = d <= a.max_hops ? a.meet[d] : 0ull;
@@ -1012,6 +1008,31 @@ unsigned graph_blocks(int64_t items, int64_t per_block)
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, per_block), (int64_t)current_device_cus() * 8));
 }
 
+// The range of an argument that several entry points take, refused in the name of the one that was called.
+int check_nq(const char *who, int nq)
+{
+    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: nq=%d outside 1..%d", who, nq, CRH_GRAPH_MAX_QUERIES);
+    return CRH_OK;
+}
+
+int check_hops(const char *who, int max_hops)
+{
+    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "%s: max_hops=%d outside 1..%d", who, max_hops, CRH_GRAPH_MAX_HOPS);
+    return CRH_OK;
+}
+
+int check_n_nodes(const char *who, int64_t n_nodes)
+{
+    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "%s: n_nodes=%lld outside 0..2^31-1", who, (long long)n_nodes);
+    return CRH_OK;
+}
+
+int check_q(const char *who, int q)
+{
+    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: q=%d outside 0..%d", who, q, CRH_GRAPH_MAX_QUERIES - 1);
+    return CRH_OK;
+}
+
 }  // namespace
 }  // namespace crh
 
@@ -1027,11 +1048,11 @@ struct crh_graph {
     int64_t n_nodes = 0;
     crh_graph_relation rel[CRH_GRAPH_MAX_RELATIONS];
     int32_t *path = nullptr;                 // CRH_GRAPH_MAX_HOPS + 2 ints
-    int32_t *sources = nullptr;              // the upload of a host source list
-    int64_t cap_sources = 0;
+    void *sources = nullptr;                 // the upload of a host source list (graph_stage)
+    int64_t cap_sources = 0;                 // bytes
     float *inv[CRH_GRAPH_MAX_RELATIONS][3] = {};   // personalised PageRank: 1 / out(v) per (relation, direction), built on first use
     void *seeds = nullptr;                   // the upload of a host seed list: nodes, then weights
-    int64_t cap_seeds = 0;
+    int64_t cap_seeds = 0;                   // bytes
 };
 
 using namespace crh;
@@ -1058,11 +1079,35 @@ void graph_drop_inv(crh_graph *g, int rel)
     }
 }
 
-int ppr_shift(int nq)
+// The shift of the (node, query) layout that the PageRank state and sigma share: entry (v << shift) | q, 1 << shift = QS, the
+// smallest power of two >= nq.
+int layout_shift(int nq)
 {
     int shift = 0;
     while ((1 << shift) < nq) ++shift;
     return shift;
+}
+
+// The upload of host lists of `bytes` each, one behind the other (NULL: its place stays as it is), into a buffer of the handle's
+// that grows on demand to at least `min_cap` bytes.  Returns when the copies are done.
+int graph_stage(void **buf, int64_t *cap, int64_t bytes, int64_t min_cap, hipStream_t st, std::initializer_list<const void *> lists)
+{
+    const int64_t need = bytes * (int64_t)lists.size();
+    if (*cap < need) {
+        CRH_HIP(hipStreamSynchronize(st));   // (a call in flight on this stream still reads the old upload)
+        if (*buf) (void)hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+        CRH_TRY(graph_alloc(buf, std::max(need, min_cap)));
+        *cap = std::max(need, min_cap);
+    }
+    char *at = static_cast<char *>(*buf);
+    for (const void *list : lists) {
+        if (list) CRH_HIP(hipMemcpyAsync(at, list, (size_t)bytes, hipMemcpyHostToDevice, st));
+        at += bytes;
+    }
+    CRH_HIP(hipStreamSynchronize(st));       // (the caller may free its lists on return; pageable memory is staged anyway)
+    return CRH_OK;
 }
 
 // The CSRs a traversal in `direction` PULLS through: travelling along the edges, a node looks at its sources (the reverse CSR).
@@ -1079,6 +1124,14 @@ int graph_pull(const crh_graph *g, int rel, int direction, const int64_t **off, 
         adj[n++] = r.adj[0];
     }
     return n;
+}
+
+// The one pull CSR of ALONG or AGAINST, for the callers that have refused CRH_GRAPH_BOTH.
+void graph_pull_one(const crh_graph *g, int rel, int direction, const int64_t **off, const int32_t **adj)
+{
+    const int c = direction == CRH_GRAPH_ALONG ? 1 : 0;              // ALONG pulls through a node's sources
+    *off = g->rel[rel].off[c];
+    *adj = g->rel[rel].adj[c];
 }
 
 int graph_check_rel(const crh_graph *g, int rel, int direction, const char *who)
@@ -1186,8 +1239,8 @@ int graph_bfs_run(const char *who, crh_graph *g, int rel, int direction, int nq,
                   int max_hops, int include_self, const uint64_t *avoid_dev, uint64_t *levels_dev, uint64_t *seen_dev, uint64_t *active_dev, void *stream)
 {
     CRH_TRY(graph_check_rel(g, rel, direction, who));
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: nq=%d outside 1..%d", who, nq, CRH_GRAPH_MAX_QUERIES);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "%s: max_hops=%d outside 1..%d", who, max_hops, CRH_GRAPH_MAX_HOPS);
+    CRH_TRY(check_nq(who, nq));
+    CRH_TRY(check_hops(who, max_hops));
     if (!src_off_host) return fail(CRH_E_INVALID, "%s: NULL pointer", who);
     if (src_off_host[0] != 0) return fail(CRH_E_INVALID, "%s: src_off[0]=%lld, not 0", who, (long long)src_off_host[0]);
     for (int q = 0; q < nq; ++q)
@@ -1206,19 +1259,8 @@ int graph_bfs_run(const char *who, crh_graph *g, int rel, int direction, int nq,
     u64 *levels = reinterpret_cast<u64 *>(levels_dev), *seen = reinterpret_cast<u64 *>(seen_dev), *active = reinterpret_cast<u64 *>(active_dev);
     const int32_t *nodes_dev = src_nodes;
     if (!sources_on_device && total > 0) {
-        if (g->cap_sources < total) {
-            CRH_HIP(hipStreamSynchronize(st));   // (a BFS in flight on this stream still reads the old upload)
-            if (g->sources) (void)hipFree(g->sources);
-            g->sources = nullptr;
-            g->cap_sources = 0;
-            void *p = nullptr;
-            CRH_TRY(graph_alloc(&p, std::max<int64_t>(total, 1024) * 4));
-            g->sources = static_cast<int32_t *>(p);
-            g->cap_sources = std::max<int64_t>(total, 1024);
-        }
-        CRH_HIP(hipMemcpyAsync(g->sources, src_nodes, (size_t)total * 4, hipMemcpyHostToDevice, st));
-        CRH_HIP(hipStreamSynchronize(st));       // (the caller may free its list on return; pageable memory is staged anyway)
-        nodes_dev = g->sources;
+        CRH_TRY(graph_stage(&g->sources, &g->cap_sources, total * 4, 1024 * 4, st, {src_nodes}));
+        nodes_dev = static_cast<const int32_t *>(g->sources);
     }
     CRH_HIP(hipMemsetAsync(levels, 0, (size_t)(max_hops + 1) * (size_t)n * 8, st));
     CRH_HIP(hipMemsetAsync(active, 0, (size_t)(max_hops + 1) * 8, st));
@@ -1241,7 +1283,7 @@ int graph_bfs_run(const char *who, crh_graph *g, int rel, int direction, int nq,
     la.ncsr = graph_pull(g, rel, direction, la.off, la.adj);
     la.seen = seen;
     la.n = n;
-    la.qmask = nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+    la.qmask = query_mask(nq);
     la.avoid = reinterpret_cast<const u64 *>(avoid_dev);
     const unsigned blocks = graph_blocks(n, kGraphThreads);
     for (int d = 1; d <= max_hops; ++d) {
@@ -1283,8 +1325,8 @@ int crh_graph_list(crh_graph *g, int nq, const uint64_t *levels_dev, int max_hop
                    int32_t *out_depth_dev, int64_t *out_count_dev, void *stream)
 {
     if (!g) return fail(CRH_E_INVALID, "graph handle is NULL");
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_list: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_list: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    CRH_TRY(check_nq("graph_list", nq));
+    CRH_TRY(check_hops("graph_list", max_hops));
     if (first_level < 0 || first_level > max_hops) return fail(CRH_E_INVALID, "graph_list: first_level=%d outside 0..%d", first_level, max_hops);
     if (limit < 0 || limit > CRH_GRAPH_MAX_LIMIT) return fail(CRH_E_INVALID, "graph_list: limit=%d outside 0..%d", limit, CRH_GRAPH_MAX_LIMIT);
     if (!out_count_dev || (limit > 0 && (!out_nodes_dev || !out_depth_dev)) || (g->n_nodes > 0 && !levels_dev))
@@ -1301,7 +1343,7 @@ int crh_graph_row_words(const int32_t *row_node_dev, int64_t n_rows, const uint6
                         int64_t n_words, void *stream)
 {
     if (n_rows < 0 || n_rows >= (1LL << 31) || n_nodes < 0) return fail(CRH_E_INVALID, "graph_row_words: n_rows=%lld, n_nodes=%lld", (long long)n_rows, (long long)n_nodes);
-    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_row_words: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
+    CRH_TRY(check_q("graph_row_words", q));
     if (n_words < ceil_div(n_rows, 32)) return fail(CRH_E_INVALID, "graph_row_words: %lld words for %lld rows", (long long)n_words, (long long)n_rows);
     if (n_words == 0) return CRH_OK;
     if (!out_words_dev || (n_rows > 0 && (!row_node_dev || (n_nodes > 0 && !seen_dev)))) return fail(CRH_E_INVALID, "graph_row_words: NULL pointer");
@@ -1318,8 +1360,8 @@ int crh_graph_path(crh_graph *g, int rel, int direction, const uint64_t *levels_
     CRH_TRY(graph_check_rel(g, rel, direction, "graph_path"));
     if (!out_len || !out_nodes_host) return fail(CRH_E_INVALID, "graph_path: NULL pointer");
     *out_len = 0;
-    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_path: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_path: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    CRH_TRY(check_q("graph_path", q));
+    CRH_TRY(check_hops("graph_path", max_hops));
     if (target < 0 || target >= g->n_nodes) return fail(CRH_E_INVALID, "graph_path: target=%lld is no node of %lld", (long long)target, (long long)g->n_nodes);
     if (!levels_dev) return fail(CRH_E_INVALID, "graph_path: NULL pointer");
     DeviceGuard guard(g->device);
@@ -1348,7 +1390,7 @@ int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int
                   float restart, int steps, float *work_dev, float *out_dev, void *stream)
 {
     CRH_TRY(graph_check_rel(g, rel, direction, "graph_ppr"));
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    CRH_TRY(check_nq("graph_ppr", nq));
     if (c < 1 || c > CRH_MAX_K) return fail(CRH_E_INVALID, "graph_ppr: c=%d outside 1..%d", c, CRH_MAX_K);
     if (steps < 1 || steps > CRH_GRAPH_PPR_MAX_STEPS) return fail(CRH_E_INVALID, "graph_ppr: steps=%d outside 1..%d", steps, CRH_GRAPH_PPR_MAX_STEPS);
     if (!(restart > 0.0f && restart < 1.0f)) return fail(CRH_E_INVALID, "graph_ppr: restart=%g is not inside (0, 1)", (double)restart);
@@ -1365,7 +1407,7 @@ int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int
     if (!work_dev || !out_dev) return fail(CRH_E_INVALID, "graph_ppr: NULL pointer");
     DeviceGuard guard(g->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int shift = ppr_shift(nq);
+    const int shift = layout_shift(nq);
     const int64_t plane = n << shift;
     float *&inv = g->inv[rel][direction];
     if (!inv) {                              // built once per (relation, direction); crh_graph_set_relation drops it
@@ -1384,22 +1426,9 @@ int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int
     const int32_t *nodes_dev = seed_nodes;
     const float *weights_dev = seed_weights;
     if (!seeds_on_device) {
-        if (g->cap_seeds < total) {
-            CRH_HIP(hipStreamSynchronize(st));   // (a call in flight on this stream still reads the old upload)
-            if (g->seeds) (void)hipFree(g->seeds);
-            g->seeds = nullptr;
-            g->cap_seeds = 0;
-            const int64_t cap = std::max<int64_t>(total, 4096);
-            CRH_TRY(graph_alloc(&g->seeds, cap * 8));
-            g->cap_seeds = cap;
-        }
-        int32_t *up_nodes = static_cast<int32_t *>(g->seeds);
-        float *up_weights = reinterpret_cast<float *>(up_nodes + g->cap_seeds);
-        CRH_HIP(hipMemcpyAsync(up_nodes, seed_nodes, (size_t)total * 4, hipMemcpyHostToDevice, st));
-        if (seed_weights) CRH_HIP(hipMemcpyAsync(up_weights, seed_weights, (size_t)total * 4, hipMemcpyHostToDevice, st));
-        CRH_HIP(hipStreamSynchronize(st));       // (the caller may free its lists on return)
-        nodes_dev = up_nodes;
-        weights_dev = seed_weights ? up_weights : nullptr;
+        CRH_TRY(graph_stage(&g->seeds, &g->cap_seeds, total * 4, 4096 * 8, st, {seed_nodes, seed_weights}));
+        nodes_dev = static_cast<const int32_t *>(g->seeds);
+        weights_dev = seed_weights ? reinterpret_cast<const float *>(nodes_dev + total) : nullptr;
     }
     float *p0 = work_dev, *ping = work_dev + plane, *pong = work_dev + 2 * plane;
     CRH_HIP(hipMemsetAsync(p0, 0, (size_t)plane * 2 * 4, st));       // p0 and contrib_0: +0 wherever no seed lands
@@ -1428,13 +1457,13 @@ int crh_graph_ppr(crh_graph *g, int rel, int direction, int nq, int c, const int
 
 int crh_graph_ppr_bins(int64_t n_nodes, int nq, const float *scores_dev, int c, const int32_t *exclude_dev, int64_t *out_bins_dev, void *stream)
 {
-    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_ppr_bins: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr_bins: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    CRH_TRY(check_n_nodes("graph_ppr_bins", n_nodes));
+    CRH_TRY(check_nq("graph_ppr_bins", nq));
     if (c < 0 || c > CRH_MAX_K || (c > 0 && !exclude_dev)) return fail(CRH_E_INVALID, "graph_ppr_bins: %d exclusions per query (0..%d) at %p", c, CRH_MAX_K, (const void *)exclude_dev);
     if (n_nodes == 0) return CRH_OK;
     if (!scores_dev || !out_bins_dev) return fail(CRH_E_INVALID, "graph_ppr_bins: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_ppr_bins, dim3(graph_blocks(n_nodes, 64)), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, ppr_shift(nq), nq, out_bins_dev);
+    hipLaunchKernelGGL(k_ppr_bins, dim3(graph_blocks(n_nodes, 64)), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, layout_shift(nq), nq, out_bins_dev);
     if (c > 0)
         hipLaunchKernelGGL(k_ppr_bins_exclude, dim3(graph_blocks((int64_t)nq * c, kGraphThreads)), dim3(kGraphThreads), 0, st, exclude_dev, nq, c, n_nodes,
                            out_bins_dev);
@@ -1445,13 +1474,13 @@ int crh_graph_ppr_bins(int64_t n_nodes, int nq, const float *scores_dev, int c, 
 int crh_graph_ppr_order(int64_t n_nodes, int nq, int c, const float *scores_dev, const int64_t *rows_dev, const float *cosine_dev,
                         const int32_t *nodes_dev, float *out_fuse_scores_dev, int64_t *out_fuse_rows_dev, float *out_graph_score_dev, void *stream)
 {
-    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_ppr_order: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_ppr_order: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
+    CRH_TRY(check_n_nodes("graph_ppr_order", n_nodes));
+    CRH_TRY(check_nq("graph_ppr_order", nq));
     if (c < 1 || c > CRH_MAX_K) return fail(CRH_E_INVALID, "graph_ppr_order: c=%d outside 1..%d", c, CRH_MAX_K);
     if (!rows_dev || !cosine_dev || !nodes_dev || !out_fuse_scores_dev || !out_fuse_rows_dev || !out_graph_score_dev || (n_nodes > 0 && !scores_dev))
         return fail(CRH_E_INVALID, "graph_ppr_order: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_ppr_order, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, ppr_shift(nq), c, rows_dev, cosine_dev, nodes_dev,
+    hipLaunchKernelGGL(k_ppr_order, dim3((unsigned)nq), dim3(kGraphThreads), 0, st, scores_dev, n_nodes, layout_shift(nq), c, rows_dev, cosine_dev, nodes_dev,
                        out_fuse_scores_dev, out_fuse_rows_dev, out_graph_score_dev);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
@@ -1556,7 +1585,7 @@ int crh_graph_scc(crh_graph *g, int rel, int32_t *comp_out_dev, int32_t *work_de
 
 int crh_graph_scc_bins(int64_t n_nodes, const int32_t *comp_dev, const int32_t *self_nodes_dev, int64_t n_self, int64_t *out_bins_dev, void *stream)
 {
-    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_scc_bins: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    CRH_TRY(check_n_nodes("graph_scc_bins", n_nodes));
     if (n_self < 0 || n_self > n_nodes || (n_self > 0 && !self_nodes_dev))
         return fail(CRH_E_INVALID, "graph_scc_bins: %lld self-loop nodes (0..%lld) at %p", (long long)n_self, (long long)n_nodes, (const void *)self_nodes_dev);
     if (n_nodes == 0) return CRH_OK;
@@ -1582,11 +1611,8 @@ int crh_graph_layers(crh_graph *g, int rel, int direction, const int32_t *comp_d
     if (!comp_dev || !out_dev || !work_dev) return fail(CRH_E_INVALID, "graph_layers: NULL pointer");
     DeviceGuard guard(g->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const crh_graph_relation &r = g->rel[rel];
-    const int c = direction == CRH_GRAPH_ALONG ? 1 : 0;              // ALONG pulls through a node's sources
     LayerArgs a{};
-    a.off = r.off[c];
-    a.adj = r.adj[c];
+    graph_pull_one(g, rel, direction, &a.off, &a.adj);
     a.comp = comp_dev;
     a.layer = out_dev;
     a.n = n;
@@ -1617,10 +1643,10 @@ int crh_graph_layers(crh_graph *g, int rel, int direction, const int32_t *comp_d
 int crh_graph_node_words(int64_t n_nodes, int mode, const int32_t *values_dev, const int64_t *bins_dev, int64_t lo, int64_t hi, int q,
                          uint64_t *out_words_dev, void *stream)
 {
-    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_node_words: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
+    CRH_TRY(check_n_nodes("graph_node_words", n_nodes));
     if (mode != CRH_GRAPH_WORDS_IN_CYCLE && mode != CRH_GRAPH_WORDS_SAME_COMPONENT && mode != CRH_GRAPH_WORDS_RANGE)
         return fail(CRH_E_INVALID, "graph_node_words: mode=%d is none of CRH_GRAPH_WORDS_*", mode);
-    if (q < 0 || q >= CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_node_words: q=%d outside 0..%d", q, CRH_GRAPH_MAX_QUERIES - 1);
+    CRH_TRY(check_q("graph_node_words", q));
     if (n_nodes == 0) return CRH_OK;
     if (!values_dev || !out_words_dev || (mode == CRH_GRAPH_WORDS_IN_CYCLE && !bins_dev)) return fail(CRH_E_INVALID, "graph_node_words: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1642,9 +1668,8 @@ int chains_check(const char *who, crh_graph *g, int rel, int direction, int nq, 
     CRH_TRY(graph_check_rel(g, rel, direction, who));
     if (direction == CRH_GRAPH_BOTH)
         return fail(CRH_E_INVALID, "%s: direction is CRH_GRAPH_ALONG or CRH_GRAPH_AGAINST (taken both ways a chain may turn back on itself)", who);
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "%s: nq=%d outside 1..%d", who, nq, CRH_GRAPH_MAX_QUERIES);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "%s: max_hops=%d outside 1..%d", who, max_hops, CRH_GRAPH_MAX_HOPS);
-    return CRH_OK;
+    CRH_TRY(check_nq(who, nq));
+    return check_hops(who, max_hops);
 }
 
 }  // namespace
@@ -1662,15 +1687,11 @@ int crh_graph_sigma(crh_graph *g, int rel, int direction, int nq, const uint64_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     const u64 *levels = reinterpret_cast<const u64 *>(levels_dev);
     SigmaArgs a{};
-    const int64_t *off[2];
-    const int32_t *adj[2];
-    (void)graph_pull(g, rel, direction, off, adj);
-    a.off = off[0];
-    a.adj = adj[0];
+    graph_pull_one(g, rel, direction, &a.off, &a.adj);
     a.sigma = reinterpret_cast<u64 *>(sigma_out_dev);
     a.n = n;
-    a.shift = ppr_shift(nq);
-    a.qmask = nq == 64 ? ~0ull : (1ull << nq) - 1ull;
+    a.shift = layout_shift(nq);
+    a.qmask = query_mask(nq);
     hipLaunchKernelGGL(k_sigma_init, dim3(graph_blocks(n << a.shift, kGraphThreads)), dim3(kGraphThreads), 0, st, levels, n, a.shift, a.qmask, a.sigma);
     const unsigned blocks = graph_blocks(ceil_div(n, 64 >> a.shift), kGraphWaves);
     for (int d = 1; d <= max_hops; ++d) {
@@ -1702,15 +1723,11 @@ int crh_graph_chains(crh_graph *g, int rel, int direction, int nq, const uint64_
     DeviceGuard guard(g->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ChainArgs a{};
-    const int64_t *off[2];
-    const int32_t *adj[2];
-    (void)graph_pull(g, rel, direction, off, adj);
-    a.off = off[0];
-    a.adj = adj[0];
+    graph_pull_one(g, rel, direction, &a.off, &a.adj);
     a.levels = reinterpret_cast<const u64 *>(levels_dev);
     a.sigma = reinterpret_cast<const u64 *>(sigma_dev);
     a.n = n;
-    a.shift = ppr_shift(nq);
+    a.shift = layout_shift(nq);
     a.nq = nq;
     a.max_hops = max_hops;
     a.K = K;
@@ -1729,9 +1746,9 @@ int crh_graph_chains(crh_graph *g, int rel, int direction, int nq, const uint64_
 int crh_graph_between(int64_t n_nodes, int nq, const uint64_t *levels_fwd_dev, const uint64_t *levels_back_dev, int max_hops, int mode, uint64_t *meet_dev,
                       uint64_t *out_words_dev, int32_t *out_dist_dev, void *stream)
 {
-    if (n_nodes < 0 || n_nodes >= (1LL << 31)) return fail(CRH_E_INVALID, "graph_between: n_nodes=%lld outside 0..2^31-1", (long long)n_nodes);
-    if (nq < 1 || nq > CRH_GRAPH_MAX_QUERIES) return fail(CRH_E_INVALID, "graph_between: nq=%d outside 1..%d", nq, CRH_GRAPH_MAX_QUERIES);
-    if (max_hops < 1 || max_hops > CRH_GRAPH_MAX_HOPS) return fail(CRH_E_INVALID, "graph_between: max_hops=%d outside 1..%d", max_hops, CRH_GRAPH_MAX_HOPS);
+    CRH_TRY(check_n_nodes("graph_between", n_nodes));
+    CRH_TRY(check_nq("graph_between", nq));
+    CRH_TRY(check_hops("graph_between", max_hops));
     if (mode != CRH_GRAPH_BETWEEN_ANY && mode != CRH_GRAPH_BETWEEN_SHORTEST) return fail(CRH_E_INVALID, "graph_between: mode=%d is none of CRH_GRAPH_BETWEEN_*", mode);
     if (n_nodes == 0) return CRH_OK;
     if (!levels_fwd_dev || !levels_back_dev || !meet_dev || !out_words_dev) return fail(CRH_E_INVALID, "graph_between: NULL pointer");

@@ -1386,6 +1386,18 @@ def graph_sources(sources) -> tuple[np.ndarray, np.ndarray]:
     return off, nodes
 
 
+class _GraphWorkspace:
+    """What one BFS writes: levels u64 [hops + 1, n_nodes], seen [n_nodes], active [GRAPH_MAX_HOPS + 1] as int64 device tensors,
+    and ``last``, the (nq, max_hops) of the bfs that wrote them."""
+
+    def __init__(self):
+        self.levels = self.seen = self.active = self.last = None
+
+
+def _workspace_attr(back: bool, name: str):
+    return property(lambda self: getattr(self._ws[back], name))
+
+
 class Graph:
     """Owning wrapper of one ``crh_graph`` handle: up to ``GRAPH_MAX_RELATIONS`` relations over ``n_nodes``
     nodes, and the workspace of its traversals -- levels u64 [hops + 1, n_nodes], seen [n_nodes], active [GRAPH_MAX_HOPS + 1],
@@ -1399,21 +1411,22 @@ class Graph:
         h = C.c_void_p()
         check(lib().crh_graph_create(device, int(n_nodes), C.byref(h)))
         self._h = h
-        self.levels = self.seen = self.active = None
-        self.last = None      # (nq, max_hops) of the last bfs
+        self._ws = (_GraphWorkspace(), _GraphWorkspace())   # [False]: the first workspace, [True]: the second, bfs(..., back=True)
         self.ppr_work = None  # f32 [4, n_nodes, QS]: p0, two contribution planes, the scores of the last ppr
         self.ppr_last = None  # (nq, QS) of the last ppr
-        self.levels_back = self.seen_back = self.active_back = None   # the second workspace: bfs(..., back=True)
-        self.last_back = None   # (nq, max_hops) of the last bfs there
         self.sigma_buf = None   # u64 [n_nodes, QS] as int64: the chain counts of the last sigma
         self.sigma_last = None  # (nq, max_hops, the tensor it wrote)
+
+    levels, seen, active, last = (_workspace_attr(False, name) for name in ("levels", "seen", "active", "last"))
+    levels_back, seen_back, active_back, last_back = (_workspace_attr(True, name) for name in ("levels", "seen", "active", "last"))
 
     def close(self) -> None:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.crh_graph_destroy(self._h)
             self._h = None
-            self.levels = self.seen = self.active = self.ppr_work = None
-            self.levels_back = self.seen_back = self.active_back = self.sigma_buf = self.sigma_last = None
+            for ws in self._ws:
+                ws.levels = ws.seen = ws.active = None
+            self.ppr_work = self.sigma_buf = self.sigma_last = None
 
     __del__ = close
 
@@ -1437,26 +1450,26 @@ class Graph:
         check(lib().crh_graph_set_relation(self._handle(), int(rel), int(af.size), of.ctypes.data, af.ctypes.data if af.size else None,
                                            orv.ctypes.data, ar.ctypes.data if ar.size else None))
 
-    def _workspace(self, max_hops: int):
+    def _grow(self, holder, name: str, rows: int, dtype, cols: tuple = ()):
+        """The grow-only buffer ``holder.name``: kept while it has ``rows`` rows, else replaced by one of [rows, *cols]."""
         import torch
-        dev = f"cuda:{self.device}"
-        if self.levels is None or int(self.levels.shape[0]) < max_hops + 1:
-            self.levels = None                                         # (released before the larger one is taken)
-            self.levels = torch.empty((max_hops + 1, self.n_nodes), dtype=torch.int64, device=dev)
-        if self.seen is None:
-            self.seen = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
-            self.active = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
+        have = getattr(holder, name)
+        have = -1 if have is None else int(have.shape[0])
+        if have < rows:
+            setattr(holder, name, None)                                # (released before the larger one is taken: the peak is one buffer)
+            setattr(holder, name, torch.empty((max(rows, 1),) + cols, dtype=dtype, device=f"cuda:{self.device}"))
+        return getattr(holder, name)
 
-    def _workspace_back(self, max_hops: int):
-        """The second workspace: the search from the other end, which ``between`` reads beside the first."""
+    def _workspace(self, max_hops: int, back: bool = False) -> _GraphWorkspace:
+        """The workspace a bfs writes, with ``max_hops + 1`` levels at least.  ``back``: the second one, for the
+        search from the other end, which ``between`` reads beside the first."""
         import torch
-        dev = f"cuda:{self.device}"
-        if self.levels_back is None or int(self.levels_back.shape[0]) < max_hops + 1:
-            self.levels_back = None                                    # (released before the larger one is taken)
-            self.levels_back = torch.empty((max_hops + 1, self.n_nodes), dtype=torch.int64, device=dev)
-        if self.seen_back is None:
-            self.seen_back = torch.empty((self.n_nodes,), dtype=torch.int64, device=dev)
-            self.active_back = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=dev)
+        ws = self._ws[bool(back)]
+        self._grow(ws, "levels", max_hops + 1, torch.int64, (self.n_nodes,))
+        if ws.seen is None:
+            ws.seen = torch.empty((self.n_nodes,), dtype=torch.int64, device=f"cuda:{self.device}")
+            ws.active = torch.zeros((GRAPH_MAX_HOPS + 1,), dtype=torch.int64, device=f"cuda:{self.device}")
+        return ws
 
     def bfs(self, rel: int, direction, sources, max_hops: int, include_self: bool = False, stream: int = 0, back: bool = False, avoid=None):
         """``crh_graph_bfs`` from up to ``GRAPH_MAX_QUERIES`` source sets: ``sources`` is an iterable of iterables of node ids
@@ -1477,12 +1490,8 @@ class Graph:
             off, nodes = graph_sources(sources)
             nq = off.size - 1
         hops = max_hops if 1 <= max_hops <= GRAPH_MAX_HOPS else 1           # (a max_hops the library refuses allocates one level)
-        if back:
-            self._workspace_back(hops)
-            levels, seen, active = self.levels_back, self.seen_back, self.active_back
-        else:
-            self._workspace(hops)
-            levels, seen, active = self.levels, self.seen, self.active
+        ws = self._workspace(hops, back)
+        levels, seen, active = ws.levels, ws.seen, ws.active
         Graph.bfs_calls += 1
         head = (self._handle(), int(rel), graph_direction(direction), nq, off.ctypes.data, _ptr(nodes) if int(off[-1]) else None, on_dev, max_hops,
                 int(bool(include_self)))
@@ -1491,19 +1500,22 @@ class Graph:
         else:
             self._node_array(avoid, "int64", "avoid")
             check(lib().crh_graph_bfs_avoiding(*head, _ptr(avoid), _ptr(levels), _ptr(seen), _ptr(active), stream))
-        if back:
-            self.last_back = (nq, max_hops)
-        else:
-            self.last = (nq, max_hops)
+        ws.last = (nq, max_hops)
         return levels[: max_hops + 1], seen, active[: max_hops + 1]
 
     # -- chains in full
+    def _query_nodes(self, nodes) -> tuple[np.ndarray, bool]:
+        """A host list of one node per query (-1: none) as int64 [len(nodes)], and whether it is at most ``GRAPH_MAX_QUERIES``
+        nodes of this graph."""
+        nodes = np.asarray(list(nodes), np.int64).reshape(-1)
+        return nodes, nodes.size <= GRAPH_MAX_QUERIES and not (nodes.size and (nodes.min() < -1 or nodes.max() >= self.n_nodes))
+
     def avoid_words(self, nodes):
         """The ``avoid`` words of :meth:`bfs_avoiding` from one node per query (a host sequence, -1: the query avoids nothing):
         an int64 device tensor [n_nodes] with bit q set at ``nodes[q]``."""
         import torch
-        nodes = np.asarray(list(nodes), np.int64).reshape(-1)
-        if nodes.size > GRAPH_MAX_QUERIES or (nodes.size and (nodes.min() < -1 or nodes.max() >= self.n_nodes)):
+        nodes, ok = self._query_nodes(nodes)
+        if not ok:
             raise NativeError(E_INVALID, f"avoid: at most {GRAPH_MAX_QUERIES} nodes of 0..{self.n_nodes - 1} (or -1)")
         dev = f"cuda:{self.device}"
         out = torch.zeros((self.n_nodes,), dtype=torch.int64, device=dev)
@@ -1525,9 +1537,9 @@ class Graph:
         """Bit q of ``seen[nodes[q]]`` per query q (host bool [len(nodes)]; False for -1): gathered on the device, so the host
         sees the finished bits only.  ``seen``: default the last :meth:`bfs`'s.  Waits for the device."""
         import torch
-        nodes = np.asarray(list(nodes), np.int64).reshape(-1)
+        nodes, ok = self._query_nodes(nodes)
         seen = self.seen if seen is None else seen
-        if seen is None or nodes.size > GRAPH_MAX_QUERIES or (nodes.size and (nodes.min() < -1 or nodes.max() >= self.n_nodes)):
+        if seen is None or not ok:
             raise NativeError(E_INVALID, f"seen_bits: a bfs first, then at most {GRAPH_MAX_QUERIES} nodes of 0..{self.n_nodes - 1} (or -1)")
         if not nodes.size or not self.n_nodes:
             return np.zeros((nodes.size,), bool)
@@ -1536,13 +1548,15 @@ class Graph:
         return (got.cpu().numpy() != 0) & (nodes >= 0)
 
     def _levels_arg(self, levels, nq, max_hops, what: str, back: bool = False):
+        """The levels a call reads, with their nq and max_hops: what the last bfs left in the workspace (``back``: the second),
+        or ``levels`` of the caller's own, checked."""
         if levels is None:
-            last = self.last_back if back else self.last
-            if last is None:
+            ws = self._ws[bool(back)]
+            if ws.last is None:
                 raise NativeError(E_INVALID, f"{what}: no bfs has run on this graph")
-            levels = self.levels_back if back else self.levels
-            nq = last[0] if nq is None else nq
-            max_hops = last[1] if max_hops is None else max_hops
+            levels = ws.levels
+            nq = ws.last[0] if nq is None else nq
+            max_hops = ws.last[1] if max_hops is None else max_hops
         if nq is None or max_hops is None:
             raise NativeError(E_INVALID, f"{what}: levels of its own need nq and max_hops")
         _typed(levels, "int64", "levels")
@@ -1573,10 +1587,7 @@ class Graph:
             raise NativeError(E_INVALID, "active must be a device tensor of max_hops + 1 words")
         qs = self._qs(nq)
         if out is None:
-            if self.sigma_buf is None or int(self.sigma_buf.numel()) < self.n_nodes * qs:
-                self.sigma_buf = None                                  # (released before the larger one is taken)
-                self.sigma_buf = torch.empty((max(self.n_nodes * qs, 1),), dtype=torch.int64, device=f"cuda:{self.device}")
-            out = self.sigma_buf[: self.n_nodes * qs].view(self.n_nodes, qs)
+            out = self._grow(self, "sigma_buf", self.n_nodes * qs, torch.int64)[: self.n_nodes * qs].view(self.n_nodes, qs)
         _out(out, "int64", "out", (self.n_nodes, qs))
         check(lib().crh_graph_sigma(self._handle(), int(rel), graph_direction(direction), nq, _ptr(levels), _ptr(active), max_hops, _ptr(out), stream))
         self.sigma_last = (nq, max_hops, out)
@@ -1656,15 +1667,7 @@ class Graph:
         """``crh_graph_list`` over the last BFS's levels (or ``levels``, with ``nq`` and ``max_hops``): ``(nodes int32 [nq, limit],
         depth int32 [nq, limit], count int64 [nq])`` device tensors; (depth, node id) order, padding -1, exact counts."""
         import torch
-        if levels is None:
-            if self.last is None:
-                raise NativeError(E_INVALID, "list: no bfs has run on this graph")
-            levels = self.levels
-            nq = self.last[0] if nq is None else nq
-            max_hops = self.last[1] if max_hops is None else max_hops
-        _typed(levels, "int64", "levels")
-        if not _is_dev(levels) or levels.ndim != 2 or int(levels.shape[0]) < int(max_hops) + 1 or int(levels.shape[1]) != self.n_nodes:
-            raise NativeError(E_INVALID, f"levels must be a device tensor of at least {int(max_hops) + 1} levels x {self.n_nodes} nodes")
+        levels, nq, max_hops = self._levels_arg(levels, nq, max_hops, "list")
         dev = f"cuda:{self.device}"
         lim = max(int(limit), 0)
         nodes = torch.empty((max(int(nq), 0), lim), dtype=torch.int32, device=dev)
@@ -1701,13 +1704,7 @@ class Graph:
     def path(self, rel: int, direction, q: int, target: int, max_hops: int | None = None, levels=None, stream: int = 0) -> np.ndarray:
         """``crh_graph_path``: the nodes of one shortest path of query ``q`` of the last BFS (same ``rel`` and ``direction``) from
         a source to ``target``, int32; empty when the target was not reached.  Waits on ``stream``."""
-        if levels is None:
-            if self.last is None:
-                raise NativeError(E_INVALID, "path: no bfs has run on this graph")
-            levels, max_hops = self.levels, self.last[1] if max_hops is None else max_hops
-        _typed(levels, "int64", "levels")
-        if not _is_dev(levels) or levels.ndim != 2 or int(levels.shape[0]) < int(max_hops) + 1 or int(levels.shape[1]) != self.n_nodes:
-            raise NativeError(E_INVALID, f"levels must be a device tensor of at least {int(max_hops) + 1} levels x {self.n_nodes} nodes")
+        levels, _, max_hops = self._levels_arg(levels, None if levels is None else 0, max_hops, "path")   # (a path has no nq: 0 stands in beside levels of its own)
         out = np.full((GRAPH_MAX_HOPS + 1,), -1, np.int32)
         n = C.c_int(0)
         check(lib().crh_graph_path(self._handle(), int(rel), graph_direction(direction), _ptr(levels), int(q), int(target), int(max_hops),
@@ -1717,11 +1714,7 @@ class Graph:
     # -- personalised PageRank
     def _ppr_workspace(self, qs: int):
         import torch
-        need = 4 * self.n_nodes * qs                                    # p0, two contribution planes, the scores
-        if self.ppr_work is None or int(self.ppr_work.numel()) < need:
-            self.ppr_work = None                                       # (released before the larger one is taken)
-            self.ppr_work = torch.empty((max(need, 1),), dtype=torch.float32, device=f"cuda:{self.device}")
-        return self.ppr_work
+        return self._grow(self, "ppr_work", 4 * self.n_nodes * qs, torch.float32)   # p0, two contribution planes, the scores
 
     def ppr(self, rel: int, direction, seeds, weights=None, restart: float = 0.15, steps: int = 16, stream: int = 0):
         """``crh_graph_ppr``: personalised PageRank from up to ``GRAPH_MAX_QUERIES`` seed lists.  ``seeds`` is an iterable of
@@ -1753,9 +1746,7 @@ class Graph:
                     raise NativeError(E_INVALID, "ppr: weights must have the shape of seeds")
                 for q, x in enumerate(given):
                     w[q, : x.size] = x
-        qs = 1
-        while qs < min(max(nq, 1), GRAPH_MAX_QUERIES):
-            qs *= 2
+        qs = self._qs(nq)
         work = self._ppr_workspace(qs)
         plane = self.n_nodes * qs
         check(lib().crh_graph_ppr(self._handle(), int(rel), graph_direction(direction), nq, c, _ptr(nodes), _ptr(w), on_dev, float(restart),
